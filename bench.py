@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """Throughput of the QuartzNet-CTC training hot path on MI355X (BASELINE.json metric): audio-seconds/sec of training.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg4|cfg5] [--dtype bf16|f32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg4|cfg5] [--dtype bf16|f32] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the result line (ms_per_step = wall time of the K timed steps / K).
+--full adds what takes runs of its own: the roofline leg (extra eager steps with HIP-event brackets per kernel class), the `comm`
+record (N > 1), the `trainer` sub-record (one GPU) and the CPU-oracle `cpu_baseline` (--no-cpu-baseline drops the last two).
+--dump-outputs DIR: after the timed steps, what the last timed step handed back (loss, per-utterance nll, argmax) and the training
+state it left (parameters, their gradients, BN running statistics) as DIR/<name>.npy in float32 - the inputs are seeded, so two
+builds can be compared output for output.
 
   cfg2 (default; the configuration BASELINE.json's metric is quoted on): asr13x1, bs=32/GPU, 10 s 16 kHz clips, labels.txt (C=28)
   cfg4: QuartNetContextSE (SE + BiLSTM context block), bs=32, 10 s clips, C=28
@@ -201,6 +208,30 @@ def cpu_baseline(cfg_name: str, V: int):
             "thread_sweep_s_per_step": {str(k): v for k, v in sweep.items()}}
 
 
+# --dump-outputs: at most this many float32 elements per file (a fixed, seeded sample of a longer array): 2 x 6 M for params and
+# grads + 4 x 0.5 M for the rest stays under 64 MB in all.  cfg2's 5.04 M parameters are written whole.
+DUMP_MAX_ELEMS = {"params": 6_000_000, "grads": 6_000_000}
+DUMP_MAX_ELEMS_OTHER = 500_000
+
+
+def dump_outputs(out_dir: str, last, model) -> None:
+    """DIR/<name>.npy (float32) of the last timed step: its returned (loss, nll, argmax) and the model state it left behind"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    loss, nll, _logp, am = last
+    arrays = {"loss": loss, "nll": nll, "argmax": am, "params": model.params, "grads": model.grads,
+              "buffers": model.buffers[:model.n_buffer]}
+    for name, t in arrays.items():
+        if t is None or t.numel() == 0:
+            continue
+        t = t.detach()
+        cap = DUMP_MAX_ELEMS.get(name, DUMP_MAX_ELEMS_OTHER)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def watchdog_sync(what: str, timeout_s: float = 180.0) -> None:
     """the first replay of a captured step that holds RCCL collectives must COMPLETE before anything is timed: a capture failure falls
     back to eager launches, a replay hang is caught here (exit code 3 with a message; never a re-exec) - step.sync_with_timeout"""
@@ -379,6 +410,32 @@ def trainer_path(args, cfg, emit: bool = True, steps=None, warmup=None):
     return out
 
 
+def result_line(args, cfg, world, B, V, value, ms_per_step, final_loss, timed_audio_s, batches, use_graph, ts) -> dict:
+    """the step path's JSON line (rank 0); --full adds roofline, comm, cpu_baseline and trainer to it"""
+    from lightning_asr_amd import launch
+    metric = "audio-seconds/sec training (asr13x1, bs=32, 10 s clips)" if args.config == "cfg2" else \
+        "audio-seconds/sec training (%s)" % args.config
+    out = {
+        "metric": metric, "value": value, "unit": "audio-seconds/sec",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": (cfg["workload"] % B) + ", HIP mel+conv+CTC+NovoGrad, random-init weights", "name": args.config,
+                   "global_batch": B * world, "clip_seconds": cfg["clip_s"] if cfg["clip_s"] else "2-16 (ragged)",
+                   "audio_seconds_per_step_per_gpu": timed_audio_s / args.steps,
+                   "padding_frac": sum(b[5] for b in batches) / len(batches),
+                   "n_class": V + 1, "parallelism": "dp%d" % world, "feature_prefetch": bool(args.prefetch), "hip_graph": bool(use_graph),
+                   "staged_backward": bool(ts.overlap and (ts.world > 1 or ts.force_staged)),
+                   "grad_exchange": None if world == 1 else ("lasr_comm (librccl on the library's side stream, %d buckets overlapped with backward)"
+                                                             % int(os.environ.get("LASR_DP_BUCKETS", "2")) if ts.comm is not None
+                                                             else "torch.distributed all_reduce"),
+                   "excluded": "H2D of the PCM (waves resident in HBM); the reference's per-step greedy decode + WER logging (train.py:80)"},
+        "final_loss": final_loss,
+    }
+    if launch.rung_info() is not None:
+        out["config"]["launch_rung"] = launch.rung_info()["rung_index"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -398,8 +455,16 @@ def main():
                     help="step: TrainStep on batches resident in HBM (default); trainer: manifest -> LibriDataModule -> Trainer.fit")
     ap.add_argument("--ingest-threads", type=int, default=8, help="--path trainer: host threads decoding wav files (data.num_worker)")
     ap.add_argument("--no-trainer-record", dest="trainer_record", action="store_false",
-                    help="skip the `trainer` sub-record (60 + 30 steps through Trainer.fit) of the default one-GPU line")
+                    help="skip the `trainer` sub-record (60 + 30 steps through Trainer.fit) of the --full one-GPU line")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline leg, the comm record (N > 1), the trainer sub-record and the CPU baseline (runs of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs and the model state it left as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.path != "step":
+        ap.error("--dump-outputs applies to --path step")
     cfg = CONFIGS[args.config]
     # N > 1 from the plain command (`python bench.py --gpus N`, no outer launcher) or under torch.distributed.run: a supervisor that
     # never touches the GPU starts FRESH worker processes, one per GPU, relays rank 0's JSON line (plus a `launcher` record: which
@@ -554,7 +619,7 @@ def main():
     audio_s[0] = 0.0
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, *_ = one_step()
+        last = one_step()
     barrier()
     dt = time.perf_counter() - t0
     timed_audio_s = audio_s[0]
@@ -562,9 +627,18 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    final_loss = float(loss.item())
+    final_loss = float(last[0].item())
     ms_per_step = 1e3 * dt / args.steps
     value = timed_audio_s * world / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model)       # before anything else steps the model
+    if not args.full:
+        if dist is not None:
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(result_line(args, cfg, world, B, V, value, ms_per_step, final_loss, timed_audio_s, batches, use_graph, ts)),
+                  flush=True)
+        return
 
     # ---- roofline leg: the same steps again with HIP events around every launch of the dominant
     # kernel class (the 1x1-conv GEMMs), recorded on the launch stream inside liblasr.
@@ -672,32 +746,13 @@ def main():
         dist = None
     if rank != 0:
         return
-    metric = "audio-seconds/sec training (asr13x1, bs=32, 10 s clips)" if args.config == "cfg2" else \
-        "audio-seconds/sec training (%s)" % args.config
-    out = {
-        "metric": metric, "value": value, "unit": "audio-seconds/sec",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": (cfg["workload"] % B) + ", HIP mel+conv+CTC+NovoGrad, random-init weights", "name": args.config,
-                   "global_batch": B * world, "clip_seconds": cfg["clip_s"] if cfg["clip_s"] else "2-16 (ragged)",
-                   "audio_seconds_per_step_per_gpu": timed_audio_s / args.steps,
-                   "padding_frac": sum(b[5] for b in batches) / len(batches),
-                   "n_class": V + 1, "parallelism": "dp%d" % world, "feature_prefetch": bool(args.prefetch), "hip_graph": bool(use_graph),
-                   "staged_backward": bool(ts.overlap and (ts.world > 1 or ts.force_staged)),
-                   "grad_exchange": None if world == 1 else ("lasr_comm (librccl on the library's side stream, %d buckets overlapped with backward)"
-                                                             % int(os.environ.get("LASR_DP_BUCKETS", "2")) if ts.comm is not None
-                                                             else "torch.distributed all_reduce"),
-                   "excluded": "H2D of the PCM (waves resident in HBM); the reference's per-step greedy decode + WER logging (train.py:80)"},
-        "final_loss": final_loss,
-        "roofline": roofline,
-    }
+    out = result_line(args, cfg, world, B, V, value, ms_per_step, final_loss, timed_audio_s, batches, use_graph, ts)
+    out["roofline"] = roofline
     if comm_rec is not None:
         out["comm"] = comm_rec
     if not args.no_cpu_baseline:
         # rank 0 only; at N > 1 AFTER the process group is gone and the other ranks have left the GPU box's cores alone
         out["cpu_baseline"] = cpu_baseline(args.config, V)
-    if launch.rung_info() is not None:
-        out["config"]["launch_rung"] = launch.rung_info()["rung_index"]
     if trainer_rec is not None:
         out["trainer"] = trainer_rec
     print(json.dumps(out), flush=True)

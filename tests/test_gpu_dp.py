@@ -598,7 +598,7 @@ def test_bench_two_ranks_over_stub_prints_the_comm_record(dev, tmp_path):
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                          "--batch", "8", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
+                          "--batch", "8", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                                     # ONE JSON line, relayed by rank 0's supervisor
@@ -630,13 +630,13 @@ def test_bench_plain_command_starts_its_own_ranks(dev):
     """`python bench.py --gpus 2` with NO outer launcher and no RANK in the environment (the form the driver uses for one GPU; the
     reference's Lightning DDP starts its per-GPU children from the plain command too, /root/reference/train.py:233-252,
     conf/conf.yaml:21,30): the parent - which never initialises the GPU - starts two fresh workers, relays rank 0's ONE JSON line and
-    adds the `launcher` record.  The N > 1 line carries `cpu_baseline` beside `roofline` and `comm` (SURVEY 8d / VERDICT r4 1c)."""
+    adds the `launcher` record.  The --full N > 1 line carries `cpu_baseline` beside `roofline` and `comm` (SURVEY 8d / VERDICT r4 1c)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "8"],
-                         env=_bench_env(), capture_output=True, text=True, timeout=900, cwd=root)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "8",
+                          "--full"], env=_bench_env(), capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -659,7 +659,7 @@ def test_bench_plain_command_falls_down_the_ladder(dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8",
-                          "--no-cpu-baseline"], env=_bench_env(LASR_LAUNCH_FAULT="0:1"), capture_output=True, text=True, timeout=900, cwd=root)
+                          "--full", "--no-cpu-baseline"], env=_bench_env(LASR_LAUNCH_FAULT="0:1"), capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     la = d["launcher"]

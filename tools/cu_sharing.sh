@@ -9,7 +9,7 @@ root=${GRAFT_REPO_ROOT:-$PWD}
 for buckets in 2 1; do
 for n in 0 4 8 16 32 64; do
   LASR_FORCE_OVERLAP=1 LASR_DP_BUCKETS=$buckets LASR_RCCL_PATH=$root/tests/stub_rccl/libstubrccl.so LASR_STUB_HOLD_CUS=$n \
-    python $root/bench.py --steps $steps --warmup 10 --no-cpu-baseline 2> /tmp/cu_sharing.err | \
+    python $root/bench.py --steps $steps --warmup 10 --full --no-cpu-baseline 2> /tmp/cu_sharing.err | \
     python -c "import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps({'buckets': $buckets, 'held_cus': $n, 'ms_per_step': d['ms_per_step'], 'hip_graph': d['config']['hip_graph'], 'staged': d['config']['staged_backward'], 'comm': d.get('comm')}))" >> $out || { tail -5 /tmp/cu_sharing.err; exit 1; }
 done
 done

@@ -9,7 +9,7 @@ root=${GRAFT_REPO_ROOT:-$PWD}
 run() {  # label, env...
   label=$1; shift
   env LASR_FORCE_OVERLAP=1 LASR_DP_BUCKETS=2 LASR_RCCL_PATH=$root/tests/stub_rccl/libstubrccl.so "$@" \
-    python $root/bench.py --steps $steps --warmup 10 --no-cpu-baseline 2> /tmp/cu2.err | \
+    python $root/bench.py --steps $steps --warmup 10 --full --no-cpu-baseline 2> /tmp/cu2.err | \
     python -c "import sys,json; d=json.loads(sys.stdin.read()); c=d.get('comm') or {}; print(json.dumps({'case': '$label', 'ms_per_step': d['ms_per_step'], 'exposed_wait_us': c.get('exposed_wait_us_per_step'), 'buckets': [(round(b['mb'],1), round(b['allreduce_us'],1)) for b in c.get('buckets', [])]}))" >> $out || { tail -5 /tmp/cu2.err; exit 1; }
 }
 run "hold0" LASR_STUB_HOLD_CUS=0

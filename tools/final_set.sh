@@ -5,7 +5,7 @@ tag=${1:-final}
 root=${GRAFT_REPO_ROOT:-$PWD}
 cd $root && mkdir -p gpurun_out
 for cfg in cfg2 cfg4 cfg5; do
-  extra=""; [ $cfg = cfg2 ] || extra="--no-cpu-baseline"
+  extra="--full"; [ $cfg = cfg2 ] || extra="--full --no-cpu-baseline"
   python bench.py --config $cfg --steps 200 --warmup 20 $extra > gpurun_out/${tag}_${cfg}_step.json 2> gpurun_out/${tag}_${cfg}_step.err || { tail -n 5 gpurun_out/${tag}_${cfg}_step.err; exit 1; }
   python bench.py --config $cfg --path trainer --steps 200 --warmup 20 --no-cpu-baseline > gpurun_out/${tag}_${cfg}_trainer.json 2> gpurun_out/${tag}_${cfg}_trainer.err || { tail -n 5 gpurun_out/${tag}_${cfg}_trainer.err; exit 1; }
   echo "$cfg bench lines done"
