@@ -340,6 +340,13 @@ int lasr_log_softmax(const float* logits, float* logp, int32_t* argmax, int64_t 
 int lasr_log_softmax_bwd(const float* logp, const float* grad_logp, float* grad_logits, int64_t N, int64_t C,
                          void* stream);
 
+/* Longest label sequence the CTC heads take (lasr_ctc_loss, lasr_ctc_loss_mel, lasr_ctc_loss_lean, the model's loss): a
+ * feasible sample needs S + repeats <= T', so 2047 covers every transcript of a 40 s clip (T' = 2001).  Above it the
+ * workspace functions return 0 and the losses LASR_E_SHAPE. */
+#define LASR_CTC_MAX_LABELS 2047
+/* alpha + beta lattices + the same-label chains.  Rows hold 64 * 4/8/16 states for S_max <= 511 and 1024 * W states for
+ * longer labels (W = ceil((2 S_max + 1) / 1024) = 2..4 waves per direction): for B = 32, T' = 2001 and S_max = 600 (W = 2)
+ * that is about 1 GB.  0 when S_max > LASR_CTC_MAX_LABELS. */
 size_t lasr_ctc_workspace_bytes(int64_t B, int64_t T, int64_t S_max);
 /* logp (B, T, C) f32 log-probs; targets (B, S_max) int64 zero padded; in_lens/tgt_lens (B) int32.
  * nll (B) f32 per-sample negative log-likelihood (+inf when infeasible).
@@ -347,7 +354,8 @@ size_t lasr_ctc_workspace_bytes(int64_t B, int64_t T, int64_t S_max);
  *   CTCLoss backward returns for grad_output = gscale.  Its class-sum is 0, so log_softmax backward
  *   maps it to itself: it is also d/d(logits).  Rows t >= in_lens[b] are zero; rows of an infeasible
  *   sample are NaN (zero_infinity=False).  gscale (B) f32 or NULL (= 1/B: batch mean, train.py:77).
- *   S_max <= 511 (lattice of 2S+1 states held 4/8/16 per lane of one wave).                       */
+ *   S_max <= LASR_CTC_MAX_LABELS (2047).  Up to 511 the 2S+1 states of a direction are held 4/8/16 per lane of one
+ *   wave; longer labels run each direction on 2..4 waves of 16 states per lane.                     */
 int lasr_ctc_loss(const float* logp, const int64_t* targets, const int32_t* in_lens, const int32_t* tgt_lens,
                   int64_t B, int64_t T, int64_t C, int64_t S_max, int blank, float* nll, float* grad,
                   const float* gscale, void* workspace, size_t workspace_bytes, void* stream);
@@ -519,7 +527,9 @@ int lasr_lr_schedule_step(void* state_dev, float* lr_dev, void* stream);
  *   of the STORED values: row_stat [M][tiles][2] = (max, sum exp(x - max)), row_arg [M][tiles] = first argmax column.
  * lasr_ctc_loss_lean: from those, lse and argmax per row, the lattice over the gathered target / blank emissions only, and
  *   grad [B*T][ldc] bf16 = gscale_b * d nll_b / d logits (1/B when gscale is NULL; zero rows past in_lens, NaN for an
- *   infeasible utterance like torch), bias_grad (C) f32 = column sums of the unrounded gradient.  ldc = C rounded up to 8. */
+ *   infeasible utterance like torch), bias_grad (C) f32 = column sums of the unrounded gradient.  ldc = C rounded up to 8.
+ *   S_max <= LASR_CTC_MAX_LABELS; the workspace holds the lattice of lasr_ctc_workspace_bytes plus B*T*(S_max+1) f32
+ *   emissions (0 above the bound). */
 int lasr_gemm_rowstat(const void* A, const void* B, const float* bias, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                       float* row_stat, int32_t* row_arg, int* n_col_tiles, void* stream);
 size_t lasr_gemm_rowstat_bytes(int64_t M, int64_t N);

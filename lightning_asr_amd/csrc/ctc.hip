@@ -95,6 +95,22 @@ __global__ __launch_bounds__(128) void ctc_alpha_beta_kernel(const float* __rest
   ctc_alpha_beta_body<NS, EM_LDS, 128>(logp, targets, in_lens, tgt_lens, T, C, S_max, blank, alpha, beta, next_same, nll, blockIdx.x, s_tg, s_lp);
 }
 
+// The long-label lattice (ctc_lattice.h ctc_alpha_beta_mw_body): 2B workgroups of 64 NW threads, LDS label table of 2048.
+template <bool EM_LDS>
+__global__ __launch_bounds__(256) void ctc_alpha_beta_mw_kernel(const float* __restrict__ logp, const int64_t* __restrict__ targets,
+                                                                const int32_t* __restrict__ in_lens,
+                                                                const int32_t* __restrict__ tgt_lens, int64_t T, int64_t C,
+                                                                int64_t S_max, int blank, float* __restrict__ alpha,
+                                                                float* __restrict__ beta, int32_t* __restrict__ next_same,
+                                                                float* __restrict__ nll) {
+  __shared__ int32_t s_tg[kCtcMwMaxS];
+  __shared__ float s_ring[2 * (kCtcMwMaxWaves + 2) * 2];
+  __shared__ float s_fin[2];
+  extern __shared__ __attribute__((aligned(16))) float s_lp[];
+  ctc_alpha_beta_mw_body<EM_LDS, false>(logp, targets, in_lens, tgt_lens, T, C, S_max, blank, alpha, beta, next_same, nll, s_tg, s_lp,
+                                        s_ring, s_fin);
+}
+
 // One wave per (b, t) row: grad[b][t][c] = gs * (exp(logp) - occupancy_c), zero for t >= in_len.
 // grid: ceil(B*T/4) blocks of 256 threads; dynamic LDS: 4 * (C + S_max) floats.
 template <int NS>
@@ -179,6 +195,98 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
   }
 }
 
+// The same over the multi-wave lattice (rows of NW chunks of 1024 states): each lane walks its 16 states of every chunk, all
+// 16-byte lattice loads of the row issued together.
+template <int NW>
+__global__ __launch_bounds__(256) void ctc_grad_mw_kernel(const float* __restrict__ logp, const int64_t* __restrict__ targets,
+                                                 const int32_t* __restrict__ in_lens, const int32_t* __restrict__ tgt_lens,
+                                                 int64_t B, int64_t T, int64_t C, int64_t S_max, int blank,
+                                                 const float* __restrict__ alpha, const float* __restrict__ beta,
+                                                 const int32_t* __restrict__ next_same, const float* __restrict__ nll,
+                                                 const float* __restrict__ gscale, float* __restrict__ grad) {
+  constexpr int NS = kCtcMwNS, SP1 = 64 * NS, SP = SP1 * NW;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + wid;
+  float* s_row = smem + (size_t)wid * (C + S_max);
+  float* s_v = s_row + C;
+  const bool live = row < B * T;
+  const int64_t b = live ? row / T : 0;
+  const int64_t t = live ? row - b * T : 0;
+  const int Tb = in_lens[b];
+  const int S = tgt_lens[b];
+  const int SS = 2 * S + 1;
+  const float gs = gscale ? gscale[b] : 1.0f / (float)B;
+  float* g = grad + row * C;
+  const float* lp = logp + row * C;
+  if (live && t >= Tb) {
+    for (int64_t c = lane; c < C; c += 64) g[c] = 0.f;
+  }
+  const bool work = live && t < Tb;
+  const float nl = nll[b];
+  const bool infeasible = isinf(nl);
+  if (work) {
+    for (int64_t c = lane; c < C; c += 64) s_row[c] = expf(lp[c]);
+    // occupancy of every lattice state
+    const float* al = alpha + (b * T + t) * SP;
+    const float* be = beta + (b * T + t) * SP;
+    const int64_t* tg = targets + b * S_max;
+    float blank_occ = 0.f;
+    // the lane's NS lattice values of either direction as 16-byte loads, its labels and their log-probs requested with them (clamped
+    // indices, no branch around a load): as eight scalar loads + a label load + a gather per state inside `if (s < SS)` the row was a
+    // chain of dependent round trips (round 5)
+    float av[NW * NS], bv[NW * NS], lpc[NS];
+    int cls[NS];
+#pragma unroll
+    for (int k = 0; k < NW; ++k)
+#pragma unroll
+      for (int i = 0; i < NS; i += 4) {
+        const float4 a4 = *reinterpret_cast<const float4*>(al + k * SP1 + lane * NS + i);
+        const float4 b4 = *reinterpret_cast<const float4*>(be + k * SP1 + lane * NS + i);
+        float* ak = av + k * NS;
+        float* bk = bv + k * NS;
+        ak[i] = a4.x; ak[i + 1] = a4.y; ak[i + 2] = a4.z; ak[i + 3] = a4.w;
+        bk[i] = b4.x; bk[i + 1] = b4.y; bk[i + 2] = b4.z; bk[i + 3] = b4.w;
+      }
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+      if (k * SP1 >= SS) break;   // (wave-uniform) the chunk holds no state of this utterance
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const int s = k * SP1 + lane * NS + i;
+        const int64_t lab = S_max > 0 ? tg[min((int64_t)(s >> 1), S_max - 1)] : 0;   // (S_max = 0: an empty targets tensor)
+        cls[i] = (s & 1) ? (int)min(max(lab, (int64_t)0), C - 1) : blank;
+      }
+#pragma unroll
+      for (int i = 0; i < NS; ++i) lpc[i] = lp[cls[i]];
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const int s = k * SP1 + lane * NS + i;
+        if (s < SS) {
+          const float v = expf(av[k * NS + i] + bv[k * NS + i] + nl - lpc[i]);
+          if (s & 1) s_v[s >> 1] = v;
+          else blank_occ += v;
+        }
+      }
+    }
+    blank_occ = wave_sum(blank_occ);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS writes have landed (single-wave hand-off)
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) s_row[blank] -= blank_occ;
+    const int32_t* nx = next_same + b * S_max * 2;
+    for (int i = lane; i < S; i += 64) {
+      if (nx[S_max + i]) {  // first occurrence of its label: sum the chain in target order
+        float acc = 0.f;
+        for (int j = i; j >= 0; j = nx[j]) acc += s_v[j];
+        s_row[min(max(tg[i], (int64_t)0), C - 1)] -= acc;
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    for (int64_t c = lane; c < C; c += 64) g[c] = infeasible ? __builtin_nanf("") : gs * s_row[c];
+  }
+}
+
 // ------------------------------------------------------------------ greedy collapse -----------
 // one wave per utterance; ballot-compaction of the kept frames, 64 frames per step
 __global__ __launch_bounds__(64) void greedy_decode_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ lens,
@@ -204,14 +312,6 @@ __global__ __launch_bounds__(64) void greedy_decode_kernel(const int32_t* __rest
   }
   for (int64_t t = count + lane; t < T; t += 64) o[t] = -1;
   if (lane == 0) n_tokens[b] = count;
-}
-
-static inline int ctc_ns(int64_t S_max) {
-  const int64_t ss = 2 * S_max + 1;
-  if (ss <= 64 * 4) return 4;
-  if (ss <= 64 * 8) return 8;
-  if (ss <= 64 * 16) return 16;
-  return 0;
 }
 
 }  // namespace lasr
@@ -247,9 +347,9 @@ extern "C" int lasr_log_softmax_bwd(const float* logp, const float* grad_logp, f
 }
 
 extern "C" size_t lasr_ctc_workspace_bytes(int64_t B, int64_t T, int64_t S_max) {
-  const int ns = ctc_ns(S_max);
-  if (!ns) return 0;
-  return align_up((size_t)2 * B * T * 64 * ns * sizeof(float), 256) + align_up((size_t)B * (S_max > 0 ? S_max : 1) * 2 * sizeof(int32_t), 256);
+  const CtcGeom g = ctc_geom(S_max);   // (S_max <= 511: pitch 64 * ns - the one-wave layout)
+  if (!g.pitch) return 0;
+  return align_up((size_t)2 * B * T * g.pitch * sizeof(float), 256) + align_up((size_t)B * (S_max > 0 ? S_max : 1) * 2 * sizeof(int32_t), 256);
 }
 
 // gradient pass over a lattice already in `workspace` (layout of lasr_ctc_loss)
@@ -257,8 +357,9 @@ namespace lasr {
 int launch_ctc_grad(const float* logp, const int64_t* targets, const int32_t* in_lens, const int32_t* tgt_lens, int64_t B, int64_t T,
                     int64_t C, int64_t S_max, int blank, const float* nll, float* grad, const float* gscale, void* workspace,
                     void* stream) {
-  const int ns = ctc_ns(S_max);
-  const size_t ab = (size_t)B * T * 64 * ns;
+  const CtcGeom geo = ctc_geom(S_max);
+  const int ns = geo.ns;                 // 4 / 8 / 16 states per lane of one wave; 0: the multi-wave lattice
+  const size_t ab = (size_t)B * T * geo.pitch;
   float* alpha = reinterpret_cast<float*>(workspace);
   float* beta = alpha + ab;
   int32_t* next_same = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + align_up(2 * ab * sizeof(float), 256));
@@ -267,13 +368,14 @@ int launch_ctc_grad(const float* logp, const int64_t* targets, const int32_t* in
   const size_t shmem = 4 * (size_t)(C + sm) * sizeof(float);
   LASR_CHECK_SHAPE(shmem <= 160 * 1024, "lasr_ctc_loss: C=%lld too large for the LDS row buffer", (long long)C);
   dim3 grid((unsigned)cdiv(B * T, 4));
-#define LASR_CTC_G(NS_)                                                                                                    \
+#define LASR_CTC_G(K_)                                                                                                     \
   do {                                                                                                                     \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_grad_kernel<NS_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL(ctc_grad_kernel<NS_>, grid, dim3(256), shmem, st, logp, targets, in_lens, tgt_lens, B, T, C, sm, blank, alpha, \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K_), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+    hipLaunchKernelGGL(K_, grid, dim3(256), shmem, st, logp, targets, in_lens, tgt_lens, B, T, C, sm, blank, alpha,      \
                        beta, next_same, nll, gscale, grad);                                                                \
   } while (0)
-  if (ns == 4) LASR_CTC_G(4); else if (ns == 8) LASR_CTC_G(8); else LASR_CTC_G(16);
+  if (ns == 4) LASR_CTC_G(ctc_grad_kernel<4>); else if (ns == 8) LASR_CTC_G(ctc_grad_kernel<8>); else if (ns == 16) LASR_CTC_G(ctc_grad_kernel<16>);
+  else if (geo.nw == 2) LASR_CTC_G(ctc_grad_mw_kernel<2>); else if (geo.nw == 3) LASR_CTC_G(ctc_grad_mw_kernel<3>); else LASR_CTC_G(ctc_grad_mw_kernel<4>);
 #undef LASR_CTC_G
   LASR_LAUNCH_CHECK("ctc_grad_kernel");
   return 0;
@@ -285,10 +387,12 @@ extern "C" int lasr_ctc_loss(const float* logp, const int64_t* targets, const in
                              void* workspace, size_t workspace_bytes, void* stream) {
   LASR_CHECK_ARG(logp && targets && in_lens && tgt_lens && nll && workspace, "lasr_ctc_loss: null pointer");
   LASR_CHECK_SHAPE(B > 0 && T > 0 && C > 1 && S_max >= 0 && blank >= 0 && blank < C, "lasr_ctc_loss: shape");
-  const int ns = ctc_ns(S_max);
-  LASR_CHECK_SHAPE(ns != 0, "lasr_ctc_loss: S_max=%lld exceeds the 511-label lattice the kernels are built for", (long long)S_max);
+  const CtcGeom geo = ctc_geom(S_max);
+  const int ns = geo.ns;                 // 4 / 8 / 16 states per lane of one wave; 0: the multi-wave lattice
+  LASR_CHECK_SHAPE(geo.pitch != 0, "lasr_ctc_loss: S_max=%lld exceeds the %d-label bound of the CTC lattice", (long long)S_max,
+                   LASR_CTC_MAX_LABELS);
   if (workspace_bytes < lasr_ctc_workspace_bytes(B, T, S_max)) return fail(LASR_E_WORKSPACE, "lasr_ctc_loss: workspace");
-  const size_t ab = (size_t)B * T * 64 * ns;
+  const size_t ab = (size_t)B * T * geo.pitch;
   float* alpha = reinterpret_cast<float*>(workspace);
   float* beta = alpha + ab;
   int32_t* next_same = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + align_up(2 * ab * sizeof(float), 256));
@@ -310,9 +414,26 @@ extern "C" int lasr_ctc_loss(const float* logp, const int64_t* targets, const in
                          tgt_lens, T, C, sm, blank, alpha, beta, next_same, nll);                                          \
     }                                                                                                                      \
   } while (0)
-  if (ns == 4) LASR_CTC_AB(4); else if (ns == 8) LASR_CTC_AB(8); else LASR_CTC_AB(16);
+  if (ns) {
+    if (ns == 4) LASR_CTC_AB(4); else if (ns == 8) LASR_CTC_AB(8); else LASR_CTC_AB(16);
+    LASR_LAUNCH_CHECK("ctc_alpha_beta_kernel");
+  } else {
+    // long labels: one workgroup of geo.nw waves per (utterance, direction); emission rows in LDS beside the 8 KB label table
+    // (C = 28: up to T' = 1386), the register ring of ctc_lattice otherwise
+    const bool mw_lds = em_bytes <= 150 * 1024 && C % 4 == 0 && reinterpret_cast<uintptr_t>(logp) % 16 == 0 && !getenv("LASR_CTC_NO_LDS");
+    const dim3 grid((unsigned)(2 * B)), block((unsigned)(64 * geo.nw));
+    if (mw_lds) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_alpha_beta_mw_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                150 * 1024);
+      hipLaunchKernelGGL(ctc_alpha_beta_mw_kernel<true>, grid, block, em_bytes, st, logp, targets, in_lens, tgt_lens, T, C, sm, blank, alpha, beta,
+                         next_same, nll);
+    } else {
+      hipLaunchKernelGGL(ctc_alpha_beta_mw_kernel<false>, grid, block, 0, st, logp, targets, in_lens, tgt_lens, T, C, sm, blank, alpha, beta,
+                         next_same, nll);
+    }
+    LASR_LAUNCH_CHECK("ctc_alpha_beta_mw_kernel");
+  }
 #undef LASR_CTC_AB
-  LASR_LAUNCH_CHECK("ctc_alpha_beta_kernel");
   if (grad) return launch_ctc_grad(logp, targets, in_lens, tgt_lens, B, T, C, S_max, blank, nll, grad, gscale, workspace, stream);
   return 0;
 }

@@ -274,6 +274,253 @@ __device__ __forceinline__ void ctc_alpha_beta_body(const float* __restrict__ lo
     ctc_lattice<NS, EM_LDS, false, COMPACT>(lp, s_lp + C, s_tg, lane, Tb, S, (int)C, blank, alpha + (int64_t)b * T * SP, nll + b);
 }
 
+// ------------------------------------------------------------------ multi-wave lattice (S_max > 511) ------------------
+// Above 511 labels the 2S+1 states of one direction do not fit one wave.  The long form runs each direction on NW waves
+// (NW = ceil((2 S_max + 1) / 1024) = 2, 3 or 4), 16 states per lane: wave w owns states [1024 w, 1024 (w + 1)).  The
+// per-state arithmetic is that of ctc_lattice<16, ..>; what changes is where the two states across a wave edge come from.
+// Each step the recursion needs the previous step's two edge states of the neighbouring wave (alpha: wave w-1's top two,
+// beta: wave w+1's bottom two).  They pass through a two-slot LDS ring indexed by the parity of the step: step k reads the
+// slot written at step k-1 and writes the other, then one s_barrier.  The barrier of step k orders step k's writes before
+// step k+1's reads and step k's reads before step k+1's overwrite of the same slot two steps later, so one barrier per step
+// suffices without skewing the waves against each other.  The barrier waits on LDS only (lds_barrier, common.h): the lattice
+// stores and the emission prefetches stay in flight across it.
+// Ring entry 0 (alpha) / NW + 1 (beta) is a permanent kDead sentinel: the outermost waves take it as the fill the one-wave
+// kernel gives lane 0 / lane 63, so with all live states inside wave 0 the rows and the nll are bit-identical to it.
+static constexpr int kCtcMwNS = 16;                    // states per lane
+static constexpr int kCtcMwWaveStates = 64 * kCtcMwNS;  // 1024 states per wave
+static constexpr int kCtcMwMaxWaves = 4;
+static constexpr int kCtcMwMaxS = 2048;                // label table entries (S_max <= 2047 = LASR_CTC_MAX_LABELS)
+
+// One direction of the lattice for one utterance on NW waves (this is wave `wv`).  s_ring: 2 x (NW + 2) x 2 floats, every
+// entry kDead on entry; s_fin: 2 floats, -inf on entry (alpha only).  Emission arguments as ctc_lattice.  Every wave of the
+// workgroup calls this with the same Tb (the barrier count is Tb - 1, + 1 for the nll).
+template <bool EM_LDS, bool BETA, bool COMPACT>
+__device__ __forceinline__ void ctc_lattice_mw(const float* __restrict__ lp, const float* s_rows, const int32_t* s_tg, int lane, int wv, int NW,
+                                               int Tb, int S, int C, int blank, float* __restrict__ out, float* s_ring, float* s_fin,
+                                               float* __restrict__ nll_b) {
+  constexpr int NS = kCtcMwNS;
+  const int SP = kCtcMwWaveStates * NW;
+  const int SS = 2 * S + 1;
+  const int s0 = wv * kCtcMwWaveStates + lane * NS;    // this lane's first state
+  int cls4[NS];
+  bool skip_ok[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    const int s = s0 + i;
+    int c = blank;
+    bool sk = false;
+    if (s < SS && (s & 1)) {
+      const int lab = s_tg[s >> 1];
+      c = COMPACT ? (s >> 1) : lab;
+      if (!BETA) sk = s >= 3 ? (s_tg[(s >> 1) - 1] != lab) : false;
+      else sk = (s + 2 < SS) ? (s_tg[(s >> 1) + 1] != lab) : false;
+    }
+    cls4[i] = c * 4;
+    skip_ok[i] = sk;
+  }
+  float a[NS], em[NS];
+  const int t_first = BETA ? Tb - 1 : 0;
+  constexpr int dt = BETA ? -1 : 1;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    const int s = s0 + i;
+    const bool start = BETA ? (s == SS - 1 || s == SS - 2) : (s == 0 || s == 1);
+    a[i] = (start && s < SS) ? lp[(int64_t)t_first * C + (cls4[i] >> 2)] : kDead;
+  }
+  float* o = out + (int64_t)t_first * SP + s0;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) o[i] = a[i];
+  constexpr int kRingRow = 2 * (kCtcMwMaxWaves + 2);
+  const int r_in = BETA ? 2 * (wv + 2) : 2 * wv;       // neighbour's entry: wave w+1 (beta) / w-1 (alpha), sentinels at the ends
+  const int r_out = 2 * (wv + 1);
+  // publish the edge states of step 0 (slot 0)
+  if (!BETA && lane == 63) { s_ring[r_out] = a[NS - 2]; s_ring[r_out + 1] = a[NS - 1]; }
+  if (BETA && lane == 0) { s_ring[r_out] = a[0]; s_ring[r_out + 1] = a[1]; }
+  lds_barrier();
+  int par = 0;                                          // slot of the previous step
+  auto advance = [&]() {
+    const float* rin = s_ring + par * kRingRow + r_in;
+    float n[NS];
+    if (!BETA) {
+      const float p1 = wave_shr1(a[NS - 1], rin[1]);   // lane 0: wave w-1's top state, then its second from the top
+      const float p2 = wave_shr1(a[NS - 2], rin[0]);
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const float s1 = i >= 1 ? a[i - 1] : p1;
+        const float s2v = (i == 0) ? p2 : (i == 1 ? p1 : a[i - 2]);
+        n[i] = ((i & 1) ? lse3_fast(a[i], s1, skip_ok[i] ? s2v : kDead) : lse2_fast(a[i], s1)) + em[i];
+      }
+    } else {
+      const float q1 = wave_shl1(a[0], rin[0]);         // lane 63: wave w+1's bottom state, then its second
+      const float q2 = wave_shl1(a[1], rin[1]);
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const float s1 = i + 1 < NS ? a[i + 1] : q1;
+        const float s2v = (i + 2 < NS) ? a[i + 2] : (i + 2 == NS ? q1 : q2);
+        n[i] = ((i & 1) ? lse3_fast(a[i], s1, skip_ok[i] ? s2v : kDead) : lse2_fast(a[i], s1)) + em[i];
+      }
+    }
+    par ^= 1;
+    float* rout = s_ring + par * kRingRow + r_out;
+    if (!BETA && lane == 63) { rout[0] = n[NS - 2]; rout[1] = n[NS - 1]; }
+    if (BETA && lane == 0) { rout[0] = n[0]; rout[1] = n[1]; }
+    o += dt * SP;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      a[i] = n[i];
+      o[i] = n[i];
+    }
+    lds_barrier();
+  };
+  if (EM_LDS) {
+    const char* row = reinterpret_cast<const char*>(s_rows) + (int64_t)(t_first + dt) * C * 4;
+    const int drow = dt * C * 4;
+    float nx[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) nx[i] = *reinterpret_cast<const float*>(row + cls4[i]);
+    for (int step = 1; step < Tb; ++step) {
+#pragma unroll
+      for (int i = 0; i < NS; ++i) em[i] = nx[i];
+      row += drow;
+#pragma unroll
+      for (int i = 0; i < NS; ++i) nx[i] = *reinterpret_cast<const float*>(row + cls4[i]);
+      advance();
+    }
+  } else {
+    constexpr int kPre = 8;                             // register ring of emissions, as ctc_lattice
+    float ring[kPre][NS];
+#pragma unroll
+    for (int u = 0; u < kPre; ++u)
+#pragma unroll
+      for (int i = 0; i < NS; ++i)
+        ring[u][i] = (1 + u < Tb) ? lp[(int64_t)(t_first + dt * (1 + u)) * C + (cls4[i] >> 2)] : 0.f;
+    for (int step0 = 1; step0 < Tb; step0 += kPre) {
+#pragma unroll
+      for (int u = 0; u < kPre; ++u) {
+        const int step = step0 + u;
+        if (step < Tb) {  // workgroup-uniform
+          const int t = t_first + dt * step;
+#pragma unroll
+          for (int i = 0; i < NS; ++i) em[i] = ring[u][i];
+          {
+            const int tq = BETA ? max(t - kPre, 0) : min(t + kPre, Tb - 1);
+#pragma unroll
+            for (int i = 0; i < NS; ++i) ring[u][i] = lp[(int64_t)tq * C + (cls4[i] >> 2)];
+          }
+          advance();
+        }
+      }
+    }
+  }
+  if (!BETA) {
+    // ll = lse(alpha_{T-1}(SS-1), alpha_{T-1}(SS-2)): the owning lanes (one or two, possibly in two waves) leave their lse2 partial
+    // in s_fin, the lane of SS-1 in [1], a different lane holding SS-2 in [0]; wave 0 then reduces exactly as ctc_lattice does
+    // (the max and a sum of at most two non-zero terms do not depend on which lanes hold them)
+    float v = kNegInf;
+    bool own1 = false, own2 = false;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int s = s0 + i;
+      own1 |= s == SS - 1;
+      own2 |= s == SS - 2;
+      if ((s == SS - 1 || s == SS - 2) && a[i] > 0.5f * kDead) v = lse2(v, a[i]);
+    }
+    if (own1) s_fin[1] = v;
+    else if (own2) s_fin[0] = v;
+    lds_barrier();
+    if (wv == 0) {
+      v = lane < 2 ? s_fin[lane] : kNegInf;
+      const float m = wave_max(v);
+      float e = (v == kNegInf) ? 0.f : expf(v - m);
+      e = wave_sum(e);
+      if (lane == 0) *nll_b = (m == kNegInf) ? INFINITY : -(m + logf(e));
+    }
+  }
+}
+
+// Workspace layout per utterance: alpha [T][1024 NW], beta [T][1024 NW], then next_same [2][S_max] int32 (as the one-wave
+// form, with the wider row).  grid: 2B workgroups of 64 NW threads, workgroup 2b + 0 runs alpha, 2b + 1 beta, so that each
+// barrier couples only the waves of one recursion.  The same-label chain is split between the two.
+// s_tg: kCtcMwMaxS ints; s_lp (EM_LDS): (T + 2) * C floats; s_ring / s_fin as ctc_lattice_mw.
+template <bool EM_LDS, bool COMPACT>
+__device__ __forceinline__ void ctc_alpha_beta_mw_body(const float* __restrict__ logp, const int64_t* __restrict__ targets,
+                                                       const int32_t* __restrict__ in_lens, const int32_t* __restrict__ tgt_lens,
+                                                       int64_t T, int64_t C, int64_t S_max, int blank, float* __restrict__ alpha,
+                                                       float* __restrict__ beta, int32_t* __restrict__ next_same,
+                                                       float* __restrict__ nll, int32_t* s_tg, float* s_lp, float* s_ring, float* s_fin) {
+  const int NT = (int)blockDim.x;
+  const int NW = NT >> 6;
+  const int SP = kCtcMwWaveStates * NW;
+  const int b = (int)(blockIdx.x >> 1);
+  const bool is_beta = (blockIdx.x & 1) != 0;
+  const int lane = threadIdx.x & 63;
+  const int Tb = in_lens[b];
+  const int S = tgt_lens[b];
+  const int64_t* tg = targets + (int64_t)b * S_max;
+  const float* lp = logp + (int64_t)b * T * C;
+  for (int i = threadIdx.x; i < S; i += NT) s_tg[i] = (int32_t)min(max(tg[i], (int64_t)0), (int64_t)(COMPACT ? 0x7fffffff : C - 1));
+  if (threadIdx.x < 2 * (kCtcMwMaxWaves + 2) * 2) s_ring[threadIdx.x] = kDead;
+  if (threadIdx.x < 2) s_fin[threadIdx.x] = kNegInf;
+  if (EM_LDS && Tb > 0) {
+    const int n4 = (int)(((int64_t)Tb * C) >> 2);   // the host checked C % 4 == 0 and the 16-byte alignment of logp
+    const float4* src = reinterpret_cast<const float4*>(lp);
+    float4* dst = reinterpret_cast<float4*>(s_lp + C);
+    for (int i0 = threadIdx.x; i0 < n4; i0 += 4 * NT) {
+      float4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = src[min(i0 + u * NT, n4 - 1)];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (i0 + u * NT < n4) dst[i0 + u * NT] = v[u];
+    }
+    for (int i = threadIdx.x; i < (int)C; i += NT) {
+      s_lp[i] = 0.f;
+      s_lp[(int64_t)(Tb + 1) * C + i] = 0.f;
+    }
+  }
+  __syncthreads();
+  // same-label chain (see ctc_alpha_beta_body): labels i of the alpha workgroup's half, then the beta workgroup's
+  for (int i = (int)threadIdx.x + (is_beta ? NT : 0); i < S; i += 2 * NT) {
+    const int me = s_tg[i];
+    int nx = -1, first = 1;
+#pragma unroll 8
+    for (int j = S - 1; j >= 0; --j) {
+      const bool same = s_tg[j] == me;
+      nx = (same && j > i) ? j : nx;
+      first = (same && j < i) ? 0 : first;
+    }
+    next_same[(int64_t)b * S_max * 2 + i] = nx;
+    next_same[(int64_t)b * S_max * 2 + S_max + i] = first;
+  }
+  if (Tb <= 0) {
+    if (!is_beta && threadIdx.x == 0) nll[b] = (S == 0) ? 0.f : INFINITY;
+    return;
+  }
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (is_beta)
+    ctc_lattice_mw<EM_LDS, true, COMPACT>(lp, s_lp + C, s_tg, lane, wv, NW, Tb, S, (int)C, blank, beta + (int64_t)b * T * SP, s_ring, s_fin, nullptr);
+  else
+    ctc_lattice_mw<EM_LDS, false, COMPACT>(lp, s_lp + C, s_tg, lane, wv, NW, Tb, S, (int)C, blank, alpha + (int64_t)b * T * SP, s_ring, s_fin,
+                                           nll + b);
+}
+
+// Lattice geometry for a label width S_max: ns = 4 / 8 / 16 states per lane on one wave (S_max <= 511), or 0 with nw = 2..4
+// waves of 16 states per lane (S_max <= 2047); pitch = floats per lattice row, 0 above the bound.
+struct CtcGeom {
+  int ns, nw;
+  int64_t pitch;
+};
+static inline CtcGeom ctc_geom(int64_t S_max) {
+  const int64_t ss = 2 * S_max + 1;
+  if (ss <= 64 * 4) return {4, 1, 64 * 4};
+  if (ss <= 64 * 8) return {8, 1, 64 * 8};
+  if (ss <= 64 * 16) return {16, 1, 64 * 16};
+  if (S_max <= LASR_CTC_MAX_LABELS) {
+    const int nw = (int)((ss + kCtcMwWaveStates - 1) / kCtcMwWaveStates);
+    return {0, nw, (int64_t)kCtcMwWaveStates * nw};
+  }
+  return {0, 0, 0};
+}
 
 // ctc.hip
 int launch_ctc_grad(const float* logp, const int64_t* targets, const int32_t* in_lens, const int32_t* tgt_lens, int64_t B, int64_t T,

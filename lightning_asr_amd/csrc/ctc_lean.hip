@@ -223,13 +223,180 @@ __global__ __launch_bounds__(256, 2) void ctc_grad_lean_kernel(const bf16_t* __r
     bias_partials[(size_t)blockIdx.x * C + c] = (smem[c] + smem[pitch + c]) + (smem[2 * pitch + c] + smem[3 * pitch + c]);
 }
 
-static inline int lean_ns(int64_t S_max) {
-  const int64_t ss = 2 * S_max + 1;
-  if (ss <= 64 * 4) return 4;
-  if (ss <= 64 * 8) return 8;
-  if (ss <= 64 * 16) return 16;
-  return 0;
+// The same for the multi-wave lattice (S_max > 511, rows of 1024 NW states).  4 rows x (cpad + 4 S_max) floats of LDS would not fit
+// at S_max = 2047 (C = 5207: 191 KB), so a wave's LDS holds its softmax row, the label-state occupancies and the chain links only
+// (cpad + 2 S_max floats: 149 KB for the four waves at that shape); the labels and the first-occurrence flags are read from global
+// memory where they are needed (once per label and row).  The lattice values are loaded per 1024-state chunk as the row is
+// processed; only the logits of the next row are prefetched.  Without a second workgroup per CU to hide behind (the LDS allows one),
+// launch bounds of one wave per SIMD give the accumulators the register file of the SIMD (no scratch).
+// floats of LDS per wave: softmax row (cpad), occupancies and chain links (S_max each), rounded up to whole 16-byte vectors so that
+// every wave's row stays 16-byte aligned for its float4 accesses
+static inline __host__ __device__ size_t lean_mw_pitch(int64_t C, int64_t S_max) {
+  return ((size_t)((C + 7) & ~(int64_t)7) + 2 * (size_t)S_max + 3) & ~(size_t)3;
 }
+template <int KV>
+__global__ __launch_bounds__(256) void ctc_grad_lean_mw_kernel(const bf16_t* __restrict__ logits, int64_t ldc, const float* __restrict__ lse,
+                                                               const float* __restrict__ E, int CE, const int64_t* __restrict__ targets,
+                                                               const int32_t* __restrict__ in_lens, const int32_t* __restrict__ tgt_lens,
+                                                               int64_t B, int64_t T, int64_t C, int64_t S_max, int blank, int NW,
+                                                               const float* __restrict__ alpha, const float* __restrict__ beta,
+                                                               const int32_t* __restrict__ next_same, const float* __restrict__ nll,
+                                                               const float* __restrict__ gscale, bf16_t* __restrict__ grad,
+                                                               float* __restrict__ bias_partials, int rows_per_wg) {
+  constexpr int NS = kCtcMwNS;
+  const int64_t SP = (int64_t)kCtcMwWaveStates * NW;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int cpad = (int)((C + 7) & ~(int64_t)7);
+  const size_t pitch = lean_mw_pitch(C, S_max);
+  float* s_row = smem + (size_t)wid * pitch;
+  float* s_v = s_row + cpad;                                          // [S_max] occupancy of the label states
+  int32_t* s_nx = reinterpret_cast<int32_t*>(s_v + S_max);            // [S_max] next position with the same label
+  const int nvec = (int)(ldc >> 3);
+  float acc[KV][8];
+#pragma unroll
+  for (int j = 0; j < KV; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
+  const int rpw = rows_per_wg >> 2;
+  const int64_t NT = B * T;
+  const int64_t r_begin = (int64_t)blockIdx.x * rows_per_wg + (int64_t)wid * rpw;
+  uint4 xr[KV];
+  float pl;
+  auto issue = [&](int64_t row_) {
+    const int64_t r = row_ < NT ? row_ : NT - 1;
+    const bf16_t* x = logits + r * ldc;
+#pragma unroll
+    for (int j = 0; j < KV; ++j) xr[j] = Vec<bf16_t>::raw(x + (size_t)min(lane + 64 * j, nvec - 1) * 8);
+    pl = lse[r];
+  };
+  int64_t cached_b = -1;
+  int Tb = 0, S = 0;
+  float gs = 0.f, nl = 0.f;
+  const int64_t* tg = targets;
+  const int32_t* nx = next_same;
+  if (r_begin < NT) issue(r_begin);
+  for (int k = 0; k < rpw; ++k) {
+    const int64_t row = r_begin + k;
+    if (row >= NT) break;                             // wave-uniform
+    const int64_t b = row / T, t = row - b * T;
+    if (b != cached_b) {                              // wave-uniform, once per utterance
+      cached_b = b;
+      Tb = in_lens[b]; S = tgt_lens[b];
+      gs = gscale ? gscale[b] : 1.0f / (float)B;
+      nl = nll[b];
+      tg = targets + b * S_max;
+      nx = next_same + b * S_max * 2;
+      for (int i = lane; i < (int)S_max; i += 64) s_nx[i] = nx[i];
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+    }
+    uint4 cx[KV];
+#pragma unroll
+    for (int j = 0; j < KV; ++j) cx[j] = xr[j];
+    const float l = pl;
+    issue(row + 1);
+    bf16_t* g = grad + row * ldc;
+    if (t >= Tb) {
+#pragma unroll
+      for (int j = 0; j < KV; ++j) {
+        const int v = lane + 64 * j;
+        if (v < nvec) *reinterpret_cast<uint4*>(g + (size_t)v * 8) = make_uint4(0u, 0u, 0u, 0u);
+      }
+      continue;
+    }
+    const int SS = 2 * S + 1;
+    const bool infeasible = isinf(nl);
+#pragma unroll
+    for (int j = 0; j < KV; ++j) {
+      const int v = lane + 64 * j;
+      if (v < nvec) {
+        float xv[8];
+        Vec<bf16_t>::unpack(cx[j], xv);
+        float4 lo, hi;
+        lo.x = __expf(xv[0] - l); lo.y = __expf(xv[1] - l); lo.z = __expf(xv[2] - l); lo.w = __expf(xv[3] - l);
+        hi.x = __expf(xv[4] - l); hi.y = __expf(xv[5] - l); hi.z = __expf(xv[6] - l); hi.w = __expf(xv[7] - l);
+        *reinterpret_cast<float4*>(s_row + (size_t)v * 8) = lo;
+        *reinterpret_cast<float4*>(s_row + (size_t)v * 8 + 4) = hi;
+      }
+    }
+    // occupancy of every lattice state, chunk by chunk (16-byte loads of the lane's 16 alpha and beta values)
+    float blank_occ = 0.f;
+    const float* al = alpha + row * SP;
+    const float* be = beta + row * SP;
+    const float* er = E + row * CE;
+    for (int c = 0; c < NW && c * kCtcMwWaveStates < SS; ++c) {   // wave-uniform
+      const int s0 = c * kCtcMwWaveStates + lane * NS;
+      float ca[NS], cb[NS], ce[NS];
+#pragma unroll
+      for (int i = 0; i < NS; i += 4) {
+        const float4 a4 = *reinterpret_cast<const float4*>(al + s0 + i);
+        const float4 b4 = *reinterpret_cast<const float4*>(be + s0 + i);
+        ca[i] = a4.x; ca[i + 1] = a4.y; ca[i + 2] = a4.z; ca[i + 3] = a4.w;
+        cb[i] = b4.x; cb[i + 1] = b4.y; cb[i + 2] = b4.z; cb[i + 3] = b4.w;
+      }
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const int st = s0 + i;
+        ce[i] = (st & 1) ? er[min(st >> 1, (int)S_max)] : er[S_max];
+      }
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const int st = s0 + i;
+        if (st < SS) {
+          const float v = expf(ca[i] + cb[i] + nl - ce[i]);
+          if (st & 1) s_v[st >> 1] = v;
+          else blank_occ += v;
+        }
+      }
+    }
+    blank_occ = wave_sum(blank_occ);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) s_row[blank] -= blank_occ;
+    for (int i = lane; i < S; i += 64) {
+      if (nx[S_max + i]) {   // first occurrence of its label: sum the chain in target order (deterministic)
+        float a = 0.f;
+        for (int j = i; j >= 0; j = s_nx[j]) a += s_v[j];
+        s_row[(int)min(max(tg[i], (int64_t)0), C - 1)] -= a;
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < KV; ++j) {
+      const int v = lane + 64 * j;
+      if (v < nvec) {
+        const float4 lo = *reinterpret_cast<const float4*>(s_row + (size_t)v * 8);
+        const float4 hi = *reinterpret_cast<const float4*>(s_row + (size_t)v * 8 + 4);
+        float o[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const bool real = v * 8 + e < C;
+          o[e] = real ? (infeasible ? __builtin_nanf("") : gs * o[e]) : 0.f;
+          acc[j][e] += o[e];
+        }
+        Vec<bf16_t>::store(g + (size_t)v * 8, o);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < KV; ++j) {
+    const int v = lane + 64 * j;
+    if (v < nvec) {
+      *reinterpret_cast<float4*>(s_row + (size_t)v * 8) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+      *reinterpret_cast<float4*>(s_row + (size_t)v * 8 + 4) = make_float4(acc[j][4], acc[j][5], acc[j][6], acc[j][7]);
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256)
+    bias_partials[(size_t)blockIdx.x * C + c] = (smem[c] + smem[pitch + c]) + (smem[2 * pitch + c] + smem[3 * pitch + c]);
+}
+
 static constexpr int kLeanRowsPerWg = 64;
 
 template <int NS, bool EM_LDS>
@@ -245,11 +412,25 @@ __global__ __launch_bounds__(128) void ctc_alpha_beta_compact_kernel(const float
                                              s_tg, s_lp);
 }
 
+__global__ __launch_bounds__(256) void ctc_alpha_beta_compact_mw_kernel(const float* __restrict__ E, const int64_t* __restrict__ targets,
+                                                                        const int32_t* __restrict__ in_lens,
+                                                                        const int32_t* __restrict__ tgt_lens, int64_t T, int64_t CE,
+                                                                        int64_t S_max, int blank_col, float* __restrict__ alpha,
+                                                                        float* __restrict__ beta, int32_t* __restrict__ next_same,
+                                                                        float* __restrict__ nll) {
+  __shared__ int32_t s_tg[kCtcMwMaxS];
+  __shared__ float s_ring[2 * (kCtcMwMaxWaves + 2) * 2];
+  __shared__ float s_fin[2];
+  ctc_alpha_beta_mw_body<false, true>(E, targets, in_lens, tgt_lens, T, CE, S_max, blank_col, alpha, beta, next_same, nll, s_tg, nullptr,
+                                    s_ring, s_fin);
+}
+
 }  // namespace lasr
 
 using namespace lasr;
 
 extern "C" size_t lasr_ctc_lean_workspace_bytes(int64_t B, int64_t T, int64_t C, int64_t S_max) {
+  if (S_max > LASR_CTC_MAX_LABELS) return 0;
   const int64_t sm = S_max > 0 ? S_max : 1;
   const int64_t CE = (sm + 1 + 3) & ~(int64_t)3;
   return align_up(lasr_ctc_workspace_bytes(B, T, S_max), 256) + align_up((size_t)B * T * sizeof(float), 256) +
@@ -277,8 +458,10 @@ int lasr::ctc_loss_lean_job(const void* logits, int64_t ldc, const float* row_st
   LASR_CHECK_SHAPE(B > 0 && T > 0 && C > 1 && S_max >= 0 && blank >= 0 && blank < C && ldc == ((C + 7) & ~(int64_t)7) && ldc <= 9216 &&
                        n_col_tiles >= 1 && n_col_tiles <= 64 && B * T * ldc < ((int64_t)1 << 31),
                    "lasr_ctc_loss_lean: shape (C=%lld ldc=%lld tiles=%d)", (long long)C, (long long)ldc, n_col_tiles);
-  const int ns = lean_ns(S_max);
-  LASR_CHECK_SHAPE(ns != 0, "lasr_ctc_loss_lean: S_max=%lld exceeds the 511-label lattice the kernels are built for", (long long)S_max);
+  const CtcGeom geo = ctc_geom(S_max);
+  const int ns = geo.ns;                 // 4 / 8 / 16 states per lane of one wave; 0: the multi-wave lattice
+  LASR_CHECK_SHAPE(geo.pitch != 0, "lasr_ctc_loss_lean: S_max=%lld exceeds the %d-label bound of the CTC lattice", (long long)S_max,
+                   LASR_CTC_MAX_LABELS);
   if (workspace_bytes < lasr_ctc_lean_workspace_bytes(B, T, C, S_max)) return fail(LASR_E_WORKSPACE, "lasr_ctc_loss_lean: workspace");
   const int64_t sm = S_max > 0 ? S_max : 1, N = B * T;
   const int CE = (int)((sm + 1 + 3) & ~(int64_t)3);
@@ -294,7 +477,7 @@ int lasr::ctc_loss_lean_job(const void* logits, int64_t ldc, const float* row_st
   hipLaunchKernelGGL(lse_gather_kernel, dim3((unsigned)cdiv(N, 4)), dim3(256), 0, st, reinterpret_cast<const bf16_t*>(logits), ldc, row_stat,
                      row_arg, n_col_tiles, targets, tgt_lens, N, T, sm, CE, blank, lse, argmax, E);
   LASR_LAUNCH_CHECK("lse_gather_kernel");
-  const size_t ab = (size_t)B * T * 64 * ns;
+  const size_t ab = (size_t)B * T * geo.pitch;
   float* alpha = reinterpret_cast<float*>(lattice_ws);
   float* beta = alpha + ab;
   int32_t* next_same = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(lattice_ws) + align_up(2 * ab * sizeof(float), 256));
@@ -314,7 +497,13 @@ int lasr::ctc_loss_lean_job(const void* logits, int64_t ldc, const float* row_st
     }                                                                                                                          \
   } while (0)
   bool job_done = false;
-  if (job && em_lds && compact_lattice_mel_fits(T, CE)) {
+  if (!ns) {
+    // long labels: 2B workgroups of geo.nw waves on the register ring of emissions (CE > 512 columns: the rows of any feasible
+    // T' >= S_max do not fit LDS), no fused feature grid (the features follow the gradient kernel)
+    hipLaunchKernelGGL(ctc_alpha_beta_compact_mw_kernel, dim3((unsigned)(2 * B)), dim3((unsigned)(64 * geo.nw)), 0, st, E, targets, in_lens, tgt_lens,
+                       T, (int64_t)CE, sm, (int)sm, alpha, beta, next_same, nll);
+    LASR_LAUNCH_CHECK("ctc_alpha_beta_compact_mw_kernel");
+  } else if (job && em_lds && compact_lattice_mel_fits(T, CE)) {
     LASR_TRY(launch_compact_lattice_mel(E, targets, in_lens, tgt_lens, B, T, CE, sm, (int)sm, alpha, beta, next_same, nll, ns, *job, stream));
     job_done = true;
   } else {
@@ -323,10 +512,27 @@ int lasr::ctc_loss_lean_job(const void* logits, int64_t ldc, const float* row_st
   }
 #undef LASR_CTC_AB
   const int cpad = (int)((C + 7) & ~(int64_t)7);
-  const size_t shmem = 4 * ((size_t)cpad + 4 * (size_t)sm) * sizeof(float);
+  const size_t shmem = 4 * (ns ? (size_t)cpad + 4 * (size_t)sm : lean_mw_pitch(C, sm)) * sizeof(float);
   LASR_CHECK_SHAPE(shmem <= 160 * 1024 && ldc / 8 <= 64 * 18, "lasr_ctc_loss_lean: C=%lld too large for the LDS row buffers", (long long)C);
   const int nwg = (int)cdiv(N, kLeanRowsPerWg);
   const bool kv9 = ldc / 8 <= 64 * 9;
+  if (!ns) {
+#define LASR_CTC_GMW(KV_)                                                                                                      \
+  do {                                                                                                                         \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_grad_lean_mw_kernel<KV_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+    hipLaunchKernelGGL((ctc_grad_lean_mw_kernel<KV_>), dim3((unsigned)nwg), dim3(256), shmem, st, reinterpret_cast<const bf16_t*>(logits), ldc, lse, \
+                       E, CE, targets, in_lens, tgt_lens, B, T, C, sm, blank, geo.nw, alpha, beta, next_same, nll, gscale,        \
+                       reinterpret_cast<bf16_t*>(grad), bias_partials, kLeanRowsPerWg);                                       \
+  } while (0)
+    if (kv9) LASR_CTC_GMW(9); else LASR_CTC_GMW(18);
+#undef LASR_CTC_GMW
+    LASR_LAUNCH_CHECK("ctc_grad_lean_mw_kernel");
+    LASR_TRY(launch_reduce_partials(bias_partials, nwg, C, bias_grad, C, nullptr, st));
+    if (job)
+      return mel_fwd_src(job->src, job->sample_lens, job->aug, job->B, job->L, job->normalize, nullptr, job->out_btf, job->dtype, job->frames_out,
+                         job->pct_out, job->ws, job->ws_bytes, stream);
+    return 0;
+  }
 #define LASR_CTC_G2(NS_, KV_)                                                                                                  \
   do {                                                                                                                         \
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_grad_lean_kernel<NS_, KV_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \

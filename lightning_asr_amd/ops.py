@@ -387,11 +387,17 @@ def log_softmax(logits: torch.Tensor, want_argmax: bool = True):
     return out, am
 
 
+CTC_MAX_LABELS = 2047   # LASR_CTC_MAX_LABELS (include/lasr.h): the longest label sequence the CTC kernels take
+
+
 def ctc_loss(logp: torch.Tensor, targets: torch.Tensor, in_lens: torch.Tensor, tgt_lens: torch.Tensor, blank: int,
              want_grad: bool = True, gscale: Optional[torch.Tensor] = None):
-    """logp (B,T,C) f32 -> (nll (B), grad (B,T,C) | None); grad is torch's CTCLoss backward for grad_output=gscale."""
+    """logp (B,T,C) f32 -> (nll (B), grad (B,T,C) | None); grad is torch's CTCLoss backward for grad_output=gscale.
+    targets (B, S) with S <= CTC_MAX_LABELS."""
     B, T, Cc = logp.shape
     S = targets.shape[1] if targets.dim() == 2 else 0
+    if S > CTC_MAX_LABELS:
+        raise ValueError("ctc_loss: targets are %d labels wide; the CTC kernels take at most %d" % (S, CTC_MAX_LABELS))
     nll = torch.empty(B, dtype=torch.float32, device=logp.device)
     grad = torch.empty_like(logp) if want_grad else None
     nb = _lib.load().lasr_ctc_workspace_bytes(B, T, max(S, 1))
