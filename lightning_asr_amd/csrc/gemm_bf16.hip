@@ -1,11 +1,14 @@
-// bf16 MFMA GEMM (v_mfma_f32_32x32x16_bf16, f32 accumulate) for the 1x1 convolutions and their
+// bf16 MFMA GEMM (v_mfma_f32_16x16x32_bf16, f32 accumulate) for the 1x1 convolutions and their
 // gradients in the bf16 activation mode.  Same contract as gemm.hip:
 //   C[M][N] = sum_k opA(A)[m][k] * opB(B)[n][k] (+bias) with row masking and BN column sums.
 //
-// 128x128x64 block tile, 4 waves as 2x2, each wave 2x2 MFMA tiles of 32x32 (64 accumulator VGPRs).
+// 128x128x64 block tile, 4 waves as 2x2, each wave 4x4 MFMA tiles of 16x16 (64 accumulator VGPRs).
+// Every tile runs on the 16x16x32 shape rather than 32x32x16: the same cycles per FLOP, but the chip holds
+// a higher clock under the 16x16x32 loop on random data.
 // Operand staging in LDS depends on which index is contiguous in HBM:
 //   K-contiguous  (activations [rows][K], weights [N][K]):  image [128 rows][64 k], 144-byte rows
-//                  (9 sixteen-byte slots: odd, so a half-wave's ds_read_b128 is conflict-free);
+//                  (9 sixteen-byte slots), k-chunks 2j and 2j+1 trading places on rows 4..11 of every 16
+//                  (kc_slot), so the 16x16x32 fragment reads (ds_read_b128) are conflict-free;
 //   row-contiguous ([K][rows]: the gradients' transposed operands): image [64 k][128 rows],
 //                  320-byte rows, fragments fetched with ds_read_b64_tr_b16 (hardware 4x16
 //                  transpose), so no operand is ever transposed through HBM or VALU.
@@ -18,23 +21,21 @@
 
 namespace lasr {
 
-// The lane's bias values for its 2 x 4 accumulator quads (columns nbase + ni*32 + 8*j + e), fetched in ONE batch and masked with bit
+// The lane's bias values for its 4 accumulator quads (columns nbase + ni*16 + e), fetched in ONE batch and masked with bit
 // operations.  Written as `col < N ? bias[col] : 0.f` inside the epilogue loops, every value became a branch around its load with a
 // wait behind it: 32 memory round trips one after the other per tile (and per mi), read off the ISA in round 4.
-__device__ __forceinline__ void load_bias_quads(const float* __restrict__ bias, int nbase, int N, float (&bv)[2][4][4]) {
+__device__ __forceinline__ void load_bias_quads(const float* __restrict__ bias, int nbase, int N, float (&bv)[4][4]) {
 #pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
+  for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int n = nbase + ni * 32 + 8 * j + e;
-        bv[ni][j][e] = __uint_as_float(__float_as_uint(bias[min(n, N - 1)]) & (n < N ? 0xffffffffu : 0u));
-      }
+    for (int e = 0; e < 4; ++e) {
+      const int n = nbase + ni * 16 + e;
+      bv[ni][e] = __uint_as_float(__float_as_uint(bias[min(n, N - 1)]) & (n < N ? 0xffffffffu : 0u));
+    }
 }
 
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -76,6 +77,11 @@ struct Bf16Batch { Bf16Args p[2]; int tiles0, total; };
 // when they are written to LDS (chunks past the M/N edge repeat the last row: those outputs are never
 // stored).  Per-lane bounds branches around the loads (the generic path, kept for unaligned shapes)
 // make the compiler drain vmcnt at every join.
+// slot of 16-byte k-chunk ch (0..7) in row `row` of a K-contiguous image: rows 4..11 of every 16 swap the chunks of each pair.
+// Plain rows leave a 16x16x32 fragment read (rows rb..rb+15, one chunk per 16 lanes) 2-way bank-conflicted at the 144-byte
+// pitch (SQ_LDS_BANK_CONFLICT = half of SQ_LDS_IDX_ACTIVE); swapped, all 16 lanes of each ds_read_b128 group hit distinct banks.
+__device__ __forceinline__ int kc_slot(int row, int ch) { return ch ^ (((row >> 2) ^ (row >> 3)) & 1); }
+
 // 16-byte chunk of 8 bf16 of which the first `nvalid` (any integer; <= 0 none, >= 8 all) are inside the K range
 __device__ __forceinline__ uint4 mask_chunk(const uint4& v, int nvalid) {
   const int n = max(0, min(nvalid, 8));
@@ -106,7 +112,7 @@ __device__ __forceinline__ void store_vec(char* __restrict__ s, const uint4 (&re
 #pragma unroll
   for (int p = 0; p < NCH; ++p) {
     const int c = tid + NT * p;
-    const int off = !TRANS ? (c >> 3) * LDK_ + ((c & 7) << 4) : (c / RCH) * LDR_ + ((c % RCH) << 4);
+    const int off = !TRANS ? (c >> 3) * LDK_ + (kc_slot(c >> 3, c & 7) << 4) : (c / RCH) * LDR_ + ((c % RCH) << 4);
     if constexpr (FULL) {
       *reinterpret_cast<uint4*>(s + off) = reg[p];
     } else {
@@ -135,7 +141,7 @@ template <bool TRANS, int ROWS, int NT, int LDK_, int LDR_, bool FULL = false>
 __device__ __forceinline__ void store_chunk(char* __restrict__ s, const uint4& v, int k0, int kend, int p) {
   constexpr int RCH = ROWS / 8;
   const int c = threadIdx.x + NT * p;
-  const int off = !TRANS ? (c >> 3) * LDK_ + ((c & 7) << 4) : (c / RCH) * LDR_ + ((c % RCH) << 4);
+  const int off = !TRANS ? (c >> 3) * LDK_ + (kc_slot(c >> 3, c & 7) << 4) : (c / RCH) * LDR_ + ((c % RCH) << 4);
   if constexpr (FULL) {
     *reinterpret_cast<uint4*>(s + off) = v;
   } else {
@@ -177,23 +183,23 @@ __device__ __forceinline__ void store_oper(char* __restrict__ s, const uint4 (&r
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     const int c = tid + 256 * p;
-    const int off = !TRANS ? (c >> 3) * LD_KC + ((c & 7) << 4) : (c >> 4) * LD_RC + ((c & 15) << 4);
+    const int off = !TRANS ? (c >> 3) * LD_KC + (kc_slot(c >> 3, c & 7) << 4) : (c >> 4) * LD_RC + ((c & 15) << 4);
     *reinterpret_cast<uint4*>(s + off) = reg[p];
   }
 }
 
-// ---- LDS -> MFMA fragment: 8 consecutive k of row (rb + lane&31), k = ks*16 + 8*(lane>>5) + j ----
+// ---- LDS -> 16x16x32 MFMA fragment: 8 consecutive k of row (rb + lane&15), k = ks*32 + 8*(lane>>4) + j ----
 template <bool TRANS, int LD_RC_ = LD_RC>
 __device__ __forceinline__ bf16x8 load_frag(const char* __restrict__ s, int rb, int ks, int lane) {
   Frag f;
   if (!TRANS) {
-    f.u = *reinterpret_cast<const uint4*>(s + (rb + (lane & 31)) * LD_KC + ks * 32 + (lane >> 5) * 16);
+    f.u = *reinterpret_cast<const uint4*>(s + (rb + (lane & 15)) * LD_KC + ks * 64 + kc_slot(lane & 15, lane >> 4) * 16);   // rb % 16 == 0
   } else {
-    // 16-lane group g: rows rb + 16*(g&1) .. +15, k-half (g>>1).  Lane 4q+p of the group addresses
-    // k-row q, columns 4p..4p+3 of the 4x16 block; it receives column (lane&15), rows 0..3.
+    // 16-lane group g: rows rb .. rb+15, k = ks*32 + 8g .. +7.  Lane 4q+p of the group addresses
+    // k-row q (then q+4), columns 4p..4p+3 of the 4x16 block; it receives column (lane&15), rows 0..3.
     const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const int kbase = ks * 16 + 8 * (g >> 1) + q;
-    const int col = rb + 16 * (g & 1) + 4 * p;
+    const int kbase = ks * 32 + 8 * g + q;
+    const int col = rb + 4 * p;
     typedef __attribute__((address_space(3))) s16x4 lds_s4;
     const char* a0 = s + kbase * LD_RC_ + col * 2;
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(a0));
@@ -255,13 +261,13 @@ __device__ __forceinline__ void gemm_bf16_tile(const Bf16Args& g, const int lid)
     s_keep[tid] = keep ? 1.f : 0.f;
   }
 
-  f32x16 acc[2][2];
+  f32x4 acc[4][4];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
 
   // Two register sets: the global loads of K-tile i+2 are issued while tile i is multiplied, so a
   // load has two full iterations to land (one CU holds 2 workgroups x 64 KB in flight).  With K of
@@ -296,15 +302,15 @@ __device__ __forceinline__ void gemm_bf16_tile(const Bf16Args& g, const int lid)
     LASR_STORE(RA_, RB_, KCUR_)                                                          \
     __syncthreads();                                                                     \
     if ((KNEXT_) < kend) { LASR_LOAD(RA_, RB_, KNEXT_) }                                  \
-    _Pragma("unroll") for (int ks = 0; ks < TK / 16; ++ks) {                             \
-      const bf16x8 a0 = load_frag<TRANS_A>(sA, wm * 64, ks, lane);                       \
-      const bf16x8 a1 = load_frag<TRANS_A>(sA, wm * 64 + 32, ks, lane);                  \
-      const bf16x8 b0 = load_frag<TRANS_B>(sB, wn * 64, ks, lane);                       \
-      const bf16x8 b1 = load_frag<TRANS_B>(sB, wn * 64 + 32, ks, lane);                  \
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a0, acc[0][0], 0, 0, 0);   \
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a0, acc[0][1], 0, 0, 0);   \
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, a1, acc[1][0], 0, 0, 0);   \
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, acc[1][1], 0, 0, 0);   \
+    _Pragma("unroll") for (int ks = 0; ks < TK / 32; ++ks) {                             \
+      bf16x8 a[4], b[4];                                                                 \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                    \
+        a[i] = load_frag<TRANS_A>(sA, wm * 64 + i * 16, ks, lane);                       \
+        b[i] = load_frag<TRANS_B>(sB, wn * 64 + i * 16, ks, lane);                       \
+      }                                                                                  \
+      _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                                   \
+        _Pragma("unroll") for (int ni = 0; ni < 4; ++ni)                                 \
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ni], a[mi], acc[mi][ni], 0, 0, 0); \
     }                                                                                    \
   }
   for (int k0 = kbeg; k0 < kend; k0 += 2 * TK) {
@@ -315,11 +321,11 @@ __device__ __forceinline__ void gemm_bf16_tile(const Bf16Args& g, const int lid)
 #undef LASR_STORE
 #undef LASR_K_STEP
 
-  const int half = lane >> 5, l31 = lane & 31;
+  const int g4 = lane >> 4, l15 = lane & 15;
   // The MFMA operands are swapped (D = B_tile * A_tile^T), so the tile sits TRANSPOSED in the accumulators:
-  // acc[mi][ni][r]: row = wm*64 + mi*32 + l31, col = wn*64 + ni*32 + 8*(r>>2) + 4*half + (r&3) - a lane owns one output
-  // row per MFMA tile and 4 consecutive columns per register quad: 16-byte f32 stores, or packed bf16 pairs and 8-byte
-  // LDS writes (the natural order left one 4-byte store / one 2-byte LDS write per element).
+  // acc[mi][ni][e]: row = wm*64 + mi*16 + l15, col = wn*64 + ni*16 + 4*g4 + e - a lane owns one output row per MFMA
+  // tile and 4 consecutive columns in its register quad: 16-byte f32 stores, or packed bf16 pairs and 8-byte LDS
+  // writes (the natural order left one 4-byte store / one 2-byte LDS write per element).
   if constexpr (Elem<TC>::kDtype == LASR_F32) {
     // f32 destinations (split-K slabs, logits, weight gradients): straight from the accumulators
     float* W = g.split_ws ? g.split_ws + (size_t)tz * (size_t)g.M * (size_t)g.N : reinterpret_cast<float*>(g.C);
@@ -327,33 +333,30 @@ __device__ __forceinline__ void gemm_bf16_tile(const Bf16Args& g, const int lid)
     const bool vec4 = (ldw & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0;
     const bool plain = g.split_ws != nullptr;                 // slabs: no bias, no mask
     const bool has_bias = !plain && g.bias != nullptr;      // workgroup-uniform
-    float bv[2][4][4];
-    if (has_bias) load_bias_quads(g.bias, n0 + wn * 64 + 4 * half, g.N, bv);
+    float bv[4][4];
+    if (has_bias) load_bias_quads(g.bias, n0 + wn * 64 + 4 * g4, g.N, bv);
 #pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-      const int lr = wm * 64 + mi * 32 + l31;
+    for (int mi = 0; mi < 4; ++mi) {
+      const int lr = wm * 64 + mi * 16 + l15;
       const int m = m0 + lr;
       const float kf = plain ? 1.f : s_keep[lr];
       if (m < g.M) {
         float* wrow = W + (uint32_t)m * (uint32_t)ldw;
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
+        for (int ni = 0; ni < 4; ++ni) {
+          const int n = n0 + wn * 64 + ni * 16 + 4 * g4;
+          float v[4];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 64 + ni * 32 + 8 * j + 4 * half;
-            float v[4];
+          for (int e = 0; e < 4; ++e) {
+            v[e] = acc[mi][ni][e];
+            if (!plain) v[e] = (v[e] + (has_bias ? bv[ni][e] : 0.f)) * kf;
+          }
+          if (vec4 && n + 3 < g.N) {
+            *reinterpret_cast<float4*>(wrow + n) = make_float4(v[0], v[1], v[2], v[3]);
+          } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              v[e] = acc[mi][ni][4 * j + e];
-              if (!plain) v[e] = (v[e] + (has_bias ? bv[ni][j][e] : 0.f)) * kf;
-            }
-            if (vec4 && n + 3 < g.N) {
-              *reinterpret_cast<float4*>(wrow + n) = make_float4(v[0], v[1], v[2], v[3]);
-            } else {
-#pragma unroll
-              for (int e = 0; e < 4; ++e)
-                if (n + e < g.N) wrow[n + e] = v[e];
-            }
+            for (int e = 0; e < 4; ++e)
+              if (n + e < g.N) wrow[n + e] = v[e];
           }
         }
       }
@@ -363,48 +366,43 @@ __device__ __forceinline__ void gemm_bf16_tile(const Bf16Args& g, const int lid)
     //      column sums (statistics of the values as stored) and the stores (8 rows x 128 B per instruction)
     // addend (the accumulating data-gradient GEMMs of the context branch): 4 consecutive bf16 per register quad, all 16 loads
     // of the lane issued before the barrier
-    uint2 adv[2][2][4];
+    uint2 adv[4][4];
     const bool has_add = g.addend != nullptr;                 // workgroup-uniform
     if (has_add) {
 #pragma unroll
-      for (int mi = 0; mi < 2; ++mi) {
-        const uint32_t mrow = (uint32_t)min(m0 + wm * 64 + mi * 32 + l31, g.M - 1) * (uint32_t)g.ldc;
+      for (int mi = 0; mi < 4; ++mi) {
+        const uint32_t mrow = (uint32_t)min(m0 + wm * 64 + mi * 16 + l15, g.M - 1) * (uint32_t)g.ldc;
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            adv[mi][ni][j] = *reinterpret_cast<const uint2*>(g.addend + mrow + (uint32_t)min(n0 + wn * 64 + ni * 32 + 8 * j + 4 * half, g.N - 4));
+        for (int ni = 0; ni < 4; ++ni)
+          adv[mi][ni] = *reinterpret_cast<const uint2*>(g.addend + mrow + (uint32_t)min(n0 + wn * 64 + ni * 16 + 4 * g4, g.N - 4));
       }
     }
     __syncthreads();  // every wave is done reading the operand images
     char* epi = smem + wid * (64 * EPI_LD);
     const bool has_bias = g.bias != nullptr;
-    float bv[2][4][4];
-    if (has_bias) load_bias_quads(g.bias, n0 + wn * 64 + 4 * half, g.N, bv);
+    float bv[4][4];
+    if (has_bias) load_bias_quads(g.bias, n0 + wn * 64 + 4 * g4, g.N, bv);
 #pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-      const uint32_t km = s_keep[wm * 64 + mi * 32 + l31] != 0.f ? 0xffffffffu : 0u;
+    for (int mi = 0; mi < 4; ++mi) {
+      const uint32_t km = s_keep[wm * 64 + mi * 16 + l15] != 0.f ? 0xffffffffu : 0u;
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
+      for (int ni = 0; ni < 4; ++ni) {
+        float v[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float v[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = acc[mi][ni][4 * j + e];
-          if (has_add) {
-            const uint2 a = adv[mi][ni][j];
-            v[0] += __uint_as_float(a.x << 16); v[1] += __uint_as_float(a.x & 0xffff0000u);
-            v[2] += __uint_as_float(a.y << 16); v[3] += __uint_as_float(a.y & 0xffff0000u);
-          }
-          if (has_bias) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += bv[ni][j][e];
-          }
-          uint2 pk;
-          pk.x = pack_bf16x2(v[0], v[1]) & km;
-          pk.y = pack_bf16x2(v[2], v[3]) & km;
-          *reinterpret_cast<uint2*>(epi + (mi * 32 + l31) * EPI_LD + (ni * 32 + 8 * j + 4 * half) * 2) = pk;
+        for (int e = 0; e < 4; ++e) v[e] = acc[mi][ni][e];
+        if (has_add) {
+          const uint2 a = adv[mi][ni];
+          v[0] += __uint_as_float(a.x << 16); v[1] += __uint_as_float(a.x & 0xffff0000u);
+          v[2] += __uint_as_float(a.y << 16); v[3] += __uint_as_float(a.y & 0xffff0000u);
         }
+        if (has_bias) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] += bv[ni][e];
+        }
+        uint2 pk;
+        pk.x = pack_bf16x2(v[0], v[1]) & km;
+        pk.y = pack_bf16x2(v[2], v[3]) & km;
+        *reinterpret_cast<uint2*>(epi + (mi * 16 + l15) * EPI_LD + (ni * 16 + 4 * g4) * 2) = pk;
       }
     }
     __syncthreads();
@@ -496,7 +494,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_multi_kernel(Bf16Multi gm) {
 }
 
 // =====================================================================================================
-// 256x256x64 tile, 512 threads (8 waves as 2 x 4, each 128 x 64 = 4 x 2 MFMA tiles, 128 accumulator
+// 256x256x64 tile, 512 threads (8 waves as 2 x 4, each 128 x 64 = 8 x 4 MFMA tiles of 16x16, 128 accumulator
 // VGPRs), ONE workgroup per CU, operand images double-buffered in LDS (2 x 72 KB) with one barrier per
 // K step.  Against the 128x128 tile it halves the operand bytes pulled from L2 and written to LDS per
 // FLOP and reads 0.75 instead of 1 fragment per MFMA; a unit's main + residual problem (63 x 2 tiles
@@ -505,14 +503,14 @@ namespace big {
 static constexpr int BTM = 256, NT = 512;
 static constexpr int LDR = 576;               // [k][256 rows] image: 512 B + 64 B pad (bank residue 16 dwords, as LD_RC)
 static constexpr int OPER = 36864;            // A image: 256*144 == 64*576
-// Two tile widths.  WIDE: 256x256, 8 waves as 2 x 4, wave tile 128x64 (4 x 2 MFMA tiles).  NARROW: 256x128, 8 waves as
-// 4 x 2, wave tile 64x64 (2 x 2): for problems with N <= 256 (the 256-channel blocks), where 256-wide tiles would leave
+// Two tile widths.  WIDE: 256x256, 8 waves as 2 x 4, wave tile 128x64 (8 x 4 MFMA tiles).  NARROW: 256x128, 8 waves as
+// 4 x 2, wave tile 64x64 (4 x 4): for problems with N <= 256 (the 256-channel blocks), where 256-wide tiles would leave
 // half of the CUs without a workgroup (63 x 1 tiles per problem).
 template <bool NARROW>
 struct Cfg {
   static constexpr int BN = NARROW ? 128 : 256;
   static constexpr int WN = NARROW ? 2 : 4;             // waves along N (8 / WN along M)
-  static constexpr int MI = NARROW ? 2 : 4;             // 32-row MFMA tiles per wave
+  static constexpr int MI = NARROW ? 4 : 8;             // 16-row MFMA tiles per wave (4 16-column tiles)
   static constexpr int NCB = BN * 8 / NT;               // 16-byte B chunks per thread and K step: 2 / 4
   static constexpr int LDRB = BN * 2 + 64;              // pitch of a row-contiguous B image: 320 / 576
   static constexpr int OPER_B = (BN * LD_KC > 64 * LDRB) ? BN * LD_KC : 64 * LDRB;   // 20480 / 36864
@@ -521,10 +519,12 @@ struct Cfg {
 };
 }  // namespace big
 
-// One K step of the 256x256 tile: 4 groups of (6 fragment reads, 8 MFMAs); after group ks the thread moves
-// its chunk ks of the NEXT step from registers into the other LDS image and (re)issues the global load of
-// the step after that into the same registers, so LDS writes and VMEM issue ride in the MFMA shadows
-// instead of forming a separate all-waves staging phase in front of them.
+// One K step of the 256x256 tile: two 32-deep substeps, each MI/2 groups of (2 A fragments, 8 MFMAs) over the substep's 4 B
+// fragments (16 in all, 8 on the narrow tile).  The fragments of group gi+1 (and, ahead of a substep's first group, its 4 B
+// fragments) are requested before the MFMAs of group gi, so at most 2 x (2 + 4) fragments are live, as with the 32x32x16 form's
+// (6 reads, 8 MFMAs) groups.  After every (MI/4)-th group the thread moves its next chunk of the NEXT step from registers into
+// the other LDS image and (re)issues the global load of the step after that into the same registers, so LDS writes and VMEM
+// issue ride in the MFMA shadows instead of forming a separate all-waves staging phase in front of them.
 // A operand of the folded eval form: K range [0, K1) from A (rows past their utterance's length read as zero: km),
 // [K1, K) from A2; K1 and K - K1 are multiples of the K step, so a step lies in one operand
 __device__ __forceinline__ uint4 load_chunk_dual(const Bf16Args& g, int m0, int k0, int p, const uint32_t (&kma)[4]) {
@@ -546,46 +546,54 @@ __device__ __forceinline__ uint4 dual_row_mask(const Bf16Args& g, uint4 v, int k
 // FULLST: the step being staged (k_store) is not the slice's last one (store_chunk<FULL>)
 template <bool TRANS_A, bool TRANS_B, bool NARROW, bool STORE, bool LOAD, bool DUAL = false, bool NTL = false, bool FULLST = false>
 __device__ __forceinline__ void big_step(const char* __restrict__ sA, const char* __restrict__ sB, char* __restrict__ dA,
-                                         char* __restrict__ dB, f32x16 (&acc)[big::Cfg<NARROW>::MI][2], uint4 (&ra)[4],
+                                         char* __restrict__ dB, f32x4 (&acc)[big::Cfg<NARROW>::MI][4], uint4 (&ra)[4],
                                          uint4 (&rb)[big::Cfg<NARROW>::NCB], const Bf16Args& g, int m0, int n0, int k_store,
                                          int k_load, int kend, int wm, int wn, int lane, const uint32_t (&kma)[4]) {
   using namespace big;
   using CF = Cfg<NARROW>;
   constexpr int MI = CF::MI;
-  // fragments of group ks+1 are requested before the MFMAs of group ks are issued (two register sets), so a
+  // fragments of group gi+1 are requested before the MFMAs of group gi are issued (two register sets), so a
   // wave's MFMA stream does not stop for its own LDS latency; only the first group after the barrier waits
-  bf16x8 a[2][MI], b[2][2];
+  constexpr int NG = MI;                                  // groups per K step: 2 substeps x MI/2 row pairs
+  constexpr int GPC = NG / 4;                             // groups per staged chunk
+  bf16x8 a[2][2], b[2][4];
 #pragma unroll
-  for (int ni = 0; ni < 2; ++ni) b[0][ni] = load_frag<TRANS_B, CF::LDRB>(sB, wn * 64 + ni * 32, 0, lane);
+  for (int ni = 0; ni < 4; ++ni) b[0][ni] = load_frag<TRANS_B, CF::LDRB>(sB, wn * 64 + ni * 16, 0, lane);
 #pragma unroll
-  for (int mi = 0; mi < MI; ++mi) a[0][mi] = load_frag<TRANS_A, LDR>(sA, wm * (32 * MI) + mi * 32, 0, lane);
+  for (int h = 0; h < 2; ++h) a[0][h] = load_frag<TRANS_A, LDR>(sA, wm * (16 * MI) + h * 16, 0, lane);
 #pragma unroll
-  for (int ks = 0; ks < TK / 16; ++ks) {
-    const int cur = ks & 1, nxt = cur ^ 1;
-    if (ks + 1 < TK / 16) {
+  for (int gi = 0; gi < NG; ++gi) {
+    const int ks = gi / (MI / 2), mp = gi % (MI / 2);
+    if (gi + 1 < NG) {
+      const int ks1 = (gi + 1) / (MI / 2), mp1 = (gi + 1) % (MI / 2);
+      if (mp1 == 0) {
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni) b[nxt][ni] = load_frag<TRANS_B, CF::LDRB>(sB, wn * 64 + ni * 32, ks + 1, lane);
+        for (int ni = 0; ni < 4; ++ni) b[ks1 & 1][ni] = load_frag<TRANS_B, CF::LDRB>(sB, wn * 64 + ni * 16, ks1, lane);
+      }
 #pragma unroll
-      for (int mi = 0; mi < MI; ++mi) a[nxt][mi] = load_frag<TRANS_A, LDR>(sA, wm * (32 * MI) + mi * 32, ks + 1, lane);
+      for (int h = 0; h < 2; ++h) a[(gi + 1) & 1][h] = load_frag<TRANS_A, LDR>(sA, wm * (16 * MI) + (2 * mp1 + h) * 16, ks1, lane);
     }
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
+    for (int h = 0; h < 2; ++h)
 #pragma unroll
-      // operands swapped: D = B_tile * A_tile^T, i.e. the tile TRANSPOSED in the accumulators - lane (l31, half) holds output
-      // row l31 and, per register quad, 4 CONSECUTIVE output columns 8*(r>>2) + 4*half + (r&3): the epilogue packs them into
-      // 8-byte row-major LDS writes (the natural order left 2-byte writes: 128 ds_write_b16 per lane, 9 us per launch)
-      for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[cur][ni], a[cur][mi], acc[mi][ni], 0, 0, 0);
+      // operands swapped: D = B_tile * A_tile^T, i.e. the tile TRANSPOSED in the accumulators - lane (l15, g4) holds output
+      // row l15 and 4 CONSECUTIVE output columns 4*g4 + e of each 16x16 tile: the epilogue packs them into 8-byte row-major
+      // LDS writes (the natural order left 2-byte writes: 128 ds_write_b16 per lane, 9 us per launch)
+      for (int ni = 0; ni < 4; ++ni)
+        acc[2 * mp + h][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[ks & 1][ni], a[gi & 1][h], acc[2 * mp + h][ni], 0, 0, 0);
+    if (gi % GPC != GPC - 1) continue;
+    const int c = gi / GPC;                               // staging chunk 0..3
     if constexpr (STORE) {
-      if constexpr (DUAL) store_chunk<TRANS_A, BTM, NT, LD_KC, LDR, FULLST>(dA, dual_row_mask(g, ra[ks], k_store, ks, kma), k_store, kend, ks);
-      else store_chunk<TRANS_A, BTM, NT, LD_KC, LDR, FULLST>(dA, ra[ks], k_store, kend, ks);
-      if constexpr (CF::NCB == 4) store_chunk<TRANS_B, CF::BN, NT, LD_KC, CF::LDRB, FULLST>(dB, rb[ks], k_store, kend, ks);
-      else if (ks < CF::NCB) store_chunk<TRANS_B, CF::BN, NT, LD_KC, CF::LDRB, FULLST>(dB, rb[ks < CF::NCB ? ks : 0], k_store, kend, ks);
+      if constexpr (DUAL) store_chunk<TRANS_A, BTM, NT, LD_KC, LDR, FULLST>(dA, dual_row_mask(g, ra[c], k_store, c, kma), k_store, kend, c);
+      else store_chunk<TRANS_A, BTM, NT, LD_KC, LDR, FULLST>(dA, ra[c], k_store, kend, c);
+      if constexpr (CF::NCB == 4) store_chunk<TRANS_B, CF::BN, NT, LD_KC, CF::LDRB, FULLST>(dB, rb[c], k_store, kend, c);
+      else if (c < CF::NCB) store_chunk<TRANS_B, CF::BN, NT, LD_KC, CF::LDRB, FULLST>(dB, rb[c < CF::NCB ? c : 0], k_store, kend, c);
     }
     if constexpr (LOAD) {
-      if constexpr (DUAL) ra[ks] = load_chunk_dual(g, m0, k_load, ks, kma);
-      else ra[ks] = load_chunk<TRANS_A, BTM, NT, NTL>(g.A, g.lda, g.M, m0, k_load, kend, ks);
-      if constexpr (CF::NCB == 4) rb[ks] = load_chunk<TRANS_B, CF::BN, NT, NTL>(g.B, g.ldb, g.N, n0, k_load, kend, ks);
-      else if (ks < CF::NCB) rb[ks < CF::NCB ? ks : 0] = load_chunk<TRANS_B, CF::BN, NT, NTL>(g.B, g.ldb, g.N, n0, k_load, kend, ks);
+      if constexpr (DUAL) ra[c] = load_chunk_dual(g, m0, k_load, c, kma);
+      else ra[c] = load_chunk<TRANS_A, BTM, NT, NTL>(g.A, g.lda, g.M, m0, k_load, kend, c);
+      if constexpr (CF::NCB == 4) rb[c] = load_chunk<TRANS_B, CF::BN, NT, NTL>(g.B, g.ldb, g.N, n0, k_load, kend, c);
+      else if (c < CF::NCB) rb[c < CF::NCB ? c : 0] = load_chunk<TRANS_B, CF::BN, NT, NTL>(g.B, g.ldb, g.N, n0, k_load, kend, c);
     }
   }
 }
@@ -613,7 +621,9 @@ __device__ __forceinline__ void gemm_bf16_big_tile(const Bf16Args& g, const int 
   constexpr int BTN = CF::BN, BUF = CF::BUF, MI = CF::MI;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
   __shared__ float s_keep[BTM];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  // the wave index lives in an SGPR and the lane index is rematerialised (v_mbcnt): with the 16x16x32 accumulators the row-major-A
+  // wide kernels otherwise kept thread-index VGPRs alive across the K loop and spilled them to scratch
+  const int tid = threadIdx.x, lane = __lane_id(), wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid / CF::WN, wn = wid % CF::WN;
   const int tn = lid % g.gn, tm = (lid / g.gn) % g.gm, tz = lid / (g.gn * g.gm);
   const int m0 = tm * BTM, n0 = tn * BTN;
@@ -635,13 +645,13 @@ __device__ __forceinline__ void gemm_bf16_big_tile(const Bf16Args& g, const int 
     keep_len = *lp;
   }
 
-  f32x16 acc[MI][2];
+  f32x4 acc[MI][4];
 #pragma unroll
   for (int i = 0; i < MI; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
 
   uint4 ra[4], rb[CF::NCB];
   uint32_t kma[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};   // DUAL: row masks of this thread's four A chunks
@@ -720,8 +730,8 @@ __device__ __forceinline__ void gemm_bf16_big_tile(const Bf16Args& g, const int 
   }
 #endif
   // ---- epilogue: bias, row mask, bf16 rounding, BN column sums.  The whole tile is laid out row-major in LDS as
-  //      bf16 (528 / 272-byte rows over the operand images, free after the last barrier): a lane owns output row l31
-  //      of each of its MFMA tiles and 4 consecutive columns per register quad -> one packed conversion per pair and
+  //      bf16 (528 / 272-byte rows over the operand images, free after the last barrier): a lane owns output row l15
+  //      of each of its MFMA tiles and 4 consecutive columns in its register quad -> one packed conversion per pair and
   //      one 8-byte LDS write per quad (conflict-free: pitch = 4 dwords mod 32).  Then every wave reads 32 complete
   //      tile rows back as 16-byte vectors, adds them into its column sums (the statistics are of the values as
   //      stored) and stores them: one instruction = 2 rows x 512 contiguous bytes.
@@ -729,7 +739,7 @@ __device__ __forceinline__ void gemm_bf16_big_tile(const Bf16Args& g, const int 
   //      conversion, statistics and 2-byte LDS writes in the natural accumulator order, of which the global stores
   //      themselves were 1 us.)
   constexpr int EPB = CF::EPB;
-  const int half = lane >> 5, l31 = lane & 31;
+  const int g4 = lane >> 4, l15 = lane & 15;
   const int nb = n0 + wn * 64;
   if constexpr (SLAB) {
     // split-K slice: f32 straight from the accumulators, 16 bytes (4 consecutive columns) per lane and quad; a 128-byte
@@ -738,21 +748,18 @@ __device__ __forceinline__ void gemm_bf16_big_tile(const Bf16Args& g, const int 
     const bool vec4 = (g.N & 3) == 0;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
-      const int m = m0 + wm * (32 * MI) + mi * 32 + l31;
+      const int m = m0 + wm * (16 * MI) + mi * 16 + l15;
       if (m < g.M) {
         float* wrow = W + (size_t)m * (size_t)g.N;
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
+        for (int ni = 0; ni < 4; ++ni) {
+          const int n = nb + ni * 16 + 4 * g4;
+          if (vec4 && n + 3 < g.N) {
+            *reinterpret_cast<float4*>(wrow + n) = make_float4(acc[mi][ni][0], acc[mi][ni][1], acc[mi][ni][2], acc[mi][ni][3]);
+          } else {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int n = nb + ni * 32 + 8 * j + 4 * half;
-            if (vec4 && n + 3 < g.N) {
-              *reinterpret_cast<float4*>(wrow + n) = make_float4(acc[mi][ni][4 * j], acc[mi][ni][4 * j + 1], acc[mi][ni][4 * j + 2], acc[mi][ni][4 * j + 3]);
-            } else {
-#pragma unroll
-              for (int e = 0; e < 4; ++e)
-                if (n + e < g.N) wrow[n + e] = acc[mi][ni][4 * j + e];
-            }
+            for (int e = 0; e < 4; ++e)
+              if (n + e < g.N) wrow[n + e] = acc[mi][ni][e];
           }
         }
       }
@@ -761,36 +768,33 @@ __device__ __forceinline__ void gemm_bf16_big_tile(const Bf16Args& g, const int 
   }
   bf16_t* C = reinterpret_cast<bf16_t*>(g.C);
   {
-    char* img = smem + (wm * (32 * MI) + l31) * EPB + (wn * 64 + 4 * half) * 2;
+    char* img = smem + (wm * (16 * MI) + l15) * EPB + (wn * 64 + 4 * g4) * 2;
     const bool has_bias = g.bias != nullptr;               // workgroup-uniform
-    float bv[2][4][4];
-    if (has_bias) load_bias_quads(g.bias, nb + 4 * half, g.N, bv);
+    float bv[4][4];
+    if (has_bias) load_bias_quads(g.bias, nb + 4 * g4, g.N, bv);
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
-      const uint32_t km = s_keep[wm * (32 * MI) + mi * 32 + l31] != 0.f ? 0xffffffffu : 0u;   // MaskCNN / M edge: the row is stored as zeros
+      const uint32_t km = s_keep[wm * (16 * MI) + mi * 16 + l15] != 0.f ? 0xffffffffu : 0u;   // MaskCNN / M edge: the row is stored as zeros
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
+      for (int ni = 0; ni < 4; ++ni) {
+        float v[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float v[4];
+        for (int e = 0; e < 4; ++e) v[e] = acc[mi][ni][e];
+        if (has_bias) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = acc[mi][ni][4 * j + e];
-          if (has_bias) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += bv[ni][j][e];
-          }
-          if constexpr (DUAL) {                             // folded eval form: activation in the epilogue
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              if (g.act == LASR_ACT_RELU) v[e] = fmaxf(v[e], 0.f);
-              else if (g.act == LASR_ACT_SWISH) v[e] = v[e] / (1.f + __expf(-v[e]));
-            }
-          }
-          uint2 pk;
-          pk.x = pack_bf16x2(v[0], v[1]) & km;
-          pk.y = pack_bf16x2(v[2], v[3]) & km;
-          *reinterpret_cast<uint2*>(img + mi * 32 * EPB + (ni * 32 + 8 * j) * 2) = pk;
+          for (int e = 0; e < 4; ++e) v[e] += bv[ni][e];
         }
+        if constexpr (DUAL) {                             // folded eval form: activation in the epilogue
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (g.act == LASR_ACT_RELU) v[e] = fmaxf(v[e], 0.f);
+            else if (g.act == LASR_ACT_SWISH) v[e] = v[e] / (1.f + __expf(-v[e]));
+          }
+        }
+        uint2 pk;
+        pk.x = pack_bf16x2(v[0], v[1]) & km;
+        pk.y = pack_bf16x2(v[2], v[3]) & km;
+        *reinterpret_cast<uint2*>(img + mi * 16 * EPB + ni * 16 * 2) = pk;
       }
     }
   }
@@ -885,13 +889,14 @@ __device__ __forceinline__ void gemm_bf16_big_tile(const Bf16Args& g, const int 
       }
     }
     __syncthreads();
-    if (tid < BTN) {
-      const int n = n0 + tid;
+    const int t = wid * 64 + lane;
+    if (t < BTN) {
+      const int n = n0 + t;
       if (n < g.N) {
         float* P = g.stat_partials + (size_t)tm * 2 * g.N;
         float s0 = 0.f, s1 = 0.f;
 #pragma unroll
-        for (int w = 0; w < 8; ++w) { s0 += s_part[(w * 2 + 0) * BTN + tid]; s1 += s_part[(w * 2 + 1) * BTN + tid]; }
+        for (int w = 0; w < 8; ++w) { s0 += s_part[(w * 2 + 0) * BTN + t]; s1 += s_part[(w * 2 + 1) * BTN + t]; }
         P[n] = s0;
         P[g.N + n] = s1;
       }
