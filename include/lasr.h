@@ -25,8 +25,9 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 102   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
-                              102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing* */
+#define LASR_VERSION 103   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+                              102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
+                              103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -375,6 +376,25 @@ int lasr_ctc_loss_mel(const float* logp, const int64_t* targets, const int32_t* 
  * tokens (B, T) int32, n_tokens (B) int32.   utils/asr_metrics.py:159-166                      */
 int lasr_greedy_decode(const int32_t* ids, const int32_t* lens, int64_t B, int64_t T, int blank,
                        int32_t* tokens, int32_t* n_tokens, void* stream);
+
+/* CTC prefix beam search without an external scorer: beam_search.py:17-57 (ctc_decoders' ctc_beam_search_decoder_batch with
+ * ext_scoring_func=None).  Per frame the classes ranked by (log-prob desc, id asc) are cut to the shortest leading run whose
+ * cumulative probability reaches cutoff_prob (when < 1), then to cutoff_top_n; blank is pruned like any class.  Each prefix
+ * keeps log_b / log_nb, score = logaddexp of the two; an extension p+c merges with a live prefix equal to it.  The beam_width
+ * best entries survive, ties broken by (rank of the source prefix, "no new label" before a label, label id ascending).
+ * Supported: beam_width 1..128, cutoff_top_n 1..64 (above C it acts as C), C <= 8192, any B and T with B*T and 1 + T*beam_width
+ * below 2^31.  Outside that range the workspace function returns 0 and the decode LASR_E_SHAPE.  The workspace holds the
+ * pruned frames (B*T*64 (class, log-prob)) and the prefix trie (B * (1 + T*beam_width) nodes of 8 bytes). */
+size_t lasr_ctc_beam_workspace_bytes(int64_t B, int64_t T, int64_t C, int beam_width, int cutoff_top_n);
+/* logp (B, T, C) f32 log-probs (log_softmax output); lens (B) int32 frames per utterance (NULL = T; clamped to [0, T]).
+ * tokens (B, n_best, T) int32: hypothesis j of utterance b in tokens[b][j][0 .. n_tokens[b][j]), -1 after it.
+ * n_tokens (B, n_best) int32, scores (B, n_best) f32 = log-probability of the prefix, best first; slots past the number of
+ * live prefixes hold n_tokens = -1 and score = -inf.  lens[b] = 0 gives the empty hypothesis with score 0.
+ * LASR_E_ARG (nothing launched) for a null pointer, n_best outside [1, beam_width], cutoff_prob outside (0, 1] or blank outside
+ * [0, C).  f32 arithmetic with a stable log-add; deterministic.  Two launches on `stream`, nothing allocated or synchronised. */
+int lasr_ctc_beam_decode(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank, int beam_width,
+                         int cutoff_top_n, float cutoff_prob, int n_best, int32_t* tokens, int32_t* n_tokens, float* scores,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- optimiser ----------------
  * scheduler/novograd.py:75-145 with betas=(0.8,0.5), eps=1e-8, no amsgrad/grad_averaging/luc

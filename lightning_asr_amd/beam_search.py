@@ -1,0 +1,63 @@
+"""``BeamSearchDecoderWithLM`` of the reference (beam_search.py:17-57) on the HIP CTC prefix beam search (csrc/ctc_beam.hip).
+
+The reference runs ctc_decoders' ``ctc_beam_search_decoder_batch`` on the host, optionally with a KenLM scorer.  Here the
+search without a scorer runs on the GPU: one launch prunes every frame, one workgroup per utterance searches it.  There is
+no KenLM on this path, so ``lm_path`` must be None (``alpha`` / ``beta`` are kept for the signature); ``num_cpus`` is
+accepted and ignored.  The blank is the class after the vocabulary (ctc_decoders' ``blank_id = vocabulary.size()``)."""
+from __future__ import annotations
+
+from typing import List, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+
+class BeamSearchDecoderWithLM(torch.nn.Module):
+
+    def __init__(self, vocab, beam_width, alpha, beta, lm_path, num_cpus, cutoff_prob=1.0, cutoff_top_n=40, device="cuda"):
+        super().__init__()
+        if lm_path is not None:
+            raise NotImplementedError("language-model scoring (KenLM) is not available: construct the decoder with lm_path=None")
+        self.scorer = None
+        self.vocab = list(vocab)
+        self.beam_width = int(beam_width)
+        self.alpha, self.beta = alpha, beta
+        self.num_cpus = num_cpus
+        self.cutoff_prob = float(cutoff_prob)
+        self.cutoff_top_n = int(cutoff_top_n)
+        self.device = torch.device(device)
+
+    def search(self, log_probs, log_probs_length, n_best: int = 1):
+        """(B, T, C) log-probs (numpy or tensor) + (B) lengths -> (tokens (B, n_best, T), n_tokens (B, n_best), scores (B, n_best))
+        as device tensors (ops.ctc_beam_decode)"""
+        lp = torch.as_tensor(np.ascontiguousarray(log_probs)) if isinstance(log_probs, np.ndarray) else log_probs
+        dev = lp.device if lp.is_cuda else self.device
+        lp = lp.to(dev, torch.float32).contiguous()
+        if lp.shape[-1] != len(self.vocab) + 1:
+            raise ValueError("log-probs have %d classes; the vocabulary has %d labels + blank" % (lp.shape[-1], len(self.vocab)))
+        lens = None
+        if log_probs_length is not None:
+            lens = torch.as_tensor(np.asarray(log_probs_length) if not torch.is_tensor(log_probs_length) else log_probs_length)
+            lens = lens.to(dev, torch.int32).contiguous()
+        return ops.ctc_beam_decode(lp, lens, len(self.vocab), self.beam_width, self.cutoff_top_n, self.cutoff_prob, n_best)
+
+    def _text(self, toks) -> str:
+        return "".join(self.vocab[int(c)] for c in toks)
+
+    @torch.no_grad()
+    def forward(self, log_probs, log_probs_length) -> List[str]:
+        """the best hypothesis of every utterance as text (beam_search.py:31-47)"""
+        tokens, n, _ = self.search(log_probs, log_probs_length, 1)
+        tokens, n = tokens.cpu().numpy(), n.cpu().numpy()
+        return [self._text(tokens[b, 0, :max(int(n[b, 0]), 0)]) for b in range(tokens.shape[0])]
+
+    @torch.no_grad()
+    def decode_nbest(self, log_probs, log_probs_length, n_best=None) -> List[List[Tuple[float, str]]]:
+        """ctc_decoders' output: per utterance [(score, text), ...], best first (up to n_best, default beam_width)"""
+        n_best = self.beam_width if n_best is None else int(n_best)
+        tokens, n, scores = self.search(log_probs, log_probs_length, n_best)
+        tokens, n, scores = tokens.cpu().numpy(), n.cpu().numpy(), scores.cpu().numpy()
+        return [[(float(scores[b, j]), self._text(tokens[b, j, :n[b, j]])) for j in range(n_best) if n[b, j] >= 0]
+                for b in range(tokens.shape[0])]

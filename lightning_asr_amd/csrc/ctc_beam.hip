@@ -1,0 +1,466 @@
+// CTC prefix beam search without an external scorer: ctc_decoders' ctc_beam_search_decoder as used by the reference's
+// BeamSearchDecoderWithLM (beam_search.py:17-57) with lm_path=None.  Blank is an argument (C-1 in this project).
+//
+// Two launches, no host synchronisation, no allocation:
+//   1. beam_prune_kernel: one wave per (utterance, frame).  Ranks the classes by (log-prob desc, id asc) with a radix select
+//      of the cutoff_top_n best (a direct 64-lane rank for C <= 64), applies cutoff_prob to the cumulative probability of
+//      that run and writes the kept (class, log-prob) list of the frame into the workspace.
+//   2. beam_search_kernel: one 256-thread workgroup per utterance, looping over its frames.  The beam (trie node, last
+//      label, length, prefix hash, log_b, log_nb) lives in LDS; the frame's candidates (one "no new label" entry per live
+//      prefix + one extension per (prefix, kept label)) live in registers, J per thread.  The beam_width best are found by
+//      an 8-bit radix select over (score, tie-break key) that stops as soon as the boundary bucket is taken whole; only the
+//      survivors are ordered (rank by counting).  New prefixes are appended to a parent-pointer trie in the workspace
+//      (at most beam_width nodes per frame) that is walked back once at the end.
+//
+// Prefix identity: p+c merges with a live entry q when q's parent prefix equals p and q's last label is c.  Entries carry a
+// 64-bit hash of their label sequence and of their parent's, so "q's parent equals p" is a hash compare; a trie node id
+// would not do, since a prefix that left the beam and came back gets a new node while its children may still be live.
+#include "common.h"
+
+namespace lasr {
+namespace {
+
+constexpr int kBeamMaxWidth = 128;
+constexpr int kBeamMaxTopN = 64;
+constexpr int kBeamMaxClasses = 8192;
+constexpr int kSearchThreads = 256;
+constexpr float kNegInfB = -INFINITY;
+constexpr uint64_t kRootHash = 0x6a09e667f3bcc908ull;
+
+__device__ __forceinline__ float lae(float a, float b) {
+  const float m = fmaxf(a, b);
+  if (m == kNegInfB) return m;
+  return m + log1pf(expf(fminf(a, b) - m));
+}
+
+// ascending in the result == descending in f (f is never NaN here; -0 is folded onto +0 first)
+__device__ __forceinline__ uint32_t desc_bits(float f) {
+  uint32_t u = __float_as_uint(f + 0.0f);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ~u;
+}
+
+__device__ __forceinline__ uint64_t child_hash(uint64_t h, int c) {
+  uint64_t z = h + 0x9e3779b97f4a7c15ull * (uint64_t)(c + 1);
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+
+// hist[bin] += 1 for every lane with `on`, one LDS atomic per distinct bin of the wave (the early radix digits of a frame's
+// scores fall into a handful of bins, which plain per-lane atomics would serialise on)
+__device__ __forceinline__ void wave_hist_add(uint32_t* hist, bool on, uint32_t bin, int lane) {
+  bool pend = on;
+  uint64_t act = __ballot(pend);
+  while (act) {
+    const int leader = __builtin_ctzll(act);
+    const uint32_t lb = (uint32_t)__shfl((int)bin, leader, 64);
+    const uint64_t same = __ballot(pend && bin == lb);
+    if (lane == leader) atomicAdd(&hist[lb], (uint32_t)__popcll(same));
+    pend = pend && bin != lb;
+    act &= ~same;
+  }
+}
+
+// inclusive prefix sum over the 64 lanes
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t u = (uint32_t)__shfl_up((int)v, o, 64);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+
+// One wave reads the 256-bin histogram (4 bins per lane), finds the bucket holding the need-th smallest element and zeroes
+// the bins for the next pass.  out[0] = bucket, out[1] = elements in smaller buckets, out[2] = elements in the bucket,
+// out[3] = total.
+__device__ __forceinline__ void wave_find_bucket(uint32_t* hist, uint32_t need, int lane, uint32_t* out) {
+  uint32_t h[4], s = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    h[i] = hist[lane * 4 + i];
+    s += h[i];
+  }
+  const uint32_t incl = wave_incl_scan(s, lane);
+  uint32_t excl = incl - s;
+  if (excl < need && need <= incl) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (excl < need && need <= excl + h[i]) {
+        out[0] = lane * 4 + i;
+        out[1] = excl;
+        out[2] = h[i];
+      }
+      excl += h[i];
+    }
+  }
+  if (lane == 63) out[3] = incl;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) hist[lane * 4 + i] = 0;
+}
+
+// ------------------------------------------------------------------ frame pruning ---------------------------------------
+// composite of a class: (desc log-prob) << 13 | class id: unique, ascending == the (log-prob desc, id asc) order
+__device__ __forceinline__ uint64_t class_key(float v, int c) { return ((uint64_t)desc_bits(v) << 13) | (uint64_t)c; }
+
+__global__ __launch_bounds__(64) void beam_prune_kernel(const float* __restrict__ logp, const int32_t* __restrict__ lens,
+                                                        int64_t T, int C, int topn, float cutoff_prob,
+                                                        int32_t* __restrict__ kcls, float* __restrict__ klp,
+                                                        int32_t* __restrict__ kn) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t found[4];
+  __shared__ uint64_t sel[kBeamMaxTopN];
+  __shared__ uint32_t nsel;
+  const int lane = threadIdx.x;
+  const int64_t frame = blockIdx.x;
+  const int64_t b = frame / T, t = frame - b * T;
+  const int64_t L = lens ? min((int64_t)max(lens[b], 0), T) : T;
+  if (t >= L) return;
+  const float* row = logp + frame * (int64_t)C;
+  const int K = min(topn, C);
+  uint64_t mine = ~0ull;  // lane < K: the lane-th best composite once sorted
+  if (C <= 64) {
+    const uint64_t key = lane < C ? class_key(row[lane], lane) : ~0ull;
+    int rank = 0;
+    for (int j = 0; j < C; ++j) rank += (uint64_t)__shfl((long long)key, j, 64) < key;
+    if (lane < C && rank < K) sel[rank] = key;
+    __syncthreads();
+    if (lane < K) mine = sel[lane];
+  } else {
+    // radix select of the K smallest composites (45 bits: 8-bit digits aligned to the f32 key, the last one overlapping)
+    for (int i = lane; i < 256; i += 64) hist[i] = 0;
+    if (lane == 0) nsel = 0;
+    __syncthreads();
+    uint64_t prefix = 0, mask = 0;
+    uint32_t need = (uint32_t)K;
+    for (int ps = 0; ps < 6; ++ps) {
+      const int sh = ps < 5 ? 37 - 8 * ps : 0;
+      for (int c0 = 0; c0 < C; c0 += 64) {
+        const int c = c0 + lane;
+        const uint64_t key = c < C ? class_key(row[c], c) : 0;
+        wave_hist_add(hist, c < C && (key & mask) == prefix, (uint32_t)(key >> sh) & 255u, lane);
+      }
+      __syncthreads();
+      wave_find_bucket(hist, need, lane, found);
+      __syncthreads();
+      const uint32_t bucket = found[0], before = found[1], cnt = found[2];
+      prefix |= (uint64_t)bucket << sh;
+      mask |= 0xffull << sh;
+      need -= before;
+      if (cnt == need) break;
+    }
+    for (int c0 = 0; c0 < C; c0 += 64) {
+      const int c = c0 + lane;
+      const uint64_t key = c < C ? class_key(row[c], c) : ~0ull;
+      if (c < C && (key & mask) <= prefix) {
+        const uint32_t pos = atomicAdd(&nsel, 1u);
+        if (pos < (uint32_t)kBeamMaxTopN) sel[pos] = key;   // exactly K land here; the guard only bounds the LDS index
+      }
+    }
+    __syncthreads();
+    uint64_t key = lane < K ? sel[lane] : ~0ull;
+    int rank = 0;
+    for (int j = 0; j < K; ++j) rank += (uint64_t)__shfl((long long)key, j, 64) < key;
+    __syncthreads();
+    if (lane < K) sel[rank] = key;
+    __syncthreads();
+    if (lane < K) mine = sel[lane];
+  }
+  const int cls = (int)(mine & 8191u);
+  const float v = lane < K ? row[cls] : kNegInfB;
+  int keep = K;
+  if (cutoff_prob < 1.0f) {
+    // shortest leading run whose cumulative probability reaches cutoff_prob
+    float cum = lane < K ? expf(v) : 0.f;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const float u = __shfl_up(cum, o, 64);
+      if (lane >= o) cum += u;
+    }
+    const uint64_t reached = __ballot(lane < K && cum >= cutoff_prob);
+    if (reached) keep = min(K, __builtin_ctzll(reached) + 1);
+  }
+  if (lane < keep) {
+    kcls[frame * kBeamMaxTopN + lane] = cls;
+    klp[frame * kBeamMaxTopN + lane] = v;
+  }
+  if (lane == 0) kn[frame] = keep;
+}
+
+// ------------------------------------------------------------------ the search ------------------------------------------
+struct BeamLds {
+  int node[2][kBeamMaxWidth], last[2][kBeamMaxWidth], len[2][kBeamMaxWidth];
+  float b[2][kBeamMaxWidth], nb[2][kBeamMaxWidth];
+  uint64_t h[2][kBeamMaxWidth], ph[2][kBeamMaxWidth];
+  float score[kBeamMaxWidth];             // logaddexp(b, nb) of the current beam
+  float next_b[kBeamMaxWidth], next_nb[kBeamMaxWidth];   // the "no new label" candidate of each live prefix
+  unsigned long long merged[kBeamMaxWidth];              // bit k: p + kept[k] merged into a live entry
+  uint64_t surv[kBeamMaxWidth];
+  int surv_i[kBeamMaxWidth];
+  int kcls[kBeamMaxTopN];
+  float klp[kBeamMaxTopN];
+  uint32_t hist[256];
+  uint32_t found[4];
+  uint32_t nsel;
+  int nk;
+};
+
+// the extension candidate (p, kept[k]) -> its score (-inf when it merged into a live entry or k is the blank)
+__device__ __forceinline__ float ext_score(const BeamLds& s, int cur, int p, int k, int blank) {
+  const int c = s.kcls[k];
+  if (c == blank || ((s.merged[p] >> k) & 1ull)) return kNegInfB;
+  return s.klp[k] + (c == s.last[cur][p] ? s.b[cur][p] : s.score[p]);
+}
+
+template <int J>
+__global__ __launch_bounds__(kSearchThreads) void beam_search_kernel(const int32_t* __restrict__ kcls_g,
+                                                                     const float* __restrict__ klp_g,
+                                                                     const int32_t* __restrict__ kn_g,
+                                                                     const int32_t* __restrict__ lens, int64_t T, int blank,
+                                                                     int W, int n_best, int2* __restrict__ trie_g,
+                                                                     int32_t* __restrict__ tokens, int32_t* __restrict__ n_tokens,
+                                                                     float* __restrict__ scores) {
+  __shared__ BeamLds s;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t ub = blockIdx.x;
+  const int64_t L = lens ? min((int64_t)max(lens[ub], 0), T) : T;
+  int2* trie = trie_g + ub * (1 + T * (int64_t)W);
+  const int32_t* kc = kcls_g + ub * T * kBeamMaxTopN;
+  const float* kl = klp_g + ub * T * kBeamMaxTopN;
+  const int32_t* knf = kn_g + ub * T;
+  if (tid == 0) {
+    s.node[0][0] = 0; s.last[0][0] = -1; s.len[0][0] = 0;
+    s.b[0][0] = 0.f; s.nb[0][0] = kNegInfB;
+    s.h[0][0] = kRootHash; s.ph[0][0] = 0;
+  }
+  for (int i = tid; i < 256; i += kSearchThreads) s.hist[i] = 0;
+  int nbeam = 1, cur = 0;
+  // the kept list of frame t + 1 is fetched while frame t is searched
+  int pc = 0, pn = 0;
+  float pl = 0.f;
+  if (L > 0) {
+    if (tid < kBeamMaxTopN) { pc = kc[tid]; pl = kl[tid]; }
+    pn = knf[0];
+  }
+  for (int64_t t = 0; t < L; ++t) {
+    const int nk = pn;
+    if (tid < nk) { s.kcls[tid] = pc; s.klp[tid] = pl; }
+    if (t + 1 < L) {
+      if (tid < kBeamMaxTopN) { pc = kc[(t + 1) * kBeamMaxTopN + tid]; pl = kl[(t + 1) * kBeamMaxTopN + tid]; }
+      pn = knf[t + 1];
+    }
+    if (tid == 0) s.nsel = 0;
+    __syncthreads();
+    // (1) per live prefix: score, the kept index of its last label and of the blank, its parent among the live entries
+    int lastk = -1, pr = -1;
+    float blp = kNegInfB;
+    if (tid < nbeam) {
+      const int last = s.last[cur][tid];
+      s.score[tid] = lae(s.b[cur][tid], s.nb[cur][tid]);
+      s.merged[tid] = 0ull;
+      for (int k = 0; k < nk; ++k) {
+        const int c = s.kcls[k];
+        if (c == last) lastk = k;
+        if (c == blank) blp = s.klp[k];
+      }
+      if (last >= 0) {
+        const uint64_t ph = s.ph[cur][tid];
+        for (int r = 0; r < nbeam; ++r)
+          if (s.h[cur][r] == ph) { pr = r; break; }
+      }
+    }
+    __syncthreads();
+    // (2) the "no new label" candidate of each live prefix, with what its parent's extension by its last label adds
+    if (tid < nbeam) {
+      const float sc = s.score[tid];
+      float nbn = kNegInfB;
+      if (lastk >= 0) {
+        const float lc = s.klp[lastk];
+        nbn = lc + s.nb[cur][tid];
+        if (pr >= 0) {
+          nbn = lae(nbn, lc + (s.last[cur][tid] == s.last[cur][pr] ? s.b[cur][pr] : s.score[pr]));
+          atomicOr(&s.merged[pr], 1ull << lastk);
+        }
+      }
+      s.next_b[tid] = blp + sc;
+      s.next_nb[tid] = nbn;
+    }
+    __syncthreads();
+    // (3) candidates: i < nbeam "no new label" of entry i, then nbeam * nk extensions (p, k); composite = score desc, key asc
+    const int ncand = nbeam + nbeam * nk;
+    uint64_t comp[J];
+    uint64_t valid = 0;
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      const int i = tid + j * kSearchThreads;
+      float sc = kNegInfB;
+      uint32_t key = 0;
+      if (i < nbeam) {
+        sc = lae(s.next_b[i], s.next_nb[i]);
+        key = (uint32_t)i << 14;
+      } else if (i < ncand) {
+        const int q = i - nbeam, p = q / nk, k = q - p * nk;
+        sc = ext_score(s, cur, p, k, blank);
+        key = ((uint32_t)p << 14) | (uint32_t)(s.kcls[k] + 1);
+      }
+      comp[j] = ((uint64_t)desc_bits(sc) << 32) | key;
+      if (sc > kNegInfB) valid |= 1ull << j;
+    }
+    // (4) radix select of the W smallest composites; `prefix`/`mask` end as the boundary: (comp & mask) <= prefix is taken
+    uint64_t prefix = 0, mask = 0;
+    uint32_t need = (uint32_t)W;
+    for (int ps = 0; ps < 7; ++ps) {
+      const int sh = ps < 4 ? 56 - 8 * ps : 16 - 8 * (ps - 4);   // the key is below 2^21: bits 21..31 are always 0
+#pragma unroll
+      for (int j = 0; j < J; ++j)
+        wave_hist_add(s.hist, ((valid >> j) & 1ull) && (comp[j] & mask) == prefix, (uint32_t)(comp[j] >> sh) & 255u, lane);
+      __syncthreads();
+      if (tid < 64) wave_find_bucket(s.hist, need, lane, s.found);
+      __syncthreads();
+      if (ps == 0 && s.found[3] <= need) break;        // no more finite candidates than the beam holds: take them all
+      const uint32_t bucket = s.found[0], before = s.found[1], cnt = s.found[2];
+      prefix |= (uint64_t)bucket << sh;
+      mask |= 0xffull << sh;
+      need -= before;
+      if (cnt == need) break;
+    }
+    // (5) compact the survivors, order them, write the next beam (and the trie nodes of new prefixes) in rank order
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      if (((valid >> j) & 1ull) && (comp[j] & mask) <= prefix) {
+        const uint32_t pos = atomicAdd(&s.nsel, 1u);
+        if (pos < (uint32_t)kBeamMaxWidth) {   // at most W survive; the guard only bounds the LDS index
+          s.surv[pos] = comp[j];
+          s.surv_i[pos] = tid + j * kSearchThreads;
+        }
+      }
+    }
+    __syncthreads();
+    const int nsel = min((int)s.nsel, W);
+    const int nxt = cur ^ 1;
+    if (tid < nsel) {
+      const uint64_t me = s.surv[tid];
+      int rank = 0;
+      for (int r = 0; r < nsel; ++r) rank += s.surv[r] < me;
+      const int i = s.surv_i[tid];
+      if (i < nbeam) {
+        s.node[nxt][rank] = s.node[cur][i]; s.last[nxt][rank] = s.last[cur][i]; s.len[nxt][rank] = s.len[cur][i];
+        s.h[nxt][rank] = s.h[cur][i]; s.ph[nxt][rank] = s.ph[cur][i];
+        s.b[nxt][rank] = s.next_b[i]; s.nb[nxt][rank] = s.next_nb[i];
+      } else {
+        const int q = i - nbeam, p = q / nk, k = q - p * nk;
+        const int c = s.kcls[k];
+        const int node = 1 + (int)t * W + rank;
+        trie[node] = make_int2(s.node[cur][p], c);
+        s.node[nxt][rank] = node; s.last[nxt][rank] = c; s.len[nxt][rank] = s.len[cur][p] + 1;
+        s.h[nxt][rank] = child_hash(s.h[cur][p], c); s.ph[nxt][rank] = s.h[cur][p];
+        s.b[nxt][rank] = kNegInfB; s.nb[nxt][rank] = ext_score(s, cur, p, k, blank);
+      }
+    }
+    nbeam = nsel;
+    cur = nxt;
+    __syncthreads();
+  }
+  // walk the trie back from each of the n_best final entries; the slots past the hypothesis are -1
+  __threadfence();
+  __syncthreads();
+  int32_t* tok = tokens + ub * (int64_t)n_best * T;
+  if (tid < n_best) {
+    if (tid < nbeam) {
+      const int n = s.len[cur][tid];
+      n_tokens[ub * n_best + tid] = n;
+      scores[ub * n_best + tid] = lae(s.b[cur][tid], s.nb[cur][tid]);
+      int node = s.node[cur][tid];
+      for (int pos = n - 1; pos >= 0; --pos) {
+        const int2 e = trie[node];
+        tok[(int64_t)tid * T + pos] = e.y;
+        node = e.x;
+      }
+    } else {
+      n_tokens[ub * n_best + tid] = -1;
+      scores[ub * n_best + tid] = kNegInfB;
+    }
+  }
+  for (int64_t idx = tid; idx < (int64_t)n_best * T; idx += kSearchThreads) {
+    const int j = (int)(idx / T);
+    const int64_t pos = idx - (int64_t)j * T;
+    const int n = j < nbeam ? s.len[cur][j] : 0;
+    if (pos >= n) tok[idx] = -1;
+  }
+}
+
+bool beam_shape_ok(int64_t B, int64_t T, int64_t C, int W, int topn) {
+  return B >= 1 && T >= 1 && C >= 1 && C <= kBeamMaxClasses && W >= 1 && W <= kBeamMaxWidth && topn >= 1 &&
+         topn <= kBeamMaxTopN && B * T <= 0x7fffffffLL && 1 + T * (int64_t)W <= 0x7fffffffLL;
+}
+
+struct BeamWs {
+  size_t kcls, klp, kn, trie, total;
+};
+
+BeamWs beam_ws(int64_t B, int64_t T, int64_t W) {
+  BeamWs w;
+  const size_t frames = (size_t)(B * T);
+  w.kcls = 0;
+  w.klp = align_up(w.kcls + frames * kBeamMaxTopN * sizeof(int32_t), 256);
+  w.kn = align_up(w.klp + frames * kBeamMaxTopN * sizeof(float), 256);
+  w.trie = align_up(w.kn + frames * sizeof(int32_t), 256);
+  w.total = align_up(w.trie + (size_t)B * (size_t)(1 + T * W) * sizeof(int2), 256);
+  return w;
+}
+
+template <int J>
+void launch_search(dim3 grid, hipStream_t st, const int32_t* kc, const float* kl, const int32_t* kn, const int32_t* lens, int64_t T,
+                   int blank, int W, int n_best, int2* trie, int32_t* tokens, int32_t* n_tokens, float* scores) {
+  hipLaunchKernelGGL(beam_search_kernel<J>, grid, dim3(kSearchThreads), 0, st, kc, kl, kn, lens, T, blank, W, n_best, trie, tokens,
+                     n_tokens, scores);
+}
+
+}  // namespace
+}  // namespace lasr
+
+using namespace lasr;
+
+extern "C" size_t lasr_ctc_beam_workspace_bytes(int64_t B, int64_t T, int64_t C, int beam_width, int cutoff_top_n) {
+  if (!beam_shape_ok(B, T, C, beam_width, cutoff_top_n)) return 0;
+  return beam_ws(B, T, beam_width).total;
+}
+
+extern "C" int lasr_ctc_beam_decode(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
+                                    int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, int32_t* tokens,
+                                    int32_t* n_tokens, float* scores, void* workspace, size_t workspace_bytes, void* stream) {
+  LASR_CHECK_ARG(logp && tokens && n_tokens && scores && workspace, "lasr_ctc_beam_decode: null pointer");
+  LASR_CHECK_ARG(n_best >= 1 && n_best <= beam_width, "lasr_ctc_beam_decode: n_best %d outside [1, beam_width %d]", n_best,
+                 beam_width);
+  LASR_CHECK_ARG(cutoff_prob > 0.f && cutoff_prob <= 1.f, "lasr_ctc_beam_decode: cutoff_prob %g outside (0, 1]", (double)cutoff_prob);
+  LASR_CHECK_ARG(C >= 1 && blank >= 0 && blank < C, "lasr_ctc_beam_decode: blank %d outside [0, C = %lld)", blank, (long long)C);
+  LASR_CHECK_SHAPE(beam_shape_ok(B, T, C, beam_width, cutoff_top_n),
+                   "lasr_ctc_beam_decode: B %lld T %lld C %lld beam_width %d cutoff_top_n %d outside the supported range "
+                   "(C <= %d, beam_width 1..%d, cutoff_top_n 1..%d)", (long long)B, (long long)T, (long long)C, beam_width,
+                   cutoff_top_n, kBeamMaxClasses, kBeamMaxWidth, kBeamMaxTopN);
+  const BeamWs w = beam_ws(B, T, beam_width);
+  if (workspace_bytes < w.total)
+    return fail(LASR_E_WORKSPACE, "lasr_ctc_beam_decode: workspace %zu < %zu bytes", workspace_bytes, w.total);
+  char* ws = static_cast<char*>(workspace);
+  int32_t* kc = reinterpret_cast<int32_t*>(ws + w.kcls);
+  float* kl = reinterpret_cast<float*>(ws + w.klp);
+  int32_t* kn = reinterpret_cast<int32_t*>(ws + w.kn);
+  int2* trie = reinterpret_cast<int2*>(ws + w.trie);
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(beam_prune_kernel, dim3((unsigned)(B * T)), dim3(64), 0, st, logp, lens, T, (int)C, cutoff_top_n, cutoff_prob,
+                     kc, kl, kn);
+  LASR_LAUNCH_CHECK("beam_prune_kernel");
+  // candidates per frame: beam_width "no new label" entries + beam_width * kept labels, J per thread
+  const int K = (int)(C < cutoff_top_n ? C : cutoff_top_n);
+  const int per = (int)cdiv((int64_t)beam_width * (K + 1), kSearchThreads);
+  const dim3 grid((unsigned)B);
+  if (per <= 1) launch_search<1>(grid, st, kc, kl, kn, lens, T, blank, beam_width, n_best, trie, tokens, n_tokens, scores);
+  else if (per <= 2) launch_search<2>(grid, st, kc, kl, kn, lens, T, blank, beam_width, n_best, trie, tokens, n_tokens, scores);
+  else if (per <= 4) launch_search<4>(grid, st, kc, kl, kn, lens, T, blank, beam_width, n_best, trie, tokens, n_tokens, scores);
+  else if (per <= 8) launch_search<8>(grid, st, kc, kl, kn, lens, T, blank, beam_width, n_best, trie, tokens, n_tokens, scores);
+  else if (per <= 16) launch_search<16>(grid, st, kc, kl, kn, lens, T, blank, beam_width, n_best, trie, tokens, n_tokens, scores);
+  else launch_search<33>(grid, st, kc, kl, kn, lens, T, blank, beam_width, n_best, trie, tokens, n_tokens, scores);
+  LASR_LAUNCH_CHECK("beam_search_kernel");
+  return 0;
+}

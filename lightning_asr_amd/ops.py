@@ -415,6 +415,45 @@ def greedy_decode(ids: torch.Tensor, lens: Optional[torch.Tensor], blank: int):
     return tokens, n
 
 
+CTC_BEAM_MAX_WIDTH = 128      # lasr_ctc_beam_decode's supported range (include/lasr.h)
+CTC_BEAM_MAX_TOP_N = 64
+CTC_BEAM_MAX_CLASSES = 8192
+
+
+def ctc_beam_decode(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: int, beam_width: int = 16, cutoff_top_n: int = 40,
+                    cutoff_prob: float = 1.0, n_best: int = 1):
+    """CTC prefix beam search (no LM) of logp (B,T,C) f32 log-probs, lens (B) i32 frames or None (= T).  Returns
+    (tokens (B, n_best, T) i32, -1 past each hypothesis; n_tokens (B, n_best) i32, -1 for an empty slot; scores (B, n_best) f32
+    log-probabilities, best first).  Shapes outside the kernel's range raise ValueError."""
+    if logp.dtype != torch.float32 or logp.dim() != 3:
+        raise TypeError("ctc_beam_decode takes (B, T, C) float32 log-probs")
+    B, T, Cc = logp.shape
+    cutoff_top_n = min(int(cutoff_top_n), Cc) if Cc >= 1 else int(cutoff_top_n)    # above C it acts as C
+    if not 1 <= beam_width <= CTC_BEAM_MAX_WIDTH:
+        raise ValueError("beam_width %d outside 1..%d" % (beam_width, CTC_BEAM_MAX_WIDTH))
+    if not 1 <= cutoff_top_n <= CTC_BEAM_MAX_TOP_N:
+        raise ValueError("cutoff_top_n %d outside 1..%d" % (cutoff_top_n, CTC_BEAM_MAX_TOP_N))
+    if not 1 <= Cc <= CTC_BEAM_MAX_CLASSES:
+        raise ValueError("%d classes: the beam decoder takes at most %d" % (Cc, CTC_BEAM_MAX_CLASSES))
+    if not 1 <= n_best <= beam_width:
+        raise ValueError("n_best %d outside 1..beam_width (%d)" % (n_best, beam_width))
+    if not 0.0 < cutoff_prob <= 1.0:
+        raise ValueError("cutoff_prob %r outside (0, 1]" % (cutoff_prob,))
+    if not 0 <= blank < Cc:
+        raise ValueError("blank %d outside [0, %d)" % (blank, Cc))
+    nb = int(_lib.load().lasr_ctc_beam_workspace_bytes(B, T, Cc, beam_width, cutoff_top_n))
+    if nb == 0:
+        raise ValueError("ctc_beam_decode: shape (%d, %d, %d) outside the kernel's range" % (B, T, Cc))
+    dev = logp.device
+    tokens = torch.empty(B, n_best, T, dtype=torch.int32, device=dev)
+    n = torch.empty(B, n_best, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+    ws = _ws(nb, dev)
+    call("lasr_ctc_beam_decode", _p(logp), _p(lens), B, T, Cc, int(blank), int(beam_width), int(cutoff_top_n), float(cutoff_prob),
+         int(n_best), _p(tokens), _p(n), _p(scores), _p(ws), nb, _stream())
+    return tokens, n, scores
+
+
 # ---------------------------------------------------------------------------------- optimiser
 def novograd_workspace(n_tensors: int, n_elems: int, device) -> torch.Tensor:
     """a ZEROED workspace a caller keeps across novograd_step(ws=...) calls (every call leaves it zeroed)"""
