@@ -25,9 +25,10 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 103   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 104   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
-                              103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search) */
+                              103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
+                              104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -35,7 +36,10 @@ enum { LASR_VARIANT_PLAIN = 0, LASR_VARIANT_CONTEXT = 1, LASR_VARIANT_CONTEXT_SE
 enum {
   LASR_E_ARG = -1,      /* null pointer / negative size / unsupported enum */
   LASR_E_SHAPE = -2,    /* shape outside what the kernels are built for */
-  LASR_E_WORKSPACE = -3 /* workspace too small */
+  LASR_E_WORKSPACE = -3, /* workspace too small */
+  LASR_E_FORMAT = -4,    /* malformed input file (lasr_arpa_load) */
+  LASR_E_UNSUPPORTED = -5, /* a well-formed input the library does not read (a KenLM binary model) */
+  LASR_E_IO = -6          /* an input file that cannot be opened or read */
 };
 
 int lasr_version(void);
@@ -395,6 +399,47 @@ size_t lasr_ctc_beam_workspace_bytes(int64_t B, int64_t T, int64_t C, int beam_w
 int lasr_ctc_beam_decode(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank, int beam_width,
                          int cutoff_top_n, float cutoff_prob, int n_best, int32_t* tokens, int32_t* n_tokens, float* scores,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* CTC prefix beam search fused with a character n-gram LM: beam_search.py:61-76 (BeamSearchDecoderWithLM with lm_path, i.e.
+ * ctc_decoders' ctc_beam_search_decoder_batch with a character-based Scorer).  ctc_decoders' source is not part of this project;
+ * what follows RESTATES its published behaviour (DESIGN.md "Beam search with an n-gram LM").  Everything above holds (pruning,
+ * cutoff_prob / cutoff_top_n, log_b / log_nb, merging, tie-break); in addition:
+ *  1. every label emission p -> p+c (c != blank; from score(p) when c != last(p), from log_b(p) when c == last(p)) adds
+ *     alpha * lm(c | p) + beta.  The "no new label" continuation and blank add nothing, so the term depends on p+c alone.
+ *  2. lm(c | p): the n-gram is the last N labels of p+c as strings (N = the ARPA's highest order), left-padded with <s> when
+ *     p+c has fewer; scored by ARPA backoff (log10 p of the longest stored suffix ending in c, plus the log10 backoffs of the
+ *     longer context suffixes, 0 for a context that is not stored), divided by NUM_FLT_LOGE = 0.4342944819.  If any word of the
+ *     n-gram (padding included) is outside the LM's vocabulary (a label string the ARPA lacks, "<unk>", a missing <s>), the value
+ *     is OOV_SCORE = -1000, unconverted.
+ *  3. early cutoff: when the beam held beam_width prefixes after the previous frame, min_cutoff = score(last of them) +
+ *     logp[t][blank] (unpruned) - max(0, beta); (p, c) contributes nothing where score(p) + logp[t][c] < min_cutoff (blank
+ *     always passes).
+ *  4. character-based LMs only (every ARPA word but <s>, </s>, <unk> is one code point), orders 1..6.
+ *  5. hypotheses are ranked by the fused score (acoustic + the terms of 1); scores = fused, am_scores = ctc_decoders'
+ *     approx_ctc = fused - labels * beta - alpha * sent_lm, sent_lm = the LM score of <s>^(N-1) labels </s> over N-word
+ *     windows (<s>^N </s> for no labels).
+ *
+ * lasr_arpa_load reads a text ARPA file on the host (lightning_asr_amd/csrc/arpa_io.h) for the class strings vocab[0 .. n_vocab)
+ * (UTF-8; class c uses vocab[c]; vocab may be NULL when n_vocab is 0) and returns a handle: LASR_E_ARG for a null pointer,
+ * LASR_E_IO for a file that cannot be opened or read, LASR_E_FORMAT for a malformed file (the message names the line), an order outside 1..6, counts that disagree, a missing
+ * suffix n-gram; LASR_E_UNSUPPORTED for a KenLM binary model.  lasr_arpa_info reports the order, whether the LM is
+ * character-based, the n-grams kept (those over words some label maps to, and <s> / </s>) and the size of the device image;
+ * lasr_arpa_write_image copies the image to host memory the caller then copies to the device (read-only, position-independent).
+ * No device work and no device allocation. */
+int lasr_arpa_load(const char* path, const char* const* vocab, int n_vocab, void** handle);
+int lasr_arpa_info(const void* handle, int* order, int* char_based, int64_t* n_ngrams, size_t* image_bytes);
+int lasr_arpa_write_image(const void* handle, void* host_dst, size_t bytes);
+void lasr_arpa_free(void* handle);
+/* The same workspace as lasr_ctc_beam_workspace_bytes. */
+size_t lasr_ctc_beam_lm_workspace_bytes(int64_t B, int64_t T, int64_t C, int beam_width, int cutoff_top_n);
+/* As lasr_ctc_beam_decode, with lm_image a device copy of a character-based image built for the vocabulary of classes
+ * 0 .. C-1 (the blank's entry is never read).  scores = fused, am_scores = approx_ctc (-inf for an empty slot).  An image
+ * whose header is not one lasr_arpa_write_image wrote yields empty slots (n_tokens -1) for every utterance.  LASR_E_ARG also
+ * for a non-finite alpha or beta.  Two launches on `stream`, nothing allocated or synchronised; deterministic. */
+int lasr_ctc_beam_decode_lm(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank, int beam_width,
+                            int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image, float alpha, float beta,
+                            int32_t* tokens, int32_t* n_tokens, float* scores, float* am_scores, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- optimiser ----------------
  * scheduler/novograd.py:75-145 with betas=(0.8,0.5), eps=1e-8, no amsgrad/grad_averaging/luc

@@ -90,6 +90,13 @@ SIGNATURES = {
     "lasr_greedy_decode": (_i32, [_p, _p, _i64, _i64, _i32, _p, _p, _p]),
     "lasr_ctc_beam_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32]),
     "lasr_ctc_beam_decode": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _p, _p, _p, _p, _sz, _p]),
+    "lasr_arpa_load": (_i32, [C.c_char_p, _p, _i32, C.POINTER(_p)]),
+    "lasr_arpa_info": (_i32, [_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(_sz)]),
+    "lasr_arpa_write_image": (_i32, [_p, _p, _sz]),
+    "lasr_arpa_free": (None, [_p]),
+    "lasr_ctc_beam_lm_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32]),
+    "lasr_ctc_beam_decode_lm": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _p, _f32, _f32, _p, _p, _p, _p, _p, _sz,
+                                       _p]),
     "lasr_novograd_workspace_bytes": (_sz, [_i64, _i64]),
     "lasr_novograd_step": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p, _f32, _f32, _f32, _f32, _f32, _p, _sz, _p]),
     "lasr_novograd_step_keep": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p, _f32, _f32, _f32, _f32, _f32, _p, _sz, _p]),

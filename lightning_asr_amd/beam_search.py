@@ -1,9 +1,11 @@
 """``BeamSearchDecoderWithLM`` of the reference (beam_search.py:17-57) on the HIP CTC prefix beam search (csrc/ctc_beam.hip).
 
 The reference runs ctc_decoders' ``ctc_beam_search_decoder_batch`` on the host, optionally with a KenLM scorer.  Here the
-search without a scorer runs on the GPU: one launch prunes every frame, one workgroup per utterance searches it.  There is
-no KenLM on this path, so ``lm_path`` must be None (``alpha`` / ``beta`` are kept for the signature); ``num_cpus`` is
-accepted and ignored.  The blank is the class after the vocabulary (ctc_decoders' ``blank_id = vocabulary.size()``)."""
+search runs on the GPU: one launch prunes every frame, one workgroup per utterance searches it.  With ``lm_path`` (a text
+ARPA file of a character n-gram LM, as the reference's ckpt/lm/readme.md trains) the search is fused with that LM:
+``alpha`` weighs its natural-log score, ``beta`` is added per emitted label (ops.load_arpa / ops.ctc_beam_decode_lm); KenLM
+binary models and word-level LMs raise NotImplementedError.  ``num_cpus`` is accepted and ignored.  The blank is the class
+after the vocabulary (ctc_decoders' ``blank_id = vocabulary.size()``)."""
 from __future__ import annotations
 
 from typing import List, Tuple
@@ -18,10 +20,9 @@ class BeamSearchDecoderWithLM(torch.nn.Module):
 
     def __init__(self, vocab, beam_width, alpha, beta, lm_path, num_cpus, cutoff_prob=1.0, cutoff_top_n=40, device="cuda"):
         super().__init__()
-        if lm_path is not None:
-            raise NotImplementedError("language-model scoring (KenLM) is not available: construct the decoder with lm_path=None")
-        self.scorer = None
         self.vocab = list(vocab)
+        # a missing file raises ops.ArpaNotFoundError (FileNotFoundError and NotImplementedError) before any device work
+        self.scorer = None if lm_path is None else ops.load_arpa(lm_path, self.vocab, device, alpha, beta)
         self.beam_width = int(beam_width)
         self.alpha, self.beta = alpha, beta
         self.num_cpus = num_cpus
@@ -31,7 +32,11 @@ class BeamSearchDecoderWithLM(torch.nn.Module):
 
     def search(self, log_probs, log_probs_length, n_best: int = 1):
         """(B, T, C) log-probs (numpy or tensor) + (B) lengths -> (tokens (B, n_best, T), n_tokens (B, n_best), scores (B, n_best))
-        as device tensors (ops.ctc_beam_decode)"""
+        as device tensors (ops.ctc_beam_decode; with an LM the fused scores of ops.ctc_beam_decode_lm)"""
+        return self.search_full(log_probs, log_probs_length, n_best)[:3]
+
+    def search_full(self, log_probs, log_probs_length, n_best: int = 1):
+        """search() plus ctc_decoders' approx_ctc scores (B, n_best) when an LM is fused (None without one)"""
         lp = torch.as_tensor(np.ascontiguousarray(log_probs)) if isinstance(log_probs, np.ndarray) else log_probs
         dev = lp.device if lp.is_cuda else self.device
         lp = lp.to(dev, torch.float32).contiguous()
@@ -41,23 +46,32 @@ class BeamSearchDecoderWithLM(torch.nn.Module):
         if log_probs_length is not None:
             lens = torch.as_tensor(np.asarray(log_probs_length) if not torch.is_tensor(log_probs_length) else log_probs_length)
             lens = lens.to(dev, torch.int32).contiguous()
-        return ops.ctc_beam_decode(lp, lens, len(self.vocab), self.beam_width, self.cutoff_top_n, self.cutoff_prob, n_best)
+        if self.scorer is not None:
+            if self.scorer.image.device != lp.device:
+                self.scorer.image = self.scorer.image.to(lp.device)
+            return ops.ctc_beam_decode_lm(lp, lens, len(self.vocab), self.scorer, self.beam_width, self.cutoff_top_n,
+                                          self.cutoff_prob, n_best, self.alpha, self.beta)
+        return ops.ctc_beam_decode(lp, lens, len(self.vocab), self.beam_width, self.cutoff_top_n, self.cutoff_prob,
+                                   n_best) + (None,)
 
     def _text(self, toks) -> str:
         return "".join(self.vocab[int(c)] for c in toks)
 
     @torch.no_grad()
     def forward(self, log_probs, log_probs_length) -> List[str]:
-        """the best hypothesis of every utterance as text (beam_search.py:31-47)"""
+        """the best hypothesis of every utterance as text (beam_search.py:31-47); with an LM, the best by the fused score"""
         tokens, n, _ = self.search(log_probs, log_probs_length, 1)
         tokens, n = tokens.cpu().numpy(), n.cpu().numpy()
         return [self._text(tokens[b, 0, :max(int(n[b, 0]), 0)]) for b in range(tokens.shape[0])]
 
     @torch.no_grad()
     def decode_nbest(self, log_probs, log_probs_length, n_best=None) -> List[List[Tuple[float, str]]]:
-        """ctc_decoders' output: per utterance [(score, text), ...], best first (up to n_best, default beam_width)"""
+        """ctc_decoders' output: per utterance [(score, text), ...], best first (up to n_best, default beam_width).  With an LM
+        the list is ranked by the fused score and each score is ctc_decoders' approx_ctc."""
         n_best = self.beam_width if n_best is None else int(n_best)
-        tokens, n, scores = self.search(log_probs, log_probs_length, n_best)
+        tokens, n, scores, am = self.search_full(log_probs, log_probs_length, n_best)
+        if am is not None:
+            scores = am
         tokens, n, scores = tokens.cpu().numpy(), n.cpu().numpy(), scores.cpu().numpy()
         return [[(float(scores[b, j]), self._text(tokens[b, j, :n[b, j]])) for j in range(n_best) if n[b, j] >= 0]
                 for b in range(tokens.shape[0])]

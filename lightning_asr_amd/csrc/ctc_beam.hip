@@ -464,3 +464,533 @@ extern "C" int lasr_ctc_beam_decode(const float* logp, const int32_t* lens, int6
   LASR_LAUNCH_CHECK("beam_search_kernel");
   return 0;
 }
+
+// ================================================================== with an n-gram LM ===================================
+// lasr_ctc_beam_decode_lm: the same search with ctc_decoders' character-based Scorer (include/lasr.h states the contract).
+// The prune launch is the one above.  The search keeps each entry's ACOUSTIC log_b / log_nb and beside them its LM bonus
+// (alpha * sum of lm + beta * labels, which depends on the prefix alone, so merging stays exact), its own emission term, the
+// LM word ids of its last N-1 labels and the backoff sums of its context chain.  An extension p -> p+c scores
+// lm(c | ctx(p)) = log10 p(longest stored (x_m .. x_1 c)) + sum of the backoffs of the longer stored contexts, found by a walk
+// leftward from c through the image's hash, one probe per word; the probes of a thread's candidates go out together.
+#include "arpa_io.h"
+
+namespace lasr {
+namespace {
+
+constexpr int kLmMaxCtx = host::kArpaMaxOrder - 1;
+constexpr int kLmGroup = 4;                  // candidates per thread whose probes are in flight together
+constexpr float kLmOov = -1000.f;            // ctc_decoders' OOV_SCORE (natural log, not converted)
+constexpr float kLmLogE = 0.4342944819f;     // ctc_decoders' NUM_FLT_LOGE: log10 -> natural log by division
+
+__device__ __forceinline__ uint64_t lm_hash(uint64_t k) {   // == host::arpa_hash
+  k = (k ^ (k >> 30)) * 0xbf58476d1ce4e5b9ull;
+  k = (k ^ (k >> 27)) * 0x94d049bb133111ebull;
+  return k ^ (k >> 31);
+}
+
+struct LmImg {
+  const float2* uni;
+  const int32_t* cls;
+  const uint4* slot;          // ArpaSlot as (key lo, key hi, lp bits, bow bits)
+  uint32_t mask, n_words, n_classes;
+  int nctx, bos, eos;
+  bool ok;
+};
+
+__device__ __forceinline__ LmImg lm_open(const void* image) {
+  const host::ArpaImageHeader* h = static_cast<const host::ArpaImageHeader*>(image);
+  const char* base = static_cast<const char*>(image);
+  LmImg m;
+  m.ok = h->magic == host::kArpaImageMagic && h->order >= 1 && h->order <= (uint32_t)host::kArpaMaxOrder &&
+         h->log2_slots >= 4 && h->log2_slots < 32;
+  m.uni = reinterpret_cast<const float2*>(base + h->uni_off);
+  m.cls = reinterpret_cast<const int32_t*>(base + h->cls_off);
+  m.slot = reinterpret_cast<const uint4*>(base + h->slot_off);
+  m.mask = m.ok ? (1u << h->log2_slots) - 1u : 0u;
+  m.n_words = h->n_words;
+  m.n_classes = h->n_classes;
+  m.nctx = m.ok ? (int)h->order - 1 : 0;
+  m.bos = h->bos < h->n_words ? (int)h->bos : -1;
+  m.eos = h->eos < h->n_words ? (int)h->eos : -1;
+  return m;
+}
+
+// one probe for (suffix index g, word w): slot index + n_words of the stored n-gram, or -1; v = its slot
+__device__ __forceinline__ int64_t lm_probe_rest(const LmImg& m, uint64_t key, uint32_t at, uint4 v, uint4* out) {
+  while (true) {
+    const uint64_t k = (uint64_t)v.x | ((uint64_t)v.y << 32);
+    if (k == key) { *out = v; return (int64_t)m.n_words + at; }
+    if (k == host::kArpaEmptyKey) return -1;
+    at = (at + 1) & m.mask;
+    v = m.slot[at];
+  }
+}
+
+__device__ __forceinline__ int64_t lm_probe(const LmImg& m, int64_t g, int w, uint4* out) {
+  const uint64_t key = ((uint64_t)g << 32) | (uint32_t)w;
+  const uint32_t at = (uint32_t)lm_hash(key) & m.mask;
+  return lm_probe_rest(m, key, at, m.slot[at], out);
+}
+
+// natural-log lm(w | ctx) from an entry's context ids (nearest first) and backoff sums; the single-chain form
+__device__ float lm_score_one(const LmImg& m, int w, const int* ctx, const float* cb) {
+  if (w < 0) return kLmOov;
+  for (int d = 0; d < m.nctx; ++d)
+    if (ctx[d] < 0) return kLmOov;
+  int64_t g = w;
+  float lp = m.uni[w].x;
+  int mm = 0;
+  for (int d = 0; d < m.nctx; ++d) {
+    uint4 v;
+    const int64_t f = lm_probe(m, g, ctx[d], &v);
+    if (f < 0) break;
+    g = f;
+    lp = __uint_as_float(v.z);
+    mm = d + 1;
+  }
+  return (lp + cb[mm]) / kLmLogE;
+}
+
+// the backoff sums of the context (w, ctx[0], .., ctx[nctx-2]) - the context of an entry whose last label is w
+__device__ void lm_context_sums(const LmImg& m, int w, const int* ctx, float* cb) {
+  float bows[kLmMaxCtx + 1];
+  for (int j = 0; j <= kLmMaxCtx; ++j) bows[j] = 0.f;
+  if (w >= 0 && m.nctx > 0) {
+    bows[1] = m.uni[w].y;
+    int64_t g = w;
+    for (int d = 1; d < m.nctx; ++d) {
+      if (ctx[d - 1] < 0) break;
+      uint4 v;
+      const int64_t f = lm_probe(m, g, ctx[d - 1], &v);
+      if (f < 0) break;
+      g = f;
+      bows[d + 1] = __uint_as_float(v.w);
+    }
+  }
+  float acc = 0.f;
+  cb[m.nctx] = 0.f;
+  for (int j = m.nctx - 1; j >= 0; --j) {
+    acc += bows[j + 1];
+    cb[j] = acc;
+  }
+}
+
+struct BeamLmLds {
+  int node[2][kBeamMaxWidth], last[2][kBeamMaxWidth], len[2][kBeamMaxWidth];
+  float b[2][kBeamMaxWidth], nb[2][kBeamMaxWidth];       // acoustic
+  float bonus[2][kBeamMaxWidth], term[2][kBeamMaxWidth]; // alpha * sum lm + beta * labels; the last label's own term
+  int ctx[2][kLmMaxCtx][kBeamMaxWidth];                  // LM word ids of the last N-1 labels, nearest first (-1 = OOV)
+  float cb[2][kLmMaxCtx + 1][kBeamMaxWidth];             // cb[j]: log10 backoffs of the stored contexts longer than j words
+  uint64_t h[2][kBeamMaxWidth], ph[2][kBeamMaxWidth];
+  float score[kBeamMaxWidth], ascore[kBeamMaxWidth];    // fused and acoustic logaddexp(b, nb) of the current beam
+  float next_b[kBeamMaxWidth], next_nb[kBeamMaxWidth];
+  unsigned long long merged[kBeamMaxWidth];
+  uint64_t surv[kBeamMaxWidth];
+  int surv_i[kBeamMaxWidth];
+  float surv_t[kBeamMaxWidth];                           // emission term of a surviving extension
+  int kcls[kBeamMaxTopN], kwid[kBeamMaxTopN];
+  float klp[kBeamMaxTopN];
+  uint32_t hist[256];
+  uint32_t found[4];
+  uint32_t nsel;
+  int ctx_oov[kBeamMaxWidth];
+};
+
+template <int J>
+__global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
+    const float* __restrict__ logp, const int32_t* __restrict__ kcls_g, const float* __restrict__ klp_g,
+    const int32_t* __restrict__ kn_g, const int32_t* __restrict__ lens, int64_t T, int C, int blank, int W, int n_best,
+    const void* __restrict__ image, float alpha, float beta, int2* __restrict__ trie_g, int32_t* __restrict__ tokens,
+    int32_t* __restrict__ n_tokens, float* __restrict__ scores, float* __restrict__ am_scores) {
+  __shared__ BeamLmLds s;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t ub = blockIdx.x;
+  const LmImg lm = lm_open(image);
+  const int64_t L = !lm.ok ? 0 : lens ? min((int64_t)max(lens[ub], 0), T) : T;
+  const int nctx = lm.nctx;
+  int2* trie = trie_g + ub * (1 + T * (int64_t)W);
+  const int32_t* kc = kcls_g + ub * T * kBeamMaxTopN;
+  const float* kl = klp_g + ub * T * kBeamMaxTopN;
+  const int32_t* knf = kn_g + ub * T;
+  const float* lrow = logp + ub * T * (int64_t)C;
+  const float cut_beta = fmaxf(0.f, beta);
+  if (tid == 0) {
+    s.node[0][0] = 0; s.last[0][0] = -1; s.len[0][0] = 0;
+    s.b[0][0] = 0.f; s.nb[0][0] = kNegInfB;
+    s.bonus[0][0] = 0.f; s.term[0][0] = 0.f;
+    s.h[0][0] = kRootHash; s.ph[0][0] = 0;
+    int rc[kLmMaxCtx];
+    float cb[kLmMaxCtx + 1];
+    for (int d = 0; d < kLmMaxCtx; ++d) rc[d] = lm.bos;
+    if (lm.ok) lm_context_sums(lm, lm.bos, rc, cb);
+    for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[0][d][0] = lm.bos;
+    for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[0][d][0] = lm.ok ? cb[d] : 0.f;
+  }
+  for (int i = tid; i < 256; i += kSearchThreads) s.hist[i] = 0;
+  int nbeam = 1, cur = 0;
+  int pc = 0, pn = 0;
+  float pl = 0.f, pblank = 0.f;
+  if (L > 0) {
+    if (tid < kBeamMaxTopN) { pc = kc[tid]; pl = kl[tid]; }
+    pn = knf[0];
+    pblank = lrow[blank];
+  }
+  for (int64_t t = 0; t < L; ++t) {
+    const int nk = pn;
+    const float lblank = pblank;        // the frame's unpruned blank log-prob (the early cutoff's reference)
+    if (tid < nk) {
+      s.kcls[tid] = pc; s.klp[tid] = pl;
+      s.kwid[tid] = (pc != blank && pc >= 0 && (uint32_t)pc < lm.n_classes) ? lm.cls[pc] : -1;
+    }
+    if (t + 1 < L) {
+      if (tid < kBeamMaxTopN) { pc = kc[(t + 1) * kBeamMaxTopN + tid]; pl = kl[(t + 1) * kBeamMaxTopN + tid]; }
+      pn = knf[t + 1];
+      pblank = lrow[(t + 1) * (int64_t)C + blank];
+    }
+    if (tid == 0) s.nsel = 0;
+    __syncthreads();
+    // (1) per live prefix: scores, kept index of its last label and of the blank, its parent among the live entries
+    int lastk = -1, pr = -1;
+    float blp = kNegInfB;
+    if (tid < nbeam) {
+      const int last = s.last[cur][tid];
+      const float as = lae(s.b[cur][tid], s.nb[cur][tid]);
+      s.ascore[tid] = as;
+      s.score[tid] = as + s.bonus[cur][tid];
+      s.merged[tid] = 0ull;
+      int oov = 0;
+      for (int d = 0; d < nctx; ++d) oov |= s.ctx[cur][d][tid] < 0;
+      s.ctx_oov[tid] = oov;
+      for (int k = 0; k < nk; ++k) {
+        const int c = s.kcls[k];
+        if (c == last) lastk = k;
+        if (c == blank) blp = s.klp[k];
+      }
+      if (last >= 0) {
+        const uint64_t ph = s.ph[cur][tid];
+        for (int r = 0; r < nbeam; ++r)
+          if (s.h[cur][r] == ph) { pr = r; break; }
+      }
+    }
+    __syncthreads();
+    // the early cutoff: with a full beam, (p, c) contributes nothing where score(p) + logp[c] < min_cutoff
+    const float min_cutoff = nbeam == W ? s.score[W - 1] + lblank - cut_beta : kNegInfB;
+    // (2) "no new label" candidates (acoustic), with the parent's extension by the last label folded in
+    if (tid < nbeam) {
+      const float asc = s.ascore[tid];
+      float nbn = kNegInfB;
+      if (lastk >= 0) {
+        const float lc = s.klp[lastk];
+        if (!(s.score[tid] + lc < min_cutoff)) nbn = lc + s.nb[cur][tid];
+        if (pr >= 0) {
+          if (!(s.score[pr] + lc < min_cutoff))
+            nbn = lae(nbn, lc + (s.last[cur][tid] == s.last[cur][pr] ? s.b[cur][pr] : s.ascore[pr]));
+          atomicOr(&s.merged[pr], 1ull << lastk);
+        }
+      }
+      s.next_b[tid] = blp + asc;
+      s.next_nb[tid] = nbn;
+    }
+    __syncthreads();
+    // (3) candidates with fused scores; the LM probes of kLmGroup extensions per thread are issued together
+    const int ncand = nbeam + nbeam * nk;
+    uint64_t comp[J];
+    float term[J];
+    uint64_t valid = 0;
+#pragma unroll
+    for (int j0 = 0; j0 < J; j0 += kLmGroup) {
+      float am[kLmGroup], lpv[kLmGroup];
+      int64_t g[kLmGroup];
+      int mm[kLmGroup], pp[kLmGroup], wc[kLmGroup];
+      bool act[kLmGroup], ext[kLmGroup];
+#pragma unroll
+      for (int u = 0; u < kLmGroup; ++u) {
+        const int j = j0 + u;
+        am[u] = kNegInfB; lpv[u] = 0.f; g[u] = 0; mm[u] = 0; pp[u] = 0; wc[u] = -1; act[u] = false; ext[u] = false;
+        if (j >= J) continue;
+        const int i = tid + j * kSearchThreads;
+        if (i < nbeam) {
+          am[u] = lae(s.next_b[i], s.next_nb[i]) + s.bonus[cur][i];
+        } else if (i < ncand) {
+          const int q = i - nbeam, p = q / nk, k = q - p * nk;
+          const int c = s.kcls[k];
+          pp[u] = p;
+          if (c != blank && !((s.merged[p] >> k) & 1ull) && !(s.score[p] + s.klp[k] < min_cutoff)) {
+            am[u] = s.klp[k] + (c == s.last[cur][p] ? s.b[cur][p] : s.ascore[p]);
+            ext[u] = am[u] > kNegInfB;
+            wc[u] = s.kwid[k];
+            if (ext[u] && wc[u] >= 0 && !s.ctx_oov[p]) {
+              g[u] = wc[u];
+              lpv[u] = lm.uni[wc[u]].x;
+              act[u] = nctx > 0;
+            }
+          }
+        }
+      }
+      for (int d = 0; d < nctx; ++d) {
+        uint64_t key[kLmGroup];
+        uint32_t at[kLmGroup];
+        uint4 v[kLmGroup];
+#pragma unroll
+        for (int u = 0; u < kLmGroup; ++u) {
+          if (!act[u]) continue;
+          key[u] = ((uint64_t)g[u] << 32) | (uint32_t)s.ctx[cur][d][pp[u]];
+          at[u] = (uint32_t)lm_hash(key[u]) & lm.mask;
+          v[u] = lm.slot[at[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < kLmGroup; ++u) {
+          if (!act[u]) continue;
+          uint4 hit;
+          const int64_t f = lm_probe_rest(lm, key[u], at[u], v[u], &hit);
+          if (f < 0) {
+            act[u] = false;
+          } else {
+            g[u] = f;
+            lpv[u] = __uint_as_float(hit.z);
+            mm[u] = d + 1;
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kLmGroup; ++u) {
+        const int j = j0 + u;
+        if (j >= J) continue;
+        const int i = tid + j * kSearchThreads;
+        float sc = am[u];
+        uint32_t key = 0;
+        term[j] = 0.f;
+        if (i < nbeam) {
+          key = (uint32_t)i << 14;
+        } else if (i < ncand) {
+          const int q = i - nbeam, p = pp[u], k = q - p * nk;
+          key = ((uint32_t)p << 14) | (uint32_t)(s.kcls[k] + 1);
+          if (ext[u]) {
+            const bool oov = wc[u] < 0 || s.ctx_oov[p];
+            const float lmv = oov ? kLmOov : (lpv[u] + s.cb[cur][mm[u]][p]) / kLmLogE;
+            term[j] = alpha * lmv + beta;
+            sc = am[u] + (s.bonus[cur][p] + term[j]);
+          }
+        }
+        comp[j] = ((uint64_t)desc_bits(sc) << 32) | key;
+        if (sc > kNegInfB) valid |= 1ull << j;
+      }
+    }
+    // (4) radix select of the W smallest composites (as in beam_search_kernel)
+    uint64_t prefix = 0, mask = 0;
+    uint32_t need = (uint32_t)W;
+    for (int ps = 0; ps < 7; ++ps) {
+      const int sh = ps < 4 ? 56 - 8 * ps : 16 - 8 * (ps - 4);
+#pragma unroll
+      for (int j = 0; j < J; ++j)
+        wave_hist_add(s.hist, ((valid >> j) & 1ull) && (comp[j] & mask) == prefix, (uint32_t)(comp[j] >> sh) & 255u, lane);
+      __syncthreads();
+      if (tid < 64) wave_find_bucket(s.hist, need, lane, s.found);
+      __syncthreads();
+      if (ps == 0 && s.found[3] <= need) break;
+      const uint32_t bucket = s.found[0], before = s.found[1], cnt = s.found[2];
+      prefix |= (uint64_t)bucket << sh;
+      mask |= 0xffull << sh;
+      need -= before;
+      if (cnt == need) break;
+    }
+    // (5) compact, order, write the next beam
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      if (((valid >> j) & 1ull) && (comp[j] & mask) <= prefix) {
+        const uint32_t pos = atomicAdd(&s.nsel, 1u);
+        if (pos < (uint32_t)kBeamMaxWidth) {
+          s.surv[pos] = comp[j];
+          s.surv_i[pos] = tid + j * kSearchThreads;
+          s.surv_t[pos] = term[j];
+        }
+      }
+    }
+    __syncthreads();
+    const int nsel = min((int)s.nsel, W);
+    const int nxt = cur ^ 1;
+    if (tid < nsel) {
+      const uint64_t me = s.surv[tid];
+      int rank = 0;
+      for (int r = 0; r < nsel; ++r) rank += s.surv[r] < me;
+      const int i = s.surv_i[tid];
+      if (i < nbeam) {
+        s.node[nxt][rank] = s.node[cur][i]; s.last[nxt][rank] = s.last[cur][i]; s.len[nxt][rank] = s.len[cur][i];
+        s.h[nxt][rank] = s.h[cur][i]; s.ph[nxt][rank] = s.ph[cur][i];
+        s.b[nxt][rank] = s.next_b[i]; s.nb[nxt][rank] = s.next_nb[i];
+        s.bonus[nxt][rank] = s.bonus[cur][i]; s.term[nxt][rank] = s.term[cur][i];
+        for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[nxt][d][rank] = s.ctx[cur][d][i];
+        for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[nxt][d][rank] = s.cb[cur][d][i];
+      } else {
+        const int q = i - nbeam, p = q / nk, k = q - p * nk;
+        const int c = s.kcls[k];
+        const int node = 1 + (int)t * W + rank;
+        const float tm = s.surv_t[tid];
+        trie[node] = make_int2(s.node[cur][p], c);
+        s.node[nxt][rank] = node; s.last[nxt][rank] = c; s.len[nxt][rank] = s.len[cur][p] + 1;
+        s.h[nxt][rank] = child_hash(s.h[cur][p], c); s.ph[nxt][rank] = s.h[cur][p];
+        s.b[nxt][rank] = kNegInfB;
+        s.nb[nxt][rank] = s.klp[k] + (c == s.last[cur][p] ? s.b[cur][p] : s.ascore[p]);
+        s.bonus[nxt][rank] = s.bonus[cur][p] + tm; s.term[nxt][rank] = tm;
+        int nc[kLmMaxCtx];
+        float cb[kLmMaxCtx + 1];
+        const int w = s.kwid[k];
+        nc[0] = w;
+        for (int d = 1; d < kLmMaxCtx; ++d) nc[d] = s.ctx[cur][d - 1][p];
+        lm_context_sums(lm, w, nc + 1, cb);
+        for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[nxt][d][rank] = nc[d];
+        for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[nxt][d][rank] = d <= nctx ? cb[d] : 0.f;
+      }
+    }
+    nbeam = nsel;
+    cur = nxt;
+    __syncthreads();
+  }
+  __threadfence();
+  __syncthreads();
+  int32_t* tok = tokens + ub * (int64_t)n_best * T;
+  if (tid < n_best) {
+    const int64_t o = ub * n_best + tid;
+    if (lm.ok && tid < nbeam) {
+      const int n = s.len[cur][tid];
+      const float as = lae(s.b[cur][tid], s.nb[cur][tid]);
+      int cx[kLmMaxCtx];
+      float cb[kLmMaxCtx + 1];
+      for (int d = 0; d < kLmMaxCtx; ++d) cx[d] = s.ctx[cur][d][tid];
+      for (int d = 0; d <= kLmMaxCtx; ++d) cb[d] = s.cb[cur][d][tid];
+      // ctc_decoders' approx_ctc = fused - k beta - alpha sent_lm: the emission terms cancel, the </s> window remains (and the
+      // <s> window of <s>^N </s> for an empty hypothesis)
+      float sent = lm_score_one(lm, lm.eos, cx, cb);
+      if (n == 0) sent += lm_score_one(lm, lm.bos, cx, cb);
+      n_tokens[o] = n;
+      scores[o] = as + s.bonus[cur][tid];
+      am_scores[o] = as - alpha * sent;
+      int node = s.node[cur][tid];
+      for (int pos = n - 1; pos >= 0; --pos) {
+        const int2 e = trie[node];
+        tok[(int64_t)tid * T + pos] = e.y;
+        node = e.x;
+      }
+    } else {
+      n_tokens[o] = -1;
+      scores[o] = kNegInfB;
+      am_scores[o] = kNegInfB;
+    }
+  }
+  for (int64_t idx = tid; idx < (int64_t)n_best * T; idx += kSearchThreads) {
+    const int j = (int)(idx / T);
+    const int64_t pos = idx - (int64_t)j * T;
+    const int n = (lm.ok && j < nbeam) ? s.len[cur][j] : 0;
+    if (pos >= n) tok[idx] = -1;
+  }
+}
+
+template <int J>
+void launch_search_lm(dim3 grid, hipStream_t st, const float* logp, const int32_t* kc, const float* kl, const int32_t* kn,
+                      const int32_t* lens, int64_t T, int C, int blank, int W, int n_best, const void* image, float alpha, float beta,
+                      int2* trie, int32_t* tokens, int32_t* n_tokens, float* scores, float* am_scores) {
+  hipLaunchKernelGGL(beam_search_lm_kernel<J>, grid, dim3(kSearchThreads), 0, st, logp, kc, kl, kn, lens, T, C, blank, W, n_best,
+                     image, alpha, beta, trie, tokens, n_tokens, scores, am_scores);
+}
+
+struct ArpaHandle {
+  host::ArpaModel m;
+};
+
+int arpa_code(int rc) {
+  switch (rc) {
+    case host::kArpaErrFormat: return LASR_E_FORMAT;
+    case host::kArpaErrUnsupported: return LASR_E_UNSUPPORTED;
+    case host::kArpaErrOpen: return LASR_E_IO;
+    default: return LASR_E_ARG;
+  }
+}
+
+}  // namespace
+}  // namespace lasr
+
+extern "C" int lasr_arpa_load(const char* path, const char* const* vocab, int n_vocab, void** handle) {
+  LASR_CHECK_ARG(path && handle && (vocab || n_vocab == 0) && n_vocab >= 0, "lasr_arpa_load: null pointer or negative n_vocab");
+  *handle = nullptr;
+  ArpaHandle* h = new ArpaHandle();
+  std::string err;
+  const int rc = host::arpa_load(path, vocab, n_vocab, &h->m, &err);   // arpa_io.h (also built under ASan / UBSan)
+  if (rc != host::kArpaOk) {
+    delete h;
+    return fail(arpa_code(rc), "lasr_arpa_load: %s", err.c_str());
+  }
+  *handle = h;
+  return 0;
+}
+
+extern "C" int lasr_arpa_info(const void* handle, int* order, int* char_based, int64_t* n_ngrams, size_t* image_bytes) {
+  LASR_CHECK_ARG(handle, "lasr_arpa_info: null handle");
+  const host::ArpaModel& m = static_cast<const ArpaHandle*>(handle)->m;
+  if (order) *order = m.order;
+  if (char_based) *char_based = m.char_based ? 1 : 0;
+  if (n_ngrams) *n_ngrams = m.n_ngrams;
+  if (image_bytes) *image_bytes = m.image.size();
+  return 0;
+}
+
+extern "C" int lasr_arpa_write_image(const void* handle, void* host_dst, size_t bytes) {
+  LASR_CHECK_ARG(handle && host_dst, "lasr_arpa_write_image: null pointer");
+  const host::ArpaModel& m = static_cast<const ArpaHandle*>(handle)->m;
+  if (bytes < m.image.size())
+    return fail(LASR_E_WORKSPACE, "lasr_arpa_write_image: %zu < %zu bytes", bytes, m.image.size());
+  memcpy(host_dst, m.image.data(), m.image.size());
+  return 0;
+}
+
+extern "C" void lasr_arpa_free(void* handle) { delete static_cast<ArpaHandle*>(handle); }
+
+extern "C" size_t lasr_ctc_beam_lm_workspace_bytes(int64_t B, int64_t T, int64_t C, int beam_width, int cutoff_top_n) {
+  if (!beam_shape_ok(B, T, C, beam_width, cutoff_top_n)) return 0;
+  return beam_ws(B, T, beam_width).total;
+}
+
+extern "C" int lasr_ctc_beam_decode_lm(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
+                                       int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image,
+                                       float alpha, float beta, int32_t* tokens, int32_t* n_tokens, float* scores,
+                                       float* am_scores, void* workspace, size_t workspace_bytes, void* stream) {
+  LASR_CHECK_ARG(logp && lm_image && tokens && n_tokens && scores && am_scores && workspace,
+                 "lasr_ctc_beam_decode_lm: null pointer");
+  LASR_CHECK_ARG(n_best >= 1 && n_best <= beam_width, "lasr_ctc_beam_decode_lm: n_best %d outside [1, beam_width %d]", n_best,
+                 beam_width);
+  LASR_CHECK_ARG(cutoff_prob > 0.f && cutoff_prob <= 1.f, "lasr_ctc_beam_decode_lm: cutoff_prob %g outside (0, 1]",
+                 (double)cutoff_prob);
+  LASR_CHECK_ARG(C >= 1 && blank >= 0 && blank < C, "lasr_ctc_beam_decode_lm: blank %d outside [0, C = %lld)", blank, (long long)C);
+  LASR_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "lasr_ctc_beam_decode_lm: alpha %g / beta %g not finite",
+                 (double)alpha, (double)beta);
+  LASR_CHECK_SHAPE(beam_shape_ok(B, T, C, beam_width, cutoff_top_n),
+                   "lasr_ctc_beam_decode_lm: B %lld T %lld C %lld beam_width %d cutoff_top_n %d outside the supported range "
+                   "(C <= %d, beam_width 1..%d, cutoff_top_n 1..%d)", (long long)B, (long long)T, (long long)C, beam_width,
+                   cutoff_top_n, kBeamMaxClasses, kBeamMaxWidth, kBeamMaxTopN);
+  const BeamWs w = beam_ws(B, T, beam_width);
+  if (workspace_bytes < w.total)
+    return fail(LASR_E_WORKSPACE, "lasr_ctc_beam_decode_lm: workspace %zu < %zu bytes", workspace_bytes, w.total);
+  char* ws = static_cast<char*>(workspace);
+  int32_t* kc = reinterpret_cast<int32_t*>(ws + w.kcls);
+  float* kl = reinterpret_cast<float*>(ws + w.klp);
+  int32_t* kn = reinterpret_cast<int32_t*>(ws + w.kn);
+  int2* trie = reinterpret_cast<int2*>(ws + w.trie);
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(beam_prune_kernel, dim3((unsigned)(B * T)), dim3(64), 0, st, logp, lens, T, (int)C, cutoff_top_n, cutoff_prob,
+                     kc, kl, kn);
+  LASR_LAUNCH_CHECK("beam_prune_kernel");
+  const int K = (int)(C < cutoff_top_n ? C : cutoff_top_n);
+  const int per = (int)cdiv((int64_t)beam_width * (K + 1), kSearchThreads);
+  const dim3 grid((unsigned)B);
+#define LASR_LM_LAUNCH(JJ)                                                                                                     \
+  launch_search_lm<JJ>(grid, st, logp, kc, kl, kn, lens, T, (int)C, blank, beam_width, n_best, lm_image, alpha, beta, trie, tokens, \
+                       n_tokens, scores, am_scores)
+  if (per <= 1) LASR_LM_LAUNCH(1);
+  else if (per <= 2) LASR_LM_LAUNCH(2);
+  else if (per <= 4) LASR_LM_LAUNCH(4);
+  else if (per <= 8) LASR_LM_LAUNCH(8);
+  else if (per <= 16) LASR_LM_LAUNCH(16);
+  else LASR_LM_LAUNCH(33);
+#undef LASR_LM_LAUNCH
+  LASR_LAUNCH_CHECK("beam_search_lm_kernel");
+  return 0;
+}

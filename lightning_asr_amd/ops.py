@@ -3,6 +3,9 @@ stream; every computation below is a liblasr.so (HIP, gfx950) call.  Tensors mus
 there is no CPU path."""
 from __future__ import annotations
 
+import ctypes
+import math
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -452,6 +455,115 @@ def ctc_beam_decode(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: int
     call("lasr_ctc_beam_decode", _p(logp), _p(lens), B, T, Cc, int(blank), int(beam_width), int(cutoff_top_n), float(cutoff_prob),
          int(n_best), _p(tokens), _p(n), _p(scores), _p(ws), nb, _stream())
     return tokens, n, scores
+
+
+ARPA_MAX_ORDER = 6
+_E_FORMAT, _E_UNSUPPORTED, _E_IO = -4, -5, -6      # LASR_E_FORMAT / LASR_E_UNSUPPORTED / LASR_E_IO (include/lasr.h)
+
+
+class ArpaNotFoundError(FileNotFoundError, NotImplementedError):
+    """lm_path names no file.  Also a NotImplementedError, which is what a decoder without LM support raised for any lm_path."""
+
+
+class ArpaLm:
+    """A character n-gram LM read from a text ARPA file (load_arpa): the device image lasr_ctc_beam_decode_lm reads, its order and
+    the weights the decoder applies (alpha on the natural-log LM score, beta per emitted label)."""
+
+    def __init__(self, image: torch.Tensor, order: int, char_based: bool, n_ngrams: int, vocab, alpha: float, beta: float):
+        self.image = image
+        self.order = int(order)
+        self._char_based = bool(char_based)
+        self.n_ngrams = int(n_ngrams)
+        self.vocab = list(vocab)
+        self.alpha, self.beta = float(alpha), float(beta)
+
+    def is_character_based(self) -> bool:
+        return self._char_based
+
+    def __repr__(self):
+        return "ArpaLm(order=%d, n_ngrams=%d, %d bytes on %s, alpha=%g, beta=%g)" % (
+            self.order, self.n_ngrams, self.image.numel(), self.image.device, self.alpha, self.beta)
+
+
+def load_arpa(path, vocab, device="cuda", alpha: float = 1.0, beta: float = 1.0) -> ArpaLm:
+    """Read a text ARPA LM for the class strings `vocab` (class c is vocab[c]; the blank is not part of it) and copy its image to
+    `device`.  A missing file raises ArpaNotFoundError, one that cannot be read OSError; a word-level LM or a KenLM binary model
+    NotImplementedError; a malformed file, or an order outside 1..6, ValueError naming the line."""
+    import numpy as np
+    path = os.fspath(path)
+    if not os.path.isfile(path):
+        raise ArpaNotFoundError("no ARPA language model at %r" % (path,))
+    lib = _lib.load()
+    words = [str(w).encode("utf-8") for w in vocab]
+    arr = (ctypes.c_char_p * max(len(words), 1))(*words)
+    h = ctypes.c_void_p()
+    rc = lib.lasr_arpa_load(os.fsencode(path), ctypes.cast(arr, ctypes.c_void_p), len(words), ctypes.byref(h))
+    if rc != 0:
+        msg = lib.lasr_last_error().decode(errors="replace")
+        if rc == _E_UNSUPPORTED:
+            raise NotImplementedError(msg)
+        if rc == _E_IO:
+            raise OSError(msg)
+        raise ValueError(msg)
+    try:
+        order, cb, n, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_size_t()
+        call("lasr_arpa_info", h, ctypes.byref(order), ctypes.byref(cb), ctypes.byref(n), ctypes.byref(nb))
+        if not cb.value:
+            raise NotImplementedError("%s is a word-level LM: only character-based LMs are supported (a word-level LM needs a "
+                                      "space label and a dictionary FST)" % (path,))
+        host = np.empty(int(nb.value), dtype=np.uint8)
+        call("lasr_arpa_write_image", h, host.ctypes.data, int(nb.value))
+    finally:
+        lib.lasr_arpa_free(h)
+    image = torch.from_numpy(host).to(device)
+    return ArpaLm(image, order.value, True, n.value, vocab, alpha, beta)
+
+
+def ctc_beam_decode_lm(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: int, lm: ArpaLm, beam_width: int = 16,
+                       cutoff_top_n: int = 40, cutoff_prob: float = 1.0, n_best: int = 1, alpha: Optional[float] = None,
+                       beta: Optional[float] = None):
+    """ctc_beam_decode fused with the character n-gram LM `lm` (load_arpa; alpha / beta default to lm's).  Returns (tokens, n_tokens,
+    scores, am_scores): scores are the fused log-scores the hypotheses are ranked by, am_scores ctc_decoders' approx_ctc
+    (fused - labels * beta - alpha * sentence LM score).  Shapes and ranges as ctc_beam_decode; the image must sit on logp's
+    device and hold C - 1 labels."""
+    if logp.dtype != torch.float32 or logp.dim() != 3:
+        raise TypeError("ctc_beam_decode_lm takes (B, T, C) float32 log-probs")
+    if not isinstance(lm, ArpaLm):
+        raise TypeError("lm must be an ArpaLm (ops.load_arpa)")
+    B, T, Cc = logp.shape
+    alpha = lm.alpha if alpha is None else float(alpha)
+    beta = lm.beta if beta is None else float(beta)
+    cutoff_top_n = min(int(cutoff_top_n), Cc) if Cc >= 1 else int(cutoff_top_n)
+    if not 1 <= beam_width <= CTC_BEAM_MAX_WIDTH:
+        raise ValueError("beam_width %d outside 1..%d" % (beam_width, CTC_BEAM_MAX_WIDTH))
+    if not 1 <= cutoff_top_n <= CTC_BEAM_MAX_TOP_N:
+        raise ValueError("cutoff_top_n %d outside 1..%d" % (cutoff_top_n, CTC_BEAM_MAX_TOP_N))
+    if not 1 <= Cc <= CTC_BEAM_MAX_CLASSES:
+        raise ValueError("%d classes: the beam decoder takes at most %d" % (Cc, CTC_BEAM_MAX_CLASSES))
+    if not 1 <= n_best <= beam_width:
+        raise ValueError("n_best %d outside 1..beam_width (%d)" % (n_best, beam_width))
+    if not 0.0 < cutoff_prob <= 1.0:
+        raise ValueError("cutoff_prob %r outside (0, 1]" % (cutoff_prob,))
+    if not 0 <= blank < Cc:
+        raise ValueError("blank %d outside [0, %d)" % (blank, Cc))
+    if not (math.isfinite(alpha) and math.isfinite(beta)):
+        raise ValueError("alpha %r / beta %r must be finite" % (alpha, beta))
+    if len(lm.vocab) != Cc - 1:
+        raise ValueError("the LM was loaded for %d labels; the log-probs have %d classes" % (len(lm.vocab), Cc))
+    if lm.image.device != logp.device:
+        raise ValueError("the LM image is on %s, the log-probs on %s" % (lm.image.device, logp.device))
+    nb = int(_lib.load().lasr_ctc_beam_lm_workspace_bytes(B, T, Cc, beam_width, cutoff_top_n))
+    if nb == 0:
+        raise ValueError("ctc_beam_decode_lm: shape (%d, %d, %d) outside the kernel's range" % (B, T, Cc))
+    dev = logp.device
+    tokens = torch.empty(B, n_best, T, dtype=torch.int32, device=dev)
+    n = torch.empty(B, n_best, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+    am = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+    ws = _ws(nb, dev)
+    call("lasr_ctc_beam_decode_lm", _p(logp), _p(lens), B, T, Cc, int(blank), int(beam_width), int(cutoff_top_n), float(cutoff_prob),
+         int(n_best), _p(lm.image), alpha, beta, _p(tokens), _p(n), _p(scores), _p(am), _p(ws), nb, _stream())
+    return tokens, n, scores, am
 
 
 # ---------------------------------------------------------------------------------- optimiser

@@ -1,6 +1,7 @@
 """Inference surface of the reference (predict.py:21-74): checkpoint -> ``AsrTranslator.translate`` and
 manifest evaluation, on the HIP path (mel front-end, eval-mode model forward, greedy CTC decode - or, with
-``decoder="beam"``, the CTC prefix beam search of beam_search.py without a language model).
+``decoder="beam"``, the CTC prefix beam search of beam_search.py, fused with a character n-gram LM when ``lm_path`` names
+a text ARPA file).
 
 The checkpoint is the PL-style dict the reference's ``ModelCheckpoint`` writes and ``Trainer`` here
 writes too: ``state_dict`` with the reference's key names (``encoder.encoder.block1.seq.0...``) and
@@ -26,10 +27,11 @@ EN_LABELS = [" ", "'"] + [chr(ord("a") + i) for i in range(26)]
 class AsrTranslator:
     def __init__(self, model_path: str, map_location: str = "cuda", lang: str = "en", labels: Optional[List[str]] = None,
                  verbose: bool = False, decoder: str = "greedy", beam_width: int = 16, cutoff_top_n: int = 40,
-                 cutoff_prob: float = 1.0):
+                 cutoff_prob: float = 1.0, lm_path: Optional[str] = None, alpha: float = 1.0, beta: float = 1.0):
         """model_path: a ``.ckpt`` written by the reference or by ``Trainer``; map_location must name a GPU
         ("cuda" / "cuda:0"): there is no CPU path.  ``labels`` overrides the language's vocabulary.
-        decoder: "greedy" (argmax + CTC collapse, the default) or "beam" (CTC prefix beam search, no LM)."""
+        decoder: "greedy" (argmax + CTC collapse, the default) or "beam" (CTC prefix beam search; with ``lm_path``, a text ARPA
+        character LM, fused with it: ``alpha`` weighs the LM, ``beta`` is the per-label bonus)."""
         if decoder not in ("greedy", "beam"):
             raise ValueError("decoder must be 'greedy' or 'beam', got %r" % (decoder,))
         if labels is not None:
@@ -49,7 +51,7 @@ class AsrTranslator:
         self.device = torch.device(map_location)
         self.wer = WER(vocabulary=self.labels)
         self.decoder = decoder
-        self.beam = BeamSearchDecoderWithLM(self.labels, beam_width, 1.0, 1.0, None, 1, cutoff_prob=cutoff_prob,
+        self.beam = BeamSearchDecoderWithLM(self.labels, beam_width, alpha, beta, lm_path, 1, cutoff_prob=cutoff_prob,
                                             cutoff_top_n=cutoff_top_n, device=str(map_location))
         self.model.eval()
 
