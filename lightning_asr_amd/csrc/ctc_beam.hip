@@ -10,11 +10,14 @@
 //      prefix + one extension per (prefix, kept label)) live in registers, J per thread.  The beam_width best are found by
 //      an 8-bit radix select over (score, tie-break key) that stops as soon as the boundary bucket is taken whole; only the
 //      survivors are ordered (rank by counting).  New prefixes are appended to a parent-pointer trie in the workspace
-//      (at most beam_width nodes per frame) that is walked back once at the end.
+//      (at most beam_width nodes per frame) that is walked back once at the end.  Everything but the scoring of a frame's
+//      candidates is in the beam_* functions over BeamCore, which the LM-fused search further down calls as well.
 //
 // Prefix identity: p+c merges with a live entry q when q's parent prefix equals p and q's last label is c.  Entries carry a
 // 64-bit hash of their label sequence and of their parent's, so "q's parent equals p" is a hash compare; a trie node id
 // would not do, since a prefix that left the beam and came back gets a new node while its children may still be live.
+#include <type_traits>
+
 #include "common.h"
 
 namespace lasr {
@@ -189,25 +192,181 @@ __global__ __launch_bounds__(64) void beam_prune_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------ the search ------------------------------------------
-struct BeamLds {
+// What a search keeps in LDS whether or not a language model scores the extensions.  The phases below (beam_init_root ..
+// beam_write_back) work on this alone; each search kernel owns its candidate scoring, steps (2)-(3), and its extra fields.
+struct BeamCore {
   int node[2][kBeamMaxWidth], last[2][kBeamMaxWidth], len[2][kBeamMaxWidth];
-  float b[2][kBeamMaxWidth], nb[2][kBeamMaxWidth];
+  float b[2][kBeamMaxWidth], nb[2][kBeamMaxWidth];       // acoustic log_b / log_nb
   uint64_t h[2][kBeamMaxWidth], ph[2][kBeamMaxWidth];
-  float score[kBeamMaxWidth];             // logaddexp(b, nb) of the current beam
+  float score[kBeamMaxWidth];             // what the current beam is ranked by: logaddexp(b, nb) (+ the LM bonus, if any)
   float next_b[kBeamMaxWidth], next_nb[kBeamMaxWidth];   // the "no new label" candidate of each live prefix
   unsigned long long merged[kBeamMaxWidth];              // bit k: p + kept[k] merged into a live entry
   uint64_t surv[kBeamMaxWidth];
-  int surv_i[kBeamMaxWidth];
   int kcls[kBeamMaxTopN];
   float klp[kBeamMaxTopN];
   uint32_t hist[256];
   uint32_t found[4];
   uint32_t nsel;
-  int nk;
+  // last, and aligned so that the struct has no tail padding: a per-survivor array that a search places right behind its
+  // BeamCore is then 512 bytes from surv_i, and beam_compact's store and on_keep's go out as one paired LDS write
+  alignas(8) int surv_i[kBeamMaxWidth];
 };
 
+// the root entry (the empty prefix) and a zeroed histogram; the first frame's barrier publishes them
+__device__ __forceinline__ void beam_init_root(BeamCore& s, int tid) {
+  if (tid == 0) {
+    s.node[0][0] = 0; s.last[0][0] = -1; s.len[0][0] = 0;
+    s.b[0][0] = 0.f; s.nb[0][0] = kNegInfB;
+    s.h[0][0] = kRootHash; s.ph[0][0] = 0;
+  }
+  for (int i = tid; i < 256; i += kSearchThreads) s.hist[i] = 0;
+}
+
+// The kept list of frame t + 1 is fetched into registers while frame t is searched.
+struct BeamFetch {
+  const int32_t* kc;    // this utterance's rows of the prune launch's output
+  const float* kl;
+  const int32_t* kn;
+  int pc = 0, pn = 0;
+  float pl = 0.f;
+  __device__ __forceinline__ void request(int64_t t, int tid) {
+    if (tid < kBeamMaxTopN) { pc = kc[t * kBeamMaxTopN + tid]; pl = kl[t * kBeamMaxTopN + tid]; }
+    pn = kn[t];
+  }
+};
+
+// publishes the requested frame t into kcls / klp, requests frame t + 1 and resets the survivor count; returns the number of
+// kept labels.  The caller's barrier follows.
+__device__ __forceinline__ int beam_fetch_frame(BeamCore& s, BeamFetch& f, int64_t t, int64_t L, int tid) {
+  const int nk = f.pn;
+  if (tid < nk) { s.kcls[tid] = f.pc; s.klp[tid] = f.pl; }
+  if (t + 1 < L) f.request(t + 1, tid);
+  if (tid == 0) s.nsel = 0;
+  return nk;
+}
+
+// (1) for the live prefix `tid`, whose last label is `last`: the kept index of that label, the blank's kept log-prob and the
+// prefix's parent among the live entries (found by hash); clears its merged bits
+__device__ __forceinline__ void beam_lookup(BeamCore& s, int cur, int nbeam, int nk, int blank, int tid, int last, int* lastk,
+                                            int* pr, float* blp) {
+  s.merged[tid] = 0ull;
+  for (int k = 0; k < nk; ++k) {
+    const int c = s.kcls[k];
+    if (c == last) *lastk = k;
+    if (c == blank) *blp = s.klp[k];
+  }
+  if (last >= 0) {
+    const uint64_t ph = s.ph[cur][tid];
+    for (int r = 0; r < nbeam; ++r)
+      if (s.h[cur][r] == ph) { *pr = r; break; }
+  }
+}
+
+// (4) radix select of the W smallest composites among a thread's J (bit j of `valid`: comp[j] is finite); `prefix`/`mask`
+// end as the boundary: (comp & mask) <= prefix is taken
+template <int J>
+__device__ __forceinline__ void beam_select(BeamCore& s, const uint64_t (&comp)[J], uint64_t valid, int W, int tid,
+                                            uint64_t* prefix_out, uint64_t* mask_out) {
+  const int lane = tid & 63;
+  uint64_t prefix = 0, mask = 0;
+  uint32_t need = (uint32_t)W;
+#pragma nounroll
+  for (int ps = 0; ps < 7; ++ps) {
+    const int sh = ps < 4 ? 56 - 8 * ps : 16 - 8 * (ps - 4);   // the key is below 2^21: bits 21..31 are always 0
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+      wave_hist_add(s.hist, ((valid >> j) & 1ull) && (comp[j] & mask) == prefix, (uint32_t)(comp[j] >> sh) & 255u, lane);
+    __syncthreads();
+    if (tid < 64) wave_find_bucket(s.hist, need, lane, s.found);
+    __syncthreads();
+    if (ps == 0 && s.found[3] <= need) break;        // no more finite candidates than the beam holds: take them all
+    const uint32_t bucket = s.found[0], before = s.found[1], cnt = s.found[2];
+    prefix |= (uint64_t)bucket << sh;
+    mask |= 0xffull << sh;
+    need -= before;
+    if (cnt == need) break;
+  }
+  *prefix_out = prefix;
+  *mask_out = mask;
+}
+
+// (5), first half: compacts the survivors into surv / surv_i and returns their number once every thread's are in;
+// on_keep(pos, j) lets the caller store more of candidate j at the same slot
+template <int J, class OnKeep>
+__device__ __forceinline__ int beam_compact(BeamCore& s, const uint64_t (&comp)[J], uint64_t valid, uint64_t prefix,
+                                            uint64_t mask, int W, int tid, OnKeep on_keep) {
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    if (((valid >> j) & 1ull) && (comp[j] & mask) <= prefix) {
+      const uint32_t pos = atomicAdd(&s.nsel, 1u);
+      if (pos < (uint32_t)kBeamMaxWidth) {   // at most W survive; the guard only bounds the LDS index
+        s.surv[pos] = comp[j];
+        s.surv_i[pos] = tid + j * kSearchThreads;
+        on_keep(pos, j);
+      }
+    }
+  }
+  __syncthreads();
+  return min((int)s.nsel, W);
+}
+
+// (5), second half: only the survivors are ordered, by counting; the next beam is written in rank order
+__device__ __forceinline__ int beam_rank(const BeamCore& s, int nsel, int tid) {
+  const uint64_t me = s.surv[tid];
+  int rank = 0;
+  for (int r = 0; r < nsel; ++r) rank += s.surv[r] < me;
+  return rank;
+}
+
+// entry i of the current beam survives without a new label
+__device__ __forceinline__ void beam_keep_entry(BeamCore& s, int cur, int nxt, int rank, int i) {
+  s.node[nxt][rank] = s.node[cur][i]; s.last[nxt][rank] = s.last[cur][i]; s.len[nxt][rank] = s.len[cur][i];
+  s.h[nxt][rank] = s.h[cur][i]; s.ph[nxt][rank] = s.ph[cur][i];
+  s.b[nxt][rank] = s.next_b[i]; s.nb[nxt][rank] = s.next_nb[i];
+}
+
+// entry p extended by label c survives as a new prefix: a trie node of frame t and an entry whose log_nb, the extension's
+// acoustic score, the caller writes
+__device__ __forceinline__ void beam_new_entry(BeamCore& s, int cur, int nxt, int rank, int p, int c, int64_t t, int W,
+                                               int2* trie) {
+  const int node = 1 + (int)t * W + rank;
+  trie[node] = make_int2(s.node[cur][p], c);
+  s.node[nxt][rank] = node; s.last[nxt][rank] = c; s.len[nxt][rank] = s.len[cur][p] + 1;
+  s.h[nxt][rank] = child_hash(s.h[cur][p], c); s.ph[nxt][rank] = s.h[cur][p];
+  s.b[nxt][rank] = kNegInfB;
+}
+
+// walks the trie back from each of the n_best final entries (none of them when !valid_all) into tok, this utterance's
+// (n_best, T) tokens, and writes the lengths; the slots past a hypothesis are -1, the length of an empty slot is -1
+__device__ __forceinline__ void beam_write_back(const BeamCore& s, int cur, int nbeam, int n_best, int64_t T, const int2* trie,
+                                                int32_t* tok, int32_t* n_tokens, bool valid_all, int tid) {
+  __threadfence();
+  __syncthreads();
+  if (!valid_all) nbeam = 0;
+  if (tid < n_best) {
+    if (tid < nbeam) {
+      const int n = s.len[cur][tid];
+      n_tokens[tid] = n;
+      int node = s.node[cur][tid];
+      for (int pos = n - 1; pos >= 0; --pos) {
+        const int2 e = trie[node];
+        tok[(int64_t)tid * T + pos] = e.y;
+        node = e.x;
+      }
+    } else {
+      n_tokens[tid] = -1;
+    }
+  }
+  for (int64_t idx = tid; idx < (int64_t)n_best * T; idx += kSearchThreads) {
+    const int j = (int)(idx / T);
+    const int64_t pos = idx - (int64_t)j * T;
+    const int n = j < nbeam ? s.len[cur][j] : 0;
+    if (pos >= n) tok[idx] = -1;
+  }
+}
+
 // the extension candidate (p, kept[k]) -> its score (-inf when it merged into a live entry or k is the blank)
-__device__ __forceinline__ float ext_score(const BeamLds& s, int cur, int p, int k, int blank) {
+__device__ __forceinline__ float ext_score(const BeamCore& s, int cur, int p, int k, int blank) {
   const int c = s.kcls[k];
   if (c == blank || ((s.merged[p] >> k) & 1ull)) return kNegInfB;
   return s.klp[k] + (c == s.last[cur][p] ? s.b[cur][p] : s.score[p]);
@@ -221,36 +380,17 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_kernel(const int32
                                                                      int W, int n_best, int2* __restrict__ trie_g,
                                                                      int32_t* __restrict__ tokens, int32_t* __restrict__ n_tokens,
                                                                      float* __restrict__ scores) {
-  __shared__ BeamLds s;
-  const int tid = threadIdx.x, lane = tid & 63;
+  __shared__ BeamCore s;
+  const int tid = threadIdx.x;
   const int64_t ub = blockIdx.x;
   const int64_t L = lens ? min((int64_t)max(lens[ub], 0), T) : T;
   int2* trie = trie_g + ub * (1 + T * (int64_t)W);
-  const int32_t* kc = kcls_g + ub * T * kBeamMaxTopN;
-  const float* kl = klp_g + ub * T * kBeamMaxTopN;
-  const int32_t* knf = kn_g + ub * T;
-  if (tid == 0) {
-    s.node[0][0] = 0; s.last[0][0] = -1; s.len[0][0] = 0;
-    s.b[0][0] = 0.f; s.nb[0][0] = kNegInfB;
-    s.h[0][0] = kRootHash; s.ph[0][0] = 0;
-  }
-  for (int i = tid; i < 256; i += kSearchThreads) s.hist[i] = 0;
+  BeamFetch pf{kcls_g + ub * T * kBeamMaxTopN, klp_g + ub * T * kBeamMaxTopN, kn_g + ub * T};
+  beam_init_root(s, tid);
   int nbeam = 1, cur = 0;
-  // the kept list of frame t + 1 is fetched while frame t is searched
-  int pc = 0, pn = 0;
-  float pl = 0.f;
-  if (L > 0) {
-    if (tid < kBeamMaxTopN) { pc = kc[tid]; pl = kl[tid]; }
-    pn = knf[0];
-  }
+  if (L > 0) pf.request(0, tid);
   for (int64_t t = 0; t < L; ++t) {
-    const int nk = pn;
-    if (tid < nk) { s.kcls[tid] = pc; s.klp[tid] = pl; }
-    if (t + 1 < L) {
-      if (tid < kBeamMaxTopN) { pc = kc[(t + 1) * kBeamMaxTopN + tid]; pl = kl[(t + 1) * kBeamMaxTopN + tid]; }
-      pn = knf[t + 1];
-    }
-    if (tid == 0) s.nsel = 0;
+    const int nk = beam_fetch_frame(s, pf, t, L, tid);
     __syncthreads();
     // (1) per live prefix: score, the kept index of its last label and of the blank, its parent among the live entries
     int lastk = -1, pr = -1;
@@ -258,17 +398,7 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_kernel(const int32
     if (tid < nbeam) {
       const int last = s.last[cur][tid];
       s.score[tid] = lae(s.b[cur][tid], s.nb[cur][tid]);
-      s.merged[tid] = 0ull;
-      for (int k = 0; k < nk; ++k) {
-        const int c = s.kcls[k];
-        if (c == last) lastk = k;
-        if (c == blank) blp = s.klp[k];
-      }
-      if (last >= 0) {
-        const uint64_t ph = s.ph[cur][tid];
-        for (int r = 0; r < nbeam; ++r)
-          if (s.h[cur][r] == ph) { pr = r; break; }
-      }
+      beam_lookup(s, cur, nbeam, nk, blank, tid, last, &lastk, &pr, &blp);
     }
     __syncthreads();
     // (2) the "no new label" candidate of each live prefix, with what its parent's extension by its last label adds
@@ -307,87 +437,28 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_kernel(const int32
       comp[j] = ((uint64_t)desc_bits(sc) << 32) | key;
       if (sc > kNegInfB) valid |= 1ull << j;
     }
-    // (4) radix select of the W smallest composites; `prefix`/`mask` end as the boundary: (comp & mask) <= prefix is taken
-    uint64_t prefix = 0, mask = 0;
-    uint32_t need = (uint32_t)W;
-    for (int ps = 0; ps < 7; ++ps) {
-      const int sh = ps < 4 ? 56 - 8 * ps : 16 - 8 * (ps - 4);   // the key is below 2^21: bits 21..31 are always 0
-#pragma unroll
-      for (int j = 0; j < J; ++j)
-        wave_hist_add(s.hist, ((valid >> j) & 1ull) && (comp[j] & mask) == prefix, (uint32_t)(comp[j] >> sh) & 255u, lane);
-      __syncthreads();
-      if (tid < 64) wave_find_bucket(s.hist, need, lane, s.found);
-      __syncthreads();
-      if (ps == 0 && s.found[3] <= need) break;        // no more finite candidates than the beam holds: take them all
-      const uint32_t bucket = s.found[0], before = s.found[1], cnt = s.found[2];
-      prefix |= (uint64_t)bucket << sh;
-      mask |= 0xffull << sh;
-      need -= before;
-      if (cnt == need) break;
-    }
-    // (5) compact the survivors, order them, write the next beam (and the trie nodes of new prefixes) in rank order
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      if (((valid >> j) & 1ull) && (comp[j] & mask) <= prefix) {
-        const uint32_t pos = atomicAdd(&s.nsel, 1u);
-        if (pos < (uint32_t)kBeamMaxWidth) {   // at most W survive; the guard only bounds the LDS index
-          s.surv[pos] = comp[j];
-          s.surv_i[pos] = tid + j * kSearchThreads;
-        }
-      }
-    }
-    __syncthreads();
-    const int nsel = min((int)s.nsel, W);
+    // (4) select the W best, (5) compact and order them, write the next beam (and the trie nodes of new prefixes)
+    uint64_t prefix, mask;
+    beam_select<J>(s, comp, valid, W, tid, &prefix, &mask);
+    const int nsel = beam_compact<J>(s, comp, valid, prefix, mask, W, tid, [](uint32_t, int) {});
     const int nxt = cur ^ 1;
     if (tid < nsel) {
-      const uint64_t me = s.surv[tid];
-      int rank = 0;
-      for (int r = 0; r < nsel; ++r) rank += s.surv[r] < me;
+      const int rank = beam_rank(s, nsel, tid);
       const int i = s.surv_i[tid];
       if (i < nbeam) {
-        s.node[nxt][rank] = s.node[cur][i]; s.last[nxt][rank] = s.last[cur][i]; s.len[nxt][rank] = s.len[cur][i];
-        s.h[nxt][rank] = s.h[cur][i]; s.ph[nxt][rank] = s.ph[cur][i];
-        s.b[nxt][rank] = s.next_b[i]; s.nb[nxt][rank] = s.next_nb[i];
+        beam_keep_entry(s, cur, nxt, rank, i);
       } else {
         const int q = i - nbeam, p = q / nk, k = q - p * nk;
-        const int c = s.kcls[k];
-        const int node = 1 + (int)t * W + rank;
-        trie[node] = make_int2(s.node[cur][p], c);
-        s.node[nxt][rank] = node; s.last[nxt][rank] = c; s.len[nxt][rank] = s.len[cur][p] + 1;
-        s.h[nxt][rank] = child_hash(s.h[cur][p], c); s.ph[nxt][rank] = s.h[cur][p];
-        s.b[nxt][rank] = kNegInfB; s.nb[nxt][rank] = ext_score(s, cur, p, k, blank);
+        beam_new_entry(s, cur, nxt, rank, p, s.kcls[k], t, W, trie);
+        s.nb[nxt][rank] = ext_score(s, cur, p, k, blank);
       }
     }
     nbeam = nsel;
     cur = nxt;
     __syncthreads();
   }
-  // walk the trie back from each of the n_best final entries; the slots past the hypothesis are -1
-  __threadfence();
-  __syncthreads();
-  int32_t* tok = tokens + ub * (int64_t)n_best * T;
-  if (tid < n_best) {
-    if (tid < nbeam) {
-      const int n = s.len[cur][tid];
-      n_tokens[ub * n_best + tid] = n;
-      scores[ub * n_best + tid] = lae(s.b[cur][tid], s.nb[cur][tid]);
-      int node = s.node[cur][tid];
-      for (int pos = n - 1; pos >= 0; --pos) {
-        const int2 e = trie[node];
-        tok[(int64_t)tid * T + pos] = e.y;
-        node = e.x;
-      }
-    } else {
-      n_tokens[ub * n_best + tid] = -1;
-      scores[ub * n_best + tid] = kNegInfB;
-    }
-  }
-  for (int64_t idx = tid; idx < (int64_t)n_best * T; idx += kSearchThreads) {
-    const int j = (int)(idx / T);
-    const int64_t pos = idx - (int64_t)j * T;
-    const int n = j < nbeam ? s.len[cur][j] : 0;
-    if (pos >= n) tok[idx] = -1;
-  }
+  beam_write_back(s, cur, nbeam, n_best, T, trie, tokens + ub * (int64_t)n_best * T, n_tokens + ub * n_best, true, tid);
+  if (tid < n_best) scores[ub * n_best + tid] = tid < nbeam ? lae(s.b[cur][tid], s.nb[cur][tid]) : kNegInfB;
 }
 
 bool beam_shape_ok(int64_t B, int64_t T, int64_t C, int W, int topn) {
@@ -410,11 +481,62 @@ BeamWs beam_ws(int64_t B, int64_t T, int64_t W) {
   return w;
 }
 
-template <int J>
-void launch_search(dim3 grid, hipStream_t st, const int32_t* kc, const float* kl, const int32_t* kn, const int32_t* lens, int64_t T,
-                   int blank, int W, int n_best, int2* trie, int32_t* tokens, int32_t* n_tokens, float* scores) {
-  hipLaunchKernelGGL(beam_search_kernel<J>, grid, dim3(kSearchThreads), 0, st, kc, kl, kn, lens, T, blank, W, n_best, trie, tokens,
-                     n_tokens, scores);
+// the arguments both decoders take, as `who` (the exported function) received them
+struct BeamArgs {
+  const char* who;
+  const float* logp;
+  const int32_t* lens;
+  int64_t B, T, C;
+  int blank, beam_width, cutoff_top_n;
+  float cutoff_prob;
+  int n_best;
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+};
+
+// the value checks both decoders make; ptrs_ok: every pointer the caller requires is set
+int beam_check_args(const BeamArgs& a, bool ptrs_ok) {
+  LASR_CHECK_ARG(ptrs_ok, "%s: null pointer", a.who);
+  LASR_CHECK_ARG(a.n_best >= 1 && a.n_best <= a.beam_width, "%s: n_best %d outside [1, beam_width %d]", a.who, a.n_best,
+                 a.beam_width);
+  LASR_CHECK_ARG(a.cutoff_prob > 0.f && a.cutoff_prob <= 1.f, "%s: cutoff_prob %g outside (0, 1]", a.who, (double)a.cutoff_prob);
+  LASR_CHECK_ARG(a.C >= 1 && a.blank >= 0 && a.blank < a.C, "%s: blank %d outside [0, C = %lld)", a.who, a.blank, (long long)a.C);
+  return 0;
+}
+
+// Checks the shape and the workspace, carves it, launches the prune kernel and then search(J, grid, stream, kc, kl, kn, trie)
+// with J, the candidates per thread, as a std::integral_constant: the caller launches its kernel's instantiation.
+template <class Search>
+int beam_launch(const BeamArgs& a, const char* search_name, Search search) {
+  LASR_CHECK_SHAPE(beam_shape_ok(a.B, a.T, a.C, a.beam_width, a.cutoff_top_n),
+                   "%s: B %lld T %lld C %lld beam_width %d cutoff_top_n %d outside the supported range "
+                   "(C <= %d, beam_width 1..%d, cutoff_top_n 1..%d)", a.who, (long long)a.B, (long long)a.T, (long long)a.C,
+                   a.beam_width, a.cutoff_top_n, kBeamMaxClasses, kBeamMaxWidth, kBeamMaxTopN);
+  const BeamWs w = beam_ws(a.B, a.T, a.beam_width);
+  if (a.workspace_bytes < w.total)
+    return fail(LASR_E_WORKSPACE, "%s: workspace %zu < %zu bytes", a.who, a.workspace_bytes, w.total);
+  char* ws = static_cast<char*>(a.workspace);
+  int32_t* kc = reinterpret_cast<int32_t*>(ws + w.kcls);
+  float* kl = reinterpret_cast<float*>(ws + w.klp);
+  int32_t* kn = reinterpret_cast<int32_t*>(ws + w.kn);
+  int2* trie = reinterpret_cast<int2*>(ws + w.trie);
+  hipStream_t st = as_stream(a.stream);
+  hipLaunchKernelGGL(beam_prune_kernel, dim3((unsigned)(a.B * a.T)), dim3(64), 0, st, a.logp, a.lens, a.T, (int)a.C,
+                     a.cutoff_top_n, a.cutoff_prob, kc, kl, kn);
+  LASR_LAUNCH_CHECK("beam_prune_kernel");
+  // candidates per frame: beam_width "no new label" entries + beam_width * kept labels, J per thread
+  const int K = (int)(a.C < a.cutoff_top_n ? a.C : a.cutoff_top_n);
+  const int per = (int)cdiv((int64_t)a.beam_width * (K + 1), kSearchThreads);
+  const dim3 grid((unsigned)a.B);
+  if (per <= 1) search(std::integral_constant<int, 1>{}, grid, st, kc, kl, kn, trie);
+  else if (per <= 2) search(std::integral_constant<int, 2>{}, grid, st, kc, kl, kn, trie);
+  else if (per <= 4) search(std::integral_constant<int, 4>{}, grid, st, kc, kl, kn, trie);
+  else if (per <= 8) search(std::integral_constant<int, 8>{}, grid, st, kc, kl, kn, trie);
+  else if (per <= 16) search(std::integral_constant<int, 16>{}, grid, st, kc, kl, kn, trie);
+  else search(std::integral_constant<int, 33>{}, grid, st, kc, kl, kn, trie);
+  LASR_LAUNCH_CHECK(search_name);
+  return 0;
 }
 
 }  // namespace
@@ -430,39 +552,14 @@ extern "C" size_t lasr_ctc_beam_workspace_bytes(int64_t B, int64_t T, int64_t C,
 extern "C" int lasr_ctc_beam_decode(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
                                     int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, int32_t* tokens,
                                     int32_t* n_tokens, float* scores, void* workspace, size_t workspace_bytes, void* stream) {
-  LASR_CHECK_ARG(logp && tokens && n_tokens && scores && workspace, "lasr_ctc_beam_decode: null pointer");
-  LASR_CHECK_ARG(n_best >= 1 && n_best <= beam_width, "lasr_ctc_beam_decode: n_best %d outside [1, beam_width %d]", n_best,
-                 beam_width);
-  LASR_CHECK_ARG(cutoff_prob > 0.f && cutoff_prob <= 1.f, "lasr_ctc_beam_decode: cutoff_prob %g outside (0, 1]", (double)cutoff_prob);
-  LASR_CHECK_ARG(C >= 1 && blank >= 0 && blank < C, "lasr_ctc_beam_decode: blank %d outside [0, C = %lld)", blank, (long long)C);
-  LASR_CHECK_SHAPE(beam_shape_ok(B, T, C, beam_width, cutoff_top_n),
-                   "lasr_ctc_beam_decode: B %lld T %lld C %lld beam_width %d cutoff_top_n %d outside the supported range "
-                   "(C <= %d, beam_width 1..%d, cutoff_top_n 1..%d)", (long long)B, (long long)T, (long long)C, beam_width,
-                   cutoff_top_n, kBeamMaxClasses, kBeamMaxWidth, kBeamMaxTopN);
-  const BeamWs w = beam_ws(B, T, beam_width);
-  if (workspace_bytes < w.total)
-    return fail(LASR_E_WORKSPACE, "lasr_ctc_beam_decode: workspace %zu < %zu bytes", workspace_bytes, w.total);
-  char* ws = static_cast<char*>(workspace);
-  int32_t* kc = reinterpret_cast<int32_t*>(ws + w.kcls);
-  float* kl = reinterpret_cast<float*>(ws + w.klp);
-  int32_t* kn = reinterpret_cast<int32_t*>(ws + w.kn);
-  int2* trie = reinterpret_cast<int2*>(ws + w.trie);
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(beam_prune_kernel, dim3((unsigned)(B * T)), dim3(64), 0, st, logp, lens, T, (int)C, cutoff_top_n, cutoff_prob,
-                     kc, kl, kn);
-  LASR_LAUNCH_CHECK("beam_prune_kernel");
-  // candidates per frame: beam_width "no new label" entries + beam_width * kept labels, J per thread
-  const int K = (int)(C < cutoff_top_n ? C : cutoff_top_n);
-  const int per = (int)cdiv((int64_t)beam_width * (K + 1), kSearchThreads);
-  const dim3 grid((unsigned)B);
-  if (per <= 1) launch_search<1>(grid, st, kc, kl, kn, lens, T, blank, beam_width, n_best, trie, tokens, n_tokens, scores);
-  else if (per <= 2) launch_search<2>(grid, st, kc, kl, kn, lens, T, blank, beam_width, n_best, trie, tokens, n_tokens, scores);
-  else if (per <= 4) launch_search<4>(grid, st, kc, kl, kn, lens, T, blank, beam_width, n_best, trie, tokens, n_tokens, scores);
-  else if (per <= 8) launch_search<8>(grid, st, kc, kl, kn, lens, T, blank, beam_width, n_best, trie, tokens, n_tokens, scores);
-  else if (per <= 16) launch_search<16>(grid, st, kc, kl, kn, lens, T, blank, beam_width, n_best, trie, tokens, n_tokens, scores);
-  else launch_search<33>(grid, st, kc, kl, kn, lens, T, blank, beam_width, n_best, trie, tokens, n_tokens, scores);
-  LASR_LAUNCH_CHECK("beam_search_kernel");
-  return 0;
+  const BeamArgs a{"lasr_ctc_beam_decode", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
+                   workspace_bytes, stream};
+  LASR_TRY(beam_check_args(a, logp && tokens && n_tokens && scores && workspace));
+  auto search = [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
+    hipLaunchKernelGGL(beam_search_kernel<decltype(j)::value>, grid, dim3(kSearchThreads), 0, st, kc, kl, kn, lens, T, blank,
+                       beam_width, n_best, trie, tokens, n_tokens, scores);
+  };
+  return beam_launch(a, "beam_search_kernel", search);
 }
 
 // ================================================================== with an n-gram LM ===================================
@@ -575,24 +672,15 @@ __device__ void lm_context_sums(const LmImg& m, int w, const int* ctx, float* cb
   }
 }
 
+// core.b / core.nb stay ACOUSTIC here and core.score is the fused score; the LM's share of an entry lives beside the core
 struct BeamLmLds {
-  int node[2][kBeamMaxWidth], last[2][kBeamMaxWidth], len[2][kBeamMaxWidth];
-  float b[2][kBeamMaxWidth], nb[2][kBeamMaxWidth];       // acoustic
+  BeamCore core;
+  float surv_t[kBeamMaxWidth];                           // emission term of a surviving extension (beside core.surv_i)
   float bonus[2][kBeamMaxWidth], term[2][kBeamMaxWidth]; // alpha * sum lm + beta * labels; the last label's own term
   int ctx[2][kLmMaxCtx][kBeamMaxWidth];                  // LM word ids of the last N-1 labels, nearest first (-1 = OOV)
   float cb[2][kLmMaxCtx + 1][kBeamMaxWidth];             // cb[j]: log10 backoffs of the stored contexts longer than j words
-  uint64_t h[2][kBeamMaxWidth], ph[2][kBeamMaxWidth];
-  float score[kBeamMaxWidth], ascore[kBeamMaxWidth];    // fused and acoustic logaddexp(b, nb) of the current beam
-  float next_b[kBeamMaxWidth], next_nb[kBeamMaxWidth];
-  unsigned long long merged[kBeamMaxWidth];
-  uint64_t surv[kBeamMaxWidth];
-  int surv_i[kBeamMaxWidth];
-  float surv_t[kBeamMaxWidth];                           // emission term of a surviving extension
-  int kcls[kBeamMaxTopN], kwid[kBeamMaxTopN];
-  float klp[kBeamMaxTopN];
-  uint32_t hist[256];
-  uint32_t found[4];
-  uint32_t nsel;
+  float ascore[kBeamMaxWidth];                           // acoustic logaddexp(b, nb) of the current beam
+  int kwid[kBeamMaxTopN];                                // LM word id of each kept label (-1: the blank, or not in the LM)
   int ctx_oov[kBeamMaxWidth];
 };
 
@@ -603,22 +691,19 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
     const void* __restrict__ image, float alpha, float beta, int2* __restrict__ trie_g, int32_t* __restrict__ tokens,
     int32_t* __restrict__ n_tokens, float* __restrict__ scores, float* __restrict__ am_scores) {
   __shared__ BeamLmLds s;
-  const int tid = threadIdx.x, lane = tid & 63;
+  BeamCore& core = s.core;
+  const int tid = threadIdx.x;
   const int64_t ub = blockIdx.x;
   const LmImg lm = lm_open(image);
   const int64_t L = !lm.ok ? 0 : lens ? min((int64_t)max(lens[ub], 0), T) : T;
   const int nctx = lm.nctx;
   int2* trie = trie_g + ub * (1 + T * (int64_t)W);
-  const int32_t* kc = kcls_g + ub * T * kBeamMaxTopN;
-  const float* kl = klp_g + ub * T * kBeamMaxTopN;
-  const int32_t* knf = kn_g + ub * T;
+  BeamFetch pf{kcls_g + ub * T * kBeamMaxTopN, klp_g + ub * T * kBeamMaxTopN, kn_g + ub * T};
   const float* lrow = logp + ub * T * (int64_t)C;
   const float cut_beta = fmaxf(0.f, beta);
+  beam_init_root(core, tid);
   if (tid == 0) {
-    s.node[0][0] = 0; s.last[0][0] = -1; s.len[0][0] = 0;
-    s.b[0][0] = 0.f; s.nb[0][0] = kNegInfB;
     s.bonus[0][0] = 0.f; s.term[0][0] = 0.f;
-    s.h[0][0] = kRootHash; s.ph[0][0] = 0;
     int rc[kLmMaxCtx];
     float cb[kLmMaxCtx + 1];
     for (int d = 0; d < kLmMaxCtx; ++d) rc[d] = lm.bos;
@@ -626,70 +711,49 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
     for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[0][d][0] = lm.bos;
     for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[0][d][0] = lm.ok ? cb[d] : 0.f;
   }
-  for (int i = tid; i < 256; i += kSearchThreads) s.hist[i] = 0;
   int nbeam = 1, cur = 0;
-  int pc = 0, pn = 0;
-  float pl = 0.f, pblank = 0.f;
+  float pblank = 0.f;
   if (L > 0) {
-    if (tid < kBeamMaxTopN) { pc = kc[tid]; pl = kl[tid]; }
-    pn = knf[0];
+    pf.request(0, tid);
     pblank = lrow[blank];
   }
   for (int64_t t = 0; t < L; ++t) {
-    const int nk = pn;
     const float lblank = pblank;        // the frame's unpruned blank log-prob (the early cutoff's reference)
-    if (tid < nk) {
-      s.kcls[tid] = pc; s.klp[tid] = pl;
-      s.kwid[tid] = (pc != blank && pc >= 0 && (uint32_t)pc < lm.n_classes) ? lm.cls[pc] : -1;
-    }
-    if (t + 1 < L) {
-      if (tid < kBeamMaxTopN) { pc = kc[(t + 1) * kBeamMaxTopN + tid]; pl = kl[(t + 1) * kBeamMaxTopN + tid]; }
-      pn = knf[t + 1];
-      pblank = lrow[(t + 1) * (int64_t)C + blank];
-    }
-    if (tid == 0) s.nsel = 0;
+    if (tid < pf.pn) s.kwid[tid] = (pf.pc != blank && pf.pc >= 0 && (uint32_t)pf.pc < lm.n_classes) ? lm.cls[pf.pc] : -1;
+    const int nk = beam_fetch_frame(core, pf, t, L, tid);
+    if (t + 1 < L) pblank = lrow[(t + 1) * (int64_t)C + blank];
     __syncthreads();
     // (1) per live prefix: scores, kept index of its last label and of the blank, its parent among the live entries
     int lastk = -1, pr = -1;
     float blp = kNegInfB;
     if (tid < nbeam) {
-      const int last = s.last[cur][tid];
-      const float as = lae(s.b[cur][tid], s.nb[cur][tid]);
+      const int last = core.last[cur][tid];
+      const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
       s.ascore[tid] = as;
-      s.score[tid] = as + s.bonus[cur][tid];
-      s.merged[tid] = 0ull;
+      core.score[tid] = as + s.bonus[cur][tid];
       int oov = 0;
       for (int d = 0; d < nctx; ++d) oov |= s.ctx[cur][d][tid] < 0;
       s.ctx_oov[tid] = oov;
-      for (int k = 0; k < nk; ++k) {
-        const int c = s.kcls[k];
-        if (c == last) lastk = k;
-        if (c == blank) blp = s.klp[k];
-      }
-      if (last >= 0) {
-        const uint64_t ph = s.ph[cur][tid];
-        for (int r = 0; r < nbeam; ++r)
-          if (s.h[cur][r] == ph) { pr = r; break; }
-      }
+      beam_lookup(core, cur, nbeam, nk, blank, tid, last, &lastk, &pr, &blp);
     }
     __syncthreads();
     // the early cutoff: with a full beam, (p, c) contributes nothing where score(p) + logp[c] < min_cutoff
-    const float min_cutoff = nbeam == W ? s.score[W - 1] + lblank - cut_beta : kNegInfB;
+    const float min_cutoff = nbeam == W ? core.score[W - 1] + lblank - cut_beta : kNegInfB;
     // (2) "no new label" candidates (acoustic), with the parent's extension by the last label folded in
     if (tid < nbeam) {
       const float asc = s.ascore[tid];
       float nbn = kNegInfB;
       if (lastk >= 0) {
-        const float lc = s.klp[lastk];
-        if (!(s.score[tid] + lc < min_cutoff)) nbn = lc + s.nb[cur][tid];
+        const float lc = core.klp[lastk];
+        if (!(core.score[tid] + lc < min_cutoff)) nbn = lc + core.nb[cur][tid];
         if (pr >= 0) {
-          if (!(s.score[pr] + lc < min_cutoff))
-            nbn = lae(nbn, lc + (s.last[cur][tid] == s.last[cur][pr] ? s.b[cur][pr] : s.ascore[pr]));
-          atomicOr(&s.merged[pr], 1ull << lastk);
+          if (!(core.score[pr] + lc < min_cutoff))
+            nbn = lae(nbn, lc + (core.last[cur][tid] == core.last[cur][pr] ? core.b[cur][pr] : s.ascore[pr]));
+          atomicOr(&core.merged[pr], 1ull << lastk);
         }
       }
-      s.next_b[tid] = blp + asc;
-      s.next_nb[tid] = nbn;
+      core.next_b[tid] = blp + asc;
+      core.next_nb[tid] = nbn;
     }
     __syncthreads();
     // (3) candidates with fused scores; the LM probes of kLmGroup extensions per thread are issued together
@@ -710,13 +774,13 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
         if (j >= J) continue;
         const int i = tid + j * kSearchThreads;
         if (i < nbeam) {
-          am[u] = lae(s.next_b[i], s.next_nb[i]) + s.bonus[cur][i];
+          am[u] = lae(core.next_b[i], core.next_nb[i]) + s.bonus[cur][i];
         } else if (i < ncand) {
           const int q = i - nbeam, p = q / nk, k = q - p * nk;
-          const int c = s.kcls[k];
+          const int c = core.kcls[k];
           pp[u] = p;
-          if (c != blank && !((s.merged[p] >> k) & 1ull) && !(s.score[p] + s.klp[k] < min_cutoff)) {
-            am[u] = s.klp[k] + (c == s.last[cur][p] ? s.b[cur][p] : s.ascore[p]);
+          if (c != blank && !((core.merged[p] >> k) & 1ull) && !(core.score[p] + core.klp[k] < min_cutoff)) {
+            am[u] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
             ext[u] = am[u] > kNegInfB;
             wc[u] = s.kwid[k];
             if (ext[u] && wc[u] >= 0 && !s.ctx_oov[p]) {
@@ -764,7 +828,7 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
           key = (uint32_t)i << 14;
         } else if (i < ncand) {
           const int q = i - nbeam, p = pp[u], k = q - p * nk;
-          key = ((uint32_t)p << 14) | (uint32_t)(s.kcls[k] + 1);
+          key = ((uint32_t)p << 14) | (uint32_t)(core.kcls[k] + 1);
           if (ext[u]) {
             const bool oov = wc[u] < 0 || s.ctx_oov[p];
             const float lmv = oov ? kLmOov : (lpv[u] + s.cb[cur][mm[u]][p]) / kLmLogE;
@@ -776,61 +840,26 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
         if (sc > kNegInfB) valid |= 1ull << j;
       }
     }
-    // (4) radix select of the W smallest composites (as in beam_search_kernel)
-    uint64_t prefix = 0, mask = 0;
-    uint32_t need = (uint32_t)W;
-    for (int ps = 0; ps < 7; ++ps) {
-      const int sh = ps < 4 ? 56 - 8 * ps : 16 - 8 * (ps - 4);
-#pragma unroll
-      for (int j = 0; j < J; ++j)
-        wave_hist_add(s.hist, ((valid >> j) & 1ull) && (comp[j] & mask) == prefix, (uint32_t)(comp[j] >> sh) & 255u, lane);
-      __syncthreads();
-      if (tid < 64) wave_find_bucket(s.hist, need, lane, s.found);
-      __syncthreads();
-      if (ps == 0 && s.found[3] <= need) break;
-      const uint32_t bucket = s.found[0], before = s.found[1], cnt = s.found[2];
-      prefix |= (uint64_t)bucket << sh;
-      mask |= 0xffull << sh;
-      need -= before;
-      if (cnt == need) break;
-    }
-    // (5) compact, order, write the next beam
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      if (((valid >> j) & 1ull) && (comp[j] & mask) <= prefix) {
-        const uint32_t pos = atomicAdd(&s.nsel, 1u);
-        if (pos < (uint32_t)kBeamMaxWidth) {
-          s.surv[pos] = comp[j];
-          s.surv_i[pos] = tid + j * kSearchThreads;
-          s.surv_t[pos] = term[j];
-        }
-      }
-    }
-    __syncthreads();
-    const int nsel = min((int)s.nsel, W);
+    // (4) select the W best, (5) compact and order them, write the next beam: the core fields, then the LM's
+    uint64_t prefix, mask;
+    beam_select<J>(core, comp, valid, W, tid, &prefix, &mask);
+    const int nsel =
+        beam_compact<J>(core, comp, valid, prefix, mask, W, tid, [&](uint32_t pos, int j) { s.surv_t[pos] = term[j]; });
     const int nxt = cur ^ 1;
     if (tid < nsel) {
-      const uint64_t me = s.surv[tid];
-      int rank = 0;
-      for (int r = 0; r < nsel; ++r) rank += s.surv[r] < me;
-      const int i = s.surv_i[tid];
+      const int rank = beam_rank(core, nsel, tid);
+      const int i = core.surv_i[tid];
       if (i < nbeam) {
-        s.node[nxt][rank] = s.node[cur][i]; s.last[nxt][rank] = s.last[cur][i]; s.len[nxt][rank] = s.len[cur][i];
-        s.h[nxt][rank] = s.h[cur][i]; s.ph[nxt][rank] = s.ph[cur][i];
-        s.b[nxt][rank] = s.next_b[i]; s.nb[nxt][rank] = s.next_nb[i];
+        beam_keep_entry(core, cur, nxt, rank, i);
         s.bonus[nxt][rank] = s.bonus[cur][i]; s.term[nxt][rank] = s.term[cur][i];
         for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[nxt][d][rank] = s.ctx[cur][d][i];
         for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[nxt][d][rank] = s.cb[cur][d][i];
       } else {
         const int q = i - nbeam, p = q / nk, k = q - p * nk;
-        const int c = s.kcls[k];
-        const int node = 1 + (int)t * W + rank;
+        const int c = core.kcls[k];
         const float tm = s.surv_t[tid];
-        trie[node] = make_int2(s.node[cur][p], c);
-        s.node[nxt][rank] = node; s.last[nxt][rank] = c; s.len[nxt][rank] = s.len[cur][p] + 1;
-        s.h[nxt][rank] = child_hash(s.h[cur][p], c); s.ph[nxt][rank] = s.h[cur][p];
-        s.b[nxt][rank] = kNegInfB;
-        s.nb[nxt][rank] = s.klp[k] + (c == s.last[cur][p] ? s.b[cur][p] : s.ascore[p]);
+        beam_new_entry(core, cur, nxt, rank, p, c, t, W, trie);
+        core.nb[nxt][rank] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
         s.bonus[nxt][rank] = s.bonus[cur][p] + tm; s.term[nxt][rank] = tm;
         int nc[kLmMaxCtx];
         float cb[kLmMaxCtx + 1];
@@ -846,14 +875,11 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
     cur = nxt;
     __syncthreads();
   }
-  __threadfence();
-  __syncthreads();
-  int32_t* tok = tokens + ub * (int64_t)n_best * T;
+  beam_write_back(core, cur, nbeam, n_best, T, trie, tokens + ub * (int64_t)n_best * T, n_tokens + ub * n_best, lm.ok, tid);
   if (tid < n_best) {
     const int64_t o = ub * n_best + tid;
     if (lm.ok && tid < nbeam) {
-      const int n = s.len[cur][tid];
-      const float as = lae(s.b[cur][tid], s.nb[cur][tid]);
+      const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
       int cx[kLmMaxCtx];
       float cb[kLmMaxCtx + 1];
       for (int d = 0; d < kLmMaxCtx; ++d) cx[d] = s.ctx[cur][d][tid];
@@ -861,36 +887,14 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
       // ctc_decoders' approx_ctc = fused - k beta - alpha sent_lm: the emission terms cancel, the </s> window remains (and the
       // <s> window of <s>^N </s> for an empty hypothesis)
       float sent = lm_score_one(lm, lm.eos, cx, cb);
-      if (n == 0) sent += lm_score_one(lm, lm.bos, cx, cb);
-      n_tokens[o] = n;
+      if (core.len[cur][tid] == 0) sent += lm_score_one(lm, lm.bos, cx, cb);
       scores[o] = as + s.bonus[cur][tid];
       am_scores[o] = as - alpha * sent;
-      int node = s.node[cur][tid];
-      for (int pos = n - 1; pos >= 0; --pos) {
-        const int2 e = trie[node];
-        tok[(int64_t)tid * T + pos] = e.y;
-        node = e.x;
-      }
     } else {
-      n_tokens[o] = -1;
       scores[o] = kNegInfB;
       am_scores[o] = kNegInfB;
     }
   }
-  for (int64_t idx = tid; idx < (int64_t)n_best * T; idx += kSearchThreads) {
-    const int j = (int)(idx / T);
-    const int64_t pos = idx - (int64_t)j * T;
-    const int n = (lm.ok && j < nbeam) ? s.len[cur][j] : 0;
-    if (pos >= n) tok[idx] = -1;
-  }
-}
-
-template <int J>
-void launch_search_lm(dim3 grid, hipStream_t st, const float* logp, const int32_t* kc, const float* kl, const int32_t* kn,
-                      const int32_t* lens, int64_t T, int C, int blank, int W, int n_best, const void* image, float alpha, float beta,
-                      int2* trie, int32_t* tokens, int32_t* n_tokens, float* scores, float* am_scores) {
-  hipLaunchKernelGGL(beam_search_lm_kernel<J>, grid, dim3(kSearchThreads), 0, st, logp, kc, kl, kn, lens, T, C, blank, W, n_best,
-                     image, alpha, beta, trie, tokens, n_tokens, scores, am_scores);
 }
 
 struct ArpaHandle {
@@ -945,52 +949,21 @@ extern "C" int lasr_arpa_write_image(const void* handle, void* host_dst, size_t 
 extern "C" void lasr_arpa_free(void* handle) { delete static_cast<ArpaHandle*>(handle); }
 
 extern "C" size_t lasr_ctc_beam_lm_workspace_bytes(int64_t B, int64_t T, int64_t C, int beam_width, int cutoff_top_n) {
-  if (!beam_shape_ok(B, T, C, beam_width, cutoff_top_n)) return 0;
-  return beam_ws(B, T, beam_width).total;
+  return lasr_ctc_beam_workspace_bytes(B, T, C, beam_width, cutoff_top_n);   // the LM search's own state is all in LDS
 }
 
 extern "C" int lasr_ctc_beam_decode_lm(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
                                        int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image,
                                        float alpha, float beta, int32_t* tokens, int32_t* n_tokens, float* scores,
                                        float* am_scores, void* workspace, size_t workspace_bytes, void* stream) {
-  LASR_CHECK_ARG(logp && lm_image && tokens && n_tokens && scores && am_scores && workspace,
-                 "lasr_ctc_beam_decode_lm: null pointer");
-  LASR_CHECK_ARG(n_best >= 1 && n_best <= beam_width, "lasr_ctc_beam_decode_lm: n_best %d outside [1, beam_width %d]", n_best,
-                 beam_width);
-  LASR_CHECK_ARG(cutoff_prob > 0.f && cutoff_prob <= 1.f, "lasr_ctc_beam_decode_lm: cutoff_prob %g outside (0, 1]",
-                 (double)cutoff_prob);
-  LASR_CHECK_ARG(C >= 1 && blank >= 0 && blank < C, "lasr_ctc_beam_decode_lm: blank %d outside [0, C = %lld)", blank, (long long)C);
+  const BeamArgs a{"lasr_ctc_beam_decode_lm", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
+                   workspace_bytes, stream};
+  LASR_TRY(beam_check_args(a, logp && lm_image && tokens && n_tokens && scores && am_scores && workspace));
   LASR_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "lasr_ctc_beam_decode_lm: alpha %g / beta %g not finite",
                  (double)alpha, (double)beta);
-  LASR_CHECK_SHAPE(beam_shape_ok(B, T, C, beam_width, cutoff_top_n),
-                   "lasr_ctc_beam_decode_lm: B %lld T %lld C %lld beam_width %d cutoff_top_n %d outside the supported range "
-                   "(C <= %d, beam_width 1..%d, cutoff_top_n 1..%d)", (long long)B, (long long)T, (long long)C, beam_width,
-                   cutoff_top_n, kBeamMaxClasses, kBeamMaxWidth, kBeamMaxTopN);
-  const BeamWs w = beam_ws(B, T, beam_width);
-  if (workspace_bytes < w.total)
-    return fail(LASR_E_WORKSPACE, "lasr_ctc_beam_decode_lm: workspace %zu < %zu bytes", workspace_bytes, w.total);
-  char* ws = static_cast<char*>(workspace);
-  int32_t* kc = reinterpret_cast<int32_t*>(ws + w.kcls);
-  float* kl = reinterpret_cast<float*>(ws + w.klp);
-  int32_t* kn = reinterpret_cast<int32_t*>(ws + w.kn);
-  int2* trie = reinterpret_cast<int2*>(ws + w.trie);
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(beam_prune_kernel, dim3((unsigned)(B * T)), dim3(64), 0, st, logp, lens, T, (int)C, cutoff_top_n, cutoff_prob,
-                     kc, kl, kn);
-  LASR_LAUNCH_CHECK("beam_prune_kernel");
-  const int K = (int)(C < cutoff_top_n ? C : cutoff_top_n);
-  const int per = (int)cdiv((int64_t)beam_width * (K + 1), kSearchThreads);
-  const dim3 grid((unsigned)B);
-#define LASR_LM_LAUNCH(JJ)                                                                                                     \
-  launch_search_lm<JJ>(grid, st, logp, kc, kl, kn, lens, T, (int)C, blank, beam_width, n_best, lm_image, alpha, beta, trie, tokens, \
-                       n_tokens, scores, am_scores)
-  if (per <= 1) LASR_LM_LAUNCH(1);
-  else if (per <= 2) LASR_LM_LAUNCH(2);
-  else if (per <= 4) LASR_LM_LAUNCH(4);
-  else if (per <= 8) LASR_LM_LAUNCH(8);
-  else if (per <= 16) LASR_LM_LAUNCH(16);
-  else LASR_LM_LAUNCH(33);
-#undef LASR_LM_LAUNCH
-  LASR_LAUNCH_CHECK("beam_search_lm_kernel");
-  return 0;
+  auto search = [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
+    hipLaunchKernelGGL(beam_search_lm_kernel<decltype(j)::value>, grid, dim3(kSearchThreads), 0, st, logp, kc, kl, kn, lens, T,
+                       (int)C, blank, beam_width, n_best, lm_image, alpha, beta, trie, tokens, n_tokens, scores, am_scores);
+  };
+  return beam_launch(a, "beam_search_lm_kernel", search);
 }

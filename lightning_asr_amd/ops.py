@@ -423,13 +423,10 @@ CTC_BEAM_MAX_TOP_N = 64
 CTC_BEAM_MAX_CLASSES = 8192
 
 
-def ctc_beam_decode(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: int, beam_width: int = 16, cutoff_top_n: int = 40,
-                    cutoff_prob: float = 1.0, n_best: int = 1):
-    """CTC prefix beam search (no LM) of logp (B,T,C) f32 log-probs, lens (B) i32 frames or None (= T).  Returns
-    (tokens (B, n_best, T) i32, -1 past each hypothesis; n_tokens (B, n_best) i32, -1 for an empty slot; scores (B, n_best) f32
-    log-probabilities, best first).  Shapes outside the kernel's range raise ValueError."""
+def _beam_args(logp, lens, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, who):
+    """The checks both beam decoders make (`who` names the caller).  Returns (B, T, C, cutoff_top_n clamped to C)."""
     if logp.dtype != torch.float32 or logp.dim() != 3:
-        raise TypeError("ctc_beam_decode takes (B, T, C) float32 log-probs")
+        raise TypeError("%s takes (B, T, C) float32 log-probs" % who)
     B, T, Cc = logp.shape
     cutoff_top_n = min(int(cutoff_top_n), Cc) if Cc >= 1 else int(cutoff_top_n)    # above C it acts as C
     if not 1 <= beam_width <= CTC_BEAM_MAX_WIDTH:
@@ -444,14 +441,29 @@ def ctc_beam_decode(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: int
         raise ValueError("cutoff_prob %r outside (0, 1]" % (cutoff_prob,))
     if not 0 <= blank < Cc:
         raise ValueError("blank %d outside [0, %d)" % (blank, Cc))
+    return B, T, Cc, cutoff_top_n
+
+
+def _beam_outputs(logp, n_best):
+    """the (tokens, n_tokens, scores) a beam decode of logp (B, T, C) fills"""
+    B, T, _ = logp.shape
+    tokens = torch.empty(B, n_best, T, dtype=torch.int32, device=logp.device)
+    n = torch.empty(B, n_best, dtype=torch.int32, device=logp.device)
+    scores = torch.empty(B, n_best, dtype=torch.float32, device=logp.device)
+    return tokens, n, scores
+
+
+def ctc_beam_decode(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: int, beam_width: int = 16, cutoff_top_n: int = 40,
+                    cutoff_prob: float = 1.0, n_best: int = 1):
+    """CTC prefix beam search (no LM) of logp (B,T,C) f32 log-probs, lens (B) i32 frames or None (= T).  Returns
+    (tokens (B, n_best, T) i32, -1 past each hypothesis; n_tokens (B, n_best) i32, -1 for an empty slot; scores (B, n_best) f32
+    log-probabilities, best first).  Shapes outside the kernel's range raise ValueError."""
+    B, T, Cc, cutoff_top_n = _beam_args(logp, lens, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, "ctc_beam_decode")
     nb = int(_lib.load().lasr_ctc_beam_workspace_bytes(B, T, Cc, beam_width, cutoff_top_n))
     if nb == 0:
         raise ValueError("ctc_beam_decode: shape (%d, %d, %d) outside the kernel's range" % (B, T, Cc))
-    dev = logp.device
-    tokens = torch.empty(B, n_best, T, dtype=torch.int32, device=dev)
-    n = torch.empty(B, n_best, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
-    ws = _ws(nb, dev)
+    tokens, n, scores = _beam_outputs(logp, n_best)
+    ws = _ws(nb, logp.device)
     call("lasr_ctc_beam_decode", _p(logp), _p(lens), B, T, Cc, int(blank), int(beam_width), int(cutoff_top_n), float(cutoff_prob),
          int(n_best), _p(tokens), _p(n), _p(scores), _p(ws), nb, _stream())
     return tokens, n, scores
@@ -526,26 +538,13 @@ def ctc_beam_decode_lm(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: 
     scores, am_scores): scores are the fused log-scores the hypotheses are ranked by, am_scores ctc_decoders' approx_ctc
     (fused - labels * beta - alpha * sentence LM score).  Shapes and ranges as ctc_beam_decode; the image must sit on logp's
     device and hold C - 1 labels."""
-    if logp.dtype != torch.float32 or logp.dim() != 3:
-        raise TypeError("ctc_beam_decode_lm takes (B, T, C) float32 log-probs")
-    if not isinstance(lm, ArpaLm):
+    who = "ctc_beam_decode_lm"
+    # lm's type is checked after logp's and before any range, so a bad logp is left to _beam_args' own TypeError
+    if not isinstance(lm, ArpaLm) and logp.dtype == torch.float32 and logp.dim() == 3:
         raise TypeError("lm must be an ArpaLm (ops.load_arpa)")
-    B, T, Cc = logp.shape
+    B, T, Cc, cutoff_top_n = _beam_args(logp, lens, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, who)
     alpha = lm.alpha if alpha is None else float(alpha)
     beta = lm.beta if beta is None else float(beta)
-    cutoff_top_n = min(int(cutoff_top_n), Cc) if Cc >= 1 else int(cutoff_top_n)
-    if not 1 <= beam_width <= CTC_BEAM_MAX_WIDTH:
-        raise ValueError("beam_width %d outside 1..%d" % (beam_width, CTC_BEAM_MAX_WIDTH))
-    if not 1 <= cutoff_top_n <= CTC_BEAM_MAX_TOP_N:
-        raise ValueError("cutoff_top_n %d outside 1..%d" % (cutoff_top_n, CTC_BEAM_MAX_TOP_N))
-    if not 1 <= Cc <= CTC_BEAM_MAX_CLASSES:
-        raise ValueError("%d classes: the beam decoder takes at most %d" % (Cc, CTC_BEAM_MAX_CLASSES))
-    if not 1 <= n_best <= beam_width:
-        raise ValueError("n_best %d outside 1..beam_width (%d)" % (n_best, beam_width))
-    if not 0.0 < cutoff_prob <= 1.0:
-        raise ValueError("cutoff_prob %r outside (0, 1]" % (cutoff_prob,))
-    if not 0 <= blank < Cc:
-        raise ValueError("blank %d outside [0, %d)" % (blank, Cc))
     if not (math.isfinite(alpha) and math.isfinite(beta)):
         raise ValueError("alpha %r / beta %r must be finite" % (alpha, beta))
     if len(lm.vocab) != Cc - 1:
@@ -555,12 +554,9 @@ def ctc_beam_decode_lm(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: 
     nb = int(_lib.load().lasr_ctc_beam_lm_workspace_bytes(B, T, Cc, beam_width, cutoff_top_n))
     if nb == 0:
         raise ValueError("ctc_beam_decode_lm: shape (%d, %d, %d) outside the kernel's range" % (B, T, Cc))
-    dev = logp.device
-    tokens = torch.empty(B, n_best, T, dtype=torch.int32, device=dev)
-    n = torch.empty(B, n_best, dtype=torch.int32, device=dev)
-    scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
-    am = torch.empty(B, n_best, dtype=torch.float32, device=dev)
-    ws = _ws(nb, dev)
+    tokens, n, scores = _beam_outputs(logp, n_best)
+    am = torch.empty_like(scores)
+    ws = _ws(nb, logp.device)
     call("lasr_ctc_beam_decode_lm", _p(logp), _p(lens), B, T, Cc, int(blank), int(beam_width), int(cutoff_top_n), float(cutoff_prob),
          int(n_best), _p(lm.image), alpha, beta, _p(tokens), _p(n), _p(scores), _p(am), _p(ws), nb, _stream())
     return tokens, n, scores, am

@@ -4,7 +4,9 @@ beta 1.0.  LMs are synthetic character ARPA files (tests/helpers/arpa_synth.py):
 English letters; for C=4334 a 3-gram of about 1 M n-grams and a 6-gram over an AISHELL-sized vocabulary.  Inputs are peaky
 log-softmaxed normals (tools/beam_time.py).  Prints one JSON line per (shape, LM, beam); --out writes them as JSONL.
 
-    python tools/beam_lm_time.py [--reps N] [--out profiles/r07_beam_lm_time.jsonl]"""
+    python tools/beam_lm_time.py [--reps N] [--out profiles/r07_beam_lm_time.jsonl] [--dump FILE.npz]
+
+--dump saves every timed case's outputs (tokens, n_tokens, scores and, with an LM, am_scores), as tools/beam_time.py does."""
 import argparse
 import json
 import os
@@ -19,32 +21,17 @@ import torch  # noqa: E402
 
 import arpa_synth as S  # noqa: E402
 from lightning_asr_amd import ops  # noqa: E402
-from tools.beam_time import peaky  # noqa: E402
+from tools.beam_time import dump_case, peaky, save_dump, timed  # noqa: E402
 
 EN = ["'"] + [chr(ord("a") + i) for i in range(26)]               # data/labels.txt: C = 28 with the blank
 HAN = [chr(0x4E00 + i) for i in range(4333)]
-
-
-def timed(fn, reps):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    ms.sort()
-    return ms[len(ms) // 2], ms[0], out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dump", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda")
     tmp = tempfile.mkdtemp()
@@ -58,18 +45,20 @@ def main():
     print("# LMs written in %.1f s" % (time.time() - t0), flush=True)
     shapes = [("cfg2", 32, 501, 28, (32,), ("c28_3gram", "c28_6gram")),
               ("cfg5", 32, 801, 4334, (32, 64), ("c4334_3gram", "c4334_6gram"))]
-    lines = []
+    lines, dump = [], {}
     for name, B, T, C, widths, lm_names in shapes:
         x = peaky(B, T, C, 1, dev)
         lens = torch.full((B,), T, dtype=torch.int32, device=dev)
         for W in widths:
-            base, base_min, _ = timed(lambda: ops.ctc_beam_decode(x, lens, C - 1, W, 40, 1.0, 1), a.reps)
+            base, base_min, out = timed(lambda: ops.ctc_beam_decode(x, lens, C - 1, W, 40, 1.0, 1), a.reps)
+            dump_case(dump, "%s.w%d.no_lm" % (name, W), out)
             for lm_name in lm_names:
                 vocab, path = lms[lm_name]
                 t1 = time.time()
                 lm = ops.load_arpa(path, vocab, dev, 0.5, 1.0)
                 load_s = time.time() - t1
                 ms, ms_min, out = timed(lambda: ops.ctc_beam_decode_lm(x, lens, C - 1, lm, W, 40, 1.0, 1), a.reps)
+                dump_case(dump, "%s.w%d.%s" % (name, W, lm_name), out, ("tokens", "n_tokens", "scores", "am_scores"))
                 rec = {"shape": name, "B": B, "T": T, "C": C, "beam_width": W, "cutoff_top_n": 40, "lm": lm_name,
                        "order": lm.order, "n_ngrams": lm.n_ngrams, "image_mb": round(lm.image.numel() / 2 ** 20, 2),
                        "load_s": round(load_s, 2), "ms_median": round(ms, 3), "ms_min": round(ms_min, 3),
@@ -78,6 +67,8 @@ def main():
                        "mean_tokens": round(float(out[1].float().mean()), 1)}
                 lines.append(rec)
                 print(json.dumps(rec), flush=True)
+    if a.dump:
+        save_dump(a.dump, dump)
     if a.out:
         with open(a.out, "w") as f:
             for r in lines:
