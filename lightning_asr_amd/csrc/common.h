@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include <utility>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -30,9 +31,9 @@ int hip_fail(hipError_t e, const char* what);
     hipError_t e__ = hipGetLastError();                           \
     if (e__ != hipSuccess) return ::lasr::hip_fail(e__, name);    \
   } while (0)
-#define LASR_TRY(expr)          \
+#define LASR_TRY(...)           \
   do {                          \
-    int rc__ = (expr);          \
+    int rc__ = (__VA_ARGS__);   \
     if (rc__ != 0) return rc__; \
   } while (0)
 
@@ -240,6 +241,44 @@ __device__ __forceinline__ void with_act(int act, F&& f) {
   if (act == LASR_ACT_RELU) f(std::integral_constant<int, LASR_ACT_RELU>{});
   else if (act == LASR_ACT_SWISH) f(std::integral_constant<int, LASR_ACT_SWISH>{});
   else f(std::integral_constant<int, LASR_ACT_NONE>{});
+}
+
+// ---- host-side launch dispatch -------------------------------------------------------------------
+// The same on the host: a launcher names its kernel ONCE, inside nested generic lambdas that turn its runtime flags into template
+// arguments - with_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type; with_bool(y2 != nullptr, [&](auto h2) {
+// launch_lds(kernel<T, decltype(h2)::value>, grid, block, lds, st, args...); }); }).  Only the listed combinations are instantiated.
+template <typename T>
+struct TypeTag { using type = T; };
+template <typename F>
+void with_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <typename F>
+void with_dtype(int dtype, F&& f) {       // LASR_F32 / LASR_BF16, checked by the caller
+  if (dtype == LASR_F32) f(TypeTag<float>{});
+  else f(TypeTag<bf16_t>{});
+}
+// f(std::integral_constant<int, V>) for the V of the list that equals v; LASR_E_SHAPE (f not called) when none does
+template <int... Vs, typename F>
+int with_int(int v, F&& f) {
+  const bool hit = ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+  return hit ? 0 : fail(LASR_E_SHAPE, "with_int: no kernel is instantiated for the value %d", v);
+}
+
+// Launch with `lds_bytes` of dynamic LDS.  A kernel that asks for any has its dynamic limit (64 KB by default) raised to all a
+// workgroup can have beside the kernel's static LDS: the runtime refuses a limit that, with the static part, exceeds the CU's LDS.
+static constexpr size_t kLdsBytes = 160 * 1024;     // LDS of one gfx950 CU: the most a workgroup can have, static + dynamic
+template <typename K, typename... Args>
+void launch_lds(K kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, Args&&... args) {
+  if (lds_bytes) {
+    hipFuncAttributes fa;
+    const size_t fixed = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel)) == hipSuccess && fa.sharedSizeBytes < kLdsBytes ? fa.sharedSizeBytes : 0;
+    const void* k = reinterpret_cast<const void*>(kernel);
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - fixed)) != hipSuccess)
+      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);   // at least what this launch needs
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, std::forward<Args>(args)...);
 }
 
 }  // namespace lasr

@@ -1550,6 +1550,62 @@ using namespace lasr;
 
 static int64_t conv_out_len(int64_t Tin, int k, int stride) { return (Tin + 2 * (k / 2) - k) / stride + 1; }
 
+// ---- launch side: every LASR_DW* switch and the geometry of the MFMA kernels, each defined once ------------------------------------
+// A/B switches, read once per process
+struct DwSwitches {
+  static int env_int(const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
+  const bool fma = getenv("LASR_DWCONV_FMA") != nullptr;             // forward: the f32-FMA VALU form
+  const bool dot2 = getenv("LASR_DWCONV_DOT2") != nullptr;           // forward: the dot2 VALU form
+  const bool no_half = getenv("LASR_DWCONV_NO_HALF") != nullptr;     // forward: full 512-frame tiles only
+  const bool wgrad_valu = getenv("LASR_DWWGRAD_VALU") != nullptr;    // weight gradient: the VALU form
+  const int zmax = env_int("LASR_DWWGRAD_ZSPLIT", 2);                // weight gradient: most time splits per utterance
+  const bool no_fused_bwd = getenv("LASR_DW_NO_FUSED_BWD") != nullptr;   // backward: the two launches
+  // backward, one workgroup for both consumers of dy (dwconv_bwd_uni_kernel): 32 (default: 32-channel workgroups, two per CU; k > 75
+  // takes the 64-channel form), 64 (64-channel workgroups, one per CU), 0 (the two-kind grid).  Measured in the cfg2 step (rocprofv3,
+  // profiles/r03c_*): 36.9 / 38.1 / 37.8 us per 512-channel unit - see DESIGN.md
+  const int uni = env_int("LASR_DW_UNI", 32);
+};
+static const DwSwitches& dw_switches() {
+  static const DwSwitches s;
+  return s;
+}
+
+// The stride-1 bf16 depthwise shape (B, T, C, k) as the MFMA kernels tile it.  The forward, its BN-fused form, the weight gradient and
+// the fused backward all ask here, so the grids that have to agree (the fused BN + depthwise hand-over, the two-kind backward) do.
+struct DwShape {
+  bool fwd;       // the MFMA forward / data-gradient kernels take it (dwconv_s1_mfma_kernel and its fused forms)
+  bool wgrad;     // the MFMA weight-gradient kernel takes it
+  int nks;        // 32-wide K steps of a 16-frame block's input window
+  int nset;       // MFMA sets of 256 frames per time tile: 2, or 1 = half tiles spread over gridDim.z
+  int gz_d;       // gridDim.z of the forward / data-gradient grid
+  int zsplit;     // time splits (gridDim.z) of the weight-gradient grid: partials per utterance
+};
+static DwShape dw_shape(int64_t B, int64_t T, int64_t C, int k, int dtype, bool aligned16) {
+  const DwSwitches& sw = dw_switches();
+  const int padk = k / 2, shk = ((padk + 7) & ~7) - padk;
+  const bool mfma = dtype == LASR_BF16 && aligned16 && C % 8 == 0 && T < (1 << 30);
+  DwShape s;
+  s.fwd = mfma && !sw.fma && !sw.dot2 && 15 + k + shk <= dwm::KWMAX;
+  s.wgrad = mfma && !sw.wgrad_valu && k + shk <= 16 * 7;
+  s.nks = (15 + k + shk + 31) / 32;
+  // one workgroup per (64 channels, utterance) and 512-frame tile fills the chip from C = 512 on (B = 32);
+  // narrower layers take 256-frame half tiles spread over gridDim.z
+  const bool half = !sw.no_half && T > 256 && cdiv(C, kCB) * B * cdiv(T, (int64_t)512) < 200;
+  s.nset = half ? 1 : 2;
+  s.gz_d = half ? (int)std::min<int64_t>(cdiv(T, (int64_t)256), 8) : 1;
+  // the weight gradient likewise: narrower layers split the time tiles
+  const int n_tiles = (int)((T + 15 + dwg::TU) / dwg::TU);
+  s.zsplit = 1;
+  while (s.zsplit < sw.zmax && s.zsplit * 2 <= n_tiles && cdiv(C, kCB) * B * s.zsplit < 200) s.zsplit *= 2;
+  return s;
+}
+// <NKS, NSET>, the template head of the kernels on DwShape's forward tiles, as two tags inside f
+template <typename F>
+static int with_dw_tile(const DwShape& s, F&& f) {
+  return with_int<1, 2, 3, 4>(s.nks, [&](auto nks) { with_int<1, 2>(s.nset, [&](auto nset) { f(nks, nset); }); });
+}
+static bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
 extern "C" int lasr_dwconv_fwd(const void* x, const float* w, const void* addend, void* y, int dtype, int64_t B, int64_t Tin,
                                int64_t C, int k, int stride, int flip, void* stream) {
   LASR_CHECK_ARG(x && w && y, "lasr_dwconv_fwd: null pointer");
@@ -1557,69 +1613,49 @@ extern "C" int lasr_dwconv_fwd(const void* x, const float* w, const void* addend
   LASR_CHECK_SHAPE(k >= 1 && k <= kMaxK && (k & 1) && (stride == 1 || stride == 2) && C % 4 == 0 && B > 0 && B < 65536 && Tin > 0,
                    "lasr_dwconv_fwd: k=%d stride=%d C=%lld", k, stride, (long long)C);
   LASR_CHECK_SHAPE(!(flip && stride != 1), "lasr_dwconv_fwd: flip needs stride 1");
-  LASR_CHECK_SHAPE(stride != 1 || (C % (int64_t)(16 / dtype_size(dtype)) == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0),
+  LASR_CHECK_SHAPE(stride != 1 || (C % (int64_t)(16 / dtype_size(dtype)) == 0 && al16(x)),
                    "lasr_dwconv_fwd: the stride-1 kernel loads 16-byte channel vectors (C=%lld)", (long long)C);
   const int64_t Tout = conv_out_len(Tin, k, stride);
   const int in_rows = (kTT - 1) * stride + k;
   const size_t shmem = ((size_t)in_rows + k) * kCB * sizeof(float);
   dim3 grid((unsigned)cdiv(Tout, kTT), (unsigned)cdiv(C, kCB), (unsigned)B);
-  const int tok = prof_begin(LASR_PROF_DWCONV, as_stream(stream), 2.0 * (double)B * Tout * C * k,
+  hipStream_t st = as_stream(stream);
+  const int tok = prof_begin(LASR_PROF_DWCONV, st, 2.0 * (double)B * Tout * C * k,
                              (double)B * (Tin + Tout * (addend ? 2 : 1)) * C * dtype_size(dtype));
+  int rc = 0;
   if (stride == 1) {
     const int kpad = (k + 7) & ~7;
     const size_t esz1 = dtype_size(dtype);
     const size_t sh1 = (size_t)kpad * kCB * esz1 + (size_t)(kTT + kpad + 8) * (kCB + (esz1 == 2 ? 8 : 0)) * esz1;
+    const DwShape s = dw_shape(B, Tin, C, k, dtype, true);
     if (dtype == LASR_F32) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_s1_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL(dwconv_s1_kernel<float>, grid, dim3(256), sh1, as_stream(stream), (const float*)x, w, (const float*)addend,
-                         (float*)y, Tin, C, k, flip);
+      launch_lds(dwconv_s1_kernel<float>, grid, dim3(256), sh1, st, (const float*)x, w, (const float*)addend, (float*)y, Tin, C, k, flip);
+    } else if (s.fwd) {
+      const dim3 gridm((unsigned)cdiv(C, kCB), (unsigned)B, (unsigned)s.gz_d);
+      const uint32_t* taps = dw_taps_for(w, flip, C);   // the step's precomputed tap tables, when the model call in progress made them
+      rc = with_dw_tile(s, [&](auto nks, auto nset) {
+        launch_lds(dwconv_s1_mfma_kernel<nks.value, nset.value>, gridm, dim3(512), dwm::SMEM, st, (const bf16_t*)x, w, (const bf16_t*)addend,
+                   (bf16_t*)y, (int)Tin, (int)C, k, flip, taps);
+      });
+    } else if (dw_switches().fma) {
+      launch_lds(dwconv_s1_kernel<bf16_t>, grid, dim3(256), sh1, st, (const bf16_t*)x, w, (const bf16_t*)addend, (bf16_t*)y, Tin, C, k, flip);
     } else {
-      static const bool fma_form = getenv("LASR_DWCONV_FMA") != nullptr;   // A/B switches: the f32-FMA and the dot2 VALU forms
-      static const bool dot2_form = getenv("LASR_DWCONV_DOT2") != nullptr;
-      const int padk = k / 2, shk = ((padk + 7) & ~7) - padk;
-      if (!fma_form && !dot2_form && C % 8 == 0 && 15 + k + shk <= dwm::KWMAX && Tin < (1 << 30)) {
-        const int nks = (15 + k + shk + 31) / 32;
-        // one workgroup per (64 channels, utterance) and 512-frame tile fills the chip from C = 512 on (B = 32);
-        // narrower layers take 256-frame half tiles spread over gridDim.z
-        static const bool no_half = getenv("LASR_DWCONV_NO_HALF") != nullptr;
-        const bool half = !no_half && Tin > 256 && cdiv(C, kCB) * B * cdiv(Tin, (int64_t)512) < 200;
-        const dim3 gridm((unsigned)cdiv(C, kCB), (unsigned)B, half ? (unsigned)std::min<int64_t>(cdiv(Tin, (int64_t)256), 8) : 1u);
-        const uint32_t* taps = dw_taps_for(w, flip, C);   // the step's precomputed tap tables, when the model call in progress made them
-#define LASR_DWM2(N_, S_)                                                                                                    \
-  do {                                                                                                                       \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_s1_mfma_kernel<N_, S_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((dwconv_s1_mfma_kernel<N_, S_>), gridm, dim3(512), dwm::SMEM, as_stream(stream), (const bf16_t*)x, w,  \
-                       (const bf16_t*)addend, (bf16_t*)y, (int)Tin, (int)C, k, flip, taps);                                  \
-  } while (0)
-#define LASR_DWM(N_) do { if (half) LASR_DWM2(N_, 1); else LASR_DWM2(N_, 2); } while (0)
-        if (nks == 1) LASR_DWM(1); else if (nks == 2) LASR_DWM(2); else if (nks == 3) LASR_DWM(3); else LASR_DWM(4);
-#undef LASR_DWM
-#undef LASR_DWM2
-      } else if (fma_form) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_s1_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(dwconv_s1_kernel<bf16_t>, grid, dim3(256), sh1, as_stream(stream), (const bf16_t*)x, w,
-                           (const bf16_t*)addend, (bf16_t*)y, Tin, C, k, flip);
-      } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_s1_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(dwconv_s1_bf16_kernel, grid, dim3(256), sh1, as_stream(stream), (const bf16_t*)x, w, (const bf16_t*)addend,
-                           (bf16_t*)y, Tin, C, k, flip);
-      }
+      launch_lds(dwconv_s1_bf16_kernel, grid, dim3(256), sh1, st, (const bf16_t*)x, w, (const bf16_t*)addend, (bf16_t*)y, Tin, C, k, flip);
     }
   } else {
     // 64-frame tiles when 128-frame tiles would not fill the chip (first_cnn: 64 channels, stride 2)
     const bool small = (int64_t)grid.x * grid.y * grid.z < 200;
     const dim3 g2 = small ? dim3((unsigned)cdiv(Tout, 64), grid.y, grid.z) : grid;
-#define LASR_DWF(T_, R_)                                                                                                          \
-  do {                                                                                                                            \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_fwd_kernel<T_, R_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((dwconv_fwd_kernel<T_, R_>), g2, dim3(256), shmem, as_stream(stream), (const T_*)x, w, (const T_*)addend, (T_*)y, Tin,  \
-                       Tout, C, k, stride, flip);                                                                                 \
-  } while (0)
-    if (dtype == LASR_F32) { if (small) LASR_DWF(float, 4); else LASR_DWF(float, 8); }
-    else { if (small) LASR_DWF(bf16_t, 4); else LASR_DWF(bf16_t, 8); }
-#undef LASR_DWF
+    with_dtype(dtype, [&](auto t) {
+      rc = with_int<4, 8>(small ? 4 : 8, [&](auto r) {
+        using T = typename decltype(t)::type;
+        launch_lds(dwconv_fwd_kernel<T, decltype(r)::value>, g2, dim3(256), shmem, st, (const T*)x, w, (const T*)addend, (T*)y, Tin, Tout, C, k,
+                   stride, flip);
+      });
+    });
   }
-  prof_end(tok, as_stream(stream));
+  prof_end(tok, st);
+  LASR_TRY(rc);
   LASR_LAUNCH_CHECK("dwconv_fwd_kernel");
   return 0;
 }
@@ -1627,35 +1663,24 @@ extern "C" int lasr_dwconv_fwd(const void* x, const float* w, const void* addend
 int lasr::dwconv_fwd_bn(const void* y, const float* coef, const void* y2, const float* coef2, int act, const float* w, void* out, void* u,
                         int64_t B, int64_t T, int64_t C, int k, void* stream) {
   LASR_CHECK_ARG(y && coef && w && out && u && (!y2 || coef2), "dwconv_fwd_bn: null pointer");
-  static const bool off = getenv("LASR_DWCONV_FMA") || getenv("LASR_DWCONV_DOT2");
-  const int padk = k / 2, shk = ((padk + 7) & ~7) - padk;
-  auto al16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-  if (off || k < 1 || k > kMaxK || !(k & 1) || C % 8 != 0 || C < 8 || 15 + k + shk > dwm::KWMAX || T <= 0 || T >= (1 << 30) || B <= 0 ||
-      B >= 65536 || !al16(y) || !al16(y2) || !al16(out) || !al16(u) || !al16(coef) || !al16(coef2))
-    return 1;
-  const int nks = (15 + k + shk + 31) / 32;
-  static const bool no_half = getenv("LASR_DWCONV_NO_HALF") != nullptr;
-  const bool half = !no_half && T > 256 && cdiv(C, kCB) * B * cdiv(T, (int64_t)512) < 200;     // (the grid of lasr_dwconv_fwd)
+  if (k < 1 || k > kMaxK || !(k & 1) || C < 8 || T <= 0 || B <= 0 || B >= 65536) return 1;
+  const DwShape s = dw_shape(B, T, C, k, LASR_BF16, al16(y) && al16(y2) && al16(out) && al16(u) && al16(coef) && al16(coef2));
   // Full 512-frame tiles are one workgroup per CU in ONE round, every workgroup in the same phase at the same time: the second
   // input and the extra output are pure added HBM time there (measured at C = 512: 21.6 us against 13.7 + 7.6 for the two
   // launches, and the GEMM behind it starts into twice the write-back).  Half tiles run two staggered rounds: 13.2 against 9.5 + 7.6.
   static const bool full_too = getenv("LASR_BN_DW_FUSE") && atoi(getenv("LASR_BN_DW_FUSE")) == 2;
-  if (!half && !full_too) return 1;
-  const dim3 gridm((unsigned)cdiv(C, kCB), (unsigned)B, half ? (unsigned)std::min<int64_t>(cdiv(T, (int64_t)256), 8) : 1u);
+  if (!s.fwd || (s.nset == 2 && !full_too)) return 1;
+  const dim3 gridm((unsigned)cdiv(C, kCB), (unsigned)B, (unsigned)s.gz_d);
   DwBnIn bn;
   bn.y = (const bf16_t*)y; bn.y2 = (const bf16_t*)y2; bn.coef = coef; bn.coef2 = coef2; bn.out = (bf16_t*)out; bn.act = act;
-  const int tok = prof_begin(LASR_PROF_DWCONV, as_stream(stream), 2.0 * (double)B * T * C * k, (double)B * T * C * (y2 ? 4 : 3) * 2);
+  hipStream_t st = as_stream(stream);
+  const int tok = prof_begin(LASR_PROF_DWCONV, st, 2.0 * (double)B * T * C * k, (double)B * T * C * (y2 ? 4 : 3) * 2);
   const uint32_t* taps = dw_taps_for(w, 0, C);
-#define LASR_DWMB2(N_, S_)                                                                                                  \
-  do {                                                                                                                      \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_s1_mfma_bn_kernel<N_, S_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((dwconv_s1_mfma_bn_kernel<N_, S_>), gridm, dim3(512), dwm::SMEM, as_stream(stream), bn, w, (bf16_t*)u, (int)T, (int)C, k, taps); \
-  } while (0)
-#define LASR_DWMB(N_) do { if (half) LASR_DWMB2(N_, 1); else LASR_DWMB2(N_, 2); } while (0)
-  if (nks == 1) LASR_DWMB(1); else if (nks == 2) LASR_DWMB(2); else if (nks == 3) LASR_DWMB(3); else LASR_DWMB(4);
-#undef LASR_DWMB
-#undef LASR_DWMB2
-  prof_end(tok, as_stream(stream));
+  const int rc = with_dw_tile(s, [&](auto nks, auto nset) {
+    launch_lds(dwconv_s1_mfma_bn_kernel<nks.value, nset.value>, gridm, dim3(512), dwm::SMEM, st, bn, w, (bf16_t*)u, (int)T, (int)C, k, taps);
+  });
+  prof_end(tok, st);
+  LASR_TRY(rc);
   LASR_LAUNCH_CHECK("dwconv_s1_mfma_bn_kernel");
   return 0;
 }
@@ -1687,29 +1712,21 @@ static int dwconv_wgrad_impl(const void* x, const void* dy, float* dw, int dtype
                    "lasr_dwconv_wgrad: k=%d stride=%d C=%lld", k, stride, (long long)C);
   const int64_t Tout = conv_out_len(Tin, k, stride);
   if (workspace_bytes < lasr_dwconv_wgrad_workspace_bytes(B, Tout, C, k)) return fail(LASR_E_WORKSPACE, "lasr_dwconv_wgrad: workspace");
-  {
-    static const bool valu_form = getenv("LASR_DWWGRAD_VALU") != nullptr;   // A/B switch: the VALU form below
-    const int padk = k / 2, shk = ((padk + 7) & ~7) - padk;
-    if (!valu_form && stride == 1 && dtype == LASR_BF16 && C % 8 == 0 && k + shk <= 16 * 7 && Tin < (1 << 30)) {
-      float* parts = reinterpret_cast<float*>(workspace);   // [B * zsplit][C*k]: zsplit partials per utterance
-      // one workgroup per (64 channels, utterance) fills the chip from C = 512 on; narrower layers split the time tiles
-      const int n_tiles = (int)((Tin + 15 + dwg::TU) / dwg::TU);
-      static const int zmax = getenv("LASR_DWWGRAD_ZSPLIT") ? atoi(getenv("LASR_DWWGRAD_ZSPLIT")) : 2;
-      int zsplit = 1;
-      while (zsplit < zmax && zsplit * 2 <= n_tiles && cdiv(C, kCB) * B * zsplit < 200) zsplit *= 2;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_wgrad_s1_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL(dwconv_wgrad_s1_mfma_kernel, dim3((unsigned)cdiv(C, kCB), (unsigned)B, (unsigned)zsplit), dim3(512), dwg::SMEM,
-                         as_stream(stream), (const bf16_t*)x, (const bf16_t*)dy, parts, (int)Tin, (int)C, k);
-      LASR_LAUNCH_CHECK("dwconv_wgrad_s1_mfma_kernel");
-      if (n_partials_out) { *n_partials_out = (int)B * zsplit; return 0; }
-      return launch_reduce_partials(parts, (int)B * zsplit, C * k, dw, C * k, nullptr, as_stream(stream));
-    }
+  hipStream_t st = as_stream(stream);
+  float* partials = reinterpret_cast<float*>(workspace);
+  const DwShape s = dw_shape(B, Tin, C, k, dtype, true);
+  if (stride == 1 && s.wgrad) {
+    // [B * zsplit][C*k]: zsplit partials per utterance
+    launch_lds(dwconv_wgrad_s1_mfma_kernel, dim3((unsigned)cdiv(C, kCB), (unsigned)B, (unsigned)s.zsplit), dim3(512), dwg::SMEM, st,
+               (const bf16_t*)x, (const bf16_t*)dy, partials, (int)Tin, (int)C, k);
+    LASR_LAUNCH_CHECK("dwconv_wgrad_s1_mfma_kernel");
+    if (n_partials_out) { *n_partials_out = (int)B * s.zsplit; return 0; }
+    return launch_reduce_partials(partials, (int)B * s.zsplit, C * k, dw, C * k, nullptr, st);
   }
   const int n_chunks = (int)cdiv(Tout, stride == 1 ? kWChunk : kWChunkG);
   const int in_rows = (kWT - 1) * stride + k;
   const size_t shmem = ((size_t)in_rows + kWT) * kCB * sizeof(float);
   dim3 grid((unsigned)n_chunks, (unsigned)cdiv(C, kCB), (unsigned)B);
-  float* partials = reinterpret_cast<float*>(workspace);
   if (stride == 1) {
     const int ng = (k + 7) >> 3;
     int ts = 16 / ng;
@@ -1718,28 +1735,20 @@ static int dwconv_wgrad_impl(const void* x, const void* dy, float* dw, int dtype
     size_t sh1 = (size_t)(WT + kpad + 8 + WT) * (kCB + (dtype_size(dtype) == 2 ? 8 : 0)) * dtype_size(dtype);   // padded rows
     const size_t red = (size_t)ts * kpad * kCB * sizeof(float);
     if (red > sh1) sh1 = red;
-    if (dtype == LASR_F32) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_wgrad_s1_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL(dwconv_wgrad_s1_kernel<float>, grid, dim3(256), sh1, as_stream(stream), (const float*)x, (const float*)dy,
-                         partials, Tin, C, k, ts);
-    } else {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_wgrad_s1_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL(dwconv_wgrad_s1_kernel<bf16_t>, grid, dim3(256), sh1, as_stream(stream), (const bf16_t*)x, (const bf16_t*)dy,
-                         partials, Tin, C, k, ts);
-    }
-  } else if (dtype == LASR_F32) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_wgrad_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(dwconv_wgrad_kernel<float>, grid, dim3(256), shmem, as_stream(stream), (const float*)x, (const float*)dy,
-                       partials, Tin, Tout, C, k, stride);
+    with_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      launch_lds(dwconv_wgrad_s1_kernel<T>, grid, dim3(256), sh1, st, (const T*)x, (const T*)dy, partials, Tin, C, k, ts);
+    });
   } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_wgrad_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(dwconv_wgrad_kernel<bf16_t>, grid, dim3(256), shmem, as_stream(stream), (const bf16_t*)x,
-                       (const bf16_t*)dy, partials, Tin, Tout, C, k, stride);
+    with_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      launch_lds(dwconv_wgrad_kernel<T>, grid, dim3(256), shmem, st, (const T*)x, (const T*)dy, partials, Tin, Tout, C, k, stride);
+    });
   }
   LASR_LAUNCH_CHECK("dwconv_wgrad_kernel");
   const int64_t n = C * k;
   if (n_partials_out) { *n_partials_out = (int)(B * n_chunks); return 0; }   // the caller sums the slabs later (lasr_reduce_many)
-  return launch_reduce_partials(partials, (int)(B * n_chunks), n, dw, n, nullptr, as_stream(stream));
+  return launch_reduce_partials(partials, (int)(B * n_chunks), n, dw, n, nullptr, st);
 }
 
 #ifdef LASR_DW_STAMPS
@@ -1756,88 +1765,66 @@ extern "C" int lasr_dwconv_bwd_fused(const void* x, const void* dy, const float*
   LASR_CHECK_ARG(dtype == LASR_F32 || dtype == LASR_BF16, "lasr_dwconv_bwd_fused: bad dtype");
   LASR_CHECK_SHAPE(k >= 1 && k <= kMaxK && (k & 1) && C % 4 == 0 && B > 0 && B < 65536 && T > 0, "lasr_dwconv_bwd_fused: k=%d C=%lld", k,
                    (long long)C);
-  const int padk = k / 2, shk = ((padk + 7) & ~7) - padk;
-  static const bool no_fused = getenv("LASR_DW_NO_FUSED_BWD") != nullptr;     // A/B switch: the two launches
-  static const bool valu = getenv("LASR_DWWGRAD_VALU") || getenv("LASR_DWCONV_FMA") || getenv("LASR_DWCONV_DOT2");
-  const bool ok = !no_fused && !valu && dtype == LASR_BF16 && C % 8 == 0 && 15 + k + shk <= dwm::KWMAX && k + shk <= 16 * 7 &&
-                  T < (1 << 30) && reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(dy) % 16 == 0 &&
-                  workspace_bytes >= lasr_dwconv_wgrad_workspace_bytes(B, T, C, k);
+  const DwSwitches& sw = dw_switches();
+  const DwShape s = dw_shape(B, T, C, k, dtype, al16(x) && al16(dy));
+  // one launch needs BOTH MFMA forms (any VALU switch means the two launches, each with its own fall-back)
+  const bool ok = !sw.no_fused_bwd && s.fwd && s.wgrad && workspace_bytes >= lasr_dwconv_wgrad_workspace_bytes(B, T, C, k);
   if (!ok) {
     LASR_TRY(lasr_dwconv_wgrad_partials(x, dy, dtype, B, T, C, k, 1, workspace, workspace_bytes, n_partials, stream));
     return lasr_dwconv_fwd(dy, w, addend, dx, dtype, B, T, C, k, 1, 1, stream);
   }
-  const int nks = (15 + k + shk + 31) / 32;
-  {
-    // one workgroup for both consumers of dy (dwconv_bwd_uni_kernel): LASR_DW_UNI = 32 (default: 32-channel workgroups, two per CU;
-    // k > 75 takes the 64-channel form), 64 (64-channel workgroups, one per CU), 0 (the two-kind grid below, for A/B runs).
-    // Measured in the cfg2 step (rocprofv3, profiles/r03c_*): 36.9 / 38.1 / 37.8 us per 512-channel unit - see DESIGN.md
-    static const int uni = getenv("LASR_DW_UNI") ? atoi(getenv("LASR_DW_UNI")) : 32;
-    const bool u32 = uni == 32 && nks <= 3;
-    if (uni == 64 || uni == 32) {
-      DwUni u;
-      u.x = (const bf16_t*)x; u.dy = (const bf16_t*)dy; u.w = w; u.addend = (const bf16_t*)addend; u.dx = (bf16_t*)dx;
-      u.partials = reinterpret_cast<float*>(workspace);
-      u.Tlen = (int)T; u.C = (int)C; u.k = k; u.B = (int)B;
-      {
-        const uint32_t* tp = dw_taps_for(w, 1, C);        // reversed taps: the second half of the layer's table
-        u.taps = tp ? tp + (size_t)C * kDwTapRow : nullptr;
-      }
-      const int cb = u32 ? 32 : 64;
-      u.gx = (int)cdiv(C, cb);
-      const int n_tiles = (int)cdiv(T, (int64_t)dwu::TT);
-      const int want = u32 ? 400 : 200;                  // workgroups that fill the chip (two / one per CU)
-      int gz = 1;
-      while (gz * 2 <= n_tiles && (int64_t)u.gx * B * gz < want) gz *= 2;
-      u.gz = gz;
-      u.total = (int)(u.gx * B * gz);
-      const int tok = prof_begin(LASR_PROF_DWCONV, as_stream(stream), 4.0 * (double)B * T * C * k, (double)B * T * C * (addend ? 4 : 3) * 2);
-      const bool ntl = (nt_loads_mask() & 4) != 0;
-#define LASR_DWU(N_, W_) do { if (ntl) LASR_DWU2(N_, W_, true); else LASR_DWU2(N_, W_, false); } while (0)
-#define LASR_DWU2(N_, W_, NT_)                                                                                                    \
-  do {                                                                                                                            \
-    using Kc = dwu::Cfg<N_, W_>;                                                                                                  \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_bwd_uni_kernel<N_, W_, NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    const unsigned grid = (unsigned)((u.total + 15) / 16 * 16);                                                                     \
-    hipLaunchKernelGGL((dwconv_bwd_uni_kernel<N_, W_, NT_>), dim3(grid), dim3(64 * W_), Kc::SMEM, as_stream(stream), u);             \
-  } while (0)
-      if (u32) { if (nks == 1) LASR_DWU(1, 4); else if (nks == 2) LASR_DWU(2, 4); else LASR_DWU(3, 4); }
-      else { if (nks == 1) LASR_DWU(1, 8); else if (nks == 2) LASR_DWU(2, 8); else if (nks == 3) LASR_DWU(3, 8); else LASR_DWU(4, 8); }
-#undef LASR_DWU
-#undef LASR_DWU2
-      prof_end(tok, as_stream(stream));
-      LASR_LAUNCH_CHECK("dwconv_bwd_uni_kernel");
-      *n_partials = (int)B * gz;
-      return 0;
+  hipStream_t st = as_stream(stream);
+  if (sw.uni == 64 || sw.uni == 32) {
+    const bool u32 = sw.uni == 32 && s.nks <= 3;
+    DwUni u;
+    u.x = (const bf16_t*)x; u.dy = (const bf16_t*)dy; u.w = w; u.addend = (const bf16_t*)addend; u.dx = (bf16_t*)dx;
+    u.partials = reinterpret_cast<float*>(workspace);
+    u.Tlen = (int)T; u.C = (int)C; u.k = k; u.B = (int)B;
+    {
+      const uint32_t* tp = dw_taps_for(w, 1, C);        // reversed taps: the second half of the layer's table
+      u.taps = tp ? tp + (size_t)C * kDwTapRow : nullptr;
     }
+    const int cb = u32 ? 32 : 64;
+    u.gx = (int)cdiv(C, cb);
+    const int n_tiles = (int)cdiv(T, (int64_t)dwu::TT);
+    const int want = u32 ? 400 : 200;                  // workgroups that fill the chip (two / one per CU)
+    int gz = 1;
+    while (gz * 2 <= n_tiles && (int64_t)u.gx * B * gz < want) gz *= 2;
+    u.gz = gz;
+    u.total = (int)(u.gx * B * gz);
+    const int tok = prof_begin(LASR_PROF_DWCONV, st, 4.0 * (double)B * T * C * k, (double)B * T * C * (addend ? 4 : 3) * 2);
+    auto launch = [&](auto nks, auto waves) {
+      with_bool((nt_loads_mask() & 4) != 0, [&](auto nt) {
+        constexpr int N = decltype(nks)::value, W = decltype(waves)::value;
+        launch_lds(dwconv_bwd_uni_kernel<N, W, decltype(nt)::value>, dim3((unsigned)((u.total + 15) / 16 * 16)), dim3(64 * W),
+                   dwu::Cfg<N, W>::SMEM, st, u);
+      });
+    };
+    const int rc = u32 ? with_int<1, 2, 3>(s.nks, [&](auto nks) { launch(nks, std::integral_constant<int, 4>{}); })
+                       : with_int<1, 2, 3, 4>(s.nks, [&](auto nks) { launch(nks, std::integral_constant<int, 8>{}); });
+    prof_end(tok, st);
+    LASR_TRY(rc);
+    LASR_LAUNCH_CHECK("dwconv_bwd_uni_kernel");
+    *n_partials = (int)B * gz;
+    return 0;
   }
+  // two kinds of workgroup in one grid: DwShape's weight-gradient grid, then its data-gradient grid
   DwBwd a;
   a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy; a.w = w; a.addend = (const bf16_t*)addend; a.dx = (bf16_t*)dx;
   a.partials = reinterpret_cast<float*>(workspace);
   a.Tlen = (int)T; a.C = (int)C; a.k = k; a.gx = (int)cdiv(C, kCB); a.B = (int)B;
-  // the same grid choices as the separate launches
-  const int n_tiles = (int)((T + 15 + dwg::TU) / dwg::TU);
-  static const int zmax = getenv("LASR_DWWGRAD_ZSPLIT") ? atoi(getenv("LASR_DWWGRAD_ZSPLIT")) : 2;
-  int zsplit = 1;
-  while (zsplit < zmax && zsplit * 2 <= n_tiles && cdiv(C, kCB) * B * zsplit < 200) zsplit *= 2;
-  a.gz_w = zsplit;
+  a.gz_w = s.zsplit;
   a.n_w = a.gx * a.B * a.gz_w;
-  static const bool no_half = getenv("LASR_DWCONV_NO_HALF") != nullptr;
-  const bool half = !no_half && T > 256 && cdiv(C, kCB) * B * cdiv(T, (int64_t)512) < 200;
-  a.gz_d = half ? (int)std::min<int64_t>(cdiv(T, (int64_t)256), 8) : 1;
+  a.gz_d = s.gz_d;
   const unsigned total = (unsigned)(a.n_w + a.gx * a.B * a.gz_d);
   constexpr int kSmem = dwm::SMEM > dwg::SMEM ? dwm::SMEM : dwg::SMEM;
-  const int tok = prof_begin(LASR_PROF_DWCONV, as_stream(stream), 4.0 * (double)B * T * C * k, (double)B * T * C * (addend ? 5 : 4) * 2);
-#define LASR_DWB2(N_, S_)                                                                                                      \
-  do {                                                                                                                         \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_bwd_s1_mfma_kernel<N_, S_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((dwconv_bwd_s1_mfma_kernel<N_, S_>), dim3(total), dim3(512), kSmem, as_stream(stream), a);                \
-  } while (0)
-#define LASR_DWB(N_) do { if (half) LASR_DWB2(N_, 1); else LASR_DWB2(N_, 2); } while (0)
-  if (nks == 1) LASR_DWB(1); else if (nks == 2) LASR_DWB(2); else if (nks == 3) LASR_DWB(3); else LASR_DWB(4);
-#undef LASR_DWB
-#undef LASR_DWB2
-  prof_end(tok, as_stream(stream));
+  const int tok = prof_begin(LASR_PROF_DWCONV, st, 4.0 * (double)B * T * C * k, (double)B * T * C * (addend ? 5 : 4) * 2);
+  const int rc = with_dw_tile(s, [&](auto nks, auto nset) {
+    launch_lds(dwconv_bwd_s1_mfma_kernel<nks.value, nset.value>, dim3(total), dim3(512), kSmem, st, a);
+  });
+  prof_end(tok, st);
+  LASR_TRY(rc);
   LASR_LAUNCH_CHECK("dwconv_bwd_s1_mfma_kernel");
-  *n_partials = (int)B * zsplit;
+  *n_partials = (int)B * s.zsplit;
   return 0;
 }

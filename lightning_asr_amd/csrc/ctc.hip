@@ -346,37 +346,25 @@ extern "C" int lasr_log_softmax_bwd(const float* logp, const float* grad_logp, f
   return 0;
 }
 
-extern "C" size_t lasr_ctc_workspace_bytes(int64_t B, int64_t T, int64_t S_max) {
-  const CtcGeom g = ctc_geom(S_max);   // (S_max <= 511: pitch 64 * ns - the one-wave layout)
-  if (!g.pitch) return 0;
-  return align_up((size_t)2 * B * T * g.pitch * sizeof(float), 256) + align_up((size_t)B * (S_max > 0 ? S_max : 1) * 2 * sizeof(int32_t), 256);
-}
+extern "C" size_t lasr_ctc_workspace_bytes(int64_t B, int64_t T, int64_t S_max) { return CtcWorkspace(nullptr, B, T, S_max).bytes; }
 
 // gradient pass over a lattice already in `workspace` (layout of lasr_ctc_loss)
 namespace lasr {
 int launch_ctc_grad(const float* logp, const int64_t* targets, const int32_t* in_lens, const int32_t* tgt_lens, int64_t B, int64_t T,
                     int64_t C, int64_t S_max, int blank, const float* nll, float* grad, const float* gscale, void* workspace,
                     void* stream) {
-  const CtcGeom geo = ctc_geom(S_max);
-  const int ns = geo.ns;                 // 4 / 8 / 16 states per lane of one wave; 0: the multi-wave lattice
-  const size_t ab = (size_t)B * T * geo.pitch;
-  float* alpha = reinterpret_cast<float*>(workspace);
-  float* beta = alpha + ab;
-  int32_t* next_same = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + align_up(2 * ab * sizeof(float), 256));
+  const CtcWorkspace lat(workspace, B, T, S_max);
   hipStream_t st = as_stream(stream);
   const int64_t sm = S_max > 0 ? S_max : 1;
   const size_t shmem = 4 * (size_t)(C + sm) * sizeof(float);
-  LASR_CHECK_SHAPE(shmem <= 160 * 1024, "lasr_ctc_loss: C=%lld too large for the LDS row buffer", (long long)C);
-  dim3 grid((unsigned)cdiv(B * T, 4));
-#define LASR_CTC_G(K_)                                                                                                     \
-  do {                                                                                                                     \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K_), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL(K_, grid, dim3(256), shmem, st, logp, targets, in_lens, tgt_lens, B, T, C, sm, blank, alpha,      \
-                       beta, next_same, nll, gscale, grad);                                                                \
-  } while (0)
-  if (ns == 4) LASR_CTC_G(ctc_grad_kernel<4>); else if (ns == 8) LASR_CTC_G(ctc_grad_kernel<8>); else if (ns == 16) LASR_CTC_G(ctc_grad_kernel<16>);
-  else if (geo.nw == 2) LASR_CTC_G(ctc_grad_mw_kernel<2>); else if (geo.nw == 3) LASR_CTC_G(ctc_grad_mw_kernel<3>); else LASR_CTC_G(ctc_grad_mw_kernel<4>);
-#undef LASR_CTC_G
+  LASR_CHECK_SHAPE(shmem <= kLdsBytes, "lasr_ctc_loss: C=%lld too large for the LDS row buffer", (long long)C);
+  auto launch = [&](auto kernel) {
+    launch_lds(kernel, dim3((unsigned)cdiv(B * T, 4)), dim3(256), shmem, st, logp, targets, in_lens, tgt_lens, B, T, C, sm, blank, lat.alpha,
+               lat.beta, lat.next_same, nll, gscale, grad);
+  };
+  // 4 / 8 / 16 states per lane of one wave, or (ns = 0) the multi-wave lattice on 2..4 waves
+  if (lat.geo.ns) LASR_TRY(with_int<4, 8, 16>(lat.geo.ns, [&](auto ns) { launch(ctc_grad_kernel<decltype(ns)::value>); }));
+  else LASR_TRY(with_int<2, 3, 4>(lat.geo.nw, [&](auto nw) { launch(ctc_grad_mw_kernel<decltype(nw)::value>); }));
   LASR_LAUNCH_CHECK("ctc_grad_kernel");
   return 0;
 }
@@ -387,53 +375,35 @@ extern "C" int lasr_ctc_loss(const float* logp, const int64_t* targets, const in
                              void* workspace, size_t workspace_bytes, void* stream) {
   LASR_CHECK_ARG(logp && targets && in_lens && tgt_lens && nll && workspace, "lasr_ctc_loss: null pointer");
   LASR_CHECK_SHAPE(B > 0 && T > 0 && C > 1 && S_max >= 0 && blank >= 0 && blank < C, "lasr_ctc_loss: shape");
-  const CtcGeom geo = ctc_geom(S_max);
-  const int ns = geo.ns;                 // 4 / 8 / 16 states per lane of one wave; 0: the multi-wave lattice
-  LASR_CHECK_SHAPE(geo.pitch != 0, "lasr_ctc_loss: S_max=%lld exceeds the %d-label bound of the CTC lattice", (long long)S_max,
+  const CtcWorkspace lat(workspace, B, T, S_max);
+  LASR_CHECK_SHAPE(lat.geo.pitch != 0, "lasr_ctc_loss: S_max=%lld exceeds the %d-label bound of the CTC lattice", (long long)S_max,
                    LASR_CTC_MAX_LABELS);
-  if (workspace_bytes < lasr_ctc_workspace_bytes(B, T, S_max)) return fail(LASR_E_WORKSPACE, "lasr_ctc_loss: workspace");
-  const size_t ab = (size_t)B * T * geo.pitch;
-  float* alpha = reinterpret_cast<float*>(workspace);
-  float* beta = alpha + ab;
-  int32_t* next_same = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + align_up(2 * ab * sizeof(float), 256));
+  if (workspace_bytes < lat.bytes) return fail(LASR_E_WORKSPACE, "lasr_ctc_loss: workspace");
   hipStream_t st = as_stream(stream);
   const int64_t sm = S_max > 0 ? S_max : 1;
-  // emissions in LDS when one utterance's T x C f32 block fits beside the kernel's other needs (cfg2: 56 KB)
-  const size_t em_bytes = (size_t)(T + 2) * C * sizeof(float);   // one pad row on either side
-  const bool em_lds = em_bytes <= 144 * 1024 && C % 4 == 0 && reinterpret_cast<uintptr_t>(logp) % 16 == 0 &&
-                      !getenv("LASR_CTC_NO_LDS");
-#define LASR_CTC_AB(NS_)                                                                                                   \
-  do {                                                                                                                     \
-    if (em_lds) {                                                                                                          \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_alpha_beta_kernel<NS_, true>),                           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024); /* + 2 KB static */     \
-      hipLaunchKernelGGL((ctc_alpha_beta_kernel<NS_, true>), dim3((unsigned)B), dim3(128), em_bytes, st, logp, targets, in_lens, \
-                         tgt_lens, T, C, sm, blank, alpha, beta, next_same, nll);                                          \
-    } else {                                                                                                               \
-      hipLaunchKernelGGL((ctc_alpha_beta_kernel<NS_, false>), dim3((unsigned)B), dim3(128), 0, st, logp, targets, in_lens, \
-                         tgt_lens, T, C, sm, blank, alpha, beta, next_same, nll);                                          \
-    }                                                                                                                      \
-  } while (0)
-  if (ns) {
-    if (ns == 4) LASR_CTC_AB(4); else if (ns == 8) LASR_CTC_AB(8); else LASR_CTC_AB(16);
+  if (lat.geo.ns) {
+    // 4 / 8 / 16 states per lane of one wave; emissions in LDS when one utterance's T x C f32 block fits beside the label table and
+    // the margin this kernel keeps (cfg2: 56 KB)
+    constexpr size_t kMargin = 14 * 1024;
+    const bool em_lds = ctc_em_in_lds(T, C, kCtcMaxS * sizeof(int32_t) + kMargin, logp);
+    LASR_TRY(with_int<4, 8, 16>(lat.geo.ns, [&](auto ns) {
+      with_bool(em_lds, [&](auto em) {
+        launch_lds(ctc_alpha_beta_kernel<decltype(ns)::value, decltype(em)::value>, dim3((unsigned)B), dim3(128),
+                   em_lds ? ctc_em_bytes(T, C) : 0, st, logp, targets, in_lens, tgt_lens, T, C, sm, blank, lat.alpha, lat.beta, lat.next_same,
+                   nll);
+      });
+    }));
     LASR_LAUNCH_CHECK("ctc_alpha_beta_kernel");
   } else {
     // long labels: one workgroup of geo.nw waves per (utterance, direction); emission rows in LDS beside the 8 KB label table
     // (C = 28: up to T' = 1386), the register ring of ctc_lattice otherwise
-    const bool mw_lds = em_bytes <= 150 * 1024 && C % 4 == 0 && reinterpret_cast<uintptr_t>(logp) % 16 == 0 && !getenv("LASR_CTC_NO_LDS");
-    const dim3 grid((unsigned)(2 * B)), block((unsigned)(64 * geo.nw));
-    if (mw_lds) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_alpha_beta_mw_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                150 * 1024);
-      hipLaunchKernelGGL(ctc_alpha_beta_mw_kernel<true>, grid, block, em_bytes, st, logp, targets, in_lens, tgt_lens, T, C, sm, blank, alpha, beta,
-                         next_same, nll);
-    } else {
-      hipLaunchKernelGGL(ctc_alpha_beta_mw_kernel<false>, grid, block, 0, st, logp, targets, in_lens, tgt_lens, T, C, sm, blank, alpha, beta,
-                         next_same, nll);
-    }
+    const bool mw_lds = ctc_em_in_lds(T, C, kCtcMwMaxS * sizeof(int32_t) + kCtcLdsHeadroom, logp);
+    with_bool(mw_lds, [&](auto em) {
+      launch_lds(ctc_alpha_beta_mw_kernel<decltype(em)::value>, dim3((unsigned)(2 * B)), dim3((unsigned)(64 * lat.geo.nw)),
+                 mw_lds ? ctc_em_bytes(T, C) : 0, st, logp, targets, in_lens, tgt_lens, T, C, sm, blank, lat.alpha, lat.beta, lat.next_same, nll);
+    });
     LASR_LAUNCH_CHECK("ctc_alpha_beta_mw_kernel");
   }
-#undef LASR_CTC_AB
   if (grad) return launch_ctc_grad(logp, targets, in_lens, tgt_lens, B, T, C, S_max, blank, nll, grad, gscale, workspace, stream);
   return 0;
 }

@@ -522,6 +522,35 @@ static inline CtcGeom ctc_geom(int64_t S_max) {
   return {0, 0, 0};
 }
 
+// The lattice workspace  alpha [B][T][pitch] | beta [B][T][pitch] | next_same [B][S_max][2]  over `ws`: its size and its layout, for
+// lasr_ctc_workspace_bytes and for every launcher that fills or reads a lattice.
+struct CtcWorkspace {
+  CtcGeom geo;
+  float* alpha; float* beta; int32_t* next_same;
+  size_t bytes;                                     // 0 above the label bound
+  CtcWorkspace(void* ws, int64_t B, int64_t T, int64_t S_max) : geo(ctc_geom(S_max)) {
+    const size_t ab = (size_t)B * T * geo.pitch, lattice = align_up(2 * ab * sizeof(float), 256);
+    const uintptr_t base = reinterpret_cast<uintptr_t>(ws);
+    alpha = reinterpret_cast<float*>(base);
+    beta = reinterpret_cast<float*>(base + ab * sizeof(float));
+    next_same = reinterpret_cast<int32_t*>(base + lattice);
+    bytes = geo.pitch ? lattice + align_up((size_t)B * (S_max > 0 ? S_max : 1) * 2 * sizeof(int32_t), 256) : 0;
+  }
+};
+
+// Emission rows in LDS?  One utterance's (T + 2) x cols f32 block (a pad row on either side) has to fit `lds_total` beside
+// `other_lds`, the bytes of LDS the kernel uses anyway (label table, ring, headroom), and its rows are read as 16-byte vectors.
+// LASR_CTC_NO_LDS (A/B switch, read once per process) answers no for every lattice kernel.
+static constexpr size_t kCtcLdsHeadroom = 2 * 1024;   // kept free beside the emissions and the label table in every budget below
+inline bool ctc_no_lds() {
+  static const bool off = getenv("LASR_CTC_NO_LDS") != nullptr;
+  return off;
+}
+static inline size_t ctc_em_bytes(int64_t T, int64_t cols) { return (size_t)(T + 2) * cols * sizeof(float); }
+static inline bool ctc_em_in_lds(int64_t T, int64_t cols, size_t other_lds, const void* em, size_t lds_total = kLdsBytes) {
+  return !ctc_no_lds() && cols % 4 == 0 && reinterpret_cast<uintptr_t>(em) % 16 == 0 && ctc_em_bytes(T, cols) + other_lds <= lds_total;
+}
+
 // ctc.hip
 int launch_ctc_grad(const float* logp, const int64_t* targets, const int32_t* in_lens, const int32_t* tgt_lens, int64_t B, int64_t T,
                     int64_t C, int64_t S_max, int blank, const float* nll, float* grad, const float* gscale, void* workspace,

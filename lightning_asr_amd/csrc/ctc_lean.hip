@@ -458,16 +458,16 @@ int lasr::ctc_loss_lean_job(const void* logits, int64_t ldc, const float* row_st
   LASR_CHECK_SHAPE(B > 0 && T > 0 && C > 1 && S_max >= 0 && blank >= 0 && blank < C && ldc == ((C + 7) & ~(int64_t)7) && ldc <= 9216 &&
                        n_col_tiles >= 1 && n_col_tiles <= 64 && B * T * ldc < ((int64_t)1 << 31),
                    "lasr_ctc_loss_lean: shape (C=%lld ldc=%lld tiles=%d)", (long long)C, (long long)ldc, n_col_tiles);
-  const CtcGeom geo = ctc_geom(S_max);
+  const CtcWorkspace lat(workspace, B, T, S_max);   // the lattice comes first in the workspace
+  const CtcGeom& geo = lat.geo;
   const int ns = geo.ns;                 // 4 / 8 / 16 states per lane of one wave; 0: the multi-wave lattice
   LASR_CHECK_SHAPE(geo.pitch != 0, "lasr_ctc_loss_lean: S_max=%lld exceeds the %d-label bound of the CTC lattice", (long long)S_max,
                    LASR_CTC_MAX_LABELS);
   if (workspace_bytes < lasr_ctc_lean_workspace_bytes(B, T, C, S_max)) return fail(LASR_E_WORKSPACE, "lasr_ctc_loss_lean: workspace");
   const int64_t sm = S_max > 0 ? S_max : 1, N = B * T;
   const int CE = (int)((sm + 1 + 3) & ~(int64_t)3);
-  char* w = reinterpret_cast<char*>(workspace);
-  void* lattice_ws = w;
-  w += align_up(lasr_ctc_workspace_bytes(B, T, S_max), 256);
+  float* const alpha = lat.alpha; float* const beta = lat.beta; int32_t* const next_same = lat.next_same;
+  char* w = reinterpret_cast<char*>(workspace) + align_up(lat.bytes, 256);
   float* lse = reinterpret_cast<float*>(w);
   w += align_up((size_t)N * sizeof(float), 256);
   float* E = reinterpret_cast<float*>(w);
@@ -477,25 +477,8 @@ int lasr::ctc_loss_lean_job(const void* logits, int64_t ldc, const float* row_st
   hipLaunchKernelGGL(lse_gather_kernel, dim3((unsigned)cdiv(N, 4)), dim3(256), 0, st, reinterpret_cast<const bf16_t*>(logits), ldc, row_stat,
                      row_arg, n_col_tiles, targets, tgt_lens, N, T, sm, CE, blank, lse, argmax, E);
   LASR_LAUNCH_CHECK("lse_gather_kernel");
-  const size_t ab = (size_t)B * T * geo.pitch;
-  float* alpha = reinterpret_cast<float*>(lattice_ws);
-  float* beta = alpha + ab;
-  int32_t* next_same = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(lattice_ws) + align_up(2 * ab * sizeof(float), 256));
-  const size_t em_bytes = (size_t)(T + 2) * CE * sizeof(float);
-  // (160 KB of LDS per workgroup less the 2 KB of static label storage: T' = 801 with 46 emission columns needs 147.8 KB)
-  const bool em_lds = em_bytes <= 156 * 1024 && !getenv("LASR_CTC_NO_LDS");
-#define LASR_CTC_AB(NS_)                                                                                                       \
-  do {                                                                                                                         \
-    if (em_lds) {                                                                                                              \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_alpha_beta_compact_kernel<NS_, true>),                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);                                       \
-      hipLaunchKernelGGL((ctc_alpha_beta_compact_kernel<NS_, true>), dim3((unsigned)B), dim3(128), em_bytes, st, E, targets, in_lens, \
-                         tgt_lens, T, (int64_t)CE, sm, (int)sm, alpha, beta, next_same, nll);                                  \
-    } else {                                                                                                                   \
-      hipLaunchKernelGGL((ctc_alpha_beta_compact_kernel<NS_, false>), dim3((unsigned)B), dim3(128), 0, st, E, targets, in_lens, \
-                         tgt_lens, T, (int64_t)CE, sm, (int)sm, alpha, beta, next_same, nll);                                  \
-    }                                                                                                                          \
-  } while (0)
+  // (160 KB of LDS per workgroup less the 2 KB of static label storage and the headroom: T' = 801 with 46 emission columns needs 147.8 KB)
+  const bool em_lds = ctc_em_in_lds(T, CE, kCtcMaxS * sizeof(int32_t) + kCtcLdsHeadroom, E);
   bool job_done = false;
   if (!ns) {
     // long labels: 2B workgroups of geo.nw waves on the register ring of emissions (CE > 512 columns: the rows of any feasible
@@ -507,25 +490,25 @@ int lasr::ctc_loss_lean_job(const void* logits, int64_t ldc, const float* row_st
     LASR_TRY(launch_compact_lattice_mel(E, targets, in_lens, tgt_lens, B, T, CE, sm, (int)sm, alpha, beta, next_same, nll, ns, *job, stream));
     job_done = true;
   } else {
-    if (ns == 4) LASR_CTC_AB(4); else if (ns == 8) LASR_CTC_AB(8); else LASR_CTC_AB(16);
+    LASR_TRY(with_int<4, 8, 16>(ns, [&](auto n) {
+      with_bool(em_lds, [&](auto em) {
+        launch_lds(ctc_alpha_beta_compact_kernel<decltype(n)::value, decltype(em)::value>, dim3((unsigned)B), dim3(128),
+                   em_lds ? ctc_em_bytes(T, CE) : 0, st, E, targets, in_lens, tgt_lens, T, (int64_t)CE, sm, (int)sm, alpha, beta, next_same, nll);
+      });
+    }));
     LASR_LAUNCH_CHECK("ctc_alpha_beta_compact_kernel");
   }
-#undef LASR_CTC_AB
   const int cpad = (int)((C + 7) & ~(int64_t)7);
   const size_t shmem = 4 * (ns ? (size_t)cpad + 4 * (size_t)sm : lean_mw_pitch(C, sm)) * sizeof(float);
-  LASR_CHECK_SHAPE(shmem <= 160 * 1024 && ldc / 8 <= 64 * 18, "lasr_ctc_loss_lean: C=%lld too large for the LDS row buffers", (long long)C);
+  LASR_CHECK_SHAPE(shmem <= kLdsBytes && ldc / 8 <= 64 * 18, "lasr_ctc_loss_lean: C=%lld too large for the LDS row buffers", (long long)C);
   const int nwg = (int)cdiv(N, kLeanRowsPerWg);
-  const bool kv9 = ldc / 8 <= 64 * 9;
+  const int kv = ldc / 8 <= 64 * 9 ? 9 : 18;   // 16-byte logit vectors per lane of a row's wave
   if (!ns) {
-#define LASR_CTC_GMW(KV_)                                                                                                      \
-  do {                                                                                                                         \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_grad_lean_mw_kernel<KV_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((ctc_grad_lean_mw_kernel<KV_>), dim3((unsigned)nwg), dim3(256), shmem, st, reinterpret_cast<const bf16_t*>(logits), ldc, lse, \
-                       E, CE, targets, in_lens, tgt_lens, B, T, C, sm, blank, geo.nw, alpha, beta, next_same, nll, gscale,        \
-                       reinterpret_cast<bf16_t*>(grad), bias_partials, kLeanRowsPerWg);                                       \
-  } while (0)
-    if (kv9) LASR_CTC_GMW(9); else LASR_CTC_GMW(18);
-#undef LASR_CTC_GMW
+    LASR_TRY(with_int<9, 18>(kv, [&](auto v) {
+      launch_lds(ctc_grad_lean_mw_kernel<v.value>, dim3((unsigned)nwg), dim3(256), shmem, st, reinterpret_cast<const bf16_t*>(logits), ldc, lse, E,
+                 CE, targets, in_lens, tgt_lens, B, T, C, sm, blank, geo.nw, alpha, beta, next_same, nll, gscale,
+                 reinterpret_cast<bf16_t*>(grad), bias_partials, kLeanRowsPerWg);
+    }));
     LASR_LAUNCH_CHECK("ctc_grad_lean_mw_kernel");
     LASR_TRY(launch_reduce_partials(bias_partials, nwg, C, bias_grad, C, nullptr, st));
     if (job)
@@ -533,17 +516,13 @@ int lasr::ctc_loss_lean_job(const void* logits, int64_t ldc, const float* row_st
                          job->pct_out, job->ws, job->ws_bytes, stream);
     return 0;
   }
-#define LASR_CTC_G2(NS_, KV_)                                                                                                  \
-  do {                                                                                                                         \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_grad_lean_kernel<NS_, KV_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((ctc_grad_lean_kernel<NS_, KV_>), dim3((unsigned)nwg), dim3(256), shmem, st, reinterpret_cast<const bf16_t*>(logits), ldc, lse, \
-                       E, CE, targets, in_lens, tgt_lens, B, T, C, sm, blank, alpha, beta, next_same, nll, gscale,                \
-                       reinterpret_cast<bf16_t*>(grad), bias_partials, kLeanRowsPerWg);                                       \
-  } while (0)
-#define LASR_CTC_G(NS_) do { if (kv9) LASR_CTC_G2(NS_, 9); else LASR_CTC_G2(NS_, 18); } while (0)
-  if (ns == 4) LASR_CTC_G(4); else if (ns == 8) LASR_CTC_G(8); else LASR_CTC_G(16);
-#undef LASR_CTC_G
-#undef LASR_CTC_G2
+  LASR_TRY(with_int<4, 8, 16>(ns, [&](auto n) {
+    with_int<9, 18>(kv, [&](auto v) {
+      launch_lds(ctc_grad_lean_kernel<decltype(n)::value, decltype(v)::value>, dim3((unsigned)nwg), dim3(256), shmem, st,
+                 reinterpret_cast<const bf16_t*>(logits), ldc, lse, E, CE, targets, in_lens, tgt_lens, B, T, C, sm, blank, alpha, beta, next_same,
+                 nll, gscale, reinterpret_cast<bf16_t*>(grad), bias_partials, kLeanRowsPerWg);
+    });
+  }));
   LASR_LAUNCH_CHECK("ctc_grad_lean_kernel");
   LASR_TRY(launch_reduce_partials(bias_partials, nwg, C, bias_grad, C, nullptr, st));   // f64, fixed order
   if (job && !job_done)

@@ -491,9 +491,21 @@ extern "C" int lasr_debug_set_mel_stamps(void* buf) {
 #endif
 extern "C" int64_t lasr_mel_num_frames(int64_t n_samples) { return 1 + (n_samples + 2 * kPad) / kHop; }
 
-extern "C" size_t lasr_mel_workspace_bytes(int64_t B, int64_t T) {
-  const size_t nblk = (size_t)cdiv(T, kFramesPerBlock);
-  return align_up((size_t)B * T * kMel * sizeof(float), 256) + align_up((size_t)B * nblk * 2 * sizeof(double), 256);
+// The front-end's workspace  db [B][T][kMel] f32 | partials [B][nblk][2] f64  over `ws`: its size and its layout
+struct MelWorkspace {
+  float* db; double* partials; size_t bytes;
+  MelWorkspace(void* ws, int64_t B, int64_t T) {
+    const size_t db_bytes = align_up((size_t)B * T * kMel * sizeof(float), 256);
+    db = reinterpret_cast<float*>(ws);
+    partials = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(ws) + db_bytes);
+    bytes = db_bytes + align_up((size_t)B * cdiv(T, kFramesPerBlock) * 2 * sizeof(double), 256);
+  }
+};
+extern "C" size_t lasr_mel_workspace_bytes(int64_t B, int64_t T) { return MelWorkspace(nullptr, B, T).bytes; }
+// A/B switch, read once per process: never put a feature transform into a lattice launch's grid
+static bool mel_ctc_off() {
+  static const bool off = getenv("LASR_NO_MEL_CTC") != nullptr;
+  return off;
 }
 
 namespace lasr {
@@ -514,12 +526,11 @@ int wave_src_from_c(const lasr_wave_src* s, WaveSrc* out, const char* who) {
 static void launch_norm(int dtype, dim3 grid, hipStream_t st, const float* db, const double* partials, const int32_t* frames_out, int64_t T,
                         int nblk, int normalize, float* out_bft, void* out_btf, const WaveSrc& src) {
   unsigned long long* bump = const_cast<unsigned long long*>(src.dstep);
-  if (dtype == LASR_F32)
-    hipLaunchKernelGGL(mel_norm_kernel<float>, grid, dim3(256), 0, st, db, partials, frames_out, T, nblk, normalize, out_bft,
-                       reinterpret_cast<float*>(out_btf), bump);
-  else
-    hipLaunchKernelGGL(mel_norm_kernel<bf16_t>, grid, dim3(256), 0, st, db, partials, frames_out, T, nblk, normalize, out_bft,
-                       reinterpret_cast<bf16_t*>(out_btf), bump);
+  with_dtype(dtype, [&](auto t) {
+    using E = typename decltype(t)::type;
+    hipLaunchKernelGGL(mel_norm_kernel<E>, grid, dim3(256), 0, st, db, partials, frames_out, T, nblk, normalize, out_bft,
+                       reinterpret_cast<E*>(out_btf), bump);
+  });
 }
 
 int mel_fwd_src(const WaveSrc& src, const int32_t* sample_lens, const int32_t* aug, int64_t B, int64_t L, int normalize,
@@ -530,15 +541,14 @@ int mel_fwd_src(const WaveSrc& src, const int32_t* sample_lens, const int32_t* a
   LASR_CHECK_ARG(dtype == LASR_F32 || dtype == LASR_BF16, "lasr_mel_fwd: bad dtype %d", dtype);
   LASR_CHECK_SHAPE(B > 0 && B < 65536 && L >= 2 && L < (1ll << 30), "lasr_mel_fwd: B=%lld L=%lld", (long long)B, (long long)L);
   const int64_t T = lasr_mel_num_frames(L);
-  if (workspace_bytes < lasr_mel_workspace_bytes(B, T)) return fail(LASR_E_WORKSPACE, "lasr_mel_fwd: workspace too small");
+  const MelWorkspace mw(workspace, B, T);
+  if (workspace_bytes < mw.bytes) return fail(LASR_E_WORKSPACE, "lasr_mel_fwd: workspace too small");
   LASR_TRY(init_tables());
-  float* db = reinterpret_cast<float*>(workspace);
-  double* partials = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + align_up((size_t)B * T * kMel * sizeof(float), 256));
   const int nblk = (int)cdiv(T, kFramesPerBlock);
   dim3 grid(nblk, (unsigned)B);
-  hipLaunchKernelGGL(mel_db_kernel, grid, dim3(256), 0, as_stream(stream), src, sample_lens, aug, L, T, db, partials, frames_out, pct_out);
+  hipLaunchKernelGGL(mel_db_kernel, grid, dim3(256), 0, as_stream(stream), src, sample_lens, aug, L, T, mw.db, mw.partials, frames_out, pct_out);
   LASR_LAUNCH_CHECK("mel_db_kernel");
-  launch_norm(dtype, grid, as_stream(stream), db, partials, frames_out, T, nblk, normalize, out_bft, out_btf, src);
+  launch_norm(dtype, grid, as_stream(stream), mw.db, mw.partials, frames_out, T, nblk, normalize, out_bft, out_btf, src);
   LASR_LAUNCH_CHECK("mel_norm_kernel");
   return 0;
 }
@@ -551,11 +561,11 @@ int ctc_loss_mel_src(const float* logp, const int64_t* targets, const int32_t* i
   LASR_CHECK_ARG(logp && targets && in_lens && tgt_lens && nll && ctc_workspace && src.wave && frames_out && pct_out && mel_workspace,
                  "lasr_ctc_loss_mel: null pointer");
   const int64_t sm = S_max > 0 ? S_max : 1;
-  const size_t em_bytes = (size_t)(T + 2) * C * sizeof(float);
-  const size_t lds = std::max(sizeof(MelSmem), kCtcMaxS * sizeof(int32_t) + em_bytes);
-  static const bool no_fused = getenv("LASR_NO_MEL_CTC") != nullptr;     // A/B switch
-  const bool fused = !no_fused && B > 0 && T > 0 && C > 1 && 2 * S_max + 1 <= 256 && lds <= 80 * 1024 && C % 4 == 0 &&
-                     reinterpret_cast<uintptr_t>(logp) % 16 == 0 && !getenv("LASR_CTC_NO_LDS") && (out_bft || out_btf) &&
+  // the lattice's LDS (label table + emissions) beside a feature workgroup's: both kinds at two workgroups per CU
+  static_assert(sizeof(MelSmem) <= kLdsBytes / 2, "a feature workgroup takes at most half a CU's LDS");
+  const size_t lds = std::max(sizeof(MelSmem), kCtcMaxS * sizeof(int32_t) + ctc_em_bytes(T, C));
+  const bool fused = !mel_ctc_off() && B > 0 && T > 0 && C > 1 && 2 * S_max + 1 <= 256 &&
+                     ctc_em_in_lds(T, C, kCtcMaxS * sizeof(int32_t), logp, kLdsBytes / 2) && (out_bft || out_btf) &&
                      (dtype == LASR_F32 || dtype == LASR_BF16) && Bm > 0 && Bm < 65536 && L >= 2 && L < (1ll << 30) &&
                      ctc_workspace_bytes >= lasr_ctc_workspace_bytes(B, T, S_max) &&
                      mel_workspace_bytes >= lasr_mel_workspace_bytes(Bm, lasr_mel_num_frames(L));
@@ -568,20 +578,17 @@ int ctc_loss_mel_src(const float* logp, const int64_t* targets, const int32_t* i
   LASR_TRY(init_tables());
   const int64_t Tm = lasr_mel_num_frames(L);
   MelCtcArgs a;
-  const size_t ab = (size_t)B * T * 64 * 4;
+  const CtcWorkspace lat(ctc_workspace, B, T, S_max);
+  const MelWorkspace mw(mel_workspace, Bm, Tm);
   a.logp = logp; a.targets = targets; a.in_lens = in_lens; a.tgt_lens = tgt_lens; a.T = T; a.C = C; a.S_max = sm; a.blank = blank;
-  a.alpha = reinterpret_cast<float*>(ctc_workspace);
-  a.beta = a.alpha + ab;
-  a.next_same = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ctc_workspace) + align_up(2 * ab * sizeof(float), 256));
+  a.alpha = lat.alpha; a.beta = lat.beta; a.next_same = lat.next_same;
   a.nll = nll; a.n_ctc = (int)B;
   a.src = src; a.sample_lens = sample_lens; a.aug = aug; a.L = L; a.Tm = Tm;
-  a.db_out = reinterpret_cast<float*>(mel_workspace);
-  a.partials = reinterpret_cast<double*>(reinterpret_cast<char*>(mel_workspace) + align_up((size_t)Bm * Tm * kMel * sizeof(float), 256));
+  a.db_out = mw.db; a.partials = mw.partials;
   a.frames_out = frames_out; a.pct_out = pct_out;
   const int nblk = (int)cdiv(Tm, kFramesPerBlock);
   a.nbx = nblk;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mel_ctc_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-  hipLaunchKernelGGL(mel_ctc_kernel<4>, dim3((unsigned)(B + (int64_t)nblk * Bm)), dim3(256), lds, as_stream(stream), a);
+  launch_lds(mel_ctc_kernel<4>, dim3((unsigned)(B + (int64_t)nblk * Bm)), dim3(256), lds, as_stream(stream), a);
   LASR_LAUNCH_CHECK("mel_ctc_kernel");
   if (grad) LASR_TRY(launch_ctc_grad(logp, targets, in_lens, tgt_lens, B, T, C, S_max, blank, nll, grad, gscale, ctc_workspace, stream));
   dim3 grid(nblk, (unsigned)Bm);
@@ -591,8 +598,7 @@ int ctc_loss_mel_src(const float* logp, const int64_t* targets, const int32_t* i
 }
 
 bool compact_lattice_mel_fits(int64_t T, int64_t CE) {
-  static const bool off = getenv("LASR_NO_MEL_CTC") != nullptr || getenv("LASR_CTC_NO_LDS") != nullptr;
-  return !off && kCtcMaxS * sizeof(int32_t) + (size_t)(T + 2) * CE * sizeof(float) <= 158 * 1024;
+  return !mel_ctc_off() && ctc_em_in_lds(T, CE, kCtcMaxS * sizeof(int32_t) + kCtcLdsHeadroom, nullptr);
 }
 
 int launch_compact_lattice_mel(const float* E, const int64_t* targets, const int32_t* in_lens, const int32_t* tgt_lens, int64_t B, int64_t T,
@@ -603,26 +609,20 @@ int launch_compact_lattice_mel(const float* E, const int64_t* targets, const int
   LASR_CHECK_SHAPE(job.B > 0 && job.B < 65536 && job.L >= 2 && job.L < (1ll << 30), "lasr_ctc_loss_lean (+features): B=%lld L=%lld", (long long)job.B,
                    (long long)job.L);
   const int64_t Tm = lasr_mel_num_frames(job.L);
-  if (job.ws_bytes < lasr_mel_workspace_bytes(job.B, Tm)) return fail(LASR_E_WORKSPACE, "lasr_ctc_loss_lean (+features): workspace");
+  const MelWorkspace mw(job.ws, job.B, Tm);
+  if (job.ws_bytes < mw.bytes) return fail(LASR_E_WORKSPACE, "lasr_ctc_loss_lean (+features): workspace");
   LASR_TRY(init_tables());
   MelCtcArgs a;
   a.logp = E; a.targets = targets; a.in_lens = in_lens; a.tgt_lens = tgt_lens; a.T = T; a.C = CE; a.S_max = S_max; a.blank = blank_col;
   a.alpha = alpha; a.beta = beta; a.next_same = next_same; a.nll = nll; a.n_ctc = (int)B;
   a.src = job.src; a.sample_lens = job.sample_lens; a.aug = job.aug; a.L = job.L; a.Tm = Tm;
-  a.db_out = reinterpret_cast<float*>(job.ws);
-  a.partials = reinterpret_cast<double*>(reinterpret_cast<char*>(job.ws) + align_up((size_t)job.B * Tm * kMel * sizeof(float), 256));
+  a.db_out = mw.db; a.partials = mw.partials;
   a.frames_out = job.frames_out; a.pct_out = job.pct_out;
   const int nblk = (int)cdiv(Tm, kFramesPerBlock);
   a.nbx = nblk;
-  const size_t lds = std::max(sizeof(MelSmem), kCtcMaxS * sizeof(int32_t) + (size_t)(T + 2) * CE * sizeof(float));
+  const size_t lds = std::max(sizeof(MelSmem), kCtcMaxS * sizeof(int32_t) + ctc_em_bytes(T, CE));
   const dim3 grid((unsigned)(B + (int64_t)nblk * job.B));
-#define LASR_MCK(NS_)                                                                                                              \
-  do {                                                                                                                             \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mel_ctc_kernel<NS_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((mel_ctc_kernel<NS_, true>), grid, dim3(256), lds, as_stream(stream), a);                                     \
-  } while (0)
-  if (ns == 4) LASR_MCK(4); else if (ns == 8) LASR_MCK(8); else LASR_MCK(16);
-#undef LASR_MCK
+  LASR_TRY(with_int<4, 8, 16>(ns, [&](auto n) { launch_lds(mel_ctc_kernel<n.value, true>, grid, dim3(256), lds, as_stream(stream), a); }));
   LASR_LAUNCH_CHECK("mel_ctc_kernel (compact)");
   launch_norm(job.dtype, dim3(nblk, (unsigned)job.B), as_stream(stream), a.db_out, a.partials, job.frames_out, Tm, nblk, job.normalize, nullptr,
               job.out_btf, job.src);

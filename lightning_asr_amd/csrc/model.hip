@@ -12,51 +12,6 @@
 #include <vector>
 #include <math.h>
 
-extern "C" size_t lasr_bn_bwd_workspace_bytes(int64_t B, int64_t T, int64_t C);
-extern "C" size_t lasr_gemm_workspace_bytes(int64_t M, int64_t N, int split_k, int want_stats);
-extern "C" size_t lasr_dwconv_wgrad_workspace_bytes(int64_t B, int64_t Tout, int64_t C, int k);
-extern "C" int lasr_log_softmax_bwd(const float*, const float*, float*, int64_t, int64_t, void*);
-extern "C" int lasr_cast_f32_to_bf16(const float*, void*, int64_t, void*);
-extern "C" int lasr_colsum_f32(const float* x, float* out, int64_t rows, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
-extern "C" size_t lasr_colsum_workspace_bytes(int64_t rows, int64_t C);
-extern "C" int lasr_scale_sum_f32(const float* x, int64_t n, float scale, float* out, void* stream);
-extern "C" int lasr_seqsum(const void* x, int dtype, int64_t B, int64_t T, int64_t C, float* sums, void* stream);
-extern "C" int lasr_se_fwd(const float* sums, const float* coef, const float* W1, const float* W2, int64_t B, int64_t T, int64_t C,
-                           float* pooled, float* hidden, float* scale, void* stream);
-extern "C" size_t lasr_se_bwd_workspace_bytes(int64_t B, int64_t C);
-extern "C" int lasr_se_bwd(const void* dout, const void* y, const float* coef, const void* y2, const float* coef2, const float* scale,
-                           const float* hidden, const float* pooled, const float* W1, const float* W2, int dtype, int64_t B, int64_t T,
-                           int64_t C, int act, float* seg, float* dW1, float* dW2, void* workspace, size_t workspace_bytes, void* stream);
-extern "C" size_t lasr_bilstm_saved_bytes(int64_t B, int64_t T);
-extern "C" int lasr_bilstm_fwd(const float* gx_f, const float* gx_r, const float* whh_f, const float* whh_r, const float* bih_f,
-                               const float* bhh_f, const float* bih_r, const float* bhh_r, const int32_t* lens, int64_t B, int64_t T,
-                               void* out, int dtype, int64_t ld_out, int64_t col0, float* saved, void* stream);
-extern "C" size_t lasr_bilstm_bwd_workspace_bytes(int64_t B);
-extern "C" int lasr_bilstm_bwd(const void* dout, int dtype, int64_t ld_dout, int64_t col0, const float* whh_f, const float* whh_r,
-                               const int32_t* lens, int64_t B, int64_t T, const float* saved, float* dg_f, float* dg_r, float* dwhh_f,
-                               float* dwhh_r, void* workspace, size_t workspace_bytes, void* stream);
-extern "C" int lasr_se_bwd_drop(const void* dout, const void* y, const float* coef, const void* y2, const float* coef2, const float* scale,
-                                const float* hidden, const float* pooled, const float* W1, const float* W2, int dtype, int64_t B, int64_t T,
-                                int64_t C, int act, const lasr_dropout* dropout, float* seg, float* dW1, float* dW2, void* workspace,
-                                size_t workspace_bytes, void* stream);
-extern "C" size_t lasr_bn_se_bwd_workspace_bytes(int64_t B, int64_t T, int64_t C);
-extern "C" int lasr_bn_se_bwd(const void* dout, const void* y, const float* coef, const float* saved, const float* gamma, const float* beta,
-                              const void* y2, const float* coef2, const float* saved2, const float* gamma2, const float* se_scale,
-                              const float* se_hidden, const float* se_pooled, const float* ysum, const float* W1, const float* W2,
-                              const int32_t* row_lens, void* dy, void* dy2, float* dgamma, float* dbeta, float* dgamma2, float* dbeta2,
-                              float* dW1, float* dW2, float* seg_out, int dtype, int64_t B, int64_t T, int64_t C, int act,
-                              const lasr_dropout* dropout, void* workspace, size_t workspace_bytes, void* stream);
-extern "C" int lasr_gemm_rowstat(const void* A, const void* B, const float* bias, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
-                                 float* row_stat, int32_t* row_arg, int* n_col_tiles, void* stream);
-extern "C" size_t lasr_gemm_rowstat_bytes(int64_t M, int64_t N);
-extern "C" size_t lasr_ctc_lean_workspace_bytes(int64_t B, int64_t T, int64_t C, int64_t S_max);
-extern "C" int lasr_ctc_loss_lean(const void* logits, int64_t ldc, const float* row_stat, const int32_t* row_arg, int n_col_tiles,
-                                  const int64_t* targets, const int32_t* in_lens, const int32_t* tgt_lens, int64_t B, int64_t T, int64_t C,
-                                  int64_t S_max, int blank, float* nll, int32_t* argmax, void* grad, float* bias_grad, const float* gscale,
-                                  void* workspace, size_t workspace_bytes, void* stream);
-extern "C" int lasr_copy_cols(const void* src, int src_dtype, int64_t ld_src, int64_t scol0, void* dst, int dst_dtype, int64_t ld_dst,
-                              int64_t dcol0, int64_t rows, int64_t ncols, int accumulate, void* stream);
-
 namespace lasr {
 
 static constexpr float kBnEps = 1e-3f;   // nn.BatchNorm1d(out_ch, eps=1e-3)  models/QuartNet.py:24

@@ -883,9 +883,13 @@ static int bn_bwd_stats_impl(const void* dout, const void* y, const float* coef,
                              float* sums, float* sums2, int dtype, int64_t B, int64_t T_, int64_t C, int act,
                              const lasr_dropout* dropout, void* workspace, size_t workspace_bytes, void* stream, int per_utt);
 
-#define DISPATCH_DTYPE(dtype, ...)                      \
-  if ((dtype) == LASR_F32) { using T = float; __VA_ARGS__; } \
-  else { using T = bf16_t; __VA_ARGS__; }
+// dtype x HAS2 x SE x DROP - the template head of the three row-slab kernels - as four tags inside f
+template <typename F>
+static void with_bn_variant(int dtype, bool has2, bool se, bool drop, F&& f) {
+  with_dtype(dtype, [&](auto t) {
+    with_bool(has2, [&](auto h2) { with_bool(se, [&](auto s) { with_bool(drop, [&](auto d) { f(t, h2, s, d); }); }); });
+  });
+}
 
 // public descriptor -> kernel arguments (p = 0 or a null descriptor: dropout off)
 static DropArgs make_drop(const lasr_dropout* d) {
@@ -905,7 +909,9 @@ extern "C" int lasr_bct_to_btc(const float* in, void* out, int dtype, int64_t B,
   LASR_CHECK_ARG(in && out && (dtype == LASR_F32 || dtype == LASR_BF16), "lasr_bct_to_btc: bad argument");
   LASR_CHECK_SHAPE(B > 0 && C > 0 && T_ > 0 && B < 65536, "lasr_bct_to_btc: shape");
   dim3 grid((unsigned)cdiv(T_, 32), (unsigned)cdiv(C, 32), (unsigned)B);
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((transpose_kernel<T, true>), grid, dim3(256), 0, as_stream(stream), in, out, C, T_));
+  with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL((transpose_kernel<typename decltype(t)::type, true>), grid, dim3(256), 0, as_stream(stream), in, out, C, T_);
+  });
   LASR_LAUNCH_CHECK("transpose_kernel");
   return 0;
 }
@@ -913,7 +919,9 @@ extern "C" int lasr_btc_to_bct(const void* in, int dtype, float* out, int64_t B,
   LASR_CHECK_ARG(in && out && (dtype == LASR_F32 || dtype == LASR_BF16), "lasr_btc_to_bct: bad argument");
   LASR_CHECK_SHAPE(B > 0 && C > 0 && T_ > 0 && B < 65536, "lasr_btc_to_bct: shape");
   dim3 grid((unsigned)cdiv(T_, 32), (unsigned)cdiv(C, 32), (unsigned)B);
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((transpose_kernel<T, false>), grid, dim3(256), 0, as_stream(stream), in, out, C, T_));
+  with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL((transpose_kernel<typename decltype(t)::type, false>), grid, dim3(256), 0, as_stream(stream), in, out, C, T_);
+  });
   LASR_LAUNCH_CHECK("transpose_kernel");
   return 0;
 }
@@ -1009,27 +1017,11 @@ extern "C" int lasr_bn_act_fwd_drop(const void* y, const float* coef, const void
   const DropArgs da = make_drop(dropout);
   const int64_t rows = B * T_;
   const size_t shmem = (size_t)4 * C * sizeof(float);
-  if (y2) {
-    if (se_scale) { DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_act_fwd_kernel<T, true, true, true>), dim3((unsigned)cdiv(rows, kFwdSlabRows)), dim3(256), shmem,
-                                             as_stream(stream), (const T*)y, coef, (const T*)y2, coef2, se_scale, (T*)out, (int)rows,
-                                             (int)T_, (int)C, act, da); } else { hipLaunchKernelGGL((bn_act_fwd_kernel<T, true, true, false>), dim3((unsigned)cdiv(rows, kFwdSlabRows)), dim3(256), shmem,
-                                             as_stream(stream), (const T*)y, coef, (const T*)y2, coef2, se_scale, (T*)out, (int)rows,
-                                             (int)T_, (int)C, act, da); } }); } else { DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_act_fwd_kernel<T, true, false, true>), dim3((unsigned)cdiv(rows, kFwdSlabRows)), dim3(256), shmem,
-                                             as_stream(stream), (const T*)y, coef, (const T*)y2, coef2, se_scale, (T*)out, (int)rows,
-                                             (int)T_, (int)C, act, da); } else { hipLaunchKernelGGL((bn_act_fwd_kernel<T, true, false, false>), dim3((unsigned)cdiv(rows, kFwdSlabRows)), dim3(256), shmem,
-                                             as_stream(stream), (const T*)y, coef, (const T*)y2, coef2, se_scale, (T*)out, (int)rows,
-                                             (int)T_, (int)C, act, da); } }); }
-  } else {
-    if (se_scale) { DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_act_fwd_kernel<T, false, true, true>), dim3((unsigned)cdiv(rows, kFwdSlabRows)), dim3(256), shmem,
-                                             as_stream(stream), (const T*)y, coef, (const T*)y2, coef2, se_scale, (T*)out, (int)rows,
-                                             (int)T_, (int)C, act, da); } else { hipLaunchKernelGGL((bn_act_fwd_kernel<T, false, true, false>), dim3((unsigned)cdiv(rows, kFwdSlabRows)), dim3(256), shmem,
-                                             as_stream(stream), (const T*)y, coef, (const T*)y2, coef2, se_scale, (T*)out, (int)rows,
-                                             (int)T_, (int)C, act, da); } }); } else { DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_act_fwd_kernel<T, false, false, true>), dim3((unsigned)cdiv(rows, kFwdSlabRows)), dim3(256), shmem,
-                                             as_stream(stream), (const T*)y, coef, (const T*)y2, coef2, se_scale, (T*)out, (int)rows,
-                                             (int)T_, (int)C, act, da); } else { hipLaunchKernelGGL((bn_act_fwd_kernel<T, false, false, false>), dim3((unsigned)cdiv(rows, kFwdSlabRows)), dim3(256), shmem,
-                                             as_stream(stream), (const T*)y, coef, (const T*)y2, coef2, se_scale, (T*)out, (int)rows,
-                                             (int)T_, (int)C, act, da); } }); }
-  }
+  with_bn_variant(dtype, y2 != nullptr, se_scale != nullptr, da.step != nullptr, [&](auto t, auto h2, auto se, auto drop) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((bn_act_fwd_kernel<T, h2.value, se.value, drop.value>), dim3((unsigned)cdiv(rows, kFwdSlabRows)), dim3(256), shmem,
+                       as_stream(stream), (const T*)y, coef, (const T*)y2, coef2, se_scale, (T*)out, (int)rows, (int)T_, (int)C, act, da);
+  });
   LASR_LAUNCH_CHECK("bn_act_fwd_kernel");
   return 0;
 }
@@ -1075,13 +1067,13 @@ static int bn_bwd_stats_impl(const void* dout, const void* y, const float* coef,
   if (const int rpc = bn_sliced_rpc(dtype, rows, C, se_scale != nullptr, da.step != nullptr, per_utt, sums != nullptr)) {
     const dim3 grid((unsigned)(C / kSlCh), (unsigned)cdiv(rows, rpc));
     float* partials = reinterpret_cast<float*>(workspace);
-#define LASR_STATS_SL(H2_, NT_)                                                                                                         \
-  hipLaunchKernelGGL((bn_bwd_stats_sliced_kernel<H2_, false, NT_>), grid, dim3(kSlThreads), 0, as_stream(stream), (const bf16_t*)dout, \
-                     (const bf16_t*)y, coef, saved, (const bf16_t*)y2, coef2, saved2, nullptr, partials, (int)rows, (int)C, act, rpc)
-    const bool ntl = (nt_loads_mask() & 1) != 0;
-    if (y2) { if (ntl) LASR_STATS_SL(true, true); else LASR_STATS_SL(true, false); }
-    else { if (ntl) LASR_STATS_SL(false, true); else LASR_STATS_SL(false, false); }
-#undef LASR_STATS_SL
+    with_bool(y2 != nullptr, [&](auto h2) {
+      with_bool((nt_loads_mask() & 1) != 0, [&](auto nt) {
+        hipLaunchKernelGGL((bn_bwd_stats_sliced_kernel<decltype(h2)::value, false, decltype(nt)::value>), grid, dim3(kSlThreads), 0,
+                           as_stream(stream), (const bf16_t*)dout, (const bf16_t*)y, coef, saved, (const bf16_t*)y2, coef2, saved2, nullptr,
+                           partials, (int)rows, (int)C, act, rpc);
+      });
+    });
     LASR_LAUNCH_CHECK("bn_bwd_stats_sliced_kernel");
     return 0;
   }
@@ -1091,27 +1083,12 @@ static int bn_bwd_stats_impl(const void* dout, const void* y, const float* coef,
   const size_t shmem = (size_t)row_lanes * 4 * C * sizeof(float);
   LASR_CHECK_SHAPE(shmem <= 64 * 1024, "lasr_bn_act_bwd_stats: C too large for LDS staging");
   float* partials = reinterpret_cast<float*>(workspace);
-  if (y2) {
-    if (se_scale) { DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_bwd_stats_kernel<T, true, true, true>), dim3(nblk), dim3(256), shmem, as_stream(stream),
-                                             (const T*)dout, (const T*)y, coef, saved, (const T*)y2, coef2, saved2, se_scale, se_grad,
-                                             partials, (int)rows, (int)T_, (int)C, act, da, per_utt); } else { hipLaunchKernelGGL((bn_bwd_stats_kernel<T, true, true, false>), dim3(nblk), dim3(256), shmem, as_stream(stream),
-                                             (const T*)dout, (const T*)y, coef, saved, (const T*)y2, coef2, saved2, se_scale, se_grad,
-                                             partials, (int)rows, (int)T_, (int)C, act, da, per_utt); } }); } else { DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_bwd_stats_kernel<T, true, false, true>), dim3(nblk), dim3(256), shmem, as_stream(stream),
-                                             (const T*)dout, (const T*)y, coef, saved, (const T*)y2, coef2, saved2, se_scale, se_grad,
-                                             partials, (int)rows, (int)T_, (int)C, act, da, per_utt); } else { hipLaunchKernelGGL((bn_bwd_stats_kernel<T, true, false, false>), dim3(nblk), dim3(256), shmem, as_stream(stream),
-                                             (const T*)dout, (const T*)y, coef, saved, (const T*)y2, coef2, saved2, se_scale, se_grad,
-                                             partials, (int)rows, (int)T_, (int)C, act, da, per_utt); } }); }
-  } else {
-    if (se_scale) { DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_bwd_stats_kernel<T, false, true, true>), dim3(nblk), dim3(256), shmem, as_stream(stream),
-                                             (const T*)dout, (const T*)y, coef, saved, (const T*)y2, coef2, saved2, se_scale, se_grad,
-                                             partials, (int)rows, (int)T_, (int)C, act, da, per_utt); } else { hipLaunchKernelGGL((bn_bwd_stats_kernel<T, false, true, false>), dim3(nblk), dim3(256), shmem, as_stream(stream),
-                                             (const T*)dout, (const T*)y, coef, saved, (const T*)y2, coef2, saved2, se_scale, se_grad,
-                                             partials, (int)rows, (int)T_, (int)C, act, da, per_utt); } }); } else { DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_bwd_stats_kernel<T, false, false, true>), dim3(nblk), dim3(256), shmem, as_stream(stream),
-                                             (const T*)dout, (const T*)y, coef, saved, (const T*)y2, coef2, saved2, se_scale, se_grad,
-                                             partials, (int)rows, (int)T_, (int)C, act, da, per_utt); } else { hipLaunchKernelGGL((bn_bwd_stats_kernel<T, false, false, false>), dim3(nblk), dim3(256), shmem, as_stream(stream),
-                                             (const T*)dout, (const T*)y, coef, saved, (const T*)y2, coef2, saved2, se_scale, se_grad,
-                                             partials, (int)rows, (int)T_, (int)C, act, da, per_utt); } }); }
-  }
+  with_bn_variant(dtype, y2 != nullptr, se_scale != nullptr, da.step != nullptr, [&](auto t, auto h2, auto se, auto drop) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((bn_bwd_stats_kernel<T, h2.value, se.value, drop.value>), dim3(nblk), dim3(256), shmem, as_stream(stream),
+                       (const T*)dout, (const T*)y, coef, saved, (const T*)y2, coef2, saved2, se_scale, se_grad, partials, (int)rows,
+                       (int)T_, (int)C, act, da, per_utt);
+  });
   LASR_LAUNCH_CHECK("bn_bwd_stats_kernel");
   if (!sums) return 0;   // partials stay in the workspace for lasr_bn_act_bwd_apply(sums = NULL)
   return launch_reduce_partials(partials, nblk, 4 * C, sums, 2 * C, sums2, as_stream(stream));
@@ -1152,23 +1129,22 @@ extern "C" int lasr_bn_act_bwd_apply_drop(const void* dout, const void* y, const
     // the cfg2 step, one call: split 1 / 2 / 3 / 4 = 2.228 / 2.191 / 2.220 / 2.235 ms.  (The statistics pass does not gain from the
     // same treatment: 2.219 with both split against 2.198.)  The arithmetic per element is unchanged.
     static const int asplit = getenv("LASR_BN_APPLY_SPLIT") ? atoi(getenv("LASR_BN_APPLY_SPLIT")) : 2;
-    const bool ntl = (nt_loads_mask() & 2) != 0;
-#define LASR_APPLY_SL(H2_, RB_, W_, RPC_, G_) do { if (ntl) LASR_APPLY_SL2(H2_, RB_, W_, RPC_, G_, true); else LASR_APPLY_SL2(H2_, RB_, W_, RPC_, G_, false); } while (0)
-#define LASR_APPLY_SL2(H2_, RB_, W_, RPC_, G_, NT_)                                                                                    \
-  hipLaunchKernelGGL((bn_bwd_apply_sliced_kernel<H2_, false, RB_, W_, NT_>), G_, dim3(kSlThreads), 0, st, (const bf16_t*)dout, (const bf16_t*)y, \
-                     (const bf16_t*)y2, partials, nchunk, nullptr, nullptr, nullptr, coef, saved, gamma, coef2, saved2, gamma2,          \
-                     1.0f / (float)rows, row_lens, (bf16_t*)dy, (bf16_t*)dy2, dgamma, dbeta, dgamma2, dbeta2, (int)rows, (int)T_, (int)C, \
-                     act, RPC_)
+    // rb = rows in flight per thread, wpe = workgroups per CU the kernel is bounded for: (1, 4) on the half chunks, (2, 2) on whole ones
+    auto launch = [&](auto rb, auto wpe, int rows_per_chunk) {
+      const dim3 grid((unsigned)(C / kSlCh), (unsigned)cdiv(rows, rows_per_chunk));
+      with_bool(y2 != nullptr, [&](auto h2) {
+        with_bool((nt_loads_mask() & 2) != 0, [&](auto nt) {
+          constexpr bool H2 = decltype(h2)::value, NT = decltype(nt)::value;
+          hipLaunchKernelGGL((bn_bwd_apply_sliced_kernel<H2, false, decltype(rb)::value, decltype(wpe)::value, NT>), grid, dim3(kSlThreads),
+                             0, st, (const bf16_t*)dout, (const bf16_t*)y, (const bf16_t*)y2, partials, nchunk, nullptr, nullptr, nullptr,
+                             coef, saved, gamma, coef2, saved2, gamma2, 1.0f / (float)rows, row_lens, (bf16_t*)dy, (bf16_t*)dy2, dgamma,
+                             dbeta, dgamma2, dbeta2, (int)rows, (int)T_, (int)C, act, rows_per_chunk);
+        });
+      });
+    };
     const int rpc2 = asplit > 1 ? (int)cdiv(rows, (int64_t)nchunk * asplit) : rpc;
-    if (asplit > 1 && rpc2 >= kSlLanes) {
-      const dim3 grid2((unsigned)(C / kSlCh), (unsigned)cdiv(rows, rpc2));
-      if (y2) LASR_APPLY_SL(true, 1, 4, rpc2, grid2); else LASR_APPLY_SL(false, 1, 4, rpc2, grid2);
-    } else {
-      const dim3 grid((unsigned)(C / kSlCh), (unsigned)nchunk);
-      if (y2) LASR_APPLY_SL(true, 2, 2, rpc, grid); else LASR_APPLY_SL(false, 2, 2, rpc, grid);
-    }
-#undef LASR_APPLY_SL
-#undef LASR_APPLY_SL2
+    if (asplit > 1 && rpc2 >= kSlLanes) launch(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{}, rpc2);
+    else launch(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, rpc);
     LASR_LAUNCH_CHECK("bn_bwd_apply_sliced_kernel");
     return 0;
   }
@@ -1191,27 +1167,12 @@ extern "C" int lasr_bn_act_bwd_apply_drop(const void* dout, const void* y, const
   }
   const size_t shmem = (size_t)10 * C * sizeof(float);
   LASR_CHECK_SHAPE(shmem <= 64 * 1024, "lasr_bn_act_bwd_apply: C too large for the LDS coefficient table");
-  if (y2) {
-    if (se_scale) { DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, true, true>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem, st,
-                                             (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, se_grad, row_lens, (T*)dy,
-                                             (T*)dy2, (int)rows, (int)T_, (int)C, act, da); } else { hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, true, false>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem, st,
-                                             (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, se_grad, row_lens, (T*)dy,
-                                             (T*)dy2, (int)rows, (int)T_, (int)C, act, da); } }); } else { DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, false, true>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem, st,
-                                             (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, se_grad, row_lens, (T*)dy,
-                                             (T*)dy2, (int)rows, (int)T_, (int)C, act, da); } else { hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, false, false>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem, st,
-                                             (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, se_grad, row_lens, (T*)dy,
-                                             (T*)dy2, (int)rows, (int)T_, (int)C, act, da); } }); }
-  } else {
-    if (se_scale) { DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, true, true>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem, st,
-                                             (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, se_grad, row_lens, (T*)dy,
-                                             (T*)dy2, (int)rows, (int)T_, (int)C, act, da); } else { hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, true, false>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem, st,
-                                             (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, se_grad, row_lens, (T*)dy,
-                                             (T*)dy2, (int)rows, (int)T_, (int)C, act, da); } }); } else { DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, false, true>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem, st,
-                                             (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, se_grad, row_lens, (T*)dy,
-                                             (T*)dy2, (int)rows, (int)T_, (int)C, act, da); } else { hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, false, false>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem, st,
-                                             (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, se_grad, row_lens, (T*)dy,
-                                             (T*)dy2, (int)rows, (int)T_, (int)C, act, da); } }); }
-  }
+  with_bn_variant(dtype, y2 != nullptr, se_scale != nullptr, da.step != nullptr, [&](auto t, auto h2, auto se, auto drop) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, h2.value, se.value, drop.value>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem,
+                       st, (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, se_grad, row_lens, (T*)dy, (T*)dy2, (int)rows, (int)T_,
+                       (int)C, act, da);
+  });
   LASR_LAUNCH_CHECK("bn_bwd_apply_kernel");
   return 0;
 }
@@ -1251,10 +1212,10 @@ extern "C" int lasr_bn_se_bwd(const void* dout, const void* y, const float* coef
                       B * (C / kSlCh) >= 128 && T_ >= 64;
   if (sliced) {
     const dim3 grid((unsigned)(C / kSlCh), (unsigned)B);
-    if (y2) hipLaunchKernelGGL((bn_bwd_stats_sliced_kernel<true, true>), grid, dim3(kSlThreads), 0, st, (const bf16_t*)dout, (const bf16_t*)y, coef,
-                               saved, (const bf16_t*)y2, coef2, saved2, se_scale, partials, (int)(B * T_), (int)C, act, (int)T_);
-    else hipLaunchKernelGGL((bn_bwd_stats_sliced_kernel<false, true>), grid, dim3(kSlThreads), 0, st, (const bf16_t*)dout, (const bf16_t*)y, coef,
-                            saved, (const bf16_t*)y2, coef2, saved2, se_scale, partials, (int)(B * T_), (int)C, act, (int)T_);
+    with_bool(y2 != nullptr, [&](auto h2) {
+      hipLaunchKernelGGL((bn_bwd_stats_sliced_kernel<h2.value, true>), grid, dim3(kSlThreads), 0, st, (const bf16_t*)dout, (const bf16_t*)y,
+                         coef, saved, (const bf16_t*)y2, coef2, saved2, se_scale, partials, (int)(B * T_), (int)C, act, (int)T_);
+    });
     LASR_LAUNCH_CHECK("bn_bwd_stats_sliced_kernel");
     SeBwdBn bn;
     bn.partials = partials; bn.nslab = 1; bn.gamma = gamma; bn.beta = beta; bn.ysum = ysum;
@@ -1263,12 +1224,11 @@ extern "C" int lasr_bn_se_bwd(const void* dout, const void* y, const float* coef
     LASR_TRY(launch_se_bwd(nullptr, &bn, se_scale, se_hidden, se_pooled, W1, W2, B, T_, C, seg_out, dW1, dW2, se_work, st));
     // (the apply pass stays on whole-utterance chunks here: the half-utterance form of lasr_bn_act_bwd_apply_drop needs the SE
     //  constants in 128 registers, spills 9 of them and measured 3.80 against 3.78 ms per cfg4 step)
-    if (y2) hipLaunchKernelGGL((bn_bwd_apply_sliced_kernel<true, true>), grid, dim3(kSlThreads), 0, st, (const bf16_t*)dout, (const bf16_t*)y,
-                               (const bf16_t*)y2, nullptr, 0, tab, se_scale, seg_out, coef, saved, gamma, coef2, saved2, gamma2, 0.f, row_lens,
-                               (bf16_t*)dy, (bf16_t*)dy2, dgamma, dbeta, dgamma2, dbeta2, (int)(B * T_), (int)T_, (int)C, act, (int)T_);
-    else hipLaunchKernelGGL((bn_bwd_apply_sliced_kernel<false, true>), grid, dim3(kSlThreads), 0, st, (const bf16_t*)dout, (const bf16_t*)y,
-                            (const bf16_t*)y2, nullptr, 0, tab, se_scale, seg_out, coef, saved, gamma, coef2, saved2, gamma2, 0.f, row_lens,
-                            (bf16_t*)dy, (bf16_t*)dy2, dgamma, dbeta, dgamma2, dbeta2, (int)(B * T_), (int)T_, (int)C, act, (int)T_);
+    with_bool(y2 != nullptr, [&](auto h2) {
+      hipLaunchKernelGGL((bn_bwd_apply_sliced_kernel<h2.value, true>), grid, dim3(kSlThreads), 0, st, (const bf16_t*)dout, (const bf16_t*)y,
+                         (const bf16_t*)y2, nullptr, 0, tab, se_scale, seg_out, coef, saved, gamma, coef2, saved2, gamma2, 0.f, row_lens,
+                         (bf16_t*)dy, (bf16_t*)dy2, dgamma, dbeta, dgamma2, dbeta2, (int)(B * T_), (int)T_, (int)C, act, (int)T_);
+    });
     LASR_LAUNCH_CHECK("bn_bwd_apply_sliced_kernel");
     return 0;
   }
@@ -1286,17 +1246,13 @@ extern "C" int lasr_bn_se_bwd(const void* dout, const void* y, const float* coef
   const int64_t rows = B * T_;
   const size_t shmem = (size_t)10 * C * sizeof(float);
   LASR_CHECK_SHAPE(shmem <= 64 * 1024, "lasr_bn_se_bwd: C too large for the LDS coefficient table");
-  if (y2) {
-    DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, true, true>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem, st,
-                                             (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, seg_out, row_lens, (T*)dy, (T*)dy2, (int)rows, (int)T_, (int)C, act, da); }
-                            else { hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, true, false>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem, st,
-                                             (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, seg_out, row_lens, (T*)dy, (T*)dy2, (int)rows, (int)T_, (int)C, act, da); } });
-  } else {
-    DISPATCH_DTYPE(dtype, { if (da.step) { hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, true, true>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem, st,
-                                             (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, seg_out, row_lens, (T*)dy, (T*)dy2, (int)rows, (int)T_, (int)C, act, da); }
-                            else { hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, true, false>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem, st,
-                                             (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, seg_out, row_lens, (T*)dy, (T*)dy2, (int)rows, (int)T_, (int)C, act, da); } });
-  }
+  // (SE is always on here; the dispatcher's SE = false kernels are the ones lasr_bn_act_bwd_apply_drop launches)
+  with_bn_variant(dtype, y2 != nullptr, true, da.step != nullptr, [&](auto t, auto h2, auto se, auto drop) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, h2.value, se.value, drop.value>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem,
+                       st, (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, seg_out, row_lens, (T*)dy, (T*)dy2, (int)rows, (int)T_,
+                       (int)C, act, da);
+  });
   LASR_LAUNCH_CHECK("bn_bwd_apply_kernel");
   return 0;
 }

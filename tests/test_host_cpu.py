@@ -424,3 +424,40 @@ def test_fit_reserves_the_workspace_for_the_longest_clip():
     me2 = SimpleNamespace(dm=SimpleNamespace(train_datasets=SimpleNamespace(datasets=[]), train_bs=8), native=me.native)
     FusedLoop._reserve_workspace(me2)                      # nothing to size from: no call
     assert len(calls) == 1
+
+
+def test_workspace_sizes_match_the_recorded_table():
+    """The *_workspace_bytes entry points are the one definition of each workspace's size (the launchers carve their layout from
+    the same lines).  tests/golden/workspace_sizes.json holds what they returned BEFORE the launch side was rewritten around
+    shared definitions, over a table that crosses every geometry boundary: the CTC lattice's one-wave / multi-wave label widths
+    and its bound, the feature tile, the depthwise chunkings at the model's k values, the BN row slabs."""
+    import itertools
+    import json
+    from lightning_asr_amd import _lib
+    lib = _lib.load()
+    S = [0, 1, 127, 128, 255, 256, 511, 512, 1023, 2047, 2048]
+    B = [1, 8, 32]
+    T = [1, 201, 501, 801, 2001]
+    V = [28, 300, 4334, 5207]
+    CD = [64, 256, 336, 512]
+    K = [33, 39, 51, 63, 75, 87]
+    CB = CD + [1024]
+    tables = {
+        "lasr_ctc_workspace_bytes": itertools.product(B, T, S),
+        "lasr_ctc_lean_workspace_bytes": itertools.product(B, T, V, S),
+        "lasr_mel_workspace_bytes": itertools.product(B, T),
+        "lasr_dwconv_wgrad_workspace_bytes": itertools.product(B, T, CD, K),
+        "lasr_bn_bwd_workspace_bytes": itertools.product(B, T, CB),
+        "lasr_bn_se_bwd_workspace_bytes": itertools.product(B, T, CB),
+    }
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "workspace_sizes.json")))
+    assert set(golden) == set(tables)
+    for name, rows in tables.items():
+        want = {tuple(r[:-1]): r[-1] for r in golden[name]}
+        rows = list(rows)
+        assert set(want) == set(rows), name                     # the fixture covers exactly the table
+        fn = getattr(lib, name)
+        for r in rows:
+            assert fn(*r) == want[r], (name, r, fn(*r), want[r])
+    # the bound of the lattice: nothing to reserve above it, something at it
+    assert lib.lasr_ctc_workspace_bytes(8, 201, 2048) == 0 and lib.lasr_ctc_workspace_bytes(8, 201, 2047) > 0
