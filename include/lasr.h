@@ -25,10 +25,11 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 104   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 105   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
-                              104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it) */
+                              104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
+                              105: lasr_ctc_align_workspace_bytes / lasr_ctc_align (CTC forced alignment) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -375,6 +376,27 @@ int lasr_ctc_loss_mel(const float* logp, const int64_t* targets, const int32_t* 
                       const int32_t* sample_lens, const float* dither, const int32_t* aug, int64_t Bm, int64_t L,
                       int normalize, float* out_bft, void* out_btf, int dtype, int32_t* frames_out, float* pct_out,
                       void* mel_workspace, size_t mel_workspace_bytes, void* stream);
+
+/* CTC forced alignment: the Viterbi (max-product) path of the lasr_ctc_loss lattice, its backtrace and the per-label spans, in
+ * one launch of one workgroup per utterance on `stream`; nothing is allocated or synchronised, so the call can be captured.
+ * Arguments and states as lasr_ctc_loss: logp (B, T, C) f32, targets (B, S_max) int64 (clamped into the row on the device),
+ * tgt_lens (B) int32 clamped to [0, S_max], in_lens (B) int32 clamped to [0, T] or NULL (= T); state 2i+1 is label i, even
+ * states are blanks, the skip s-2 -> s exists only between different labels.
+ *   v[0][s] = logp[0][cls(s)] for s in {0, 1}, dead otherwise; v[t][s] = max(stay, step, skip) + logp[t][cls(s)] in f32 (one
+ *   rounding per state per frame).  Backpointer: the candidate that attains the max, on equality stay, then step, then skip.
+ *   Final state: 2S if v[Tb-1][2S] >= v[Tb-1][2S-1] or S == 0, else 2S-1.  A final score that is not above -5e29 (a dead state,
+ *   -inf or NaN) is infeasible - in particular Tb < S + (adjacent equal labels): score -inf, every index output -1, frame_logp 0.
+ *   Tb == 0: score 0 when S == 0, infeasible otherwise.
+ * score (B) f32; frame_state (B, T) int32: the state 0..2S of every frame, -1 past in_lens; frame_logp (B, T) f32: logp of that
+ * state's class, 0 where frame_state is -1; label_start / label_end (B, S_max) int32: first frame of label i and one past its
+ * last, -1 for i >= tgt_lens.  S_max may be 0 (targets and the label outputs may then be NULL).
+ * The workspace holds the backpointers, 2 bits per state (T rows of 64 dwords per wave and utterance); S_max above
+ * LASR_CTC_MAX_LABELS: workspace bytes 0 and LASR_E_SHAPE, nothing launched. */
+size_t lasr_ctc_align_workspace_bytes(int64_t B, int64_t T, int64_t S_max);
+int lasr_ctc_align(const float* logp, const int64_t* targets, const int32_t* in_lens, const int32_t* tgt_lens,
+                   int64_t B, int64_t T, int64_t C, int64_t S_max, int blank, float* score, int32_t* frame_state,
+                   float* frame_logp, int32_t* label_start, int32_t* label_end, void* workspace, size_t workspace_bytes,
+                   void* stream);
 
 /* Greedy CTC collapse of argmax ids (B, T) int32 truncated to lens (B) (NULL = T):
  * tokens (B, T) int32, n_tokens (B) int32.   utils/asr_metrics.py:159-166                      */

@@ -55,6 +55,7 @@ class AudioParser:
         if int(win_len * sr) != 320 or sr != 16000:
             raise NotImplementedError("the HIP front-end is built for win_len=0.02, sr=16000 (data_module.py:59)")
         self.win_len, self.sr = win_len, sr
+        self.hop_length = int(win_len * sr) // 2          # hop of the mel front-end in samples (data_module.py:66-67)
         self.rand = random.Random()
         self.device = torch.device(device)
 

@@ -6,7 +6,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -408,6 +408,53 @@ def ctc_loss(logp: torch.Tensor, targets: torch.Tensor, in_lens: torch.Tensor, t
     call("lasr_ctc_loss", _p(logp), _p(targets), _p(in_lens), _p(tgt_lens), B, T, Cc, max(S, 1), blank, _p(nll), _p(grad),
          _p(gscale), _p(ws), nb, _stream())
     return nll, grad
+
+
+class CtcAlignment(NamedTuple):
+    score: torch.Tensor          # (B,) f32 Viterbi log-probability, -inf when no alignment exists
+    frame_state: torch.Tensor    # (B, T) i32 lattice state 0..2S of every frame, -1 past in_lens / infeasible
+    frame_logp: torch.Tensor     # (B, T) f32 log-prob of that state's class, 0 where frame_state is -1
+    label_start: torch.Tensor    # (B, S) i32 first frame of label i, -1 for i >= tgt_lens / infeasible
+    label_end: torch.Tensor      # (B, S) i32 one past its last frame
+
+
+def ctc_align(logp: torch.Tensor, targets: torch.Tensor, in_lens: Optional[torch.Tensor], tgt_lens: torch.Tensor,
+              blank: int) -> CtcAlignment:
+    """CTC forced alignment (Viterbi path of the ctc_loss lattice, include/lasr.h lasr_ctc_align) of logp (B,T,C) f32 to targets
+    (B,S) i64, S <= CTC_MAX_LABELS; in_lens (B) i32 or None (= T), tgt_lens (B) i32.  One launch, nothing synchronised - except
+    that the labels inside tgt_lens are checked on the host first (skipped while the stream is being captured into a graph;
+    the kernel clamps them)."""
+    if logp.dim() != 3 or logp.dtype != torch.float32:
+        raise ValueError("ctc_align takes (B, T, C) float32 log-probs")
+    B, T, Cc = logp.shape
+    if targets.dim() != 2 or targets.shape[0] != B or targets.dtype != torch.int64:
+        raise ValueError("ctc_align: targets must be (B, S) int64")
+    S = targets.shape[1]
+    if S > CTC_MAX_LABELS:
+        raise ValueError("ctc_align: targets are %d labels wide; the CTC kernels take at most %d" % (S, CTC_MAX_LABELS))
+    for name, t in (("in_lens", in_lens), ("tgt_lens", tgt_lens)):
+        if t is None and name == "in_lens":
+            continue
+        if t is None or t.shape != (B,) or t.dtype != torch.int32:
+            raise ValueError("ctc_align: %s must be (B,) int32" % name)
+    if B < 1 or T < 1 or not 0 <= blank < Cc or Cc < 2:
+        raise ValueError("ctc_align: shape (%d, %d, %d) with blank %d" % (B, T, Cc, blank))
+    if S > 0 and not (logp.is_cuda and torch.cuda.is_current_stream_capturing()):
+        live = torch.arange(S, device=targets.device).unsqueeze(0) < tgt_lens.unsqueeze(1)
+        bad = live & ((targets == blank) | (targets < 0) | (targets >= Cc))
+        if bool(bad.any()):
+            b, i = [int(v) for v in bad.nonzero()[0]]
+            raise ValueError("ctc_align: targets[%d][%d] = %d is the blank or outside [0, %d)" % (b, i, int(targets[b, i]), Cc))
+    nb = int(_lib.load().lasr_ctc_align_workspace_bytes(B, T, S))
+    dev = logp.device
+    out = CtcAlignment(torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, T, dtype=torch.int32, device=dev),
+                       torch.empty(B, T, dtype=torch.float32, device=dev), torch.empty(B, S, dtype=torch.int32, device=dev),
+                       torch.empty(B, S, dtype=torch.int32, device=dev))
+    ws = _ws(nb, dev)
+    call("lasr_ctc_align", _p(logp), _p(targets) if S else None, _p(in_lens), _p(tgt_lens), B, T, Cc, S, int(blank), _p(out.score),
+         _p(out.frame_state), _p(out.frame_logp), _p(out.label_start) if S else None, _p(out.label_end) if S else None, _p(ws), nb,
+         _stream())
+    return out
 
 
 def greedy_decode(ids: torch.Tensor, lens: Optional[torch.Tensor], blank: int):

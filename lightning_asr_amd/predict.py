@@ -1,7 +1,8 @@
 """Inference surface of the reference (predict.py:21-74): checkpoint -> ``AsrTranslator.translate`` and
 manifest evaluation, on the HIP path (mel front-end, eval-mode model forward, greedy CTC decode - or, with
 ``decoder="beam"``, the CTC prefix beam search of beam_search.py, fused with a character n-gram LM when ``lm_path`` names
-a text ARPA file).
+a text ARPA file).  ``align`` / ``translate_timed`` / ``align_manifest`` add word timings: the CTC forced alignment of a known
+transcript (or of the decoder's own hypothesis) to the audio, ``ops.ctc_align`` + the record functions of align.py.
 
 The checkpoint is the PL-style dict the reference's ``ModelCheckpoint`` writes and ``Trainer`` here
 writes too: ``state_dict`` with the reference's key names (``encoder.encoder.block1.seq.0...``) and
@@ -9,12 +10,16 @@ writes too: ``state_dict`` with the reference's key names (``encoder.encoder.blo
 The SSL / LM-beam-search translator (predict.py:76-) belongs to the wav2vec2 branch, out of scope."""
 from __future__ import annotations
 
+import json
+import math
+import os
 import time
 from typing import List, Optional, Tuple
 
 import torch
 
-from .data_module import AudioParser, LibriDataModule
+from .align import frame_seconds, unit_records
+from .data_module import AudioParser, LibriDataModule, load_wav
 from .lightning_compat import Trainer
 from .train import LightingModule
 from . import ops
@@ -125,3 +130,109 @@ class AsrTranslator:
                          "path": batch[-1]})
         model.test_epoch_end(outs)
         return outs
+
+    # ------------------------------------------------------------------------------------------ forced alignment
+    def frame_seconds(self) -> float:
+        """seconds per output frame: the parser's hop times the model's time stride over the sample rate (0.02 s for the shipped
+        variants: 160 samples at 16 kHz, stride 2).  The stride is read off the native model's own frame count."""
+        native = self.model.encoder.native
+        n = 4096
+        stride = max(1, round(n / max(1, native.out_frames(2 * n) - native.out_frames(n))))
+        return frame_seconds(self.audio_parser.hop_length, self.audio_parser.sr, stride)
+
+    def text_to_ids(self, text: str) -> List[int]:
+        """the dataset's char2index mapping (data_module.py MyAudioDataset); a character outside the vocabulary is an error"""
+        char2index = dict((c, i) for i, c in enumerate(self.labels))
+        ids = []
+        for ch in text:
+            if ch not in char2index:
+                raise ValueError("align: character %r of the transcript is not in the vocabulary" % (ch,))
+            ids.append(char2index[ch])
+        return ids
+
+    def _encode_file(self, audio_path):
+        """one audio file -> (log-probs (1, T', C) f32, duration in seconds): translate()'s feature chain and forward"""
+        if isinstance(audio_path, str) and not os.path.exists(audio_path):
+            raise Exception("音频路径不存在 " + audio_path)
+        y = load_wav(audio_path)
+        inputs = self.audio_parser.features([y[0]], False, leads=[0])[0]
+        pct = torch.ones(inputs.shape[0], dtype=torch.float32, device=self.device)
+        out = self.model._encode(inputs, pct)
+        return out, y.shape[1] / float(self.audio_parser.sr)
+
+    def _decode(self, out) -> str:
+        if self.decoder == "beam":
+            return self.beam(out, None)[0]
+        return self.wer.ctc_decoder_predictions_tensor(torch.argmax(out, dim=-1, keepdim=False))[0]
+
+    def _align_ids(self, out, ids: List[int], duration: float) -> List[dict]:
+        """word records of the label ids on the log-probs (1, T', C) of one utterance"""
+        if not ids:
+            return []
+        logp = out.float().contiguous()
+        tg = torch.tensor([ids], dtype=torch.int64, device=logp.device)
+        tl = torch.tensor([len(ids)], dtype=torch.int32, device=logp.device)
+        al = ops.ctc_align(logp, tg, None, tl, logp.shape[-1] - 1)
+        if not math.isfinite(float(al.score[0])):
+            raise ValueError("align: no alignment exists: the transcript (%d labels) is too long for the clip (%d frames)"
+                             % (len(ids), logp.shape[1]))
+        return unit_records(ids, al.label_start[0].tolist(), al.label_end[0].tolist(), al.frame_logp[0].tolist(), self.labels,
+                            self.frame_seconds(), duration)
+
+    @torch.no_grad()
+    def align(self, audio_path, text: str) -> List[dict]:
+        """Forced alignment of a known transcript to one audio file: one record per word (per label for a vocabulary without a
+        space), {"word", "start", "end", "score", "labels": [{"label", "start", "end", "score"}, ...]}, times in seconds.
+        ValueError for a character outside the vocabulary and for a transcript too long for the clip."""
+        ids = self.text_to_ids(text)
+        out, duration = self._encode_file(audio_path)
+        return self._align_ids(out, ids, duration)
+
+    @torch.no_grad()
+    def translate_timed(self, audio_path) -> Tuple[str, List[dict]]:
+        """translate() with timings: decodes with the translator's own decoder and aligns that hypothesis on the same log-probs.
+        Returns (text, word records); an empty hypothesis gives ("", [])."""
+        out, duration = self._encode_file(audio_path)
+        text = self._decode(out)
+        if not text:
+            return "", []
+        return text, self._align_ids(out, self.text_to_ids(text), duration)
+
+    @torch.no_grad()
+    def align_manifest(self, manifest: str, out_path: str, batch_size: int = 32) -> List[dict]:
+        """Forced alignment of every line of a manifest to its audio, batched over the eval loader (the eval forward of
+        evalute_manifest, one ops.ctc_align per batch).  Writes one JSON line per utterance to out_path - audio_filepath, text,
+        score (Viterbi log-probability), score_per_frame, words - and returns the records.  An utterance without an alignment
+        (transcript too long for its clip) has "words": null and score -inf."""
+        dm = LibriDataModule(train_manifest=manifest, dev_manifest=manifest, test_manifest=manifest, dev_bs=batch_size,
+                             num_worker=0, labels=self.labels, device=str(self.model.encoder.native.device),
+                             act_dtype=self.model.encoder.native.act_dtype)
+        trainer = Trainer(gpus=1, device=str(self.model.encoder.native.device))
+        model = self.model
+        model.trainer = trainer
+        model.eval()
+        dm.trainer = trainer
+        dm.setup("test")
+        loader = dm.test_dataloader()
+        durations = dict((d["audio_filepath"], float(d["duration"])) for d in dm.test_datasets.datasets)
+        secs = self.frame_seconds()
+        records = []
+        for batch in trainer._eval_batches(loader, dm, len(loader)):
+            out, _, t_lengths, trans, trans_lengths = model._shared(batch)
+            logp = out.float().contiguous()
+            tg = trans.to(logp.device, torch.int64).contiguous()
+            tl = trans_lengths.to(logp.device, torch.int32).contiguous()
+            al = ops.ctc_align(logp, tg, t_lengths.contiguous(), tl, logp.shape[-1] - 1)
+            score, start, end, flp = al.score.tolist(), al.label_start.tolist(), al.label_end.tolist(), al.frame_logp.tolist()
+            tg_h, tl_h, frames = tg.tolist(), tl.tolist(), t_lengths.tolist()
+            for b, path in enumerate(batch[-1]):
+                ids = tg_h[b][:tl_h[b]]
+                rec = {"audio_filepath": path, "text": "".join(self.labels[c] for c in ids), "score": score[b],
+                       "score_per_frame": score[b] / max(frames[b], 1), "words": None}
+                if math.isfinite(score[b]):
+                    rec["words"] = unit_records(ids, start[b], end[b], flp[b], self.labels, secs, durations.get(path))
+                records.append(rec)
+        with open(out_path, "w", encoding="utf-8") as f:
+            for rec in records:
+                f.write(json.dumps(rec, ensure_ascii=False) + "\n")
+        return records
