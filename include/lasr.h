@@ -25,11 +25,12 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 105   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 106   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
-                              105: lasr_ctc_align_workspace_bytes / lasr_ctc_align (CTC forced alignment) */
+                              105: lasr_ctc_align_workspace_bytes / lasr_ctc_align (CTC forced alignment)
+                              106: lasr_arpa_load_words / lasr_arpa_lexicon_info / lasr_ctc_beam_decode_wlm (word-level LM) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -462,6 +463,49 @@ int lasr_ctc_beam_decode_lm(const float* logp, const int32_t* lens, int64_t B, i
                             int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image, float alpha, float beta,
                             int32_t* tokens, int32_t* n_tokens, float* scores, float* am_scores, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* CTC prefix beam search fused with a WORD-level n-gram LM and its lexicon (DESIGN.md "Beam search with a word-level LM").  It
+ * restates ctc_decoders' word-based Scorer in this project's own words; ctc_decoders' source is not part of this project.
+ * Everything of lasr_ctc_beam_decode holds (pruning, cutoff_prob / cutoff_top_n, log_b / log_nb, merging, tie-break).
+ *  Mode.  An ARPA file is word-level when some word other than <s>, </s>, <unk> has more than one code point (lasr_arpa_info's
+ *     char_based == 0).  It can be used when the vocabulary has exactly one label equal to " ": the space.
+ *  Spellable words.  An LM word is spellable when every one of its code points is a one-code-point, non-space label.
+ *     Unspellable words, <unk>, and every n-gram that contains one of them are left out of the image (the "drop unmapped
+ *     words" rule, per word); <s> and </s> are kept.  The suffix-closure check runs on the file as read, before dropping.
+ *  Lexicon.  A trie over the label ids of all spellable words; each prefix carries its trie node.  The empty prefix and a
+ *     prefix that ends in the space sit at the root.  An extension by a non-space, non-blank label c exists only if the node
+ *     has a child c; an extension by the space exists only if the node is a complete word - so no leading space, no double
+ *     space, no out-of-lexicon word.  An extension that does not exist contributes nothing (-inf), like a candidate the early
+ *     cutoff drops.  The trie state is reset at once on a space (ctc_decoders' one-frame delay after a word is not reproduced).
+ *  Scoring.  A non-space label adds no LM term and no beta.  The space after word w adds alpha * lm(w | previous N-1 words,
+ *     <s>-padded) + beta, lm as for lasr_ctc_beam_decode_lm: ARPA backoff in log10 divided by NUM_FLT_LOGE, OOV_SCORE = -1000
+ *     unconverted if <s> is needed and the LM lacks it.  The term depends on the new prefix alone, so merging stays exact;
+ *     beta is a per-word bonus.
+ *  End of utterance.  A non-empty final prefix that does not end in a space gets one more term: alpha * lm(w | ...) + beta if
+ *     its node is a complete word, alpha * OOV_SCORE + beta if it is not.  The <= beam_width final entries are then re-ranked
+ *     by the new fused score, ties by their order before the term; n_best is cut from that order.
+ *  Early cutoff.  As lasr_ctc_beam_decode_lm: min_cutoff = score(beam_width-th) + logp[t][blank] - max(0, beta) on a full
+ *     beam, score the fused score without any end-of-utterance term.
+ *  Outputs.  tokens / n_tokens as lasr_ctc_beam_decode_lm; scores = the fused score, end-of-utterance term included;
+ *     am_scores = the acoustic logaddexp(log_b, log_nb), i.e. the fused score minus every term the search added.  This deviates
+ *     from ctc_decoders' approx_ctc, which in word mode subtracts beta once per label while adding it once per word.
+ *  Ranges.  Orders 1..6; beam width, cutoff_top_n, C, T, n_best and the workspace (lasr_ctc_beam_lm_workspace_bytes) as
+ *     lasr_ctc_beam_decode_lm.
+ *
+ * lasr_arpa_load_words builds the word image (the n-gram sections of lasr_arpa_load over the spellable words, a lexicon behind
+ * them, another magic: each search rejects the other kind of image) for vocab[0 .. n_vocab) with vocab[space_id] the only " ":
+ * error codes and line-numbered messages as lasr_arpa_load, LASR_E_UNSUPPORTED also for a character-level file or a bad
+ * space_id, LASR_E_FORMAT for a lexicon of more than 2^31 - 1 trie nodes.  lasr_arpa_info / _write_image / _free take its
+ * handle; lasr_arpa_lexicon_info reports the spellable words, the trie nodes (the root included) and the words dropped as
+ * unspellable (LASR_E_ARG for a handle of lasr_arpa_load). */
+int lasr_arpa_load_words(const char* path, const char* const* vocab, int n_vocab, int space_id, void** handle);
+int lasr_arpa_lexicon_info(const void* handle, int64_t* n_lexicon_words, int64_t* n_nodes, int64_t* n_dropped_words);
+/* Arguments, checks and launches as lasr_ctc_beam_decode_lm, with lm_image a device copy of a word image.  Any other image
+ * yields empty slots (n_tokens -1, scores -inf) for every utterance. */
+int lasr_ctc_beam_decode_wlm(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank, int beam_width,
+                             int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image, float alpha, float beta,
+                             int32_t* tokens, int32_t* n_tokens, float* scores, float* am_scores, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- optimiser ----------------
  * scheduler/novograd.py:75-145 with betas=(0.8,0.5), eps=1e-8, no amsgrad/grad_averaging/luc

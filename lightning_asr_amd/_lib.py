@@ -99,6 +99,10 @@ SIGNATURES = {
     "lasr_ctc_beam_lm_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32]),
     "lasr_ctc_beam_decode_lm": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _p, _f32, _f32, _p, _p, _p, _p, _p, _sz,
                                        _p]),
+    "lasr_arpa_load_words": (_i32, [C.c_char_p, _p, _i32, _i32, C.POINTER(_p)]),
+    "lasr_arpa_lexicon_info": (_i32, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "lasr_ctc_beam_decode_wlm": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _p, _f32, _f32, _p, _p, _p, _p, _p, _sz,
+                                        _p]),
     "lasr_novograd_workspace_bytes": (_sz, [_i64, _i64]),
     "lasr_novograd_step": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p, _f32, _f32, _f32, _f32, _f32, _p, _sz, _p]),
     "lasr_novograd_step_keep": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p, _f32, _f32, _f32, _f32, _f32, _p, _sz, _p]),

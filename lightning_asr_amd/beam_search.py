@@ -2,9 +2,12 @@
 
 The reference runs ctc_decoders' ``ctc_beam_search_decoder_batch`` on the host, optionally with a KenLM scorer.  Here the
 search runs on the GPU: one launch prunes every frame, one workgroup per utterance searches it.  With ``lm_path`` (a text
-ARPA file of a character n-gram LM, as the reference's ckpt/lm/readme.md trains) the search is fused with that LM:
-``alpha`` weighs its natural-log score, ``beta`` is added per emitted label (ops.load_arpa / ops.ctc_beam_decode_lm); KenLM
-binary models and word-level LMs raise NotImplementedError.  ``num_cpus`` is accepted and ignored.  The blank is the class
+ARPA file) the search is fused with that LM (ops.load_arpa / ops.ctc_beam_decode_lm).  A character n-gram LM, as the
+reference's ckpt/lm/readme.md trains: ``alpha`` weighs its natural-log score, ``beta`` is added per emitted label.  A word
+n-gram LM, with a vocabulary that has exactly one " " label: only words the LM knows and the labels can spell are decoded,
+``alpha`` weighs the LM score of each word, given at the space after it or at the end of the utterance, ``beta`` is added per
+word.  KenLM binary models, and word-level LMs with a vocabulary without a space label, raise NotImplementedError.
+``num_cpus`` is accepted and ignored.  The blank is the class
 after the vocabulary (ctc_decoders' ``blank_id = vocabulary.size()``)."""
 from __future__ import annotations
 
@@ -36,7 +39,8 @@ class BeamSearchDecoderWithLM(torch.nn.Module):
         return self.search_full(log_probs, log_probs_length, n_best)[:3]
 
     def search_full(self, log_probs, log_probs_length, n_best: int = 1):
-        """search() plus ctc_decoders' approx_ctc scores (B, n_best) when an LM is fused (None without one)"""
+        """search() plus, when an LM is fused, ctc_decoders' approx_ctc scores (B, n_best) for a character LM and the acoustic
+        scores for a word LM (None without an LM)"""
         lp = torch.as_tensor(np.ascontiguousarray(log_probs)) if isinstance(log_probs, np.ndarray) else log_probs
         dev = lp.device if lp.is_cuda else self.device
         lp = lp.to(dev, torch.float32).contiguous()
@@ -67,7 +71,7 @@ class BeamSearchDecoderWithLM(torch.nn.Module):
     @torch.no_grad()
     def decode_nbest(self, log_probs, log_probs_length, n_best=None) -> List[List[Tuple[float, str]]]:
         """ctc_decoders' output: per utterance [(score, text), ...], best first (up to n_best, default beam_width).  With an LM
-        the list is ranked by the fused score and each score is ctc_decoders' approx_ctc."""
+        the list is ranked by the fused score and each score is ctc_decoders' approx_ctc (a word LM: the acoustic score)."""
         n_best = self.beam_width if n_best is None else int(n_best)
         tokens, n, scores, am = self.search_full(log_probs, log_probs_length, n_best)
         if am is not None:

@@ -18,6 +18,14 @@
 //                  (index of its suffix w2..wn) << 32 | (LM word id of w1).  The index of an n-gram is its word id for a
 //                  unigram and n_words + slot for a higher order, so a key never collides with another n-gram's.
 // Only n-grams over words some vocabulary label maps to (plus <s> and </s>) are kept: no query can reach the others.
+//
+// Word-level files (arpa_parse_words / arpa_load_words, for lasr_ctc_beam_decode_wlm): the same uni / cls / slot sections under
+// another magic (kArpaWordImageMagic, so that each search kernel rejects the other kind of image), kept for the SPELLABLE words
+// - every code point a one-code-point, non-space label - plus <s> and </s>; cls is all -1 (a label is no LM word here).  An
+// ArpaLexHeader (64 bytes) follows the ArpaImageHeader and names the lexicon appended behind the slots:
+//   edge[1 << log2_edges] ArpaLexEdge: open-addressing hash (linear probing, load <= 1/2) keyed exactly by
+//                  (trie node << 32 | class id) -> child node; node 0 is the root
+//   node_word[n_nodes] int32: LM word id of the word a node spells, -1 for a node that is no complete word
 #pragma once
 #include <cmath>
 #include <math.h>
@@ -34,6 +42,7 @@ namespace host {
 
 constexpr int kArpaMaxOrder = 6;                 // KenLM's default limit
 constexpr uint32_t kArpaImageMagic = 0x4d4c5341u;  // "ASLM"
+constexpr uint32_t kArpaWordImageMagic = 0x574c5341u;  // "ASLW"
 constexpr uint64_t kArpaEmptyKey = ~0ull;
 enum { kArpaOk = 0, kArpaErrOpen = 1, kArpaErrFormat = 2, kArpaErrUnsupported = 3, kArpaErrArg = 4 };
 
@@ -43,6 +52,19 @@ struct ArpaImageHeader {
   uint64_t uni_off, cls_off, slot_off, n_ngrams;
 };
 static_assert(sizeof(ArpaImageHeader) == 64, "image header is 64 bytes");
+
+struct ArpaLexHeader {                           // at byte 64 of a word image
+  uint64_t edge_off, node_off;
+  uint32_t log2_edges, n_nodes, space_id, n_lexicon_words, n_dropped_words;
+  uint32_t reserved[7];
+};
+static_assert(sizeof(ArpaLexHeader) == 64, "lexicon header is 64 bytes");
+
+struct ArpaLexEdge {
+  uint64_t key;                                  // node << 32 | class, kArpaEmptyKey when free
+  int32_t child, reserved;
+};
+static_assert(sizeof(ArpaLexEdge) == 16, "one 16-byte load per probe");
 
 struct ArpaSlot {
   uint64_t key;
@@ -61,7 +83,19 @@ struct ArpaModel {
   int order = 0;
   bool char_based = false;
   int64_t n_ngrams = 0;            // n-grams kept in the image
+  bool word_mode = false;          // built by arpa_parse_words, which also sets the three counts below
+  int64_t n_lexicon_words = 0, n_nodes = 0, n_dropped_words = 0;
   std::vector<unsigned char> image;
+};
+
+// a text ARPA file as read: an n-gram's index is its word id for a unigram, n_words + running count above
+struct ArpaFile {
+  std::unordered_map<std::string, uint32_t> wid;
+  std::vector<std::string> words;
+  std::vector<float> lp, bow;
+  std::vector<uint32_t> first, suffix;            // per index >= n_words: w1 id and suffix index
+  int order = 0;
+  bool char_based = true;
 };
 
 namespace arpa_detail {
@@ -113,21 +147,24 @@ static inline bool special(const std::string& w) { return w == "<s>" || w == "</
 
 }  // namespace arpa_detail
 
-// Parses `text` (the whole file) and builds the device image for the class strings vocab[0 .. n_vocab).  Returns kArpaOk or an
-// error code with *err set.
-static inline int arpa_parse(const std::string& text, const char* const* vocab, int n_vocab, ArpaModel* m, std::string* err) {
-  using namespace arpa_detail;
+// the checks every build makes before it reads the text
+static inline int arpa_check_args(const std::string& text, const char* const* vocab, int n_vocab, const ArpaModel* m,
+                                  std::string* err) {
   if ((!vocab && n_vocab > 0) || n_vocab < 0 || !m) { *err = "null vocabulary or model"; return kArpaErrArg; }
   for (int i = 0; i < n_vocab; ++i)
     if (!vocab[i]) { *err = "vocabulary entry " + std::to_string(i) + " is null"; return kArpaErrArg; }
   if (text.compare(0, 8, "mmap lm ") == 0) { *err = "a KenLM binary model: only text ARPA files are read"; return kArpaErrUnsupported; }
+  return kArpaOk;
+}
 
-  // full-file n-gram store: index = word id for unigrams, n_words + running count above
-  std::unordered_map<std::string, uint32_t> wid;
-  std::vector<std::string> words;
+// Parses `text` (the whole file) into *f and checks suffix closure.  Returns kArpaOk or kArpaErrFormat with *err set.
+static inline int arpa_read(const std::string& text, ArpaFile* f, std::string* err) {
+  using namespace arpa_detail;
+  std::unordered_map<std::string, uint32_t>& wid = f->wid;
+  std::vector<std::string>& words = f->words;
   std::unordered_map<uint64_t, uint32_t> idx;     // (suffix index << 32 | w1 id) -> index
-  std::vector<float> lp, bow;
-  std::vector<uint32_t> first, suffix;            // per index >= n_words: w1 id and suffix index
+  std::vector<float>&lp = f->lp, &bow = f->bow;
+  std::vector<uint32_t>&first = f->first, &suffix = f->suffix;
   std::vector<int64_t> declared;
   std::vector<std::string> tok;
   std::vector<uint32_t> ids;
@@ -252,19 +289,27 @@ static inline int arpa_parse(const std::string& text, const char* const* vocab, 
   if (state == kPre) { *err = "no \\data\\ section: not a text ARPA file"; return kArpaErrFormat; }
   if (state != kEnd) { *err = at_line(line, "the file ends before \\end\\"); return kArpaErrFormat; }
   if (declared.empty()) { *err = "no n-gram orders declared"; return kArpaErrFormat; }
+  f->order = (int)declared.size();
+  f->char_based = true;
+  for (const std::string& w : words)
+    if (!special(w) && code_points(w) != 1) f->char_based = false;
+  return kArpaOk;
+}
 
-  // ---- keep what the vocabulary can reach, build the image
+// Builds the header and the uni / cls / slot sections, the first of them head_bytes into the image, over the words with
+// wanted[file word id] set (<s> and </s> are added) and the class -> file word id map cls_word (-1: none).  (*dev_out)[file
+// word id] is the word's LM id in the image, -1 when it was left out.
+static inline void arpa_build_ngrams(const ArpaFile& f, std::vector<char> wanted, const std::vector<int64_t>& cls_word,
+                                     uint32_t magic, size_t head_bytes, ArpaModel* m, std::vector<int32_t>* dev_out) {
+  const std::vector<std::string>& words = f.words;
+  const std::vector<float>&lp = f.lp, &bow = f.bow;
+  const std::vector<uint32_t>&first = f.first, &suffix = f.suffix;
+  const int n_vocab = (int)cls_word.size();
+  const bool char_based = f.char_based;
   const uint32_t nw = (uint32_t)words.size();
   std::vector<int32_t> dev(nw, -1);
-  std::vector<char> wanted(nw, 0);
-  for (int i = 0; i < n_vocab; ++i) {
-    auto it = wid.find(vocab[i]);
-    if (it != wid.end() && words[it->second] != "<unk>") wanted[it->second] = 1;
-  }
-  bool char_based = true;
   uint32_t n_dev = 0, bos = 0xFFFFFFFFu, eos = 0xFFFFFFFFu;
   for (uint32_t i = 0; i < nw; ++i) {
-    if (!special(words[i]) && code_points(words[i]) != 1) char_based = false;
     if (words[i] == "<s>" || words[i] == "</s>") wanted[i] = 1;
     if (wanted[i]) {
       dev[i] = (int32_t)n_dev++;
@@ -286,15 +331,15 @@ static inline int arpa_parse(const std::string& text, const char* const* vocab, 
   auto align16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
   ArpaImageHeader h;
   memset(&h, 0, sizeof(h));
-  h.magic = kArpaImageMagic;
-  h.order = (uint32_t)declared.size();
+  h.magic = magic;
+  h.order = (uint32_t)f.order;
   h.n_words = n_dev;
   h.n_classes = (uint32_t)n_vocab;
   h.log2_slots = (uint32_t)log2_slots;
   h.bos = bos;
   h.eos = eos;
   h.char_based = char_based ? 1u : 0u;
-  h.uni_off = 64;
+  h.uni_off = head_bytes;
   h.cls_off = align16(h.uni_off + (size_t)n_dev * 8);
   h.slot_off = align16(h.cls_off + (size_t)n_vocab * 4);
   h.n_ngrams = n_dev + kept;
@@ -303,10 +348,7 @@ static inline int arpa_parse(const std::string& text, const char* const* vocab, 
   for (uint32_t i = 0; i < nw; ++i)
     if (dev[i] >= 0) { uni[2 * dev[i]] = lp[i]; uni[2 * dev[i] + 1] = bow[i]; }
   int32_t* cls = reinterpret_cast<int32_t*>(img.data() + h.cls_off);
-  for (int i = 0; i < n_vocab; ++i) {
-    auto it = wid.find(vocab[i]);
-    cls[i] = (it != wid.end() && words[it->second] != "<unk>") ? dev[it->second] : -1;
-  }
+  for (int i = 0; i < n_vocab; ++i) cls[i] = cls_word[i] >= 0 ? dev[cls_word[i]] : -1;
   ArpaSlot* slot = reinterpret_cast<ArpaSlot*>(img.data() + h.slot_off);
   for (size_t i = 0; i < n_slots; ++i) { slot[i].key = kArpaEmptyKey; slot[i].lp = 0.f; slot[i].bow = 0.f; }
   for (size_t j = 0; j < nh; ++j) {                // suffixes precede their extensions: their device index is known
@@ -322,25 +364,153 @@ static inline int arpa_parse(const std::string& text, const char* const* vocab, 
     dev_idx[j] = (int64_t)n_dev + (int64_t)at;
   }
   memcpy(img.data(), &h, sizeof(h));
-  m->order = (int)declared.size();
+  m->order = f.order;
   m->char_based = char_based;
   m->n_ngrams = (int64_t)h.n_ngrams;
   m->image.swap(img);
+  if (dev_out) dev_out->swap(dev);
+}
+
+// Parses `text` (the whole file) and builds the device image for the class strings vocab[0 .. n_vocab).  Returns kArpaOk or an
+// error code with *err set.
+static inline int arpa_parse(const std::string& text, const char* const* vocab, int n_vocab, ArpaModel* m, std::string* err) {
+  int rc = arpa_check_args(text, vocab, n_vocab, m, err);
+  if (rc != kArpaOk) return rc;
+  ArpaFile f;
+  rc = arpa_read(text, &f, err);
+  if (rc != kArpaOk) return rc;
+  // keep what the vocabulary can reach
+  std::vector<char> wanted(f.words.size(), 0);
+  std::vector<int64_t> cls_word((size_t)n_vocab, -1);
+  for (int i = 0; i < n_vocab; ++i) {
+    auto it = f.wid.find(vocab[i]);
+    if (it != f.wid.end() && f.words[it->second] != "<unk>") { wanted[it->second] = 1; cls_word[i] = it->second; }
+  }
+  arpa_build_ngrams(f, wanted, cls_word, kArpaImageMagic, sizeof(ArpaImageHeader), m, nullptr);
+  return kArpaOk;
+}
+
+// The word-level build: `text` must be a word-level file and vocab[space_id] the vocabulary's only " " label (otherwise
+// kArpaErrUnsupported).  Keeps the spellable words, builds the n-gram sections over them and appends the lexicon trie.  A label
+// string that occurs twice spells with its first class.
+static inline int arpa_parse_words(const std::string& text, const char* const* vocab, int n_vocab, int space_id, ArpaModel* m,
+                                   std::string* err) {
+  using namespace arpa_detail;
+  int rc = arpa_check_args(text, vocab, n_vocab, m, err);
+  if (rc != kArpaOk) return rc;
+  int n_space = 0;
+  for (int i = 0; i < n_vocab; ++i) n_space += strcmp(vocab[i], " ") == 0;
+  if (space_id < 0 || space_id >= n_vocab || strcmp(vocab[space_id], " ") != 0 || n_space != 1) {
+    *err = "a word-level LM needs exactly one \" \" label and space_id " + std::to_string(space_id) + " is not it";
+    return kArpaErrUnsupported;
+  }
+  ArpaFile f;
+  rc = arpa_read(text, &f, err);
+  if (rc != kArpaOk) return rc;
+  if (f.char_based) { *err = "a character-level LM: the word-level build takes a file with words of several code points"; return kArpaErrUnsupported; }
+  std::unordered_map<std::string, int32_t> label;           // one-code-point, non-space label -> class
+  for (int i = 0; i < n_vocab; ++i) {
+    const std::string s = vocab[i];
+    if (i != space_id && !s.empty() && (s[0] & 0xC0) != 0x80 && code_points(s) == 1) label.emplace(s, i);
+  }
+  // the trie over the spellable words, in file order; a word's code points are the runs (lead byte, continuation bytes)
+  const uint32_t nw = (uint32_t)f.words.size();
+  std::vector<char> wanted(nw, 0);
+  std::unordered_map<uint64_t, uint32_t> edge;
+  std::vector<int64_t> node_file_word(1, -1);                // node -> file word id
+  std::vector<int32_t> spell;
+  int64_t n_lex = 0, n_drop = 0;
+  for (uint32_t i = 0; i < nw; ++i) {
+    const std::string& w = f.words[i];
+    if (special(w)) continue;
+    spell.clear();
+    bool ok = !w.empty();
+    for (size_t a = 0; ok && a < w.size();) {
+      size_t b = a + 1;
+      while (b < w.size() && (w[b] & 0xC0) == 0x80) ++b;
+      auto it = label.find(w.substr(a, b - a));
+      if (it == label.end()) ok = false;
+      else spell.push_back(it->second);
+      a = b;
+    }
+    if (!ok) { ++n_drop; continue; }
+    uint32_t node = 0;
+    for (int32_t c : spell) {
+      const uint64_t key = ((uint64_t)node << 32) | (uint32_t)c;
+      auto it = edge.find(key);
+      if (it == edge.end()) {
+        if (node_file_word.size() >= 0x7fffffffu) { *err = "the lexicon needs more than 2^31 - 1 trie nodes"; return kArpaErrFormat; }
+        it = edge.emplace(key, (uint32_t)node_file_word.size()).first;
+        node_file_word.push_back(-1);
+      }
+      node = it->second;
+    }
+    node_file_word[node] = i;                                // words are distinct strings: no node is claimed twice
+    wanted[i] = 1;
+    ++n_lex;
+  }
+  std::vector<int32_t> dev;
+  const std::vector<int64_t> cls_word((size_t)n_vocab, -1);
+  arpa_build_ngrams(f, wanted, cls_word, kArpaWordImageMagic, sizeof(ArpaImageHeader) + sizeof(ArpaLexHeader), m, &dev);
+  int log2_edges = 4;
+  while (((size_t)1 << log2_edges) < 2 * edge.size()) ++log2_edges;
+  const size_t n_edges = (size_t)1 << log2_edges, n_nodes = node_file_word.size();
+  ArpaLexHeader lh;
+  memset(&lh, 0, sizeof(lh));
+  lh.edge_off = (m->image.size() + 15) & ~(size_t)15;
+  lh.node_off = lh.edge_off + n_edges * sizeof(ArpaLexEdge);
+  lh.log2_edges = (uint32_t)log2_edges;
+  lh.n_nodes = (uint32_t)n_nodes;
+  lh.space_id = (uint32_t)space_id;
+  lh.n_lexicon_words = (uint32_t)n_lex;
+  lh.n_dropped_words = (uint32_t)n_drop;
+  m->image.resize((size_t)lh.node_off + n_nodes * sizeof(int32_t), 0);
+  memcpy(m->image.data() + sizeof(ArpaImageHeader), &lh, sizeof(lh));
+  ArpaLexEdge* e = reinterpret_cast<ArpaLexEdge*>(m->image.data() + lh.edge_off);
+  for (size_t i = 0; i < n_edges; ++i) { e[i].key = kArpaEmptyKey; e[i].child = -1; e[i].reserved = 0; }
+  for (const auto& kv : edge) {
+    size_t at = (size_t)(arpa_hash(kv.first) & (n_edges - 1));
+    while (e[at].key != kArpaEmptyKey) at = (at + 1) & (n_edges - 1);
+    e[at].key = kv.first;
+    e[at].child = (int32_t)kv.second;
+  }
+  int32_t* nwd = reinterpret_cast<int32_t*>(m->image.data() + lh.node_off);
+  for (size_t i = 0; i < n_nodes; ++i) nwd[i] = node_file_word[i] >= 0 ? dev[node_file_word[i]] : -1;
+  m->word_mode = true;
+  m->n_lexicon_words = n_lex;
+  m->n_nodes = (int64_t)n_nodes;
+  m->n_dropped_words = n_drop;
+  return kArpaOk;
+}
+
+static inline int arpa_read_file(const char* path, std::string* text, std::string* err) {
+  if (!path) { *err = "null path"; return kArpaErrArg; }
+  FILE* f = fopen(path, "rb");
+  if (!f) { *err = std::string("cannot open ") + path; return kArpaErrOpen; }
+  char buf[1 << 16];
+  size_t got;
+  while ((got = fread(buf, 1, sizeof(buf), f)) > 0) text->append(buf, got);
+  const bool bad = ferror(f) != 0;
+  fclose(f);
+  if (bad) { *err = std::string("cannot read ") + path; return kArpaErrOpen; }
   return kArpaOk;
 }
 
 static inline int arpa_load(const char* path, const char* const* vocab, int n_vocab, ArpaModel* m, std::string* err) {
-  if (!path) { *err = "null path"; return kArpaErrArg; }
-  FILE* f = fopen(path, "rb");
-  if (!f) { *err = std::string("cannot open ") + path; return kArpaErrOpen; }
   std::string text;
-  char buf[1 << 16];
-  size_t got;
-  while ((got = fread(buf, 1, sizeof(buf), f)) > 0) text.append(buf, got);
-  const bool bad = ferror(f) != 0;
-  fclose(f);
-  if (bad) { *err = std::string("cannot read ") + path; return kArpaErrOpen; }
-  const int rc = arpa_parse(text, vocab, n_vocab, m, err);
+  int rc = arpa_read_file(path, &text, err);
+  if (rc != kArpaOk) return rc;
+  rc = arpa_parse(text, vocab, n_vocab, m, err);
+  if (rc != kArpaOk) *err = std::string(path) + ": " + *err;
+  return rc;
+}
+
+static inline int arpa_load_words(const char* path, const char* const* vocab, int n_vocab, int space_id, ArpaModel* m,
+                                  std::string* err) {
+  std::string text;
+  int rc = arpa_read_file(path, &text, err);
+  if (rc != kArpaOk) return rc;
+  rc = arpa_parse_words(text, vocab, n_vocab, space_id, m, err);
   if (rc != kArpaOk) *err = std::string(path) + ": " + *err;
   return rc;
 }

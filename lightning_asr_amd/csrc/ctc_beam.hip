@@ -594,11 +594,12 @@ struct LmImg {
   bool ok;
 };
 
-__device__ __forceinline__ LmImg lm_open(const void* image) {
+// magic: the kind of image the calling search reads (a character image, or a word image with its lexicon)
+__device__ __forceinline__ LmImg lm_open(const void* image, uint32_t magic = host::kArpaImageMagic) {
   const host::ArpaImageHeader* h = static_cast<const host::ArpaImageHeader*>(image);
   const char* base = static_cast<const char*>(image);
   LmImg m;
-  m.ok = h->magic == host::kArpaImageMagic && h->order >= 1 && h->order <= (uint32_t)host::kArpaMaxOrder &&
+  m.ok = h->magic == magic && h->order >= 1 && h->order <= (uint32_t)host::kArpaMaxOrder &&
          h->log2_slots >= 4 && h->log2_slots < 32;
   m.uni = reinterpret_cast<const float2*>(base + h->uni_off);
   m.cls = reinterpret_cast<const int32_t*>(base + h->cls_off);
@@ -897,6 +898,264 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
   }
 }
 
+
+// ================================================================== with a word n-gram LM and its lexicon ==============
+// lasr_ctc_beam_decode_wlm: the same search with a word-level scorer (include/lasr.h states the contract).  Each entry carries
+// the lexicon trie node of its unfinished word; p + c exists only where that node has a child c, p + space only where it is
+// a complete word, and the LM scores a word when the space after it is emitted.  What a prefix needs in every frame is
+// worked out once, when its entry is created: its node, the LM id of the word the node spells and `sterm`, the term the
+// space after that word adds (alpha * lm(word | context) + beta) - also the end-of-utterance term.  A frame then costs one
+// lexicon probe per (prefix, kept label) candidate, kLmGroup of them in flight per thread, and one n-gram chain per NEW prefix.
+struct WlmImg {
+  LmImg lm;
+  const uint4* edge;          // ArpaLexEdge as (key lo, key hi, child, reserved)
+  const int32_t* node_word;
+  uint32_t emask;
+  int space;
+};
+
+__device__ __forceinline__ WlmImg wlm_open(const void* image) {
+  WlmImg w;
+  w.lm = lm_open(image, host::kArpaWordImageMagic);
+  const host::ArpaLexHeader* h =
+      reinterpret_cast<const host::ArpaLexHeader*>(static_cast<const char*>(image) + sizeof(host::ArpaImageHeader));
+  const char* base = static_cast<const char*>(image);
+  w.lm.ok = w.lm.ok && h->log2_edges >= 4 && h->log2_edges < 32 && h->n_nodes >= 1;
+  w.edge = reinterpret_cast<const uint4*>(base + (w.lm.ok ? h->edge_off : 0));
+  w.node_word = reinterpret_cast<const int32_t*>(base + (w.lm.ok ? h->node_off : 0));
+  w.emask = w.lm.ok ? (1u << h->log2_edges) - 1u : 0u;
+  w.space = w.lm.ok ? (int)h->space_id : -1;
+  return w;
+}
+
+// the child of `key` = node << 32 | class, or -1; v = the edge slot at `at`, already loaded
+__device__ __forceinline__ int wlm_child_rest(const WlmImg& w, uint64_t key, uint32_t at, uint4 v) {
+  while (true) {
+    const uint64_t k = (uint64_t)v.x | ((uint64_t)v.y << 32);
+    if (k == key) return (int)v.z;
+    if (k == host::kArpaEmptyKey) return -1;
+    at = (at + 1) & w.emask;
+    v = w.edge[at];
+  }
+}
+
+// core.b / core.nb stay ACOUSTIC and core.score is the fused score, as in BeamLmLds
+struct BeamWlmLds {
+  BeamCore core;
+  int surv_n[kBeamMaxWidth];                             // lexicon node of a surviving extension (beside core.surv_i)
+  int lex[2][kBeamMaxWidth], wid[2][kBeamMaxWidth];      // trie node of the unfinished word; the LM word it spells, or -1
+  float bonus[2][kBeamMaxWidth], sterm[2][kBeamMaxWidth];// sum of the terms of the prefix's spaces; the next space's term
+  int ctx[2][kLmMaxCtx][kBeamMaxWidth];                  // LM ids of the last N-1 finished words, nearest first
+  float cb[2][kLmMaxCtx + 1][kBeamMaxWidth];             // cb[j]: log10 backoffs of the stored contexts longer than j words
+  float ascore[kBeamMaxWidth];                           // acoustic logaddexp(b, nb) of the current beam
+  float fin[kBeamMaxWidth], fin_am[kBeamMaxWidth];       // final fused score (end term included); the ranked acoustic scores
+};
+static_assert(sizeof(BeamWlmLds) < 64 * 1024, "static LDS of the word-LM search");
+
+template <int J>
+__global__ __launch_bounds__(kSearchThreads) void beam_search_wlm_kernel(
+    const float* __restrict__ logp, const int32_t* __restrict__ kcls_g, const float* __restrict__ klp_g,
+    const int32_t* __restrict__ kn_g, const int32_t* __restrict__ lens, int64_t T, int C, int blank, int W, int n_best,
+    const void* __restrict__ image, float alpha, float beta, int2* __restrict__ trie_g, int32_t* __restrict__ tokens,
+    int32_t* __restrict__ n_tokens, float* __restrict__ scores, float* __restrict__ am_scores) {
+  __shared__ BeamWlmLds s;
+  BeamCore& core = s.core;
+  const int tid = threadIdx.x;
+  const int64_t ub = blockIdx.x;
+  const WlmImg wl = wlm_open(image);
+  const LmImg& lm = wl.lm;
+  const bool ok = lm.ok && wl.space >= 0 && wl.space < C && wl.space != blank;
+  const int64_t L = !ok ? 0 : lens ? min((int64_t)max(lens[ub], 0), T) : T;
+  const int nctx = lm.nctx, space = wl.space;
+  int2* trie = trie_g + ub * (1 + T * (int64_t)W);
+  BeamFetch pf{kcls_g + ub * T * kBeamMaxTopN, klp_g + ub * T * kBeamMaxTopN, kn_g + ub * T};
+  const float* lrow = logp + ub * T * (int64_t)C;
+  const float cut_beta = fmaxf(0.f, beta);
+  beam_init_root(core, tid);
+  if (tid == 0) {
+    s.bonus[0][0] = 0.f; s.sterm[0][0] = 0.f; s.lex[0][0] = 0; s.wid[0][0] = -1;
+    int rc[kLmMaxCtx];
+    float cb[kLmMaxCtx + 1];
+    for (int d = 0; d < kLmMaxCtx; ++d) rc[d] = lm.bos;
+    if (ok) lm_context_sums(lm, lm.bos, rc, cb);
+    for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[0][d][0] = lm.bos;
+    for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[0][d][0] = ok ? cb[d] : 0.f;
+  }
+  int nbeam = 1, cur = 0;
+  float pblank = 0.f;
+  if (L > 0) {
+    pf.request(0, tid);
+    pblank = lrow[blank];
+  }
+  for (int64_t t = 0; t < L; ++t) {
+    const float lblank = pblank;        // the frame's unpruned blank log-prob (the early cutoff's reference)
+    const int nk = beam_fetch_frame(core, pf, t, L, tid);
+    if (t + 1 < L) pblank = lrow[(t + 1) * (int64_t)C + blank];
+    __syncthreads();
+    // (1) per live prefix: scores, kept index of its last label and of the blank, its parent among the live entries
+    int lastk = -1, pr = -1;
+    float blp = kNegInfB;
+    if (tid < nbeam) {
+      const int last = core.last[cur][tid];
+      const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
+      s.ascore[tid] = as;
+      core.score[tid] = as + s.bonus[cur][tid];
+      beam_lookup(core, cur, nbeam, nk, blank, tid, last, &lastk, &pr, &blp);
+    }
+    __syncthreads();
+    const float min_cutoff = nbeam == W ? core.score[W - 1] + lblank - cut_beta : kNegInfB;
+    // (2) "no new label" candidates (acoustic), with the parent's extension by the last label folded in: a live prefix
+    // came through the lexicon, so that extension exists
+    if (tid < nbeam) {
+      const float asc = s.ascore[tid];
+      float nbn = kNegInfB;
+      if (lastk >= 0) {
+        const float lc = core.klp[lastk];
+        if (!(core.score[tid] + lc < min_cutoff)) nbn = lc + core.nb[cur][tid];
+        if (pr >= 0) {
+          if (!(core.score[pr] + lc < min_cutoff))
+            nbn = lae(nbn, lc + (core.last[cur][tid] == core.last[cur][pr] ? core.b[cur][pr] : s.ascore[pr]));
+          atomicOr(&core.merged[pr], 1ull << lastk);
+        }
+      }
+      core.next_b[tid] = blp + asc;
+      core.next_nb[tid] = nbn;
+    }
+    __syncthreads();
+    // (3) candidates with fused scores; the lexicon probes of kLmGroup extensions per thread are issued together
+    const int ncand = nbeam + nbeam * nk;
+    uint64_t comp[J];
+    int child[J];
+    uint64_t valid = 0;
+#pragma unroll
+    for (int j0 = 0; j0 < J; j0 += kLmGroup) {
+      float sc[kLmGroup];
+      uint64_t key[kLmGroup];
+      uint32_t at[kLmGroup], ck[kLmGroup];
+      uint4 v[kLmGroup];
+      bool probe[kLmGroup];
+#pragma unroll
+      for (int u = 0; u < kLmGroup; ++u) {
+        const int j = j0 + u;
+        sc[u] = kNegInfB; ck[u] = 0; probe[u] = false;
+        if (j >= J) continue;
+        child[j] = -1;
+        const int i = tid + j * kSearchThreads;
+        if (i < nbeam) {
+          sc[u] = lae(core.next_b[i], core.next_nb[i]) + s.bonus[cur][i];
+          ck[u] = (uint32_t)i << 14;
+        } else if (i < ncand) {
+          const int q = i - nbeam, p = q / nk, k = q - p * nk;
+          const int c = core.kcls[k];
+          ck[u] = ((uint32_t)p << 14) | (uint32_t)(c + 1);
+          if (c != blank && !((core.merged[p] >> k) & 1ull) && !(core.score[p] + core.klp[k] < min_cutoff)) {
+            const float am = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
+            if (c == space) {
+              if (s.wid[cur][p] >= 0) {            // the node is a complete word: the space scores it and returns to the root
+                child[j] = 0;
+                sc[u] = am + (s.bonus[cur][p] + s.sterm[cur][p]);
+              }
+            } else if (am > kNegInfB) {
+              sc[u] = am + s.bonus[cur][p];
+              key[u] = ((uint64_t)(uint32_t)s.lex[cur][p] << 32) | (uint32_t)c;
+              at[u] = (uint32_t)lm_hash(key[u]) & wl.emask;
+              v[u] = wl.edge[at[u]];
+              probe[u] = true;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kLmGroup; ++u) {
+        const int j = j0 + u;
+        if (j >= J) continue;
+        if (probe[u]) {
+          child[j] = wlm_child_rest(wl, key[u], at[u], v[u]);
+          if (child[j] < 0) sc[u] = kNegInfB;      // no such word in the lexicon
+        }
+        comp[j] = ((uint64_t)desc_bits(sc[u]) << 32) | ck[u];
+        if (sc[u] > kNegInfB) valid |= 1ull << j;
+      }
+    }
+    // (4) select the W best, (5) compact and order them, write the next beam: the core fields, then the lexicon's and the LM's
+    uint64_t prefix, mask;
+    beam_select<J>(core, comp, valid, W, tid, &prefix, &mask);
+    const int nsel =
+        beam_compact<J>(core, comp, valid, prefix, mask, W, tid, [&](uint32_t pos, int j) { s.surv_n[pos] = child[j]; });
+    const int nxt = cur ^ 1;
+    if (tid < nsel) {
+      const int rank = beam_rank(core, nsel, tid);
+      const int i = core.surv_i[tid];
+      if (i < nbeam) {
+        beam_keep_entry(core, cur, nxt, rank, i);
+        s.lex[nxt][rank] = s.lex[cur][i]; s.wid[nxt][rank] = s.wid[cur][i];
+        s.bonus[nxt][rank] = s.bonus[cur][i]; s.sterm[nxt][rank] = s.sterm[cur][i];
+        for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[nxt][d][rank] = s.ctx[cur][d][i];
+        for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[nxt][d][rank] = s.cb[cur][d][i];
+      } else {
+        const int q = i - nbeam, p = q / nk, k = q - p * nk;
+        const int c = core.kcls[k];
+        beam_new_entry(core, cur, nxt, rank, p, c, t, W, trie);
+        core.nb[nxt][rank] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
+        int nc[kLmMaxCtx];
+        float cb[kLmMaxCtx + 1];
+        if (c == space) {
+          // the word of p's node is finished: it joins the context, the trie state returns to the root
+          const int w = s.wid[cur][p];
+          nc[0] = w;
+          for (int d = 1; d < kLmMaxCtx; ++d) nc[d] = s.ctx[cur][d - 1][p];
+          lm_context_sums(lm, w, nc + 1, cb);
+          for (int d = nctx + 1; d <= kLmMaxCtx; ++d) cb[d] = 0.f;
+          s.lex[nxt][rank] = 0; s.wid[nxt][rank] = -1;
+          s.bonus[nxt][rank] = s.bonus[cur][p] + s.sterm[cur][p]; s.sterm[nxt][rank] = 0.f;
+        } else {
+          const int node = s.surv_n[tid];
+          const int w = wl.node_word[node];
+          for (int d = 0; d < kLmMaxCtx; ++d) nc[d] = s.ctx[cur][d][p];
+          for (int d = 0; d <= kLmMaxCtx; ++d) cb[d] = s.cb[cur][d][p];
+          s.lex[nxt][rank] = node; s.wid[nxt][rank] = w;
+          s.bonus[nxt][rank] = s.bonus[cur][p];
+          s.sterm[nxt][rank] = w >= 0 ? alpha * lm_score_one(lm, w, nc, cb) + beta : 0.f;
+        }
+        for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[nxt][d][rank] = nc[d];
+        for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[nxt][d][rank] = cb[d];
+      }
+    }
+    nbeam = nsel;
+    cur = nxt;
+    __syncthreads();
+  }
+  // end of utterance: an unfinished last word is scored (OOV_SCORE where the node is no complete word), then the final
+  // entries are re-ranked by a counting rank, ties by their order before the term, into the other half of the beam
+  if (tid < nbeam) {
+    const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
+    float f = as + s.bonus[cur][tid];
+    if (core.len[cur][tid] > 0 && core.last[cur][tid] != space)
+      f += s.wid[cur][tid] >= 0 ? s.sterm[cur][tid] : alpha * kLmOov + beta;
+    s.ascore[tid] = as;
+    core.score[tid] = f;
+  }
+  __syncthreads();
+  const int fin = cur ^ 1;
+  if (tid < nbeam) {
+    const float f = core.score[tid];
+    int rank = 0;
+    for (int r = 0; r < nbeam; ++r) {
+      const float g = core.score[r];
+      rank += g > f || (g == f && r < tid);
+    }
+    core.node[fin][rank] = core.node[cur][tid]; core.len[fin][rank] = core.len[cur][tid];
+    s.fin[rank] = f; s.fin_am[rank] = s.ascore[tid];
+  }
+  beam_write_back(core, fin, nbeam, n_best, T, trie, tokens + ub * (int64_t)n_best * T, n_tokens + ub * n_best, ok, tid);
+  if (tid < n_best) {
+    const int64_t o = ub * n_best + tid;
+    const bool have = ok && tid < nbeam;
+    scores[o] = have ? s.fin[tid] : kNegInfB;
+    am_scores[o] = have ? s.fin_am[tid] : kNegInfB;
+  }
+}
+
 struct ArpaHandle {
   host::ArpaModel m;
 };
@@ -966,4 +1225,45 @@ extern "C" int lasr_ctc_beam_decode_lm(const float* logp, const int32_t* lens, i
                        (int)C, blank, beam_width, n_best, lm_image, alpha, beta, trie, tokens, n_tokens, scores, am_scores);
   };
   return beam_launch(a, "beam_search_lm_kernel", search);
+}
+
+extern "C" int lasr_arpa_load_words(const char* path, const char* const* vocab, int n_vocab, int space_id, void** handle) {
+  LASR_CHECK_ARG(path && handle && (vocab || n_vocab == 0) && n_vocab >= 0,
+                 "lasr_arpa_load_words: null pointer or negative n_vocab");
+  *handle = nullptr;
+  ArpaHandle* h = new ArpaHandle();
+  std::string err;
+  const int rc = host::arpa_load_words(path, vocab, n_vocab, space_id, &h->m, &err);   // arpa_io.h, as lasr_arpa_load
+  if (rc != host::kArpaOk) {
+    delete h;
+    return fail(arpa_code(rc), "lasr_arpa_load_words: %s", err.c_str());
+  }
+  *handle = h;
+  return 0;
+}
+
+extern "C" int lasr_arpa_lexicon_info(const void* handle, int64_t* n_lexicon_words, int64_t* n_nodes, int64_t* n_dropped_words) {
+  LASR_CHECK_ARG(handle, "lasr_arpa_lexicon_info: null handle");
+  const host::ArpaModel& m = static_cast<const ArpaHandle*>(handle)->m;
+  LASR_CHECK_ARG(m.word_mode, "lasr_arpa_lexicon_info: the handle is not one of lasr_arpa_load_words");
+  if (n_lexicon_words) *n_lexicon_words = m.n_lexicon_words;
+  if (n_nodes) *n_nodes = m.n_nodes;
+  if (n_dropped_words) *n_dropped_words = m.n_dropped_words;
+  return 0;
+}
+
+extern "C" int lasr_ctc_beam_decode_wlm(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
+                                        int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image,
+                                        float alpha, float beta, int32_t* tokens, int32_t* n_tokens, float* scores,
+                                        float* am_scores, void* workspace, size_t workspace_bytes, void* stream) {
+  const BeamArgs a{"lasr_ctc_beam_decode_wlm", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
+                   workspace_bytes, stream};
+  LASR_TRY(beam_check_args(a, logp && lm_image && tokens && n_tokens && scores && am_scores && workspace));
+  LASR_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "lasr_ctc_beam_decode_wlm: alpha %g / beta %g not finite",
+                 (double)alpha, (double)beta);
+  auto search = [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
+    hipLaunchKernelGGL(beam_search_wlm_kernel<decltype(j)::value>, grid, dim3(kSearchThreads), 0, st, logp, kc, kl, kn, lens, T,
+                       (int)C, blank, beam_width, n_best, lm_image, alpha, beta, trie, tokens, n_tokens, scores, am_scores);
+  };
+  return beam_launch(a, "beam_search_wlm_kernel", search);
 }

@@ -525,16 +525,20 @@ class ArpaNotFoundError(FileNotFoundError, NotImplementedError):
 
 
 class ArpaLm:
-    """A character n-gram LM read from a text ARPA file (load_arpa): the device image lasr_ctc_beam_decode_lm reads, its order and
-    the weights the decoder applies (alpha on the natural-log LM score, beta per emitted label)."""
+    """An n-gram LM read from a text ARPA file (load_arpa): the device image the fused beam search reads, its order and the
+    weights the decoder applies.  Character-based (is_character_based()): lasr_ctc_beam_decode_lm's image, alpha on the
+    natural-log LM score, beta per emitted label.  Word-level: lasr_ctc_beam_decode_wlm's image with the lexicon of the
+    n_lexicon_words words the labels can spell (n_dropped_words could not be), alpha per scored word, beta per word."""
 
-    def __init__(self, image: torch.Tensor, order: int, char_based: bool, n_ngrams: int, vocab, alpha: float, beta: float):
+    def __init__(self, image: torch.Tensor, order: int, char_based: bool, n_ngrams: int, vocab, alpha: float, beta: float,
+                 n_lexicon_words: int = 0, n_dropped_words: int = 0):
         self.image = image
         self.order = int(order)
         self._char_based = bool(char_based)
         self.n_ngrams = int(n_ngrams)
         self.vocab = list(vocab)
         self.alpha, self.beta = float(alpha), float(beta)
+        self.n_lexicon_words, self.n_dropped_words = int(n_lexicon_words), int(n_dropped_words)
 
     def is_character_based(self) -> bool:
         return self._char_based
@@ -546,8 +550,10 @@ class ArpaLm:
 
 def load_arpa(path, vocab, device="cuda", alpha: float = 1.0, beta: float = 1.0) -> ArpaLm:
     """Read a text ARPA LM for the class strings `vocab` (class c is vocab[c]; the blank is not part of it) and copy its image to
-    `device`.  A missing file raises ArpaNotFoundError, one that cannot be read OSError; a word-level LM or a KenLM binary model
-    NotImplementedError; a malformed file, or an order outside 1..6, ValueError naming the line."""
+    `device`.  The mode is the file's: a character-based LM gives lasr_ctc_beam_decode_lm's image; a word-level LM, with a
+    vocabulary that has exactly one " " label, the word image with its lexicon (ArpaLm.is_character_based() is False).  A missing
+    file raises ArpaNotFoundError, one that cannot be read OSError; a KenLM binary model, or a word-level LM with a vocabulary
+    that has no " " label or several, NotImplementedError; a malformed file, or an order outside 1..6, ValueError naming the line."""
     import numpy as np
     path = os.fspath(path)
     if not os.path.isfile(path):
@@ -555,6 +561,22 @@ def load_arpa(path, vocab, device="cuda", alpha: float = 1.0, beta: float = 1.0)
     lib = _lib.load()
     words = [str(w).encode("utf-8") for w in vocab]
     arr = (ctypes.c_char_p * max(len(words), 1))(*words)
+    h = ctypes.c_void_p()
+    spaces = [i for i, w in enumerate(words) if w == b" "]
+    # with one space label the word-level build goes first, so that a (large) word-level file is read once; it declines a
+    # character-based file, and anything else it rejects lasr_arpa_load rejects with its own message
+    if len(spaces) == 1 and lib.lasr_arpa_load_words(os.fsencode(path), ctypes.cast(arr, ctypes.c_void_p), len(words), spaces[0],
+                                                     ctypes.byref(h)) == 0:
+        try:
+            order, cb, n, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_size_t()
+            call("lasr_arpa_info", h, ctypes.byref(order), ctypes.byref(cb), ctypes.byref(n), ctypes.byref(nb))
+            n_lex, n_nodes, n_drop = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+            call("lasr_arpa_lexicon_info", h, ctypes.byref(n_lex), ctypes.byref(n_nodes), ctypes.byref(n_drop))
+            host = np.empty(int(nb.value), dtype=np.uint8)
+            call("lasr_arpa_write_image", h, host.ctypes.data, int(nb.value))
+        finally:
+            lib.lasr_arpa_free(h)
+        return ArpaLm(torch.from_numpy(host).to(device), order.value, False, n.value, vocab, alpha, beta, n_lex.value, n_drop.value)
     h = ctypes.c_void_p()
     rc = lib.lasr_arpa_load(os.fsencode(path), ctypes.cast(arr, ctypes.c_void_p), len(words), ctypes.byref(h))
     if rc != 0:
@@ -569,7 +591,8 @@ def load_arpa(path, vocab, device="cuda", alpha: float = 1.0, beta: float = 1.0)
         call("lasr_arpa_info", h, ctypes.byref(order), ctypes.byref(cb), ctypes.byref(n), ctypes.byref(nb))
         if not cb.value:
             raise NotImplementedError("%s is a word-level LM: only character-based LMs are supported (a word-level LM needs a "
-                                      "space label and a dictionary FST)" % (path,))
+                                      "space label and a dictionary FST): the vocabulary has %d \" \" labels, not one"
+                                      % (path, len(spaces)))
         host = np.empty(int(nb.value), dtype=np.uint8)
         call("lasr_arpa_write_image", h, host.ctypes.data, int(nb.value))
     finally:
@@ -581,10 +604,11 @@ def load_arpa(path, vocab, device="cuda", alpha: float = 1.0, beta: float = 1.0)
 def ctc_beam_decode_lm(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: int, lm: ArpaLm, beam_width: int = 16,
                        cutoff_top_n: int = 40, cutoff_prob: float = 1.0, n_best: int = 1, alpha: Optional[float] = None,
                        beta: Optional[float] = None):
-    """ctc_beam_decode fused with the character n-gram LM `lm` (load_arpa; alpha / beta default to lm's).  Returns (tokens, n_tokens,
-    scores, am_scores): scores are the fused log-scores the hypotheses are ranked by, am_scores ctc_decoders' approx_ctc
-    (fused - labels * beta - alpha * sentence LM score).  Shapes and ranges as ctc_beam_decode; the image must sit on logp's
-    device and hold C - 1 labels."""
+    """ctc_beam_decode fused with the n-gram LM `lm` (load_arpa; alpha / beta default to lm's).  Returns (tokens, n_tokens,
+    scores, am_scores): scores are the fused log-scores the hypotheses are ranked by.  With a character-based LM am_scores are
+    ctc_decoders' approx_ctc (fused - labels * beta - alpha * sentence LM score); with a word-level LM (lasr_ctc_beam_decode_wlm:
+    only words of the LM's lexicon are decoded, each scored at the space after it or at the end of the utterance) they are the
+    acoustic log-scores.  Shapes and ranges as ctc_beam_decode; the image must sit on logp's device and hold C - 1 labels."""
     who = "ctc_beam_decode_lm"
     # lm's type is checked after logp's and before any range, so a bad logp is left to _beam_args' own TypeError
     if not isinstance(lm, ArpaLm) and logp.dtype == torch.float32 and logp.dim() == 3:
@@ -604,7 +628,8 @@ def ctc_beam_decode_lm(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: 
     tokens, n, scores = _beam_outputs(logp, n_best)
     am = torch.empty_like(scores)
     ws = _ws(nb, logp.device)
-    call("lasr_ctc_beam_decode_lm", _p(logp), _p(lens), B, T, Cc, int(blank), int(beam_width), int(cutoff_top_n), float(cutoff_prob),
+    entry = "lasr_ctc_beam_decode_lm" if lm.is_character_based() else "lasr_ctc_beam_decode_wlm"
+    call(entry, _p(logp), _p(lens), B, T, Cc, int(blank), int(beam_width), int(cutoff_top_n), float(cutoff_prob),
          int(n_best), _p(lm.image), alpha, beta, _p(tokens), _p(n), _p(scores), _p(am), _p(ws), nb, _stream())
     return tokens, n, scores, am
 

@@ -1,8 +1,8 @@
 """Inference surface of the reference (predict.py:21-74): checkpoint -> ``AsrTranslator.translate`` and
 manifest evaluation, on the HIP path (mel front-end, eval-mode model forward, greedy CTC decode - or, with
-``decoder="beam"``, the CTC prefix beam search of beam_search.py, fused with a character n-gram LM when ``lm_path`` names
-a text ARPA file).  ``align`` / ``translate_timed`` / ``align_manifest`` add word timings: the CTC forced alignment of a known
-transcript (or of the decoder's own hypothesis) to the audio, ``ops.ctc_align`` + the record functions of align.py.
+``decoder="beam"``, the CTC prefix beam search of beam_search.py, fused with an n-gram LM when ``lm_path`` names a text ARPA
+file: a character LM, or - the labels having exactly one " ", as EN_LABELS has - a word LM with its lexicon).
+``align`` / ``translate_timed`` / ``align_manifest`` add word timings: the CTC forced alignment of a known transcript (or of the decoder's own hypothesis) to the audio, ``ops.ctc_align`` + the record functions of align.py.
 
 The checkpoint is the PL-style dict the reference's ``ModelCheckpoint`` writes and ``Trainer`` here
 writes too: ``state_dict`` with the reference's key names (``encoder.encoder.block1.seq.0...``) and
@@ -36,7 +36,8 @@ class AsrTranslator:
         """model_path: a ``.ckpt`` written by the reference or by ``Trainer``; map_location must name a GPU
         ("cuda" / "cuda:0"): there is no CPU path.  ``labels`` overrides the language's vocabulary.
         decoder: "greedy" (argmax + CTC collapse, the default) or "beam" (CTC prefix beam search; with ``lm_path``, a text ARPA
-        character LM, fused with it: ``alpha`` weighs the LM, ``beta`` is the per-label bonus)."""
+        LM, fused with it: ``alpha`` weighs the LM, ``beta`` is the per-label bonus of a character LM and the per-word bonus
+        of a word LM, under which only the LM's words are decoded)."""
         if decoder not in ("greedy", "beam"):
             raise ValueError("decoder must be 'greedy' or 'beam', got %r" % (decoder,))
         if labels is not None:
