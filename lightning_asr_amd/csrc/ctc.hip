@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void ctc_alpha_beta_mw_kernel(const float* __r
                                                                 float* __restrict__ beta, int32_t* __restrict__ next_same,
                                                                 float* __restrict__ nll) {
   __shared__ int32_t s_tg[kCtcMwMaxS];
-  __shared__ float s_ring[2 * (kCtcMwMaxWaves + 2) * 2];
+  __shared__ float s_ring[kCtcRingFloats];
   __shared__ float s_fin[2];
   extern __shared__ __attribute__((aligned(16))) float s_lp[];
   ctc_alpha_beta_mw_body<EM_LDS, false>(logp, targets, in_lens, tgt_lens, T, C, S_max, blank, alpha, beta, next_same, nll, s_tg, s_lp,
@@ -396,7 +396,7 @@ extern "C" int lasr_ctc_loss(const float* logp, const int64_t* targets, const in
     LASR_LAUNCH_CHECK("ctc_alpha_beta_kernel");
   } else {
     // long labels: one workgroup of geo.nw waves per (utterance, direction); emission rows in LDS beside the 8 KB label table
-    // (C = 28: up to T' = 1386), the register ring of ctc_lattice otherwise
+    // (C = 28: up to T' = 1386), the register ring of ctc_for_each_step otherwise
     const bool mw_lds = ctc_em_in_lds(T, C, kCtcMwMaxS * sizeof(int32_t) + kCtcLdsHeadroom, logp);
     with_bool(mw_lds, [&](auto em) {
       launch_lds(ctc_alpha_beta_mw_kernel<decltype(em)::value>, dim3((unsigned)(2 * B)), dim3((unsigned)(64 * lat.geo.nw)),

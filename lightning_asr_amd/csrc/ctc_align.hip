@@ -1,6 +1,7 @@
 // CTC forced alignment: the max-product (Viterbi) member of the lattice family of ctc_lattice.h, with its backtrace and the
-// per-label spans, in one launch.  The sum-product recursions (ctc_lattice / ctc_lattice_mw) are the training hot path and stay
-// as they are; this file shares their state layout, emission staging and helpers.
+// per-label spans, in one launch.  The walk is the one of the loss's sum-product recursion (ctc_lattice.h: label and emission
+// staging, the state table, the emission stream, the edge exchange); this file keeps the per-state operator (max + backpointer
+// with its tie rule), the packed backpointer table, the backtrace and the span pass.
 //
 // Definition (include/lasr.h, lasr_ctc_align): v[0][s] = logp[0][cls(s)] for s in {0, 1}; v[t][s] = max(stay, step, skip) +
 // logp[t][cls(s)] in f32, one rounding per state per frame; the backpointer is the candidate that attains the max, on equality
@@ -8,7 +9,7 @@
 //
 // One workgroup per utterance.  S_max <= 511: wave 0 holds the 2S+1 states 4 / 8 / 16 per lane and runs the recursion alone,
 // three helper waves take part in the LDS fill and the span pass.  Longer labels: 2..4 waves of 16 states per lane, edge states
-// through the two-slot LDS ring of ctc_lattice_mw (one lds_barrier per step).
+// through the two-slot LDS ring of CtcEdge (one lds_barrier per step).
 // Backpointers: 2 bits per state, so the NS <= 16 states of a lane are ONE dword per lane per frame: a row is 64 dwords per
 // wave (256 B where the loss lattice stores 64 * NS * 4).  The table lives in LDS when it fits beside the emission block and the
 // label table, in the workspace otherwise.
@@ -38,8 +39,8 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float* __restrict_
   constexpr int LOG_NS = NS == 4 ? 2 : (NS == 8 ? 3 : 4);
   constexpr int NWR = MW ? kCtcMwMaxWaves : 1;      // dwords per lane of one backpointer row in the backtrace
   __shared__ int32_t s_tg[kCtcMwMaxS];
-  __shared__ float s_ring[2 * (kCtcMwMaxWaves + 2) * 2];
-  __shared__ float s_fin[2];                         // v[Tb-1][2S-1], v[Tb-1][2S]
+  __shared__ float s_ring[kCtcRingFloats];
+  __shared__ float s_fin[2];
   extern __shared__ __attribute__((aligned(16))) float s_dyn[];
   const int NT = (int)blockDim.x;
   const int NW = MW ? NT >> 6 : 1;
@@ -53,36 +54,17 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float* __restrict_
   const float* lp = logp + (int64_t)b * T * C;
   // dynamic LDS: [emission block (T + 2) x C] [frame states, T] [backpointer table T x RW]
   float* s_lp = s_dyn;
-  int32_t* s_st = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(s_dyn) + (EM_LDS ? (size_t)(T + 2) * C * sizeof(float) : 0));   // = ctc_em_bytes(T, C)
+  int32_t* s_st = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(s_dyn) + (EM_LDS ? ctc_em_bytes(T, C) : 0));
   uint32_t* s_bp = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(s_st) + align_state_bytes(T));
   uint32_t* g_bp = bp_ws + (int64_t)b * T * RW;
 
-  // (labels clamped into the emission row: invalid user data must not become an out-of-bounds device access)
-  for (int i = threadIdx.x; i < S; i += NT) s_tg[i] = (int32_t)min(max(targets[(int64_t)b * S_max + i], (int64_t)0), C - 1);
+  ctc_load_labels(targets + (int64_t)b * S_max, S, C - 1, NT, s_tg);
   for (int i = threadIdx.x; i < (int)S_max; i += NT) {   // spans of labels the path does not open stay -1
     label_start[(int64_t)b * S_max + i] = -1;
     label_end[(int64_t)b * S_max + i] = -1;
   }
-  if (threadIdx.x < 2 * (kCtcMwMaxWaves + 2) * 2) s_ring[threadIdx.x] = kDead;
-  if (threadIdx.x < 2) s_fin[threadIdx.x] = kNegInf;
-  if (EM_LDS && Tb > 0) {
-    // emission rows 0..Tb-1 behind one pad row, 4 x 16-byte loads in flight per thread (as ctc_alpha_beta_body)
-    const int n4 = (int)(((int64_t)Tb * C) >> 2);   // the host checked C % 4 == 0 and the 16-byte alignment of logp
-    const float4* src = reinterpret_cast<const float4*>(lp);
-    float4* dst = reinterpret_cast<float4*>(s_lp + C);
-    for (int i0 = threadIdx.x; i0 < n4; i0 += 4 * NT) {
-      float4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = src[min(i0 + u * NT, n4 - 1)];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (i0 + u * NT < n4) dst[i0 + u * NT] = v[u];
-    }
-    for (int i = threadIdx.x; i < (int)C; i += NT) {   // pad rows (read one step past the end, never used)
-      s_lp[i] = 0.f;
-      s_lp[(int64_t)(Tb + 1) * C + i] = 0.f;
-    }
-  }
+  ctc_edge_init(s_ring, s_fin);                         // s_fin: v[Tb-1][2S-1], v[Tb-1][2S]
+  if (EM_LDS && Tb > 0) ctc_fill_emissions(lp, Tb, C, NT, s_lp);
   __syncthreads();
   if (Tb <= 0) {                                       // workgroup-uniform: no frame, so no path unless there is no label either
     if (threadIdx.x == 0) score[b] = (S == 0) ? 0.f : kNegInf;
@@ -98,103 +80,33 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float* __restrict_
     const int s0 = wv * (64 * NS) + lane * NS;          // this lane's first state
     int cls4[NS];
     bool skip_ok[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-      const int s = s0 + i;
-      int c = blank;
-      bool sk = false;
-      if (s < SS && (s & 1)) {
-        c = s_tg[s >> 1];
-        sk = s >= 3 ? (s_tg[(s >> 1) - 1] != c) : false;   // from s-2 into s: between different labels only
-      }
-      cls4[i] = c * 4;
-      skip_ok[i] = sk;
-    }
-    float a[NS], em[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-      const int s = s0 + i;
-      a[i] = ((s == 0 || s == 1) && s < SS) ? lp[cls4[i] >> 2] : kDead;
-    }
-    constexpr int kRingRow = 2 * (kCtcMwMaxWaves + 2);
-    const int r_in = 2 * wv, r_out = 2 * (wv + 1);       // ring entry 0 is the permanent kDead sentinel below wave 0
-    if (MW) {
-      if (lane == 63) { s_ring[r_out] = a[NS - 2]; s_ring[r_out + 1] = a[NS - 1]; }
-      lds_barrier();
-    }
-    int par = 0;
+    float a[NS];
+    LASR_CTC_LATTICE_STATES(NS, false, false, s_tg, s0, SS, blank, lp, cls4, skip_ok, a)
+    CtcEdge<MW, false> edge(s_ring, wv, lane, a[NS - 2], a[NS - 1]);
     uint32_t* bp = (BP_LDS ? s_bp : g_bp) + wv * 64 + lane;
-    // one step: a[] (t-1) -> a[] (t) with emissions em[]; the lane's NS backpointers leave as one dword
-    auto advance = [&]() {
-      float f1 = kDead, f2 = kDead;
-      if (MW) {
-        const float* rin = s_ring + par * kRingRow + r_in;
-        f2 = rin[0];
-        f1 = rin[1];
-      }
-      const float p1 = wave_shr1(a[NS - 1], f1);         // lane 0: the wave below's top state, then its second from the top
-      const float p2 = wave_shr1(a[NS - 2], f2);
-      float n[NS];
+    // one step: a[] (t-1) -> a[] (t) with emissions em[]; the lane's NS backpointers leave as one dword (with the table in the
+    // workspace that dword is a store like the loss's lattice row)
+    ctc_for_each_step<NS, EM_LDS, false>(lp, s_lp + C, cls4, Tb, (int)C, [&](const float (&em)[NS]) {
+      float n1, n2, n[NS];
+      edge.neighbours(a, n1, n2);
       uint32_t word = 0;
 #pragma unroll
       for (int i = 0; i < NS; ++i) {
-        const float s1 = i >= 1 ? a[i - 1] : p1;
-        const float s2v = (i == 0) ? p2 : (i == 1 ? p1 : a[i - 2]);
-        // even states are blanks (NS is even, so the parity of s is the parity of i): no skip into them
-        const float m = (i & 1) ? v_max3(a[i], s1, skip_ok[i] ? s2v : kDead) : v_max2(a[i], s1);
+        float s1, s2;
+        ctc_adjacent<NS, false>(a, n1, n2, i, s1, s2);
+        // even states are blanks: no skip into them
+        const float m = (i & 1) ? v_max3(a[i], s1, skip_ok[i] ? s2 : kDead) : v_max2(a[i], s1);
         const uint32_t back = (a[i] == m) ? 0u : ((s1 == m) ? 1u : 2u);   // stay, then step, then skip
         word |= back << (2 * i);
         n[i] = m + em[i];
       }
-      if (MW) {
-        par ^= 1;
-        float* rout = s_ring + par * kRingRow + r_out;
-        if (lane == 63) { rout[0] = n[NS - 2]; rout[1] = n[NS - 1]; }
-      }
+      edge.publish(n[NS - 2], n[NS - 1]);
       bp += RW;
       *bp = word;
 #pragma unroll
       for (int i = 0; i < NS; ++i) a[i] = n[i];
-      if (MW) lds_barrier();
-    };
-    if (EM_LDS) {
-      const char* row = reinterpret_cast<const char*>(s_lp + C) + (int64_t)C * 4;   // row 1
-      const int drow = (int)C * 4;
-      float nx[NS];
-#pragma unroll
-      for (int i = 0; i < NS; ++i) nx[i] = *reinterpret_cast<const float*>(row + cls4[i]);
-      for (int step = 1; step < Tb; ++step) {
-#pragma unroll
-        for (int i = 0; i < NS; ++i) em[i] = nx[i];
-        row += drow;                                   // next step's emissions before this step's arithmetic (the last: the pad row)
-#pragma unroll
-        for (int i = 0; i < NS; ++i) nx[i] = *reinterpret_cast<const float*>(row + cls4[i]);
-        advance();
-      }
-    } else {
-      // register ring of emissions kPre steps ahead (ctc_lattice): vmcnt counts stores in issue order on this part, and with the
-      // table in the workspace the backpointer dwords are stores
-      constexpr int kPre = 8;
-      float ring[kPre][NS];
-#pragma unroll
-      for (int u = 0; u < kPre; ++u)
-#pragma unroll
-        for (int i = 0; i < NS; ++i) ring[u][i] = (1 + u < Tb) ? lp[(int64_t)(1 + u) * C + (cls4[i] >> 2)] : 0.f;
-      for (int step0 = 1; step0 < Tb; step0 += kPre) {
-#pragma unroll
-        for (int u = 0; u < kPre; ++u) {
-          const int t = step0 + u;
-          if (t < Tb) {  // workgroup-uniform
-#pragma unroll
-            for (int i = 0; i < NS; ++i) em[i] = ring[u][i];
-            const int tq = min(t + kPre, Tb - 1);       // unconditional refill from a clamped row (no load inside a branch)
-#pragma unroll
-            for (int i = 0; i < NS; ++i) ring[u][i] = lp[(int64_t)tq * C + (cls4[i] >> 2)];
-            advance();
-          }
-        }
-      }
-    }
+      edge.barrier();
+    });
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
       const int s = s0 + i;

@@ -419,7 +419,7 @@ __global__ __launch_bounds__(256) void ctc_alpha_beta_compact_mw_kernel(const fl
                                                                         float* __restrict__ beta, int32_t* __restrict__ next_same,
                                                                         float* __restrict__ nll) {
   __shared__ int32_t s_tg[kCtcMwMaxS];
-  __shared__ float s_ring[2 * (kCtcMwMaxWaves + 2) * 2];
+  __shared__ float s_ring[kCtcRingFloats];
   __shared__ float s_fin[2];
   ctc_alpha_beta_mw_body<false, true>(E, targets, in_lens, tgt_lens, T, CE, S_max, blank_col, alpha, beta, next_same, nll, s_tg, nullptr,
                                     s_ring, s_fin);
