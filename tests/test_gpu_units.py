@@ -26,11 +26,13 @@ is there for).  All edge cases use formula weights (BN beta != 0, see the test).
 | SE fold time lanes | ts = min(256 / ((C/64) B), 4), 1 when (C/64) B >= 256 (csrc/se.hip:345) | ts = 3 (T' = 101 frames split 33/34/34): se_lanes_ts3_B20_t101 / ts = 4: b1_t17_context_se_bf16_se_lanes_4, ts = 1: se_bwd_B40_t101 |
 | SE backward with more than 32 utterances (utterance groups of the staging, csrc/se.hip:638) | B > 32 | se_bwd_B40_t101 / se_lanes_ts3_B20_t101, b1_t17_context_se_bf16_se_lanes_4 |
 | BiLSTM over packed lengths, reverse direction from len-1 | per-utterance len (csrc/lstm_body.h:87) | lengths 1, 2, 3 and one utterance: ragged_masked_1_2_3_of_17_context_bf16, ragged_masked_1_2_3_of_17_context_se_f32, b1_t17_context_f32 / full lengths: b1_t17_context_bf16 |
+| BiLSTM backward recurrence inside the weight-gradient grid (bilstm_bwd_body<T, PADDED = true>: 192-thread slots, clamped lanes, bf16 dg copy, bias partials) | bf16, context variant, B % 8 == 0, B <= 128, every collected problem K = B T' >= 1024 with M, N multiples of 8, the first problem's tiles fit beside the 2 B recurrence workgroups (csrc/gemm.hip gemm_multi_split_partials_with_bilstm_bwd, its caller in csrc/model.hip) | in the grid, masked lengths 201, 1, 2, 7, 8, 9, 16, 17: lstm_in_wgrad_grid_short_lens_B8_t201_context_bf16, lengths 91 .. 101: se_bwd_B40_t101 / separate launch: se_lanes_ts3_B20_t101 (B % 8), ragged_masked_1_2_3_of_17_context_bf16, b1_t17_context_bf16 |
 | Masked BN statistics / MaskCNN | lens = int(T' pct) in f32 (csrc/norm.hip:46) | 1, 2, 3 of 17 frames: ragged_masked_1_2_3_of_17_context_bf16, ragged_masked_1_2_3_of_17_context_se_f32 / unmasked: b1_t17_plain_f32 |
 | Lean CTC head | bf16 and 256 <= C <= 9216 and no f32 log-probs requested (csrc/model.hip:226) | vocab4334_lean_head_B3_t17 / vocab4334_dense_head_B3_t17 |
 
 Every edge case also runs loss_backward on the same inputs: the per-unit path has to be the training path (see
-_training_path_parity for what may differ and why).  Measured: profiles/r06_unit_parity_edge.json.
+_training_path_parity for what may differ and why).  Measured: profiles/r06_unit_parity_edge.json; the short-length in-grid BiLSTM
+case: profiles/unit_parity_edge_lstm_in_wgrad_grid_short_lens.json.
 """
 import json
 import os
@@ -476,6 +478,35 @@ def _branches(variant, dtype, B, T_in, n_class, lean):
     out["dw_s2_64_frame_tiles"] = _cdiv(T, 128) * B < 200        # first_cnn: 64 channels, stride 2
     out["se_bwd_B_gt_32"] = se and bf16 and B > 32
     out["lean_head"] = bool(lean and bf16 and 256 <= n_class <= 9216)
+    # The BiLSTM backward recurrence inside the weight-gradient grid (csrc/model.hip backward_from_glogits -> csrc/gemm.hip
+    # gemm_multi_split_partials_with_bilstm_bwd).  Collected when the backward reaches block3: last_cnn2, then every block down to
+    # block3 (main + residual 1x1), M = co, N = ci, K = B T'.  The launch takes the leading problems whose 256 x 256 tiles fit the
+    # budget beside the 2 B recurrence workgroups; at least one has to.
+    # A hand mirror, like the other keys: it states which side the plan takes at this shape, it does not observe the launch.  It
+    # assumes the library's defaults - LASR_WGRAD_SPLIT (16: the cap of `want`), LASR_LSTM_BESIDE_WGRAD, LASR_LSTM_PAIR (2 B
+    # workgroups, not B), LASR_LSTM_WGRAD_BUDGET, LASR_WGRAD_SMALL_TILE, LASR_NO_DEFER and LASR_NO_FUSE unset; any of them turns
+    # the recurrence back into its own launch or changes the budget.  0.36 us per step, 1.7 us per 64 rows of K and 15 us are the
+    # constants of csrc/gemm.hip.
+    beside = variant != "plain" and bf16 and B % 8 == 0 and B <= 128
+    if beside:
+        blocks = R.block_table(variant)
+        i3 = [n_ for n_, _ci, _co, _k in blocks].index("block3")
+        probs = [(1024, 512)] + [(co, ci) for _n, ci, co, _k in reversed(blocks[i3:]) for _ in (0, 1)]
+        beside = len(probs) <= 32 and M >= 1024 and all(m_ % 8 == 0 and n_ % 8 == 0 for m_, n_ in probs)
+    if beside:
+        want = 1                     # slices per tile so that the tiles are through when the recurrences are (0.36 us per step)
+        while want < 16 and _cdiv(_cdiv(M, want), 64) * 1.7 + 15.0 > 0.36 * T:
+            want += 1
+        budget = max((256 - 2 * B) // want, 1)
+        tiles = take = 0
+        for m_, n_ in probs:
+            t_ = _cdiv(m_, 256) * _cdiv(n_, 256)
+            if tiles + t_ > budget:
+                break
+            tiles += t_
+            take += 1
+        beside = take >= 1 and tiles + 2 * B <= 256
+    out["lstm_beside_wgrad"] = beside
     return out
 
 
@@ -499,6 +530,10 @@ def _edge_batch(B, L, sample_lens, V, S, seed):
 # (variant, dtype, B, L samples, sample lengths | None, classes, lean, act, the branches the case is there for)
 _L17, _L101, _L501 = 5100, 31936, 160000           # T_in = 33, 201, 1001 mel frames -> T' = 17, 101, 501
 _LENS_123 = [_L17, 200, 500, 800, 3000, 4000]     # 2, 4, 6 mel frames of 33 -> int(17 * pct) = 1, 2, 3 masked frames
+_L201 = 63936                                     # T_in = 401 mel frames -> T' = 201: B T' = 1608 >= 1024 at B = 8
+# an utterance of 2n mel frames ((2n - 1) * 160 + 40 samples) masks to int(201 * f32(2n / 401)) = n frames
+_SHORT_N = [1, 2, 7, 8, 9, 16, 17]
+_LENS_SHORT = [_L201] + [(2 * n - 1) * 160 + 40 for n in _SHORT_N]
 EDGE_CASES = [
     pytest.param("plain", torch.float32, 1, _L17, None, 28, False, "relu", {"dw_s2_64_frame_tiles": True}, id="b1_t17_plain_f32"),
     pytest.param("context", torch.float32, 1, _L17, None, 28, False, "relu", {"dw_s2_64_frame_tiles": True}, id="b1_t17_context_f32"),
@@ -508,18 +543,25 @@ EDGE_CASES = [
                  id="b1_t17_plain_bf16_dw_no_bn_fuse"),
     pytest.param("plain", torch.bfloat16, 1, _L17, None, 28, False, "swish", {"gemm_big": [False], "dw_bn_fused": [False]},
                  id="b1_t17_plain_bf16_swish"),
-    pytest.param("context", torch.bfloat16, 1, _L17, None, 28, False, "relu", {"dw_bn_fused": [False]}, id="b1_t17_context_bf16"),
+    pytest.param("context", torch.bfloat16, 1, _L17, None, 28, False, "relu", {"dw_bn_fused": [False], "lstm_beside_wgrad": False},
+                 id="b1_t17_context_bf16"),
     pytest.param("context_se", torch.bfloat16, 1, _L17, None, 28, False, "relu", {"se_ts": [4], "se_bwd_B_gt_32": False},
                  id="b1_t17_context_se_bf16_se_lanes_4"),
-    pytest.param("context", torch.bfloat16, 6, _L17, _LENS_123, 28, False, "relu", {"dw_bn_fused": [False]},
+    pytest.param("context", torch.bfloat16, 6, _L17, _LENS_123, 28, False, "relu", {"dw_bn_fused": [False], "lstm_beside_wgrad": False},
                  id="ragged_masked_1_2_3_of_17_context_bf16"),
     pytest.param("context_se", torch.float32, 6, _L17, _LENS_123, 28, False, "relu", {}, id="ragged_masked_1_2_3_of_17_context_se_f32"),
     pytest.param("plain", torch.bfloat16, 16, _L501, None, 28, False, "relu", {"gemm_big": [False, True], "dw_bn_fused": [True]},
                  id="gemm_mixed_big_small_B16_bn_fused_dw512"),
-    pytest.param("context_se", torch.bfloat16, 20, _L101, "ragged", 28, False, "relu", {"se_ts": [1, 3], "se_bwd_B_gt_32": False},
+    pytest.param("context_se", torch.bfloat16, 20, _L101, "ragged", 28, False, "relu", {"se_ts": [1, 3], "se_bwd_B_gt_32": False,
+                                                                                         "lstm_beside_wgrad": False},
                  id="se_lanes_ts3_B20_t101"),
-    pytest.param("context_se", torch.bfloat16, 40, _L101, "ragged", 28, False, "relu", {"se_ts": [1], "se_bwd_B_gt_32": True},
+    pytest.param("context_se", torch.bfloat16, 40, _L101, "ragged", 28, False, "relu", {"se_ts": [1], "se_bwd_B_gt_32": True,
+                                                                                         "lstm_beside_wgrad": True},
                  id="se_bwd_B40_t101"),
+    # seven of the eight utterances are short on purpose: a wrong short recurrence in the in-grid body moves the LSTM parameter
+    # gradients by percent, far above the 1e-3 gate (the long utterance is there for B T' >= 1024)
+    pytest.param("context", torch.bfloat16, 8, _L201, _LENS_SHORT, 28, False, "relu", {"lstm_beside_wgrad": True},
+                 id="lstm_in_wgrad_grid_short_lens_B8_t201_context_bf16"),
     pytest.param("plain", torch.bfloat16, 200, _L17, None, 28, False, "relu", {"dw_s2_64_frame_tiles": False, "dw_bn_fused": [False]},
                  id="dw_s2_128_frame_tiles_B200_t17"),
     pytest.param("plain", torch.bfloat16, 3, _L17, [_L17, 3500, 2000], 4334, False, "relu", {"lean_head": False},
@@ -591,6 +633,8 @@ def test_units_edge_shapes(dev, variant, dtype, B, L, sample_lens, n_class, lean
         assert lens[1:4].tolist() == [1, 2, 3] and int(lens[0]) == T == 17, lens
     if "ts3" in tag:
         assert T % 3 != 0
+    if "short_lens" in tag:
+        assert lens.tolist() == [201] + _SHORT_N and T == 201, lens
     # The one gate widened at an edge shape: the END-TO-END loss of one bf16 utterance of 17 frames with the BiLSTM, measured 1.355e-3
     # (39.3888 on the GPU against 39.4422 from the emulated oracle's own whole forward) while every unit of the same step stays
     # inside its per-unit gate.  The whole-step bf16 map is chaotic (module docstring); 1e-3 was set at B = 32, where the loss is a
