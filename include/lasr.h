@@ -25,12 +25,13 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 106   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 107   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
                               105: lasr_ctc_align_workspace_bytes / lasr_ctc_align (CTC forced alignment)
-                              106: lasr_arpa_load_words / lasr_arpa_lexicon_info / lasr_ctc_beam_decode_wlm (word-level LM) */
+                              106: lasr_arpa_load_words / lasr_arpa_lexicon_info / lasr_ctc_beam_decode_wlm (word-level LM)
+                              107: lasr_resample_* (sample-rate conversion, speed perturbation) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -701,6 +702,48 @@ int lasr_wav_info(const char* path, int64_t* n_frames, int32_t* n_channels, int3
  *   lens_out entry carries LASR_LEN_LEAD (see above: the reference crops AFTER pre-emphasis); the pitch counts the lead-in. */
 int lasr_wav_read_batch(const char* const* paths, int64_t n, const double* crop_u, double crop_weight, int16_t* out,
                         int64_t out_capacity, int64_t* ld_out, int32_t* lens_out, int32_t expect_rate, int n_threads, int lead_in);
+
+/* ---- sample-rate conversion: any-rate audio in, speed perturbation in training ---------------------------------------------
+ * The reference feeds whatever rate torchaudio.load returns into a 16 kHz front-end (data_module.py:153 drops the rate); this is
+ * the operator that was missing there: a polyphase Hann-windowed-sinc resampler (the interpolation torchaudio documents for
+ * `resample` with its defaults, restated in DESIGN.md "Resampling"; torchaudio is not part of this project).
+ * A conversion (sr_in, sr_out):  g = gcd; down = sr_in / g; up = sr_out / g; base = min(up, down) * rolloff;
+ *   width = ceil(lpw * down / base); taps = 2 * width + down;
+ *   h[p][k] = (base / down) * sinc(t) * cos(pi t / (2 lpw))^2,  t = clamp(((k - width) / down - p / up) * base, -lpw, lpw);
+ *   n_out = ceil(n_in * up / down);  out[j] = sum_k h[j % up][k] * x[(j / up) * down + k - width],  x = 0 outside [0, n_in).
+ * up == down == 1 is NOT run through the filter (which is no identity there): such a row is a plain copy.
+ * Speed perturbation by s = a / b is the conversion (a, b): the clip becomes b / a as long, pitch moves with tempo (sox `speed`).
+ *
+ * The bank: up to 8 conversions as one position-independent image - a header table (up, down, width, taps, offset and the
+ * kernel's tiling per conversion) followed by the taps, computed in f64, rounded once to f32, stored [tap][phase].  Built on the
+ * host (lightning_asr_amd/csrc/resample.h), uploaded by the caller, read-only afterwards.  lpw = 6 and rolloff = 0.99 are the
+ * defaults of the definition above.  LASR_E_ARG (lasr_resample_bank_bytes: 0) for a null list, n_conv outside [1, 8], a
+ * non-positive rate, up or down above 1024, up * taps above 2^20, rolloff outside (0, 1], lpw outside [1, 64], a destination
+ * smaller than the image.  No device work.
+ * lasr_resample_out_len: ceil(n_in * up / down) for up, down in [1, 1024], n_in >= 0; -1 otherwise.
+ * lasr_resample_tile: the outputs one workgroup of lasr_resample produces for the (reduced) conversion up / down - where its tests
+ * put their row lengths; -1 for arguments no bank takes. */
+size_t lasr_resample_bank_bytes(const int32_t* sr_in, const int32_t* sr_out, int n_conv, int lpw, double rolloff);
+int lasr_resample_bank_write(const int32_t* sr_in, const int32_t* sr_out, int n_conv, int lpw, double rolloff, void* host_dst,
+                             size_t bytes);
+int64_t lasr_resample_out_len(int64_t n_in, int64_t up, int64_t down);
+int64_t lasr_resample_tile(int64_t up, int64_t down, int lpw, double rolloff);
+/* B rows in one launch on `stream`; nothing is allocated or synchronised, so the call can be captured.
+ * bank_dev: a device copy of the image.  in: B rows of in_pitch elements, LASR_WAVE_F32 or LASR_WAVE_PCM16 (scaled by 1/32768,
+ * exact); in_lens (B) int32 valid samples per row (required; clamped to in_pitch); conv_id (B) int32 = the row's conversion, NULL =
+ * conversion 0 for every row.  out: B rows of out_pitch elements, f32 or PCM16 = clamp(rint(acc * 32768), -32768, 32767)
+ * (saturating); f32 accumulation.  out_lens[b] = n_out; samples [n_out, L_out) of a row are written as zero, elements
+ * [L_out, out_pitch) are not touched.  L_out must hold the longest row's n_out (a longer row is cut at L_out, out_lens says so).
+ * An identity row (up == down == 1) is copied bit for bit when the dtypes agree, otherwise only the scale (and the rounding) apply;
+ * its in_lens word passes through to out_lens, LASR_LEN_LEAD and the lead-in sample included.  On every other row a word carrying
+ * LASR_LEN_LEAD is a CALLER ERROR (a filtered row has no lead-in sample: the flag is dropped and the lead-in sample is filtered as
+ * the row's first sample).  A conv_id outside the bank, a bank without lasr_resample_bank_write's magic and count, or an entry whose
+ * factors and tiling are outside the builder's limits gives a row of zeros with out_lens 0 (the taps themselves and the image's size
+ * are the caller's: the call cannot know how long bank_dev is).  LASR_E_ARG: null pointer, unknown dtype, negative size, out_pitch < L_out; LASR_E_SHAPE: B > 65535, rows of
+ * 2^31 samples or more. */
+int lasr_resample(const void* bank_dev, const void* in, int in_dtype, int64_t in_pitch, const int32_t* in_lens,
+                  const int32_t* conv_id, void* out, int out_dtype, int64_t out_pitch, int64_t L_out, int32_t* out_lens, int64_t B,
+                  void* stream);
 
 /* ---- data-parallel gradient exchange: RCCL over xGMI, called by the library itself ------------------------------
  * Replaces the NCCL all-reduce the reference gets from Lightning's DDP plugin (conf/conf.yaml:30-31 `accelerator: ddp`,

@@ -157,6 +157,11 @@ SIGNATURES = {
     "lasr_step_metrics": (_i32, [_p, _p, _p, _i64, _p, _p]),
     "lasr_wav_info": (_i32, [C.c_char_p, C.POINTER(_i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lasr_wav_read_batch": (_i32, [_p, _i64, _p, C.c_double, _p, _i64, C.POINTER(_i64), _p, C.c_int32, _i32, _i32]),
+    "lasr_resample_bank_bytes": (_sz, [_p, _p, _i32, _i32, C.c_double]),
+    "lasr_resample_bank_write": (_i32, [_p, _p, _i32, _i32, C.c_double, _p, _sz]),
+    "lasr_resample_out_len": (_i64, [_i64, _i64, _i64]),
+    "lasr_resample_tile": (_i64, [_i64, _i64, _i32, C.c_double]),
+    "lasr_resample": (_i32, [_p, _p, _i32, _i64, _p, _p, _p, _i32, _i64, _i64, _p, _i64, _p]),
     "lasr_comm_timing": (_i32, [_p, _i32]),
     "lasr_comm_timing_collect": (_i32, [_p, _i32, _p, _p, C.POINTER(_i32), _p, C.POINTER(_i32)]),
     "lasr_comm_unique_id": (_i32, [_p, _sz]),

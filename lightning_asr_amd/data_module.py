@@ -13,6 +13,7 @@ import logging
 import os
 import random
 import wave as _wave
+from fractions import Fraction
 from typing import List, Optional, Sequence, Union
 
 import numpy as np
@@ -23,15 +24,15 @@ from . import _lib, ops
 from .lightning_compat import LightningDataModule
 
 
-def load_wav(path_or_file) -> torch.Tensor:
-    """16-bit PCM wav -> (1, L) f32 in [-1, 1) (what torchaudio.load returns, data_module.py:153)."""
+def load_wav_rate(path_or_file):
+    """16-bit PCM wav -> ((1, L) f32 in [-1, 1), sample rate of the file): what torchaudio.load returns (data_module.py:153)."""
     try:
         with _wave.open(path_or_file, "rb") as w:
             if w.getsampwidth() != 2:
                 raise ValueError("only 16-bit PCM wav is supported")
-            n, ch = w.getnframes(), w.getnchannels()
+            n, ch, rate = w.getnframes(), w.getnchannels(), w.getframerate()
             pcm = np.frombuffer(w.readframes(n), dtype="<i2").reshape(-1, ch).T
-        return torch.from_numpy(pcm[:1].astype(np.float32) / 32768.0)
+        return torch.from_numpy(pcm[:1].astype(np.float32) / 32768.0), int(rate)
     except (ValueError, _wave.Error, EOFError) as e:
         # flac / 24-bit / float wav (LibriSpeech's native format): the site's `soundfile`, if it has one (the reference's own
         # requirements list it next to torchaudio; not installed in this image).  No torchaudio anywhere in this package.
@@ -42,10 +43,45 @@ def load_wav(path_or_file) -> torch.Tensor:
         except ImportError:
             raise ValueError("%s: %s (not a 16-bit PCM wav, and no `soundfile` module to decode other formats)" % (path_or_file, e)) from e
         try:
-            data, _sr = sf.read(path_or_file, dtype="float32", always_2d=True)
+            data, sr = sf.read(path_or_file, dtype="float32", always_2d=True)
         except Exception as e2:                          # soundfile raises RuntimeError / LibsndfileError for what it cannot read
             raise ValueError("%s: neither the wave reader (%s) nor soundfile (%s) can decode it" % (path_or_file, e, e2)) from e2
-        return torch.from_numpy(np.ascontiguousarray(data.T[:1]))
+        return torch.from_numpy(np.ascontiguousarray(data.T[:1])), int(sr)
+
+
+def load_wav(path_or_file) -> torch.Tensor:
+    """16-bit PCM wav -> (1, L) f32 in [-1, 1) (what torchaudio.load returns, data_module.py:153); the file's rate is dropped, as
+    the reference drops it - ``load_wav_rate`` keeps it."""
+    return load_wav_rate(path_or_file)[0]
+
+
+SPEED_MAX_TERM = 100          # numerator and denominator of a speed factor: "a ratio of small integers"
+
+
+def parse_speed_factors(factors) -> List[Fraction]:
+    """conf key ``data.speed_perturb`` -> exact ratios.  None / [] = off.  Each factor is read as ``Fraction(str(f))`` (0.9 ->
+    9/10, "3/4" -> 3/4), must lie in [0.5, 2] and reduce to integers of at most 100; at most 8 of them (one filter bank).  Anything
+    else is a ValueError.  Speed s = a/b is the rate conversion (a, b): the clip becomes b/a as long (DESIGN.md "Resampling")."""
+    if factors is None:
+        return []
+    if isinstance(factors, (str, bytes)) or not hasattr(factors, "__iter__"):
+        raise ValueError("data.speed_perturb must be a list of factors, got %r" % (factors,))
+    out = []
+    for f in factors:
+        if isinstance(f, bool) or not isinstance(f, (int, float, str, Fraction)):
+            raise ValueError("data.speed_perturb: %r is not a number" % (f,))
+        try:
+            fr = Fraction(str(f))
+        except (ValueError, ZeroDivisionError) as e:
+            raise ValueError("data.speed_perturb: %r is not a ratio of integers" % (f,)) from e
+        if not (Fraction(1, 2) <= fr <= 2):
+            raise ValueError("data.speed_perturb: factor %s is outside [0.5, 2]" % (f,))
+        if fr.numerator > SPEED_MAX_TERM or fr.denominator > SPEED_MAX_TERM:
+            raise ValueError("data.speed_perturb: factor %s = %s is not a ratio of small integers (<= %d)" % (f, fr, SPEED_MAX_TERM))
+        out.append(fr)
+    if len(out) > 8:
+        raise ValueError("data.speed_perturb: at most 8 factors (one filter bank), got %d" % len(out))
+    return out
 
 
 class AudioParser:
@@ -58,6 +94,8 @@ class AudioParser:
         self.hop_length = int(win_len * sr) // 2          # hop of the mel front-end in samples (data_module.py:66-67)
         self.rand = random.Random()
         self.device = torch.device(device)
+        self.speed_factors: List[Fraction] = []           # speed perturbation (LibriDataModule(speed_perturb=...)); [] = off
+        self._speed_rs = None
 
     # -- the two random pieces of the training-time chain, drawn on the host like the reference ----
     def sub_secquence(self, x: torch.Tensor, weight: float = 0.1) -> torch.Tensor:
@@ -67,16 +105,33 @@ class AudioParser:
         location = int(np.random.uniform(0, length - target_length))
         return x[:, location:target_length]
 
-    def crop_raw(self, x: torch.Tensor, weight: float = 0.98):
+    def crop_raw(self, x: torch.Tensor, weight: float = 0.98, lead_in: bool = True):
         """The same two draws applied to the RAW waveform, for the device chain: the reference dithers and pre-emphasises the
         whole clip and slices afterwards (:155-159), so the crop's first sample is ``y[loc] - 0.97 y[loc-1]``.  Returns
         (row, lead): ``row`` = the slice with the sample before it in front when ``loc > 0`` (lead = 1, ``_lib.LEN_LEAD`` in the
-        length word handed to the mel kernel), which then produces exactly the reference's values."""
+        length word handed to the mel kernel), which then produces exactly the reference's values.
+        lead_in=False (speed perturbation: the crop is resampled before the mel kernel sees it, and a resampled row has no
+        sample "before" it): the bare slice, lead = 0 - its first sample is pre-emphasised as a file's first sample is."""
         length = x.shape[1]
         target_length = int(length * np.random.uniform(weight, 1))
         location = int(np.random.uniform(0, length - target_length))
-        lead = 1 if (location > 0 and target_length > location) else 0
+        lead = 1 if (lead_in and location > 0 and target_length > location) else 0
         return x[:, location - lead:target_length], lead
+
+    # -- speed perturbation (Ko et al. 2015): factor s = a/b is the rate conversion (a, b), the clip becomes b/a as long ----------
+    def draw_speed(self) -> int:
+        """index of one utterance's factor in ``speed_factors``: drawn after the crop's draws, before the SpecAugment rectangle"""
+        return self.rand.randrange(len(self.speed_factors))
+
+    def speed_out_len(self, n: int, k: int) -> int:
+        f = self.speed_factors[k]
+        return -((-int(n) * f.denominator) // f.numerator)
+
+    def speed_resampler(self):
+        """the filter bank of ``speed_factors`` on the parser's device, built on first use"""
+        if self._speed_rs is None:
+            self._speed_rs = ops.Resampler([(f.numerator, f.denominator) for f in self.speed_factors], self.device)
+        return self._speed_rs
 
     def draw_spec_augment(self, n_time: int, freq_mask: Union[int, float] = 27, time_mask: Union[int, float] = 0.07):
         """(rect_x, w_x, rect_y, w_y) with the draw order of spec_augment (:97-122)."""
@@ -112,14 +167,34 @@ class AudioParser:
                  torch.cuda.current_stream(self.device).cuda_stream)
         return out.to(x.device)
 
-    def parse_audio(self, audio_path, mask=False) -> torch.Tensor:
+    def resample_to_sr(self, y: torch.Tensor, rate: int) -> torch.Tensor:
+        """(1, L) f32 host wave at `rate` -> (1, n_out) f32 at the parser's rate, converted on the device (``ops.resample``,
+        DESIGN.md "Resampling"); a wave already at that rate is returned as it is"""
+        if int(rate) == self.sr:
+            return y
+        return ops.resample(y[0].to(self.device), int(rate), self.sr)[0].unsqueeze(0)
+
+    def parse_audio(self, audio_path, mask=False, resample=False) -> torch.Tensor:
+        """resample=True: a file whose sample rate is not 16000 is converted to it on the device before the feature chain;
+        resample=False (the default, and the reference's behaviour) feeds the samples as they are, whatever the file's rate."""
         if isinstance(audio_path, str) and not os.path.exists(path=audio_path):
             raise Exception("音频路径不存在 " + audio_path)
-        y = load_wav(audio_path)
+        if resample:
+            y = self.resample_to_sr(*load_wav_rate(audio_path))
+        else:
+            y = load_wav(audio_path)
         lead = 0
         if mask:
             y, lead = self.crop_raw(y, weight=0.98)
-        return self.features([y[0]], mask, leads=[lead])[0]
+        return self.features_one(y, mask, lead)[0]
+
+    def features_one(self, y: torch.Tensor, mask: bool = False, lead: int = 0):
+        """``features([y[0]], mask, leads=[lead])`` for one (1, L) wave; a wave that already sits on the device (a resampled file)
+        stays there: the same mel call on the same row, without the trip through the pinned staging buffer"""
+        if not y.is_cuda or mask or lead or y.shape[1] == 0:
+            return self.features([y[0]], mask, leads=[lead])
+        lens = torch.full((1,), y.shape[1], dtype=torch.int32, device=y.device)
+        return self.features_device(y.contiguous(), lens, None, True, logical_len=y.shape[1])
 
     # ---- the batched device front-end ---------------------------------------------------------------------------------------
     def device_dither(self):
@@ -156,9 +231,12 @@ class AudioParser:
             st["buf"][k] = torch.empty(int(n * 1.25) + 1024, dtype=torch.float32).pin_memory()
         return st["buf"][k][:n]
 
-    def features(self, waves: Sequence[torch.Tensor], mask: bool, dither: bool = True, leads: Optional[Sequence[int]] = None):
+    def features(self, waves: Sequence[torch.Tensor], mask: bool, dither: bool = True, leads: Optional[Sequence[int]] = None,
+                 speed: Optional[Sequence[int]] = None):
         """list of (L_i,) f32 host waves -> (inputs, input_percentages) on the GPU: padded into a reused pinned buffer, ONE H2D
-        copy for the batch, then ``features_device``.  leads[i] = 1: waves[i] starts with a lead-in sample (``crop_raw``)."""
+        copy for the batch, then ``features_device``.  leads[i] = 1: waves[i] starts with a lead-in sample (``crop_raw``).
+        speed[i]: index into ``speed_factors`` - the uploaded batch is resampled on the device (f32 -> f32) first, and the
+        SpecAugment rectangles are drawn for the resampled lengths; such waves carry no lead-in sample."""
         B = len(waves)
         L = max(int(w.numel()) for w in waves)
         host = self._staging(B * L).view(B, L)
@@ -175,6 +253,13 @@ class AudioParser:
         ev = torch.cuda.Event()
         ev.record()
         self._stage["ev"][self._stage["k"]] = ev
+        if speed is not None:
+            if leads is not None and any(int(l) for l in leads):
+                raise ValueError("a speed-perturbed wave cannot carry a lead-in sample")
+            n_sig = torch.tensor([self.speed_out_len(int(n_sig[i]), int(speed[i])) for i in range(B)], dtype=torch.int32)
+            wave, _ = self.speed_resampler()(wave, lens.to(dev), torch.tensor([int(k) for k in speed], dtype=torch.int32).to(dev),
+                                             L_out=max(int(n_sig.max()), 1))
+            lens = n_sig.clone()
         aug = self.draw_aug_batch(n_sig).to(dev) if mask else None
         # Tmax = the frames of the longest UTTERANCE (a row's lead-in sample is not part of it: it emits no frame of its own)
         return self.features_device(wave, lens.to(dev), aug, dither, logical_len=max(int(n_sig.max()), 1))
@@ -281,7 +366,7 @@ class WaveBatch(tuple):
 class LibriDataModule(LightningDataModule):
     def __init__(self, train_manifest, dev_manifest, test_manifest, labels: list, train_bs=16, dev_bs=16, num_worker=0,
                  train_max_duration=16.7, dev_max_duration=40, device="cuda", act_dtype=torch.float32,
-                 bucket_by_length: bool = False, bucket_batches: int = 50, train_crop: bool = True):
+                 bucket_by_length: bool = False, bucket_batches: int = 50, train_crop: bool = True, speed_perturb=None):
         super().__init__()
         as_list = lambda m: list(m) if isinstance(m, (list, tuple)) else [m]  # noqa: E731
         self.train_manifest, self.dev_manifest, self.test_manifest = as_list(train_manifest), as_list(dev_manifest), as_list(test_manifest)
@@ -294,8 +379,14 @@ class LibriDataModule(LightningDataModule):
         self.bucket_by_length = bool(bucket_by_length)       # BASELINE cfg5: length-bucketed batches (conf key data.bucket_by_length)
         self.bucket_batches = int(bucket_batches)            # batches per sorted mega-chunk (conf key data.bucket_batches)
         self.train_crop = bool(train_crop)                   # the reference's random sub-sequence of every training clip (data_module.py:158-159); conf key data.train_crop
+        # speed perturbation of every training clip (conf key data.speed_perturb: a list of factors, [] / absent = off): one factor
+        # per utterance, applied on the device by ops.Resampler on every route that yields training batches
+        self.speed_perturb = parse_speed_factors(speed_perturb)
+        self.audio_parser.speed_factors = self.speed_perturb
 
     def setup(self, stage=None):
+        self.speed_perturb = parse_speed_factors(self.speed_perturb)     # (a list assigned after construction is checked here)
+        self.audio_parser.speed_factors = self.speed_perturb
         self.train_datasets = MyAudioDataset(self.train_manifest, self.labels, mask=True, max_duration=self.train_max_duration)
         self.dev_datasets = MyAudioDataset(self.dev_manifest, self.labels, max_duration=self.dev_max_duration)
         self.test_datasets = MyAudioDataset(self.test_manifest, self.labels, max_duration=self.dev_max_duration)
@@ -329,9 +420,13 @@ class LibriDataModule(LightningDataModule):
     def _collate_wave(self, batch, mask: bool) -> WaveBatch:
         waves = [b[0] for b in batch]
         leads = None
+        perturb = mask and bool(getattr(self, "speed_perturb", None))
         if mask and getattr(self, "train_crop", True):   # training-time random sub-sequence (data_module.py:158-159)
-            cr = [self.audio_parser.crop_raw(w.unsqueeze(0), weight=0.98) for w in waves]
+            cr = [self.audio_parser.crop_raw(w.unsqueeze(0), weight=0.98, lead_in=not perturb) for w in waves]
             waves, leads = [c[0][0] for c in cr], [c[1] for c in cr]
+        # (the speed factors themselves are drawn where the batch reaches the GPU, in the main process - on_after_batch_transfer /
+        #  HostWaveSource - next to the SpecAugment rectangles: a worker's copy of the parser's random.Random is not reseeded per
+        #  worker, so factors drawn here would repeat across workers)
         max_trans = max(len(b[1]) for b in batch)
         targets = torch.zeros(len(batch), max_trans, dtype=torch.int64)
         target_sizes = torch.zeros(len(batch), dtype=torch.int32)
@@ -350,11 +445,18 @@ class LibriDataModule(LightningDataModule):
 
     _collate_fn = _collate_eval
 
+    def draw_speed_batch(self, n: int, mask: bool):
+        """one speed factor (index into ``speed_perturb``) per utterance of a training batch, None when off or not training"""
+        if not (mask and getattr(self, "speed_perturb", None)):
+            return None
+        return [self.audio_parser.draw_speed() for _ in range(n)]
+
     # ---- device half: ONE batched HIP mel call -> the reference's 5-tuple -------------------------
     def on_after_batch_transfer(self, batch, dataloader_idx=0):
         if not isinstance(batch, WaveBatch):
             return batch
         waves, targets, target_sizes, paths, mask = batch
-        inputs, pct = self.audio_parser.features(waves, mask, leads=batch.leads)
+        speed = self.draw_speed_batch(len(waves), mask)                 # after the crop's draws (collate), before the rectangles (features)
+        inputs, pct = self.audio_parser.features(waves, mask, leads=batch.leads, speed=speed)
         dev = inputs.device
         return inputs, targets.to(dev), pct, target_sizes.to(dev), paths

@@ -48,10 +48,12 @@ def fused_eligible(model, optimizer, scheduler) -> bool:
 
 
 class HostWaveSource:
-    """Fallback ingest for a custom dataset: the DataLoader's WaveBatch (ragged f32 waves) padded on the host and uploaded as f32"""
+    """Fallback ingest for a custom dataset: the DataLoader's WaveBatch (ragged f32 waves) padded on the host and uploaded as f32.
+    With speed perturbation on (the parser holds ``speed_factors``) a training batch gets one factor per utterance here, in the
+    main process, and is resampled on the device, f32 -> f32, by the parser's ``ops.Resampler``; its lengths are then the resampled ones."""
 
-    def __init__(self, loader, device, limit: int):
-        self.loader, self.device, self.limit = loader, torch.device(device), limit
+    def __init__(self, loader, device, limit: int, audio_parser=None):
+        self.loader, self.device, self.limit, self.ap = loader, torch.device(device), limit, audio_parser
 
     def __iter__(self):
         for k, batch in enumerate(self.loader):
@@ -72,6 +74,18 @@ class HostWaveSource:
             db = DevBatch()
             db.L, db.pitch = longest, L                      # T = the frames of the longest UTTERANCE; rows may be one lead-in sample wider
             db.pcm = host.to(self.device, non_blocking=True)
+            db.speed = None
+            if mask and self.ap is not None and getattr(self.ap, "speed_factors", None):
+                db.speed = [self.ap.draw_speed() for _ in waves]
+                if leads is not None and any(int(l) for l in leads):
+                    raise ValueError("a speed-perturbed wave cannot carry a lead-in sample")
+                n_out = [self.ap.speed_out_len(int(w.numel()), int(k)) for w, k in zip(waves, db.speed)]
+                longest = L = max(max(n_out), 1)
+                db.pcm, _ = self.ap.speed_resampler()(db.pcm, lens.to(self.device),
+                                                      torch.tensor([int(k) for k in db.speed], dtype=torch.int32).to(self.device), L_out=L)
+                lens = torch.tensor(n_out, dtype=torch.int32)
+                n_real = sum(n_out)
+                db.L, db.pitch = longest, L
             db.lens, db.sizes, db.targets = lens.to(self.device), sizes.to(self.device), targets.to(self.device)
             db.aug = None
             db.paths, db.B, db.ld, db.S, db.seconds = paths, B, L, targets.shape[1], float(n_real) / SR
@@ -90,13 +104,22 @@ class NativeSource:
     """manifest -> pinned ring -> device ring (ingest.py), ``depth`` batches ahead of the consumer"""
 
     def __init__(self, dataset, index_batches, audio_parser, device, batch_size: int, max_seconds: float, mask: bool,
-                 n_threads: int, limit: int, crop: Optional[bool] = None):
+                 n_threads: int, limit: int, crop: Optional[bool] = None, speed_perturb=None):
+        """speed_perturb: a list of factors (``data_module.parse_speed_factors``) to draw from per utterance - they become the
+        parser's ``speed_factors``; None = whatever the parser already holds, [] = off"""
         index_batches = list(index_batches)[:limit]
+        if speed_perturb is not None:
+            from .data_module import parse_speed_factors
+            audio_parser.speed_factors = parse_speed_factors(speed_perturb)
+            audio_parser._speed_rs = None
+        factors = list(getattr(audio_parser, "speed_factors", None) or [])
+        stretch = 1.0 / float(min(factors)) if factors else 1.0          # the slowest factor makes the longest clip
         cap = int(batch_size * (int(max_seconds * SR) + 64))
-        self.ring = PinnedRing(4, cap, 8 * batch_size + 2 * batch_size * 256)
-        self.feeder = DeviceFeeder(self.ring, device, n_slots=4)
+        self.ring = PinnedRing(4, cap, (10 if factors else 8) * batch_size + 2 * batch_size * 256)
+        self.feeder = DeviceFeeder(self.ring, device, n_slots=4, resampler=audio_parser.speed_resampler() if factors else None,
+                                   stretch=stretch)
         self.producer = BatchProducer(dataset, index_batches, self.ring, mask, audio_parser, n_threads=n_threads, crop=crop,
-                                      feeder=self.feeder)
+                                      feeder=self.feeder, speed=bool(factors))
         self.mask = mask
         self.n_threads = n_threads
         self.n = len(index_batches)
@@ -148,7 +171,7 @@ def make_source(datamodule, loader, device, mask: bool, limit: int, max_seconds:
         n_threads = ingest_threads_for_rank(int(getattr(datamodule, "num_worker", 0) or 0))
         return NativeSource(ds, loader.batch_sampler, datamodule.audio_parser, device, batch_size, max_seconds, mask,
                             n_threads=max(n_threads, 1), limit=limit, crop=crop)
-    return HostWaveSource(loader, device, limit)
+    return HostWaveSource(loader, device, limit, audio_parser=getattr(datamodule, "audio_parser", None))
 
 
 class FusedLoop:
@@ -297,6 +320,9 @@ class FusedLoop:
         cap = getattr(self.dm, "train_max_duration", None)
         if cap:
             max_dur = min(max_dur, float(cap))
+        factors = getattr(self.dm, "speed_perturb", None)
+        if factors:
+            max_dur = max_dur / float(min(factors))         # speed perturbation: the slowest factor stretches the longest clip
         t_in = ops.mel_num_frames(int(max_dur * 16000 + 0.5) + 1)
         self.native.workspace(int(getattr(self.dm, "train_bs", 32)), t_in, max(s_max, 1))
 

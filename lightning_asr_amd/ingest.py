@@ -9,7 +9,12 @@
   device buffers, one batch ahead of the training step, ordered by events only.
 
 The samples are scaled (1/32768), dithered, pre-emphasised and turned into log-mel features on the device
-(``lasr_mel_fwd_src``)."""
+(``lasr_mel_fwd_src``).
+
+Speed perturbation (``BatchProducer(speed=...)``, conf key ``data.speed_perturb``): the producer draws one factor per utterance,
+the raw PCM goes H2D into a per-slot staging block and ``lasr_resample`` (PCM16 -> PCM16, one launch on the copy stream) writes
+the device slot's rows; every length, the row pitch and the graph key of the batch are those of the RESAMPLED clips, so nothing
+downstream changes.  Such crops carry no lead-in sample (a resampled row has no sample before it)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -61,15 +66,17 @@ def read_wav_batch(paths: Sequence[str], out: torch.Tensor, lens_out: torch.Tens
 
 class HostBatch:
     """one batch on the host: PCM rows in ring slot ``slot`` + the packed metadata block"""
-    __slots__ = ("slot", "B", "ld", "S", "lens", "sizes", "aug", "targets", "meta", "meta_words", "paths", "mask", "seconds", "index")
+    __slots__ = ("slot", "B", "ld", "S", "lens", "sizes", "aug", "targets", "meta", "meta_words", "paths", "mask", "seconds", "index",
+                 "speed")
 
 
-def _meta_layout(B: int, S: int, with_aug: bool):
-    """int32 word offsets of [lens B][sizes B][aug 4B]...[targets B*S int64] inside the metadata block"""
+def _meta_layout(B: int, S: int, with_aug: bool, with_speed: bool = False):
+    """int32 word offsets of [lens B][sizes B][aug 4B]...[targets B*S int64] inside the metadata block; with speed perturbation
+    [raw lens B][conversion B] follow the targets (``lens`` then holds the resampled lengths)"""
     o_lens, o_sizes, o_aug = 0, B, 2 * B
     o_tg = 2 * B + (4 * B if with_aug else 0)
     o_tg += o_tg & 1                                  # int64 view needs an even word offset
-    return o_lens, o_sizes, o_aug, o_tg, o_tg + 2 * B * S
+    return o_lens, o_sizes, o_aug, o_tg, o_tg + 2 * B * S + (2 * B if with_speed else 0)
 
 
 class PinnedRing:
@@ -99,8 +106,10 @@ class BatchProducer(threading.Thread):
     from the consumer once its H2D copies are done."""
 
     def __init__(self, dataset, index_batches: Iterable[List[int]], ring: PinnedRing, mask: bool, audio_parser, n_threads: int = 8,
-                 crop_weight: float = 0.98, depth: int = 2, crop: Optional[bool] = None, feeder: Optional["DeviceFeeder"] = None):
+                 crop_weight: float = 0.98, depth: int = 2, crop: Optional[bool] = None, feeder: Optional["DeviceFeeder"] = None,
+                 speed: bool = False):
         super().__init__(daemon=True)
+        self.speed = bool(speed) and bool(getattr(audio_parser, "speed_factors", None))   # one of audio_parser.speed_factors per clip
         self.feeder = feeder         # given: this thread also issues the H2D copies and hands over DevBatch objects
         self.ds, self.batches, self.ring, self.mask, self.ap = dataset, index_batches, ring, mask, audio_parser
         self.n_threads, self.crop_weight = max(1, int(n_threads)), crop_weight
@@ -159,7 +168,7 @@ class BatchProducer(threading.Thread):
         paths = [ds.datasets[i]["audio_filepath"] for i in idx]
         ids = [self._ids(i) for i in idx]
         S = max(1, max(a.size for a in ids))
-        o_lens, o_sizes, o_aug, o_tg, words = _meta_layout(B, S, self.mask)
+        o_lens, o_sizes, o_aug, o_tg, words = _meta_layout(B, S, self.mask, self.speed)
         ring.grow(slot, meta_words=words)
         meta = ring.meta[slot]
         mnp = meta.numpy()                                   # shares the (pinned) memory
@@ -167,7 +176,8 @@ class BatchProducer(threading.Thread):
         lens = meta[o_lens:o_lens + B]
         while True:
             try:
-                ld = read_wav_batch(paths, ring.pcm[slot], lens, crop_u, self.crop_weight, self.n_threads, lead_in=self.crop)
+                ld = read_wav_batch(paths, ring.pcm[slot], lens, crop_u, self.crop_weight, self.n_threads,
+                                    lead_in=self.crop and not self.speed)
                 break
             except _lib.LasrError as e:
                 if "do not fit the buffer" not in str(e):
@@ -180,11 +190,29 @@ class BatchProducer(threading.Thread):
         for i, a in enumerate(ids):
             tg_np[i, :a.size] = a
         aug = None
-        if self.mask:       # spec_augment(27, 0.07) rectangles, drawn per clip in the reference's order (data_module.py:97-122,165)
+        speed = None
+        if self.speed:
+            # per clip: its factor (after the crop's draws above), then - below - its SpecAugment rectangle for the RESAMPLED length.
+            # The raw lengths and the conversions travel behind the targets; `lens` becomes the host-known resampled length.
+            o_raw = o_tg + 2 * B * S
+            speed, rects = [], []
+            for l in lens_np:
+                speed.append(self.ap.draw_speed())
+                if self.mask:
+                    rects.append(self.ap.draw_spec_augment(1 + (self.ap.speed_out_len(int(l), speed[-1]) + 64) // 160))
+            mnp[o_raw:o_raw + B] = lens_np
+            mnp[o_raw + B:o_raw + 2 * B] = speed
+            mnp[o_lens:o_lens + B] = [self.ap.speed_out_len(int(l), k) for l, k in zip(lens_np, speed)]
+            lens_np = mnp[o_lens:o_lens + B]
+            if self.mask:
+                mnp[o_aug:o_aug + 4 * B] = np.asarray(rects, dtype=np.int32).reshape(-1)
+                aug = meta[o_aug:o_aug + 4 * B].view(B, 4)
+        elif self.mask:     # spec_augment(27, 0.07) rectangles, drawn per clip in the reference's order (data_module.py:97-122,165)
             draw = self.ap.draw_spec_augment
             mnp[o_aug:o_aug + 4 * B] = np.asarray([draw(1 + (int(l) + 64) // 160) for l in lens_np], dtype=np.int32).reshape(-1)
             aug = meta[o_aug:o_aug + 4 * B].view(B, 4)
         hb = HostBatch()
+        hb.speed = speed
         hb.slot, hb.B, hb.ld, hb.S, hb.lens, hb.aug = slot, B, ld, S, lens, aug
         hb.sizes = meta[o_sizes:o_sizes + B]
         hb.targets = meta[o_tg:o_tg + 2 * B * S].view(torch.int64).view(B, S)
@@ -196,7 +224,7 @@ class BatchProducer(threading.Thread):
 class DevBatch:
     """one batch resident in HBM (views of a device ring slot), valid for the compute stream once ``ready`` has been waited on"""
     __slots__ = ("pcm", "lens", "sizes", "aug", "targets", "paths", "B", "ld", "S", "seconds", "ready", "dslot", "index", "key", "mask", "waited",
-                 "L", "pitch")
+                 "L", "pitch", "speed")
 
 
 class DeviceFeeder:
@@ -204,10 +232,15 @@ class DeviceFeeder:
     for the compute-stream event of the step that last read the slot (``release``), copies PCM + metadata, records ``ready``;
     a helper thread returns the pinned slot to the producer once the copies are done."""
 
-    def __init__(self, ring: PinnedRing, device, n_slots: int = 3):
+    def __init__(self, ring: PinnedRing, device, n_slots: int = 3, resampler=None, stretch: float = 1.0):
+        """resampler (ops.Resampler) + stretch = 1 / the smallest speed factor: batches that carry ``speed`` are resampled into
+        the device slots, which are sized for the stretched clips"""
         self.ring, self.device = ring, torch.device(device)
         self.n_slots = n_slots
-        self.pcm = [torch.empty(ring.capacity, dtype=torch.int16, device=self.device) for _ in range(n_slots)]
+        self.resampler = resampler
+        self.stage = [None] * n_slots          # raw PCM of a speed-perturbed batch, as the host reader laid it out
+        cap = ring.capacity if float(stretch) <= 1.0 else int(ring.capacity * float(stretch)) + 64
+        self.pcm = [torch.empty(cap, dtype=torch.int16, device=self.device) for _ in range(n_slots)]
         self.meta = [torch.empty(ring.meta_words, dtype=torch.int32, device=self.device) for _ in range(n_slots)]
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self._retired: list = []               # outgrown device blocks, kept alive until close()
@@ -250,7 +283,10 @@ class DeviceFeeder:
         longest = int((hb.lens & (_lib.LEN_LEAD - 1)).max()) if hb.B else 0
         frames = 1 + (longest + 64) // 160
         L_log, pitch = 160 * (frames - 1) + 95, 160 * (frames - 1) + 96
-        if pitch < hb.ld:                      # (cannot happen: ld = the longest row rounded up to 8 <= 160 (T - 1) + 96)
+        perturbed = hb.speed is not None       # the rows are written by lasr_resample: hb.ld is the pitch of the RAW rows only
+        if perturbed and self.resampler is None:
+            raise RuntimeError("a speed-perturbed batch needs a DeviceFeeder built with a resampler")
+        if pitch < hb.ld and not perturbed:    # (cannot happen: ld = the longest row rounded up to 8 <= 160 (T - 1) + 96)
             L_log = pitch = hb.ld
         n = hb.B * pitch
         cs = self.copy_stream
@@ -271,22 +307,32 @@ class DeviceFeeder:
                     if not idle:
                         self._retired.append((self.meta[k], released))
                     self.meta[k] = torch.empty(int(hb.meta_words * 1.5) + 64, dtype=torch.int32, device=self.device)
+        if perturbed and (self.stage[k] is None or self.stage[k].numel() < hb.B * hb.ld):
+            with torch.cuda.stream(cs):         # only ever touched on the copy stream: its pool orders the old block's reuse
+                self.stage[k] = torch.empty(int(hb.B * hb.ld * 1.25) + 64, dtype=torch.int16, device=self.device)
         if self._retired:
             self._retired = [(blk, ev_) for blk, ev_ in self._retired if not ev_.query()]
         if released is not None:
             cs.wait_event(released)             # the step that read this device slot has finished with it
         with torch.cuda.stream(cs):
             src = self.ring.pcm[hb.slot][:hb.B * hb.ld]
-            if pitch == hb.ld:
+            if perturbed:
+                self.stage[k][:hb.B * hb.ld].copy_(src, non_blocking=True)
+            elif pitch == hb.ld:
                 self.pcm[k][:n].copy_(src, non_blocking=True)
             else:                               # rows at the host reader's pitch -> rows at the class pitch (the tail of a row is never read)
                 self.pcm[k][:n].view(hb.B, pitch)[:, :hb.ld].copy_(src.view(hb.B, hb.ld), non_blocking=True)
             self.meta[k][:hb.meta_words].copy_(hb.meta[:hb.meta_words], non_blocking=True)
+            if perturbed:                       # raw rows -> the slot's rows at the class pitch, whole rows defined (zeros past n_out)
+                o_raw = _meta_layout(hb.B, hb.S, hb.aug is not None, True)[3] + 2 * hb.B * hb.S
+                mk = self.meta[k]
+                self.resampler(self.stage[k][:hb.B * hb.ld].view(hb.B, hb.ld), mk[o_raw:o_raw + hb.B], mk[o_raw + hb.B:o_raw + 2 * hb.B],
+                               out=self.pcm[k][:n].view(hb.B, pitch), L_out=pitch, out_lens=mk[:hb.B])
             ev = torch.cuda.Event()
             ev.record(cs)
         self._done_q.put((ev, hb.slot))
         B, S = hb.B, hb.S
-        o_lens, o_sizes, o_aug, o_tg, _ = _meta_layout(B, S, hb.aug is not None)
+        o_lens, o_sizes, o_aug, o_tg, _ = _meta_layout(B, S, hb.aug is not None, perturbed)
         m = self.meta[k]
         db = DevBatch()
         db.pcm = self.pcm[k][:n].view(B, pitch)
@@ -297,6 +343,7 @@ class DeviceFeeder:
         db.paths, db.B, db.ld, db.S, db.seconds, db.ready, db.dslot, db.index = hb.paths, B, hb.ld, S, hb.seconds, ev, k, hb.index
         db.key = (B, pitch, S, hb.aug is not None)
         db.waited = False
+        db.speed = hb.speed
         return db
 
     def release(self, db: DevBatch) -> None:

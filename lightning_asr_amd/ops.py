@@ -674,3 +674,100 @@ def step_metrics(loss: torch.Tensor, dist: torch.Tensor, units: torch.Tensor, ac
     if acc.dtype != torch.float64 or acc.numel() < 7:
         raise TypeError("acc must hold 7 float64 values")
     call("lasr_step_metrics", _p(loss), _p(dist), _p(units), dist.numel(), _p(acc), _stream())
+
+
+# ---- sample-rate conversion (csrc/resample.hip; DESIGN.md "Resampling") ---------------------------------------------------
+def resample_out_len(n_in: int, up: int, down: int) -> int:
+    """ceil(n_in * up / down)"""
+    n = _lib.load().lasr_resample_out_len(int(n_in), int(up), int(down))
+    if n < 0:
+        _lib.check(-1, "lasr_resample_out_len")
+    return int(n)
+
+
+class Resampler:
+    """A bank of up to 8 rate conversions [(sr_in, sr_out), ...] built on the host and uploaded ONCE; a call converts a batch of
+    rows on the device, each row by its own conversion (``conv_id``).  (1, 1)-like pairs (sr_in == sr_out) are plain copies."""
+
+    def __init__(self, conversions, device="cuda", lpw: int = 6, rolloff: float = 0.99):
+        conversions = [(int(a), int(b)) for a, b in conversions]
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.LasrError("Resampler runs on the GPU only (device=%r): there is no CPU path" % (device,))
+        n = len(conversions)
+        for a, b in conversions:                       # what does not fit the C ABI's int32 is refused here, with its rule
+            if not (0 < a < 2 ** 31 and 0 < b < 2 ** 31):
+                raise ValueError("Resampler: sample rates must be positive 31-bit integers, got %r" % ((a, b),))
+        sr_in, sr_out = (ctypes.c_int32 * max(n, 1))(*[c[0] for c in conversions]), (ctypes.c_int32 * max(n, 1))(*[c[1] for c in conversions])
+        lib = _lib.load()
+        nbytes = lib.lasr_resample_bank_bytes(sr_in, sr_out, n, int(lpw), float(rolloff))
+        if not nbytes:
+            _lib.check(-1, "lasr_resample_bank_bytes")
+        host = torch.empty(nbytes // 4, dtype=torch.int32)
+        call("lasr_resample_bank_write", sr_in, sr_out, n, int(lpw), float(rolloff), host.data_ptr(), nbytes)
+        self.conversions, self.lpw, self.rolloff = conversions, int(lpw), float(rolloff)
+        self.factors = []                               # (up, down) per conversion, from the image's own header
+        for i in range(n):
+            up, down = int(host[16 + 8 * i]), int(host[17 + 8 * i])
+            self.factors.append((up, down))
+        self.bank = host.to(self.device)
+
+    def out_len(self, n_in: int, conv: int = 0) -> int:
+        up, down = self.factors[conv]
+        return -((-int(n_in) * up) // down)
+
+    def tile(self, conv: int = 0) -> int:
+        """outputs per workgroup of conversion `conv` (where the kernel's tests put their row lengths)"""
+        up, down = self.factors[conv]
+        return int(_lib.load().lasr_resample_tile(up, down, self.lpw, self.rolloff))
+
+    def __call__(self, wave: torch.Tensor, lens: Optional[torch.Tensor] = None, conv_id: Optional[torch.Tensor] = None, out_dtype=None,
+                 out: Optional[torch.Tensor] = None, L_out: Optional[int] = None, out_lens: Optional[torch.Tensor] = None):
+        """wave (B, L) f32 | int16 on the device (rows may be strided: stride(1) == 1) -> (out (B, L_out), out_lens (B) int32).
+        lens (B) int32 valid samples per row (None = L); conv_id (B) int32 (None = conversion 0).  L_out defaults to the longest
+        row any of the bank's conversions can produce from L samples; ``out`` (B, >= L_out) is written in place when given
+        (columns past L_out are left alone), and so is ``out_lens`` (B) int32.  No host synchronisation."""
+        if wave.dim() != 2 or wave.dtype not in (torch.float32, torch.int16) or not wave.is_cuda or (wave.shape[1] > 1 and wave.stride(1) != 1):
+            raise _lib.LasrError("Resampler: wave must be a (B, L) f32 or int16 device tensor with contiguous rows")
+        B, L = wave.shape
+        in_pitch = wave.stride(0) if B > 1 else max(L, 1)
+        if lens is None:
+            lens = torch.full((B,), L, dtype=torch.int32, device=wave.device)
+        if lens.dtype != torch.int32 or lens.numel() != B or not lens.is_cuda:
+            raise _lib.LasrError("Resampler: lens must be a (B,) int32 device tensor")
+        if conv_id is not None and (conv_id.dtype != torch.int32 or conv_id.numel() != B or not conv_id.is_cuda):
+            raise _lib.LasrError("Resampler: conv_id must be a (B,) int32 device tensor")
+        out_dtype = (out.dtype if out is not None else wave.dtype) if out_dtype is None else out_dtype
+        if out_dtype not in (torch.float32, torch.int16):
+            raise _lib.LasrError("Resampler: out_dtype must be torch.float32 or torch.int16")
+        if L_out is None:
+            L_out = max(self.out_len(L, i) for i in range(len(self.factors))) if out is None else out.shape[1]
+        if out is None:
+            out = torch.empty(B, max(L_out, 1), dtype=out_dtype, device=wave.device)[:, :L_out]
+        if out.dim() != 2 or out.shape[0] != B or out.shape[1] < L_out or out.dtype != out_dtype or not out.is_cuda or (out.shape[1] > 1 and out.stride(1) != 1):
+            raise _lib.LasrError("Resampler: out must be a (B, >= L_out) device tensor of out_dtype with contiguous rows")
+        out_pitch = out.stride(0) if B > 1 else max(out.shape[1], L_out)
+        if out_lens is None:
+            out_lens = torch.empty(B, dtype=torch.int32, device=wave.device)
+        elif out_lens.dtype != torch.int32 or out_lens.numel() != B or not out_lens.is_cuda or not out_lens.is_contiguous():
+            raise _lib.LasrError("Resampler: out_lens must be a contiguous (B,) int32 device tensor")
+        code = lambda dt: _lib.WAVE_F32 if dt == torch.float32 else _lib.WAVE_PCM16  # noqa: E731
+        call("lasr_resample", _p(self.bank), wave.data_ptr(), code(wave.dtype), in_pitch, _p(lens.contiguous()),
+             _p(conv_id.contiguous()) if conv_id is not None else None, out.data_ptr(), code(out_dtype), out_pitch, L_out, _p(out_lens), B, _stream())
+        return out[:, :L_out], out_lens
+
+
+_RESAMPLERS: dict = {}
+
+
+def resample(wave: torch.Tensor, sr_in: int, sr_out: int):
+    """wave (B, L) or (L,) f32 | int16 on the device at sr_in -> (out, out_lens) at sr_out; the resampler of a (pair, device) is
+    built once and kept."""
+    w2 = wave.unsqueeze(0) if wave.dim() == 1 else wave
+    dev = w2.device
+    key = (int(sr_in), int(sr_out), dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    r = _RESAMPLERS.get(key)
+    if r is None:
+        r = _RESAMPLERS[key] = Resampler([(sr_in, sr_out)], w2.device)
+    out, n = r(w2.contiguous())
+    return (out[0] if wave.dim() == 1 else out), n

@@ -19,7 +19,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from .align import frame_seconds, unit_records
-from .data_module import AudioParser, LibriDataModule, load_wav
+from .data_module import AudioParser, LibriDataModule, load_wav, load_wav_rate
 from .lightning_compat import Trainer
 from .train import LightingModule
 from . import ops
@@ -32,12 +32,17 @@ EN_LABELS = [" ", "'"] + [chr(ord("a") + i) for i in range(26)]
 class AsrTranslator:
     def __init__(self, model_path: str, map_location: str = "cuda", lang: str = "en", labels: Optional[List[str]] = None,
                  verbose: bool = False, decoder: str = "greedy", beam_width: int = 16, cutoff_top_n: int = 40,
-                 cutoff_prob: float = 1.0, lm_path: Optional[str] = None, alpha: float = 1.0, beta: float = 1.0):
+                 cutoff_prob: float = 1.0, lm_path: Optional[str] = None, alpha: float = 1.0, beta: float = 1.0, resample: bool = False):
         """model_path: a ``.ckpt`` written by the reference or by ``Trainer``; map_location must name a GPU
         ("cuda" / "cuda:0"): there is no CPU path.  ``labels`` overrides the language's vocabulary.
         decoder: "greedy" (argmax + CTC collapse, the default) or "beam" (CTC prefix beam search; with ``lm_path``, a text ARPA
         LM, fused with it: ``alpha`` weighs the LM, ``beta`` is the per-label bonus of a character LM and the per-word bonus
-        of a word LM, under which only the LM's words are decoded)."""
+        of a word LM, under which only the LM's words are decoded).
+        resample: False (the default, the reference's behaviour) feeds a file's samples to the 16 kHz front-end whatever its
+        sample rate; True converts a file of another rate on the device first (``ops.resample``) - ``translate``,
+        ``translate_nbest``, ``align`` and ``translate_timed`` then hear it at its true speed and report its true times (each
+        takes ``resample=`` to override the translator's setting for one call); ``evalute_manifest`` / ``align_manifest`` do not
+        resample: with resample=True they refuse a manifest that holds a file of another rate."""
         if decoder not in ("greedy", "beam"):
             raise ValueError("decoder must be 'greedy' or 'beam', got %r" % (decoder,))
         if labels is not None:
@@ -57,16 +62,17 @@ class AsrTranslator:
         self.device = torch.device(map_location)
         self.wer = WER(vocabulary=self.labels)
         self.decoder = decoder
+        self.resample = bool(resample)
         self.beam = BeamSearchDecoderWithLM(self.labels, beam_width, alpha, beta, lm_path, 1, cutoff_prob=cutoff_prob,
                                             cutoff_top_n=cutoff_top_n, device=str(map_location))
         self.model.eval()
 
     @torch.no_grad()
-    def translate(self, audio_path) -> str:
+    def translate(self, audio_path, resample: Optional[bool] = None) -> str:
         """One local audio file (path or file object) -> text (predict.py:44-63): no dither-free shortcut, the same
         feature chain as training without augmentation, eval-mode BN, argmax, CTC collapse."""
         t0 = time.time()
-        inputs = self.audio_parser.parse_audio(audio_path, mask=False)
+        inputs = self.audio_parser.parse_audio(audio_path, mask=False, resample=self._resample(resample))
         pct = torch.ones(inputs.shape[0], dtype=torch.float32, device=self.device)   # torch.FloatTensor([1.])  (:55)
         t1 = time.time()
         out = self.model._encode(inputs, pct)
@@ -82,12 +88,33 @@ class AsrTranslator:
         return text
 
     @torch.no_grad()
-    def translate_nbest(self, audio_path, n: int = 5) -> List[Tuple[str, float]]:
+    def translate_nbest(self, audio_path, n: int = 5, resample: Optional[bool] = None) -> List[Tuple[str, float]]:
         """One audio file -> the n best beam hypotheses [(text, log-probability), ...], best first (any decoder setting)"""
-        inputs = self.audio_parser.parse_audio(audio_path, mask=False)
+        inputs = self.audio_parser.parse_audio(audio_path, mask=False, resample=self._resample(resample))
         pct = torch.ones(inputs.shape[0], dtype=torch.float32, device=self.device)
         out = self.model._encode(inputs, pct)
         return [(text, score) for score, text in self.beam.decode_nbest(out, None, n)[0]]
+
+    def _resample(self, override: Optional[bool]) -> bool:
+        return self.resample if override is None else bool(override)
+
+    def _require_16k(self, manifest: str, who: str) -> None:
+        """resample=True: the manifest loaders do not resample, so a file of another rate is refused by name instead of being
+        decoded at the wrong speed"""
+        from .ingest import wav_info
+        from . import _lib
+        with open(manifest, encoding="utf-8") as f:
+            for line in f:
+                if not line.strip():
+                    continue
+                path = json.loads(line)["audio_filepath"]
+                try:
+                    rate = wav_info(path)[2]
+                except _lib.LasrError:                          # not a RIFF/WAVE file the native reader takes: whatever load_wav decodes
+                    rate = load_wav_rate(path)[1]
+                if rate != self.audio_parser.sr:
+                    raise ValueError("%s: %s has a sample rate of %d Hz, not %d: the manifest loaders do not resample (convert the "
+                                     "file, or use translate / align on it)" % (who, path, rate, self.audio_parser.sr))
 
     def evalute_manifest(self, test_manifest: str, batch_size: int = 32, num_workers: int = 0, decoder: Optional[str] = None):
         """WER over a manifest (predict.py:65-74; the reference's spelling kept).  decoder: None = the translator's own.
@@ -96,6 +123,8 @@ class AsrTranslator:
         decoder = self.decoder if decoder is None else decoder
         if decoder not in ("greedy", "beam"):
             raise ValueError("decoder must be 'greedy' or 'beam', got %r" % (decoder,))
+        if self.resample:
+            self._require_16k(test_manifest, "evalute_manifest")
         data_module = LibriDataModule(train_manifest=test_manifest, dev_manifest=test_manifest, test_manifest=test_manifest,
                                       dev_bs=batch_size, num_worker=num_workers, labels=self.labels,
                                       device=str(self.model.encoder.native.device), act_dtype=self.model.encoder.native.act_dtype)
@@ -151,15 +180,22 @@ class AsrTranslator:
             ids.append(char2index[ch])
         return ids
 
-    def _encode_file(self, audio_path):
-        """one audio file -> (log-probs (1, T', C) f32, duration in seconds): translate()'s feature chain and forward"""
+    def _encode_file(self, audio_path, resample: Optional[bool] = None):
+        """one audio file -> (log-probs (1, T', C) f32, duration in seconds): translate()'s feature chain and forward.  With
+        resample on, the duration is the file's own: its samples over its sample rate; off, the samples are taken for 16 kHz."""
         if isinstance(audio_path, str) and not os.path.exists(audio_path):
             raise Exception("音频路径不存在 " + audio_path)
-        y = load_wav(audio_path)
-        inputs = self.audio_parser.features([y[0]], False, leads=[0])[0]
+        if self._resample(resample):
+            y, rate = load_wav_rate(audio_path)
+            duration = y.shape[1] / float(rate)
+            y = self.audio_parser.resample_to_sr(y, rate)
+        else:
+            y = load_wav(audio_path)
+            duration = y.shape[1] / float(self.audio_parser.sr)
+        inputs = self.audio_parser.features_one(y)[0]
         pct = torch.ones(inputs.shape[0], dtype=torch.float32, device=self.device)
         out = self.model._encode(inputs, pct)
-        return out, y.shape[1] / float(self.audio_parser.sr)
+        return out, duration
 
     def _decode(self, out) -> str:
         if self.decoder == "beam":
@@ -181,19 +217,19 @@ class AsrTranslator:
                             self.frame_seconds(), duration)
 
     @torch.no_grad()
-    def align(self, audio_path, text: str) -> List[dict]:
+    def align(self, audio_path, text: str, resample: Optional[bool] = None) -> List[dict]:
         """Forced alignment of a known transcript to one audio file: one record per word (per label for a vocabulary without a
         space), {"word", "start", "end", "score", "labels": [{"label", "start", "end", "score"}, ...]}, times in seconds.
         ValueError for a character outside the vocabulary and for a transcript too long for the clip."""
         ids = self.text_to_ids(text)
-        out, duration = self._encode_file(audio_path)
+        out, duration = self._encode_file(audio_path, resample)
         return self._align_ids(out, ids, duration)
 
     @torch.no_grad()
-    def translate_timed(self, audio_path) -> Tuple[str, List[dict]]:
+    def translate_timed(self, audio_path, resample: Optional[bool] = None) -> Tuple[str, List[dict]]:
         """translate() with timings: decodes with the translator's own decoder and aligns that hypothesis on the same log-probs.
         Returns (text, word records); an empty hypothesis gives ("", [])."""
-        out, duration = self._encode_file(audio_path)
+        out, duration = self._encode_file(audio_path, resample)
         text = self._decode(out)
         if not text:
             return "", []
@@ -205,6 +241,8 @@ class AsrTranslator:
         evalute_manifest, one ops.ctc_align per batch).  Writes one JSON line per utterance to out_path - audio_filepath, text,
         score (Viterbi log-probability), score_per_frame, words - and returns the records.  An utterance without an alignment
         (transcript too long for its clip) has "words": null and score -inf."""
+        if self.resample:
+            self._require_16k(manifest, "align_manifest")
         dm = LibriDataModule(train_manifest=manifest, dev_manifest=manifest, test_manifest=manifest, dev_bs=batch_size,
                              num_worker=0, labels=self.labels, device=str(self.model.encoder.native.device),
                              act_dtype=self.model.encoder.native.act_dtype)

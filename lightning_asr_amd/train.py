@@ -183,7 +183,8 @@ def main(argv=None):
                                   act_dtype=torch.float32 if dtype == "f32" else torch.bfloat16, device=device,
                                   bucket_by_length=bool(data_cfg.get("bucket_by_length", False)),
                                   bucket_batches=int(data_cfg.get("bucket_batches", 50)),
-                                  train_crop=bool(data_cfg.get("train_crop", True)))
+                                  train_crop=bool(data_cfg.get("train_crop", True)),
+                                  speed_perturb=data_cfg.get("speed_perturb", None))
     model = LightingModule(learning_rate=tran_cfg.get("learning_rate"), weight_decay=tran_cfg.get("weight_decay"), labels=labels,
                            total_epoch=tran_cfg.get("total_epoch"), drop_rate=model_cfg.get("drop_rate"), mask=model_cfg.get("mask"),
                            use_cer=use_cer, variant=model_cfg.get("variant", "plain"), act=model_cfg.get("act", "relu"), dtype=dtype,
