@@ -25,13 +25,14 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 107   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 108   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
                               105: lasr_ctc_align_workspace_bytes / lasr_ctc_align (CTC forced alignment)
                               106: lasr_arpa_load_words / lasr_arpa_lexicon_info / lasr_ctc_beam_decode_wlm (word-level LM)
-                              107: lasr_resample_* (sample-rate conversion, speed perturbation) */
+                              107: lasr_resample_* (sample-rate conversion, speed perturbation)
+                              108: lasr_rir_bank_* / lasr_wave_augment* (noise and reverberation augmentation) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -744,6 +745,51 @@ int64_t lasr_resample_tile(int64_t up, int64_t down, int lpw, double rolloff);
 int lasr_resample(const void* bank_dev, const void* in, int in_dtype, int64_t in_pitch, const int32_t* in_lens,
                   const int32_t* conv_id, void* out, int out_dtype, int64_t out_pitch, int64_t L_out, int32_t* out_lens, int64_t B,
                   void* stream);
+
+/* ---- waveform augmentation: reverberation with a room impulse response (RIR) and additive noise at a drawn SNR --------------
+ * Row b has n valid samples x[0..n) (PCM16 scaled by 1/32768) and a parameter word (rir_id, noise_id, noise_start, snr_cdb), int32:
+ * rir_id = -1: no reverb; noise_id = -1: no noise; snr_cdb = the SNR in hundredths of a dB.  (DESIGN.md "Noise and reverberation")
+ *   reverb  y[j] = sum_{k < K} h[k] * x[j + d - k],  x = 0 outside [0, n), j in [0, n);  else y = x
+ *   noise   v[j] = noise[off_c + (s + j) mod len_c]  for clip c = (off_c, len_c) and start s in [0, len_c);  else v = 0
+ *   E_x = sum x^2, E_y = sum y^2, E_n = sum v^2 over [0, n) in f64;  g_s = sqrt(E_x / E_y) (1 without reverb, 0 if E_y == 0);
+ *   g_n = sqrt(E_x / (E_n * 10^(snr_cdb / 1000))) (0 without noise or if E_x == 0 or E_n == 0)
+ *   out[j] = g_s * y[j] + g_n * v[j] for j < n, 0 for j in [n, L);  out_lens[b] = n.  The length never changes.
+ * f32 accumulation in ascending k, one fma per tap; the gains are formed in f64 and rounded once to f32; no float atomics: the
+ * energies go through per-tile f64 partials in the workspace, summed in tile order, so a call gives the same bits every time.
+ *
+ * The RIR bank: up to 256 RIRs as one position-independent image - a header table (taps K, delay d, offset per RIR) followed by
+ * the taps, unscaled f32 (lightning_asr_amd/csrc/wave_aug.h).  d = the first index of max |h|; K = the smallest length >= d + 1
+ * whose dropped tail holds <= 1e-6 of the RIR's energy (f64), at most 8192.  rirs = the RIRs one after the other, lens[i] samples
+ * each.  LASR_E_ARG (lasr_rir_bank_bytes: 0), naming the index: an empty RIR or one longer than 2^20 samples, an all-zero RIR,
+ * a value that is not finite, d >= 8192, more than 256 RIRs, an image above 2^21 words, a destination smaller than the image.
+ * No device work.
+ * lasr_wave_augment_tile / _chunk: the outputs one workgroup of the FIR produces and the taps it stages per chunk - where the
+ * tests put their row lengths and filter lengths.  lasr_wave_augment_workspace_bytes(B, L): 0 and LASR_E_SHAPE for B > 65535 or
+ * L >= 2^31. */
+size_t lasr_rir_bank_bytes(const float* rirs, const int64_t* lens, int n_rir);
+int lasr_rir_bank_write(const float* rirs, const int64_t* lens, int n_rir, void* host_dst, size_t bytes);
+int64_t lasr_wave_augment_tile(void);
+int64_t lasr_wave_augment_chunk(void);
+size_t lasr_wave_augment_workspace_bytes(int64_t B, int64_t L);
+/* B rows on `stream` (three launches); nothing is allocated or synchronised, so the call can be captured.
+ * rir_bank_dev: a device copy of the image, rir_bank_words its size in 4-byte words (NULL / 0: no RIRs).  noise_dev: the noise
+ * bank, noise_total samples of noise_dtype (f32 or PCM16), clip c = noise_clips[2c] (offset), noise_clips[2c + 1] (length), int32
+ * on the device (NULL / n_clips 0: no noise).  in: B rows of in_pitch elements; in_lens (B) int32 length words; params (B, 4) int32.
+ * out: B rows of out_pitch elements, f32 (not clamped) or PCM16 = clamp(rint(v * 32768), -32768, 32767); elements [L, out_pitch)
+ * are not touched.  `out` may be `in` itself (same pointer, dtype and pitch): the FIR writes y into the workspace and the mix
+ * reads only that on reverberated rows.  out_lens (B) int32 (may be in_lens); stats (B, 3) f64 = (E_x, E_y, E_n) (E_y = E_x
+ * without reverb).  workspace: lasr_wave_augment_workspace_bytes(B, L) bytes on the device, 16-byte aligned.
+ * A row with rir_id == noise_id == -1 is copied bit for bit when the dtypes agree (otherwise only the scale and the rounding
+ * apply); its length word passes through, LASR_LEN_LEAD and the lead-in sample included.  On every other row the flag is masked:
+ * an augmented row has no lead-in sample (a CALLER ERROR, refused by the Python wrappers).  An id outside its bank, a clip that
+ * runs past noise_total, a start outside [0, len_c), a bank without lasr_rir_bank_write's magic, or an entry outside the builder's
+ * limits or past rir_bank_words gives a row of zeros with out_lens 0; nothing is read out of bounds.  LASR_E_ARG: null pointer,
+ * unknown dtype, negative size, a pitch below L, a partial alias of in and out, a small or misaligned workspace; LASR_E_SHAPE:
+ * B > 65535, rows of 2^31 samples or more. */
+int lasr_wave_augment(const void* rir_bank_dev, int64_t rir_bank_words, const void* noise_dev, int noise_dtype,
+                      const int32_t* noise_clips, int n_clips, int64_t noise_total, const void* in, int in_dtype, int64_t in_pitch,
+                      const int32_t* in_lens, const int32_t* params, void* out, int out_dtype, int64_t out_pitch, int64_t L,
+                      int32_t* out_lens, double* stats, int64_t B, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- data-parallel gradient exchange: RCCL over xGMI, called by the library itself ------------------------------
  * Replaces the NCCL all-reduce the reference gets from Lightning's DDP plugin (conf/conf.yaml:30-31 `accelerator: ddp`,

@@ -162,6 +162,12 @@ SIGNATURES = {
     "lasr_resample_out_len": (_i64, [_i64, _i64, _i64]),
     "lasr_resample_tile": (_i64, [_i64, _i64, _i32, C.c_double]),
     "lasr_resample": (_i32, [_p, _p, _i32, _i64, _p, _p, _p, _i32, _i64, _i64, _p, _i64, _p]),
+    "lasr_rir_bank_bytes": (_sz, [_p, _p, _i32]),
+    "lasr_rir_bank_write": (_i32, [_p, _p, _i32, _p, _sz]),
+    "lasr_wave_augment_tile": (_i64, []),
+    "lasr_wave_augment_chunk": (_i64, []),
+    "lasr_wave_augment_workspace_bytes": (_sz, [_i64, _i64]),
+    "lasr_wave_augment": (_i32, [_p, _i64, _p, _i32, _p, _i32, _i64, _p, _i32, _i64, _p, _p, _p, _i32, _i64, _i64, _p, _p, _i64, _p, _sz, _p]),
     "lasr_comm_timing": (_i32, [_p, _i32]),
     "lasr_comm_timing_collect": (_i32, [_p, _i32, _p, _p, C.POINTER(_i32), _p, C.POINTER(_i32)]),
     "lasr_comm_unique_id": (_i32, [_p, _sz]),

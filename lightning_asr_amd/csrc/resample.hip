@@ -10,6 +10,7 @@
 // tiles x, x + gridDim.x, ... of that row's conversion.  No allocation, no host synchronisation.
 #include "common.h"
 #include "resample.h"
+#include "wave_sample.h"
 
 static_assert(lasr::resample::kMaxTile == 1024, "the kernel keeps 4 accumulators per thread of a 256-thread workgroup");
 
@@ -19,19 +20,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kAcc = resample::kMaxTile / kThreads;
-
-__device__ __forceinline__ float load_sample(const float* p) { return *p; }
-__device__ __forceinline__ float load_sample(const int16_t* p) { return (float)*p * (1.0f / 32768.0f); }
-__device__ __forceinline__ void store_sample(float* p, float v) { *p = v; }
-__device__ __forceinline__ void store_sample(int16_t* p, float v) {      // saturates, never wraps
-  const float s = rintf(v * 32768.0f);
-  *p = (int16_t)(int)fminf(fmaxf(s, -32768.0f), 32767.0f);
-}
-// an identity row keeps its bits when the dtypes agree; otherwise only the scale (and the rounding) applies
-__device__ __forceinline__ void copy_sample(float* o, const float* i) { *o = *i; }
-__device__ __forceinline__ void copy_sample(int16_t* o, const int16_t* i) { *o = *i; }
-__device__ __forceinline__ void copy_sample(float* o, const int16_t* i) { *o = load_sample(i); }
-__device__ __forceinline__ void copy_sample(int16_t* o, const float* i) { store_sample(o, *i); }
 
 template <typename TI, typename TO>
 __global__ __launch_bounds__(kThreads) void resample_kernel(const int32_t* __restrict__ bank, const TI* __restrict__ in, int64_t in_pitch,

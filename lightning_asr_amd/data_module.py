@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import json
 import logging
+import math
 import os
 import random
 import wave as _wave
@@ -84,6 +85,89 @@ def parse_speed_factors(factors) -> List[Fraction]:
     return out
 
 
+class WaveAugConfig:
+    """conf keys ``data.noise_manifest / noise_prob / noise_snr_db / noise_max_seconds / rir_manifest / rir_prob``, checked.
+    A ValueError names the key for a probability outside [0, 1], ``lo > hi``, a non-positive budget."""
+
+    def __init__(self, noise_manifest=None, noise_prob=0.5, noise_snr_db=(5, 20), noise_max_seconds=600, rir_manifest=None, rir_prob=0.3):
+        def prob(v, key):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 <= float(v) <= 1.0):      # (NaN fails the comparison)
+                raise ValueError("data.%s must be a probability in [0, 1], got %r" % (key, v))
+            return float(v)
+        self.noise_manifest = None if noise_manifest in (None, "") else str(noise_manifest)
+        self.rir_manifest = None if rir_manifest in (None, "") else str(rir_manifest)
+        self.noise_prob, self.rir_prob = prob(noise_prob, "noise_prob"), prob(rir_prob, "rir_prob")
+        try:
+            lo, hi = (float(v) for v in noise_snr_db)
+        except (TypeError, ValueError) as e:
+            raise ValueError("data.noise_snr_db must be [lo, hi] in dB, got %r" % (noise_snr_db,)) from e
+        if not (math.isfinite(lo) and math.isfinite(hi)) or lo > hi:
+            raise ValueError("data.noise_snr_db must be [lo, hi] with lo <= hi, got %r" % (noise_snr_db,))
+        self.noise_snr_db = (lo, hi)
+        if isinstance(noise_max_seconds, bool) or not isinstance(noise_max_seconds, (int, float)) or not (float(noise_max_seconds) > 0.0) \
+                or not math.isfinite(float(noise_max_seconds)):
+            raise ValueError("data.noise_max_seconds must be a positive number of seconds, got %r" % (noise_max_seconds,))
+        self.noise_max_seconds = float(noise_max_seconds)
+
+    @property
+    def on(self) -> bool:
+        return self.noise_manifest is not None or self.rir_manifest is not None
+
+
+def load_aug_manifest(path: str, key: str, audio_parser, max_seconds: Optional[float] = None) -> List[np.ndarray]:
+    """JSON lines with ``audio_filepath`` -> the files as 1-D f32 arrays at the parser's rate (``load_wav_rate``; a file at
+    another rate is converted with ``ops.resample``), in manifest order until ``max_seconds`` of audio is held (the file that
+    crosses the budget is cut at it).  An empty manifest is a ValueError that names the conf key."""
+    out, budget = [], None if max_seconds is None else int(max_seconds * audio_parser.sr)
+    with open(path, "r", encoding="utf-8") as f:
+        for line in f:
+            if not line.strip():
+                continue
+            if budget is not None and budget <= 0:
+                break
+            y = audio_parser.resample_to_sr(*load_wav_rate(json.loads(line)["audio_filepath"]))[0].cpu().numpy()
+            if budget is not None:
+                y = y[:budget]
+                budget -= y.size
+            if y.size:
+                out.append(np.ascontiguousarray(y, dtype=np.float32))
+    if not out:
+        raise ValueError("data.%s: %s lists no audio" % (key, path))
+    return out
+
+
+class WaveAug:
+    """noise and reverberation of the training clips (DESIGN.md "Noise and reverberation"): the draws on the parser's host
+    ``random.Random`` and the device operator, built on first use.  ``rirs`` / ``noises``: lists of 1-D f32 | int16 host arrays,
+    either may be empty (that kind is off)."""
+
+    def __init__(self, rirs, noises, rir_prob=0.3, noise_prob=0.5, noise_snr_db=(5, 20), device="cuda"):
+        cfg = WaveAugConfig(noise_prob=noise_prob, noise_snr_db=noise_snr_db, rir_prob=rir_prob)
+        self.rirs, self.noises, self.device = list(rirs), list(noises), device
+        self.rir_prob, self.noise_prob, self.snr = cfg.rir_prob, cfg.noise_prob, cfg.noise_snr_db
+        self.noise_lens = [int(len(c)) for c in self.noises]
+        self._op = None
+
+    def draw(self, rand) -> tuple:
+        """(rir_id, noise_id, noise_start, snr_cdb) of one utterance.  Drawn only when needed: u < rir_prob, the RIR's index,
+        u < noise_prob, the clip's index, randrange(len_c), round(100 * uniform(lo, hi)) - a kind that is off draws nothing,
+        an index is drawn only after its probability draw passes."""
+        rir = nid = -1
+        start = snr = 0
+        if self.rirs and rand.random() < self.rir_prob:
+            rir = rand.randrange(len(self.rirs))
+        if self.noises and rand.random() < self.noise_prob:
+            nid = rand.randrange(len(self.noises))
+            start = rand.randrange(self.noise_lens[nid])
+            snr = int(round(100.0 * rand.uniform(*self.snr)))
+        return rir, nid, start, snr
+
+    def op(self):
+        if self._op is None:
+            self._op = ops.WaveAugmenter(self.rirs, self.noises, self.device)
+        return self._op
+
+
 class AudioParser:
     """``parse_audio(path, mask) -> (1, 64, T)`` (data_module.py:150-174), computed on the GPU."""
 
@@ -96,6 +180,7 @@ class AudioParser:
         self.device = torch.device(device)
         self.speed_factors: List[Fraction] = []           # speed perturbation (LibriDataModule(speed_perturb=...)); [] = off
         self._speed_rs = None
+        self.wave_aug: Optional[WaveAug] = None            # noise / reverberation (LibriDataModule(noise_manifest=..., rir_manifest=...)); None = off
 
     # -- the two random pieces of the training-time chain, drawn on the host like the reference ----
     def sub_secquence(self, x: torch.Tensor, weight: float = 0.1) -> torch.Tensor:
@@ -132,6 +217,10 @@ class AudioParser:
         if self._speed_rs is None:
             self._speed_rs = ops.Resampler([(f.numerator, f.denominator) for f in self.speed_factors], self.device)
         return self._speed_rs
+
+    def draw_wave_aug(self) -> tuple:
+        """one utterance's (rir_id, noise_id, noise_start, snr_cdb): after its speed factor, before its SpecAugment rectangle"""
+        return self.wave_aug.draw(self.rand)
 
     def draw_spec_augment(self, n_time: int, freq_mask: Union[int, float] = 27, time_mask: Union[int, float] = 0.07):
         """(rect_x, w_x, rect_y, w_y) with the draw order of spec_augment (:97-122)."""
@@ -232,11 +321,13 @@ class AudioParser:
         return st["buf"][k][:n]
 
     def features(self, waves: Sequence[torch.Tensor], mask: bool, dither: bool = True, leads: Optional[Sequence[int]] = None,
-                 speed: Optional[Sequence[int]] = None):
+                 speed: Optional[Sequence[int]] = None, wave_aug: Optional[Sequence[tuple]] = None):
         """list of (L_i,) f32 host waves -> (inputs, input_percentages) on the GPU: padded into a reused pinned buffer, ONE H2D
         copy for the batch, then ``features_device``.  leads[i] = 1: waves[i] starts with a lead-in sample (``crop_raw``).
         speed[i]: index into ``speed_factors`` - the uploaded batch is resampled on the device (f32 -> f32) first, and the
-        SpecAugment rectangles are drawn for the resampled lengths; such waves carry no lead-in sample."""
+        SpecAugment rectangles are drawn for the resampled lengths; such waves carry no lead-in sample.
+        wave_aug[i]: (rir_id, noise_id, noise_start, snr_cdb) - reverberation and noise on the device (f32 -> f32) directly after
+        the resampler; the lengths do not change; no lead-in sample either."""
         B = len(waves)
         L = max(int(w.numel()) for w in waves)
         host = self._staging(B * L).view(B, L)
@@ -260,6 +351,10 @@ class AudioParser:
             wave, _ = self.speed_resampler()(wave, lens.to(dev), torch.tensor([int(k) for k in speed], dtype=torch.int32).to(dev),
                                              L_out=max(int(n_sig.max()), 1))
             lens = n_sig.clone()
+        if wave_aug is not None:
+            if leads is not None and any(int(l) for l in leads):
+                raise ValueError("an augmented wave cannot carry a lead-in sample")
+            wave, _, _ = self.wave_aug.op()(wave, lens.to(dev), torch.tensor([list(p) for p in wave_aug], dtype=torch.int32).to(dev))
         aug = self.draw_aug_batch(n_sig).to(dev) if mask else None
         # Tmax = the frames of the longest UTTERANCE (a row's lead-in sample is not part of it: it emits no frame of its own)
         return self.features_device(wave, lens.to(dev), aug, dither, logical_len=max(int(n_sig.max()), 1))
@@ -366,7 +461,8 @@ class WaveBatch(tuple):
 class LibriDataModule(LightningDataModule):
     def __init__(self, train_manifest, dev_manifest, test_manifest, labels: list, train_bs=16, dev_bs=16, num_worker=0,
                  train_max_duration=16.7, dev_max_duration=40, device="cuda", act_dtype=torch.float32,
-                 bucket_by_length: bool = False, bucket_batches: int = 50, train_crop: bool = True, speed_perturb=None):
+                 bucket_by_length: bool = False, bucket_batches: int = 50, train_crop: bool = True, speed_perturb=None,
+                 noise_manifest=None, noise_prob=0.5, noise_snr_db=(5, 20), noise_max_seconds=600, rir_manifest=None, rir_prob=0.3):
         super().__init__()
         as_list = lambda m: list(m) if isinstance(m, (list, tuple)) else [m]  # noqa: E731
         self.train_manifest, self.dev_manifest, self.test_manifest = as_list(train_manifest), as_list(dev_manifest), as_list(test_manifest)
@@ -383,10 +479,24 @@ class LibriDataModule(LightningDataModule):
         # per utterance, applied on the device by ops.Resampler on every route that yields training batches
         self.speed_perturb = parse_speed_factors(speed_perturb)
         self.audio_parser.speed_factors = self.speed_perturb
+        # additive noise at a drawn SNR and reverberation with a drawn RIR (conf keys data.noise_* / data.rir_*; a null manifest =
+        # that kind off): per training utterance, on the device directly after the resampler, on every route that yields training batches
+        self.wave_aug_cfg = WaveAugConfig(noise_manifest, noise_prob, noise_snr_db, noise_max_seconds, rir_manifest, rir_prob)
+
+    def setup_wave_aug(self):
+        """reads the noise and RIR manifests ONCE and hands the parser its ``WaveAug`` (with both manifests null the parser keeps
+        what it has: None unless a caller put one there)"""
+        cfg = self.wave_aug_cfg
+        if cfg.on and self.audio_parser.wave_aug is None:
+            ap = self.audio_parser
+            noises = load_aug_manifest(cfg.noise_manifest, "noise_manifest", ap, cfg.noise_max_seconds) if cfg.noise_manifest else []
+            rirs = load_aug_manifest(cfg.rir_manifest, "rir_manifest", ap) if cfg.rir_manifest else []
+            ap.wave_aug = WaveAug(rirs, noises, cfg.rir_prob, cfg.noise_prob, cfg.noise_snr_db, ap.device)
 
     def setup(self, stage=None):
         self.speed_perturb = parse_speed_factors(self.speed_perturb)     # (a list assigned after construction is checked here)
         self.audio_parser.speed_factors = self.speed_perturb
+        self.setup_wave_aug()
         self.train_datasets = MyAudioDataset(self.train_manifest, self.labels, mask=True, max_duration=self.train_max_duration)
         self.dev_datasets = MyAudioDataset(self.dev_manifest, self.labels, max_duration=self.dev_max_duration)
         self.test_datasets = MyAudioDataset(self.test_manifest, self.labels, max_duration=self.dev_max_duration)
@@ -420,7 +530,7 @@ class LibriDataModule(LightningDataModule):
     def _collate_wave(self, batch, mask: bool) -> WaveBatch:
         waves = [b[0] for b in batch]
         leads = None
-        perturb = mask and bool(getattr(self, "speed_perturb", None))
+        perturb = mask and (bool(getattr(self, "speed_perturb", None)) or getattr(self.audio_parser, "wave_aug", None) is not None)
         if mask and getattr(self, "train_crop", True):   # training-time random sub-sequence (data_module.py:158-159)
             cr = [self.audio_parser.crop_raw(w.unsqueeze(0), weight=0.98, lead_in=not perturb) for w in waves]
             waves, leads = [c[0][0] for c in cr], [c[1] for c in cr]
@@ -451,12 +561,19 @@ class LibriDataModule(LightningDataModule):
             return None
         return [self.audio_parser.draw_speed() for _ in range(n)]
 
+    def draw_wave_aug_batch(self, n: int, mask: bool):
+        """one (rir_id, noise_id, noise_start, snr_cdb) per utterance of a training batch, None when off or not training"""
+        if not (mask and getattr(self.audio_parser, "wave_aug", None) is not None):
+            return None
+        return [self.audio_parser.draw_wave_aug() for _ in range(n)]
+
     # ---- device half: ONE batched HIP mel call -> the reference's 5-tuple -------------------------
     def on_after_batch_transfer(self, batch, dataloader_idx=0):
         if not isinstance(batch, WaveBatch):
             return batch
         waves, targets, target_sizes, paths, mask = batch
         speed = self.draw_speed_batch(len(waves), mask)                 # after the crop's draws (collate), before the rectangles (features)
-        inputs, pct = self.audio_parser.features(waves, mask, leads=batch.leads, speed=speed)
+        wave_aug = self.draw_wave_aug_batch(len(waves), mask)           # after the speed factors, before the rectangles
+        inputs, pct = self.audio_parser.features(waves, mask, leads=batch.leads, speed=speed, wave_aug=wave_aug)
         dev = inputs.device
         return inputs, targets.to(dev), pct, target_sizes.to(dev), paths

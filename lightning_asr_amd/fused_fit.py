@@ -86,6 +86,13 @@ class HostWaveSource:
                 lens = torch.tensor(n_out, dtype=torch.int32)
                 n_real = sum(n_out)
                 db.L, db.pitch = longest, L
+            db.wave_aug = None
+            if mask and self.ap is not None and getattr(self.ap, "wave_aug", None) is not None:
+                # noise / reverberation: drawn here in the main process, after the speed factors; f32 -> f32, lengths unchanged
+                db.wave_aug = [self.ap.draw_wave_aug() for _ in waves]
+                if leads is not None and any(int(l) for l in leads):
+                    raise ValueError("an augmented wave cannot carry a lead-in sample")
+                db.pcm, _, _ = self.ap.wave_aug.op()(db.pcm, lens.to(self.device), torch.tensor([list(p) for p in db.wave_aug], dtype=torch.int32).to(self.device))
             db.lens, db.sizes, db.targets = lens.to(self.device), sizes.to(self.device), targets.to(self.device)
             db.aug = None
             db.paths, db.B, db.ld, db.S, db.seconds = paths, B, L, targets.shape[1], float(n_real) / SR
@@ -113,13 +120,14 @@ class NativeSource:
             audio_parser.speed_factors = parse_speed_factors(speed_perturb)
             audio_parser._speed_rs = None
         factors = list(getattr(audio_parser, "speed_factors", None) or [])
+        wave_aug = mask and getattr(audio_parser, "wave_aug", None) is not None      # noise / reverberation: training batches only
         stretch = 1.0 / float(min(factors)) if factors else 1.0          # the slowest factor makes the longest clip
         cap = int(batch_size * (int(max_seconds * SR) + 64))
-        self.ring = PinnedRing(4, cap, (10 if factors else 8) * batch_size + 2 * batch_size * 256)
+        self.ring = PinnedRing(4, cap, ((10 if factors else 8) + (4 if wave_aug else 0)) * batch_size + 2 * batch_size * 256)
         self.feeder = DeviceFeeder(self.ring, device, n_slots=4, resampler=audio_parser.speed_resampler() if factors else None,
-                                   stretch=stretch)
+                                   stretch=stretch, augmenter=audio_parser.wave_aug.op() if wave_aug else None)
         self.producer = BatchProducer(dataset, index_batches, self.ring, mask, audio_parser, n_threads=n_threads, crop=crop,
-                                      feeder=self.feeder, speed=bool(factors))
+                                      feeder=self.feeder, speed=bool(factors), wave_aug=wave_aug)
         self.mask = mask
         self.n_threads = n_threads
         self.n = len(index_batches)

@@ -14,7 +14,11 @@ The samples are scaled (1/32768), dithered, pre-emphasised and turned into log-m
 Speed perturbation (``BatchProducer(speed=...)``, conf key ``data.speed_perturb``): the producer draws one factor per utterance,
 the raw PCM goes H2D into a per-slot staging block and ``lasr_resample`` (PCM16 -> PCM16, one launch on the copy stream) writes
 the device slot's rows; every length, the row pitch and the graph key of the batch are those of the RESAMPLED clips, so nothing
-downstream changes.  Such crops carry no lead-in sample (a resampled row has no sample before it)."""
+downstream changes.  Such crops carry no lead-in sample (a resampled row has no sample before it).
+
+Noise and reverberation (``BatchProducer(wave_aug=...)``, conf keys ``data.noise_manifest`` / ``data.rir_manifest``): the producer
+draws one parameter word per utterance behind the speed tail of the metadata block, and ``lasr_wave_augment`` (PCM16 -> PCM16, on
+the copy stream, directly after the resampler) rewrites the slot's rows in place.  The lengths do not change; no lead-in samples."""
 from __future__ import annotations
 
 import ctypes as C
@@ -67,16 +71,17 @@ def read_wav_batch(paths: Sequence[str], out: torch.Tensor, lens_out: torch.Tens
 class HostBatch:
     """one batch on the host: PCM rows in ring slot ``slot`` + the packed metadata block"""
     __slots__ = ("slot", "B", "ld", "S", "lens", "sizes", "aug", "targets", "meta", "meta_words", "paths", "mask", "seconds", "index",
-                 "speed")
+                 "speed", "wave_aug")
 
 
-def _meta_layout(B: int, S: int, with_aug: bool, with_speed: bool = False):
+def _meta_layout(B: int, S: int, with_aug: bool, with_speed: bool = False, with_wave_aug: bool = False):
     """int32 word offsets of [lens B][sizes B][aug 4B]...[targets B*S int64] inside the metadata block; with speed perturbation
-    [raw lens B][conversion B] follow the targets (``lens`` then holds the resampled lengths)"""
+    [raw lens B][conversion B] follow the targets (``lens`` then holds the resampled lengths); with noise / reverberation the
+    parameter words [(rir_id, noise_id, noise_start, snr_cdb) B] come last"""
     o_lens, o_sizes, o_aug = 0, B, 2 * B
     o_tg = 2 * B + (4 * B if with_aug else 0)
     o_tg += o_tg & 1                                  # int64 view needs an even word offset
-    return o_lens, o_sizes, o_aug, o_tg, o_tg + 2 * B * S + (2 * B if with_speed else 0)
+    return o_lens, o_sizes, o_aug, o_tg, o_tg + 2 * B * S + (2 * B if with_speed else 0) + (4 * B if with_wave_aug else 0)
 
 
 class PinnedRing:
@@ -107,8 +112,9 @@ class BatchProducer(threading.Thread):
 
     def __init__(self, dataset, index_batches: Iterable[List[int]], ring: PinnedRing, mask: bool, audio_parser, n_threads: int = 8,
                  crop_weight: float = 0.98, depth: int = 2, crop: Optional[bool] = None, feeder: Optional["DeviceFeeder"] = None,
-                 speed: bool = False):
+                 speed: bool = False, wave_aug: bool = False):
         super().__init__(daemon=True)
+        self.wave_aug = bool(wave_aug) and getattr(audio_parser, "wave_aug", None) is not None   # audio_parser.draw_wave_aug() per clip
         self.speed = bool(speed) and bool(getattr(audio_parser, "speed_factors", None))   # one of audio_parser.speed_factors per clip
         self.feeder = feeder         # given: this thread also issues the H2D copies and hands over DevBatch objects
         self.ds, self.batches, self.ring, self.mask, self.ap = dataset, index_batches, ring, mask, audio_parser
@@ -168,7 +174,7 @@ class BatchProducer(threading.Thread):
         paths = [ds.datasets[i]["audio_filepath"] for i in idx]
         ids = [self._ids(i) for i in idx]
         S = max(1, max(a.size for a in ids))
-        o_lens, o_sizes, o_aug, o_tg, words = _meta_layout(B, S, self.mask, self.speed)
+        o_lens, o_sizes, o_aug, o_tg, words = _meta_layout(B, S, self.mask, self.speed, self.wave_aug)
         ring.grow(slot, meta_words=words)
         meta = ring.meta[slot]
         mnp = meta.numpy()                                   # shares the (pinned) memory
@@ -177,7 +183,7 @@ class BatchProducer(threading.Thread):
         while True:
             try:
                 ld = read_wav_batch(paths, ring.pcm[slot], lens, crop_u, self.crop_weight, self.n_threads,
-                                    lead_in=self.crop and not self.speed)
+                                    lead_in=self.crop and not self.speed and not self.wave_aug)
                 break
             except _lib.LasrError as e:
                 if "do not fit the buffer" not in str(e):
@@ -190,20 +196,30 @@ class BatchProducer(threading.Thread):
         for i, a in enumerate(ids):
             tg_np[i, :a.size] = a
         aug = None
-        speed = None
-        if self.speed:
-            # per clip: its factor (after the crop's draws above), then - below - its SpecAugment rectangle for the RESAMPLED length.
-            # The raw lengths and the conversions travel behind the targets; `lens` becomes the host-known resampled length.
+        speed = wave_aug = None
+        if self.speed or self.wave_aug:
+            # per clip: its factor (after the crop's draws above), its noise / reverberation word, then - below - its SpecAugment
+            # rectangle for the RESAMPLED length.  The raw lengths and the conversions travel behind the targets, the parameter
+            # words behind them; `lens` becomes the host-known resampled length.
             o_raw = o_tg + 2 * B * S
-            speed, rects = [], []
+            o_par = o_raw + (2 * B if self.speed else 0)
+            speed, wave_aug, rects = [] if self.speed else None, [] if self.wave_aug else None, []
             for l in lens_np:
-                speed.append(self.ap.draw_speed())
+                n_out = int(l)
+                if self.speed:
+                    speed.append(self.ap.draw_speed())
+                    n_out = self.ap.speed_out_len(int(l), speed[-1])
+                if self.wave_aug:
+                    wave_aug.append(self.ap.draw_wave_aug())
                 if self.mask:
-                    rects.append(self.ap.draw_spec_augment(1 + (self.ap.speed_out_len(int(l), speed[-1]) + 64) // 160))
-            mnp[o_raw:o_raw + B] = lens_np
-            mnp[o_raw + B:o_raw + 2 * B] = speed
-            mnp[o_lens:o_lens + B] = [self.ap.speed_out_len(int(l), k) for l, k in zip(lens_np, speed)]
-            lens_np = mnp[o_lens:o_lens + B]
+                    rects.append(self.ap.draw_spec_augment(1 + (n_out + 64) // 160))
+            if self.speed:
+                mnp[o_raw:o_raw + B] = lens_np
+                mnp[o_raw + B:o_raw + 2 * B] = speed
+                mnp[o_lens:o_lens + B] = [self.ap.speed_out_len(int(l), k) for l, k in zip(lens_np, speed)]
+                lens_np = mnp[o_lens:o_lens + B]
+            if self.wave_aug:
+                mnp[o_par:o_par + 4 * B] = np.asarray(wave_aug, dtype=np.int32).reshape(-1)
             if self.mask:
                 mnp[o_aug:o_aug + 4 * B] = np.asarray(rects, dtype=np.int32).reshape(-1)
                 aug = meta[o_aug:o_aug + 4 * B].view(B, 4)
@@ -212,7 +228,7 @@ class BatchProducer(threading.Thread):
             mnp[o_aug:o_aug + 4 * B] = np.asarray([draw(1 + (int(l) + 64) // 160) for l in lens_np], dtype=np.int32).reshape(-1)
             aug = meta[o_aug:o_aug + 4 * B].view(B, 4)
         hb = HostBatch()
-        hb.speed = speed
+        hb.speed, hb.wave_aug = speed, wave_aug
         hb.slot, hb.B, hb.ld, hb.S, hb.lens, hb.aug = slot, B, ld, S, lens, aug
         hb.sizes = meta[o_sizes:o_sizes + B]
         hb.targets = meta[o_tg:o_tg + 2 * B * S].view(torch.int64).view(B, S)
@@ -224,7 +240,7 @@ class BatchProducer(threading.Thread):
 class DevBatch:
     """one batch resident in HBM (views of a device ring slot), valid for the compute stream once ``ready`` has been waited on"""
     __slots__ = ("pcm", "lens", "sizes", "aug", "targets", "paths", "B", "ld", "S", "seconds", "ready", "dslot", "index", "key", "mask", "waited",
-                 "L", "pitch", "speed")
+                 "L", "pitch", "speed", "wave_aug")
 
 
 class DeviceFeeder:
@@ -232,9 +248,12 @@ class DeviceFeeder:
     for the compute-stream event of the step that last read the slot (``release``), copies PCM + metadata, records ``ready``;
     a helper thread returns the pinned slot to the producer once the copies are done."""
 
-    def __init__(self, ring: PinnedRing, device, n_slots: int = 3, resampler=None, stretch: float = 1.0):
+    def __init__(self, ring: PinnedRing, device, n_slots: int = 3, resampler=None, stretch: float = 1.0, augmenter=None):
         """resampler (ops.Resampler) + stretch = 1 / the smallest speed factor: batches that carry ``speed`` are resampled into
-        the device slots, which are sized for the stretched clips"""
+        the device slots, which are sized for the stretched clips.  augmenter (ops.WaveAugmenter): batches that carry ``wave_aug``
+        get noise and reverberation in place on the slot's rows, with a workspace this feeder owns"""
+        self.augmenter = augmenter
+        self.aug_ws = self.aug_out = None       # workspace / (out_lens, stats) of lasr_wave_augment, only ever touched on the copy stream
         self.ring, self.device = ring, torch.device(device)
         self.n_slots = n_slots
         self.resampler = resampler
@@ -286,6 +305,9 @@ class DeviceFeeder:
         perturbed = hb.speed is not None       # the rows are written by lasr_resample: hb.ld is the pitch of the RAW rows only
         if perturbed and self.resampler is None:
             raise RuntimeError("a speed-perturbed batch needs a DeviceFeeder built with a resampler")
+        augmented = hb.wave_aug is not None
+        if augmented and self.augmenter is None:
+            raise RuntimeError("an augmented batch needs a DeviceFeeder built with an augmenter")
         if pitch < hb.ld and not perturbed:    # (cannot happen: ld = the longest row rounded up to 8 <= 160 (T - 1) + 96)
             L_log = pitch = hb.ld
         n = hb.B * pitch
@@ -310,6 +332,13 @@ class DeviceFeeder:
         if perturbed and (self.stage[k] is None or self.stage[k].numel() < hb.B * hb.ld):
             with torch.cuda.stream(cs):         # only ever touched on the copy stream: its pool orders the old block's reuse
                 self.stage[k] = torch.empty(int(hb.B * hb.ld * 1.25) + 64, dtype=torch.int16, device=self.device)
+        if augmented:
+            need = int(_lib.load().lasr_wave_augment_workspace_bytes(hb.B, pitch))
+            if self.aug_ws is None or self.aug_ws.numel() < need or self.aug_out[0].numel() < hb.B:
+                with torch.cuda.stream(cs):
+                    self.aug_ws = torch.empty(int(need * 1.25) + 64, dtype=torch.uint8, device=self.device)
+                    self.aug_out = (torch.empty(2 * hb.B, dtype=torch.int32, device=self.device),
+                                    torch.empty(2 * hb.B, 3, dtype=torch.float64, device=self.device))
         if self._retired:
             self._retired = [(blk, ev_) for blk, ev_ in self._retired if not ev_.query()]
         if released is not None:
@@ -328,11 +357,16 @@ class DeviceFeeder:
                 mk = self.meta[k]
                 self.resampler(self.stage[k][:hb.B * hb.ld].view(hb.B, hb.ld), mk[o_raw:o_raw + hb.B], mk[o_raw + hb.B:o_raw + 2 * hb.B],
                                out=self.pcm[k][:n].view(hb.B, pitch), L_out=pitch, out_lens=mk[:hb.B])
+            if augmented:                       # directly after the resampler, in place: PCM16 -> PCM16, lengths unchanged
+                o_par = _meta_layout(hb.B, hb.S, hb.aug is not None, perturbed)[4]
+                mk, rows = self.meta[k], self.pcm[k][:n].view(hb.B, pitch)
+                self.augmenter(rows, mk[:hb.B], mk[o_par:o_par + 4 * hb.B].view(hb.B, 4), out=rows, out_lens=self.aug_out[0][:hb.B],
+                               stats=self.aug_out[1][:hb.B], workspace=self.aug_ws)
             ev = torch.cuda.Event()
             ev.record(cs)
         self._done_q.put((ev, hb.slot))
         B, S = hb.B, hb.S
-        o_lens, o_sizes, o_aug, o_tg, _ = _meta_layout(B, S, hb.aug is not None, perturbed)
+        o_lens, o_sizes, o_aug, o_tg, _ = _meta_layout(B, S, hb.aug is not None, perturbed, augmented)
         m = self.meta[k]
         db = DevBatch()
         db.pcm = self.pcm[k][:n].view(B, pitch)
@@ -343,7 +377,7 @@ class DeviceFeeder:
         db.paths, db.B, db.ld, db.S, db.seconds, db.ready, db.dslot, db.index = hb.paths, B, hb.ld, S, hb.seconds, ev, k, hb.index
         db.key = (B, pitch, S, hb.aug is not None)
         db.waited = False
-        db.speed = hb.speed
+        db.speed, db.wave_aug = hb.speed, hb.wave_aug
         return db
 
     def release(self, db: DevBatch) -> None:

@@ -8,6 +8,7 @@ import math
 import os
 from typing import NamedTuple, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -771,3 +772,138 @@ def resample(wave: torch.Tensor, sr_in: int, sr_out: int):
         r = _RESAMPLERS[key] = Resampler([(sr_in, sr_out)], w2.device)
     out, n = r(w2.contiguous())
     return (out[0] if wave.dim() == 1 else out), n
+
+
+# ---- noise and reverberation (csrc/wave_aug.hip; DESIGN.md "Noise and reverberation") ---------------------------------------
+def wave_augment_tile() -> int:
+    """outputs per workgroup of the augmentation's FIR (where its tests put their row lengths)"""
+    return int(_lib.load().lasr_wave_augment_tile())
+
+
+def wave_augment_chunk() -> int:
+    """taps the FIR stages per chunk (where its tests put their filter lengths)"""
+    return int(_lib.load().lasr_wave_augment_chunk())
+
+
+def _host_f32(a, what: str) -> np.ndarray:
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if a.ndim != 1 or a.dtype not in (np.float32, np.int16):
+        raise ValueError("%s must be a 1-D float32 or int16 host array" % what)
+    return a.astype(np.float32) / 32768.0 if a.dtype == np.int16 else np.ascontiguousarray(a)
+
+
+def rir_bank_image(rirs) -> torch.Tensor:
+    """the RIR bank image (int32 words, host) of a list of 1-D f32 | int16 arrays: header table (taps K, delay d, offset per
+    RIR; entry i at words 4 + 4 i) + taps.  LasrError naming the index for what the bank refuses (include/lasr.h)."""
+    arrs = [_host_f32(r, "an RIR") for r in rirs]
+    n = len(arrs)
+    flat = np.ascontiguousarray(np.concatenate(arrs)) if n and sum(a.size for a in arrs) else np.zeros(1, dtype=np.float32)
+    lens = (ctypes.c_int64 * max(n, 1))(*[a.size for a in arrs])
+    lib = _lib.load()
+    nbytes = lib.lasr_rir_bank_bytes(flat.ctypes.data, lens, n)
+    if not nbytes:
+        _lib.check(-1, "lasr_rir_bank_bytes")
+    host = torch.empty(nbytes // 4, dtype=torch.int32)
+    call("lasr_rir_bank_write", flat.ctypes.data, lens, n, host.data_ptr(), nbytes)
+    return host
+
+
+class WaveAugmenter:
+    """Reverberation and additive noise on the device.  ``rirs`` / ``noises``: lists of 1-D f32 or int16 host arrays (either may be
+    empty); both banks are built and uploaded ONCE, the noise held as PCM16 (f32 clips are rounded like every PCM16 store).  A call
+    augments a batch of rows, each by its own parameter word (rir_id, noise_id, noise_start, snr_cdb), -1 = off."""
+
+    def __init__(self, rirs, noises, device="cuda", noise_dtype=torch.int16):
+        """noise_dtype=torch.float32 keeps f32 clips as they are (the kernel reads either); the default is the PCM16 bank"""
+        self.device = torch.device(device)
+        if noise_dtype not in (torch.float32, torch.int16):
+            raise ValueError("WaveAugmenter: noise_dtype must be torch.float32 or torch.int16")
+        self.noise_dtype = noise_dtype
+        if self.device.type != "cuda":
+            raise _lib.LasrError("WaveAugmenter runs on the GPU only (device=%r): there is no CPU path" % (device,))
+        image = rir_bank_image(rirs)
+        self.n_rir = int(image[1])
+        self.rir_taps = [int(image[4 + 4 * i]) for i in range(self.n_rir)]
+        self.rir_delay = [int(image[5 + 4 * i]) for i in range(self.n_rir)]
+        self.rir_bank = image.to(self.device)
+        clips, off, table = [], 0, []
+        for i, c in enumerate(noises):
+            a = c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
+            if a.ndim != 1 or a.dtype not in (np.float32, np.int16) or a.size < 1:
+                raise ValueError("noise clip %d must be a non-empty 1-D float32 or int16 host array" % i)
+            if noise_dtype == torch.float32:
+                a = a.astype(np.float32) / 32768.0 if a.dtype == np.int16 else a
+            elif a.dtype != np.int16:
+                a = np.clip(np.rint(a.astype(np.float32) * np.float32(32768.0)), -32768, 32767).astype(np.int16)
+            clips.append(a)
+            table.append((off, a.size))
+            off += a.size
+        if off >= 2 ** 31:
+            raise ValueError("the noise bank holds %d samples, 2^31 or more" % off)
+        self.noise_lens = [t[1] for t in table]
+        self.noise_total = off
+        self.noise = torch.from_numpy(np.concatenate(clips) if clips else np.zeros(1, dtype=np.int16 if noise_dtype == torch.int16 else np.float32)).to(self.device)
+        self.clips = torch.tensor(table if table else [(0, 0)], dtype=torch.int32).to(self.device)
+        self.n_clips = len(table)
+        self._ws = None
+
+    def workspace(self, B: int, L: int) -> torch.Tensor:
+        """the call's workspace, grown when a larger batch arrives (never inside a graph capture: size it with an eager call)"""
+        need = int(_lib.load().lasr_wave_augment_workspace_bytes(int(B), int(L)))
+        if need == 0 and B:
+            _lib.check(-1, "lasr_wave_augment_workspace_bytes")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(int(need * 1.25) + 64, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def fir_rows(self, B: int, L: int) -> torch.Tensor:
+        """(B, L) f32 view of the workspace's y after a call with these sizes: the FIR's own output on the reverberated rows
+        (whole tiles up to each row's length; other rows hold whatever was there) - what the kernel's tests measure"""
+        pitch = -(-max(int(L), 1) // wave_augment_tile()) * wave_augment_tile()
+        return self._ws[:B * pitch * 4].view(torch.float32).view(B, pitch)[:, :L]
+
+    def __call__(self, wave: torch.Tensor, lens: Optional[torch.Tensor], params: torch.Tensor, out_dtype=None,
+                 out: Optional[torch.Tensor] = None, out_lens: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None):
+        """wave (B, L) f32 | int16 on the device (stride(1) == 1); lens (B) int32 length words (None = L); params (B, 4) int32 ->
+        (out (B, L), out_lens (B) int32, stats (B, 3) f64 = E_x, E_y, E_n).  ``out`` may be ``wave`` itself.  lens and params may
+        be HOST tensors: they are then checked (a row that is to be augmented must not carry LEN_LEAD) and uploaded; device
+        tensors are taken as they are, without a host synchronisation.  workspace: a uint8 device block of at least
+        lasr_wave_augment_workspace_bytes(B, L) bytes owned by the caller (None = this object's own)."""
+        if wave.dim() != 2 or wave.dtype not in (torch.float32, torch.int16) or not wave.is_cuda or (wave.shape[1] > 1 and wave.stride(1) != 1):
+            raise _lib.LasrError("WaveAugmenter: wave must be a (B, L) f32 or int16 device tensor with contiguous rows")
+        B, L = wave.shape
+        if params.dtype != torch.int32 or tuple(params.shape) != (B, 4):
+            raise _lib.LasrError("WaveAugmenter: params must be a (B, 4) int32 tensor")
+        if lens is None:
+            lens = torch.full((B,), L, dtype=torch.int32, device=wave.device)
+        if lens.dtype != torch.int32 or lens.numel() != B:
+            raise _lib.LasrError("WaveAugmenter: lens must be a (B,) int32 tensor")
+        if not lens.is_cuda and not params.is_cuda:
+            flagged = (lens & _lib.LEN_LEAD).bool() & ((params[:, 0] >= 0) | (params[:, 1] >= 0))
+            if bool(flagged.any()):
+                raise ValueError("an augmented wave cannot carry a lead-in sample (row %d)" % int(flagged.nonzero()[0]))
+        lens, params = lens.to(wave.device).contiguous(), params.to(wave.device).contiguous()
+        out_dtype = (out.dtype if out is not None else wave.dtype) if out_dtype is None else out_dtype
+        if out_dtype not in (torch.float32, torch.int16):
+            raise _lib.LasrError("WaveAugmenter: out_dtype must be torch.float32 or torch.int16")
+        if out is None:
+            out = torch.empty(B, max(L, 1), dtype=out_dtype, device=wave.device)[:, :L]
+        if out.dim() != 2 or out.shape[0] != B or out.shape[1] < L or out.dtype != out_dtype or not out.is_cuda or (out.shape[1] > 1 and out.stride(1) != 1):
+            raise _lib.LasrError("WaveAugmenter: out must be a (B, >= L) device tensor of out_dtype with contiguous rows")
+        in_pitch = wave.stride(0) if B > 1 else max(L, 1)
+        out_pitch = out.stride(0) if B > 1 else max(out.shape[1], L, 1)
+        if out_lens is None:
+            out_lens = torch.empty(B, dtype=torch.int32, device=wave.device)
+        elif out_lens.dtype != torch.int32 or out_lens.numel() != B or not out_lens.is_cuda or not out_lens.is_contiguous():
+            raise _lib.LasrError("WaveAugmenter: out_lens must be a contiguous (B,) int32 device tensor")
+        if stats is None:
+            stats = torch.empty(B, 3, dtype=torch.float64, device=wave.device)
+        elif stats.dtype != torch.float64 or tuple(stats.shape) != (B, 3) or not stats.is_cuda or not stats.is_contiguous():
+            raise _lib.LasrError("WaveAugmenter: stats must be a contiguous (B, 3) float64 device tensor")
+        ws = self.workspace(B, L) if workspace is None else workspace
+        code = lambda dt: _lib.WAVE_F32 if dt == torch.float32 else _lib.WAVE_PCM16  # noqa: E731
+        call("lasr_wave_augment", _p(self.rir_bank), self.rir_bank.numel(), _p(self.noise), code(self.noise_dtype), _p(self.clips), self.n_clips,
+             self.noise_total, wave.data_ptr(), code(wave.dtype), in_pitch, _p(lens), _p(params), out.data_ptr(), code(out_dtype),
+             out_pitch, L, _p(out_lens), _p(stats), B, _p(ws), ws.numel(), _stream())
+        return out[:, :L], out_lens, stats

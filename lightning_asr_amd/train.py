@@ -184,7 +184,10 @@ def main(argv=None):
                                   bucket_by_length=bool(data_cfg.get("bucket_by_length", False)),
                                   bucket_batches=int(data_cfg.get("bucket_batches", 50)),
                                   train_crop=bool(data_cfg.get("train_crop", True)),
-                                  speed_perturb=data_cfg.get("speed_perturb", None))
+                                  speed_perturb=data_cfg.get("speed_perturb", None),
+                                  noise_manifest=data_cfg.get("noise_manifest", None), noise_prob=data_cfg.get("noise_prob", 0.5),
+                                  noise_snr_db=data_cfg.get("noise_snr_db", (5, 20)), noise_max_seconds=data_cfg.get("noise_max_seconds", 600),
+                                  rir_manifest=data_cfg.get("rir_manifest", None), rir_prob=data_cfg.get("rir_prob", 0.3))
     model = LightingModule(learning_rate=tran_cfg.get("learning_rate"), weight_decay=tran_cfg.get("weight_decay"), labels=labels,
                            total_epoch=tran_cfg.get("total_epoch"), drop_rate=model_cfg.get("drop_rate"), mask=model_cfg.get("mask"),
                            use_cer=use_cer, variant=model_cfg.get("variant", "plain"), act=model_cfg.get("act", "relu"), dtype=dtype,
