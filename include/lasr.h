@@ -231,6 +231,12 @@ typedef struct {
 } lasr_bn_branch;
 int lasr_bn_finalize_partials(const lasr_bn_branch* branches, int n_branches, int64_t C, int64_t n_rows, float eps,
                               float momentum, void* stream);
+/* lasr_bn_finalize_partials + lasr_bn_act_fwd (no SE scale) in ONE launch, bf16 and C a multiple of 64: workgroups of 64 channels x
+ * a chunk of rows fold the coefficients of their own channels from the partial sums in their prologue (the finalize launch's
+ * arithmetic in the same order: the same bits) and apply them; coef / saved / stats / the running statistics of `branches` are
+ * written as lasr_bn_finalize_partials writes them.  n_branches = 2 with y2 (main, residual), 1 without; n_rows = B*T.      */
+int lasr_bn_act_fwd_partials(const lasr_bn_branch* branches, int n_branches, float eps, float momentum, const void* y,
+                             const void* y2, void* out, int dtype, int64_t B, int64_t T, int64_t C, int act, void* stream);
 
 /* nn.Dropout(p) of SeprationConv / last_cnn2 (models/QuartNet.py:26,38,149) folded into the BN-apply kernels as a counter-based
  * (Philox4x32-10) mask: forward and both backward passes regenerate it from (seed, *step, unit, element index); no mask tensor

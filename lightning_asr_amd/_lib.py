@@ -72,6 +72,7 @@ SIGNATURES = {
     "lasr_dwconv_bwd_fused": (_i32, [_p, _p, _p, _p, _p, _i32, _i64, _i64, _i64, _i32, _p, _sz, _p, _p]),
     "lasr_gemm_batch_partials": (_i32, [_p, _i32, _i32, _i32, _i32, _i32, _p, _sz, _p, _p, _p]),
     "lasr_bn_finalize_partials": (_i32, [_p, _i32, _i64, _i64, C.c_float, C.c_float, _p]),
+    "lasr_bn_act_fwd_partials": (_i32, [_p, _i32, C.c_float, C.c_float, _p, _p, _p, _i32, _i64, _i64, _i64, _i32, _p]),
     "lasr_seqsum": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _p]),
     "lasr_se_fwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p]),
     "lasr_se_bwd_workspace_bytes": (_sz, [_i64, _i64]),

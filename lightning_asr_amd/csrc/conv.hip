@@ -5,6 +5,7 @@
 // with their k-1 halo, channels ride the lanes so every global access is a full coalesced row.
 #include "common.h"
 #include "fused.h"
+#include "bn_slice.h"
 
 namespace lasr {
 
@@ -533,8 +534,11 @@ static_assert(LDI >= TIN * 2 && LDI % 16 == 0, "image pitch");
 // residual add + activation of the unit BELOW (bn_act_fwd_kernel's arithmetic, operation for operation) - from that unit's y / y2
 // and BN coefficients while the tile is staged; the tile's own rows are written to `out` on the way (the residual 1x1 conv and the
 // backward read them), halo rows are recomputed by the neighbouring tile.  One launch and one 16 MB read per unit less.
+// fin.nb != 0: coef / coef2 are not final yet - the workgroup folds the coefficients of its 64 channels from the GEMM's partial
+// sums in its prologue (bn_slice_finalize; its LDS scratch is the image block, free until phase 1) and the workgroup (by, bz) = (0, 0)
+// of every channel group leaves them in memory.
 struct DwBnIn {
-  const bf16_t* y; const bf16_t* y2; const float* coef; const float* coef2; bf16_t* out; int act;
+  const bf16_t* y; const bf16_t* y2; const float* coef; const float* coef2; bf16_t* out; int act; BnSliceIn fin;
 };
 typedef __bf16 dw_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float dw_f32x4 __attribute__((ext_vector_type(4)));
@@ -563,14 +567,39 @@ __device__ __forceinline__ void dwconv_s1_mfma_body(const bf16_t* __restrict__ x
   // the block's taps -> LDS once, as packed bf16 pair tables (reversed for the data gradient); a Toeplitz
   // fragment W[s .. s+7] is 4 consecutive dwords of TE (s even) or TO (s odd): no per-channel work in phase 2.
   // Loads are unconditional (clamped index, masked value) and all issued before the first conversion.
+  // FUSE: the BN coefficients of the thread's channel octet (tid & 7: the same in every chunk it stages)
+  float ca[8], cb[8], ca2[8], cb2[8];
+  auto bn_coefs = [&]() {
+  if (FUSE) {
+    const int ccl = min(c0 + ((tid & 7) << 3), C - 8);
+    auto ld8 = [](const float* p, float (&o)[8]) {
+      const float4 u = *reinterpret_cast<const float4*>(p), q = *reinterpret_cast<const float4*>(p + 4);
+      o[0] = u.x; o[1] = u.y; o[2] = u.z; o[3] = u.w; o[4] = q.x; o[5] = q.y; o[6] = q.z; o[7] = q.w;
+    };
+    if (bn.fin.nb) {                                    // workgroup-uniform; C % 64 == 0 (host)
+      double* s_acc = reinterpret_cast<double*>(img);
+      float* s_tab = reinterpret_cast<float*>(img + kBnSliceAccBytes);
+      const bool writer = by == 0 && bz == 0;
+      if (bn.y2) bn_slice_finalize<true>(bn.fin, C, c0, writer, s_acc, s_tab);
+      else bn_slice_finalize<false>(bn.fin, C, c0, writer, s_acc, s_tab);
+      const int o8 = (tid & 7) << 3;                    // (read before phase 1's first barrier: nobody has written the image yet)
+      ld8(s_tab + o8, ca); ld8(s_tab + kBnSliceCh + o8, cb);
+      if (bn.y2) { ld8(s_tab + 4 * kBnSliceCh + o8, ca2); ld8(s_tab + 5 * kBnSliceCh + o8, cb2); }
+    } else {
+      ld8(bn.coef + ccl, ca); ld8(bn.coef + C + ccl, cb);
+      if (bn.y2) { ld8(bn.coef2 + ccl, ca2); ld8(bn.coef2 + C + ccl, cb2); }
+    }
+  }
+  };
   if (taps) {   // workgroup-uniform: the step's precomputed tables (fused.h) - the workgroup's 64 rows are one contiguous 40 KB block
     static_assert(WROW == kDwTapRow, "tap table row");
     const uint4* src = reinterpret_cast<const uint4*>(taps + ((size_t)flip * C + c0) * WROW);
-    uint4 tv[kCB * WROW / 4 / 512];
-#pragma unroll
-    for (int it = 0; it < kCB * WROW / 4 / 512; ++it) tv[it] = src[tid + 512 * it];
-#pragma unroll
-    for (int it = 0; it < kCB * WROW / 4 / 512; ++it) reinterpret_cast<uint4*>(wsm)[tid + 512 * it] = tv[it];
+    // (five named registers, not an array: across the finalize's barriers and partial-sum loop an array stayed in scratch memory)
+    static_assert(kCB * WROW / 4 / 512 == 5, "tap table chunks per thread");
+    const uint4 tv0 = src[tid], tv1 = src[tid + 512], tv2 = src[tid + 1024], tv3 = src[tid + 1536], tv4 = src[tid + 2048];
+    bn_coefs();                                       // (a consumer-side finalize requests its partials right behind the table's loads)
+    uint4* wd = reinterpret_cast<uint4*>(wsm);
+    wd[tid] = tv0; wd[tid + 512] = tv1; wd[tid + 1024] = tv2; wd[tid + 1536] = tv3; wd[tid + 2048] = tv4;
   } else {   // (kept in front of the tile's loads: issued behind them it cost 4 us more)
     constexpr int kIt = kCB * WROW / 512;             // 20
     float f0[kIt], f1[kIt];
@@ -594,23 +623,12 @@ __device__ __forceinline__ void dwconv_s1_mfma_body(const bf16_t* __restrict__ x
                                                       // itself the scheduler interleaves them: five batches, five round trips)
 #pragma unroll
     for (int it = 0; it < kIt; ++it) wsm[tid + 512 * it] = (uint32_t)f32_to_bf16(f0[it]) | ((uint32_t)f32_to_bf16(f1[it]) << 16);
+    bn_coefs();
   }
   const int pad = k / 2, P = (pad + 7) & ~7, sh = P - pad;
   constexpr int KW = 32 * NKS;                        // = round-up-32(15 + k + sh) (host dispatch)
   const bf16_t* xb = FUSE ? nullptr : x + (size_t)b * Tlen * C;
   const int n16 = lane & 15, g4 = lane >> 4;          // MFMA lane coordinates
-  // FUSE: the BN coefficients of the thread's channel octet (tid & 7: the same in every chunk it stages)
-  float ca[8], cb[8], ca2[8], cb2[8];
-  if (FUSE) {
-    const int ccl = min(c0 + ((tid & 7) << 3), C - 8);
-    auto ld8 = [](const float* p, float (&o)[8]) {
-      const float4 u = *reinterpret_cast<const float4*>(p), q = *reinterpret_cast<const float4*>(p + 4);
-      o[0] = u.x; o[1] = u.y; o[2] = u.z; o[3] = u.w; o[4] = q.x; o[5] = q.y; o[6] = q.z; o[7] = q.w;
-    };
-    ld8(bn.coef + ccl, ca); ld8(bn.coef + C + ccl, cb);
-    if (bn.y2) { ld8(bn.coef2 + ccl, ca2); ld8(bn.coef2 + C + ccl, cb2); }
-  }
-
   DW_STAMP(0);
   constexpr int TTS = 256 * NSET;                     // output frames per time tile
   for (int tA = bz * TTS; tA < Tlen; tA += TTS * gz) {
@@ -1661,8 +1679,9 @@ extern "C" int lasr_dwconv_fwd(const void* x, const float* w, const void* addend
 }
 
 int lasr::dwconv_fwd_bn(const void* y, const float* coef, const void* y2, const float* coef2, int act, const float* w, void* out, void* u,
-                        int64_t B, int64_t T, int64_t C, int k, void* stream) {
+                        int64_t B, int64_t T, int64_t C, int k, void* stream, const lasr_bn_branch* partials_of, float eps, float momentum) {
   LASR_CHECK_ARG(y && coef && w && out && u && (!y2 || coef2), "dwconv_fwd_bn: null pointer");
+  LASR_CHECK_SHAPE(!partials_of || C % kCB == 0, "dwconv_fwd_bn: a consumer-side finalize needs C=%lld a multiple of 64", (long long)C);
   if (k < 1 || k > kMaxK || !(k & 1) || C < 8 || T <= 0 || B <= 0 || B >= 65536) return 1;
   const DwShape s = dw_shape(B, T, C, k, LASR_BF16, al16(y) && al16(y2) && al16(out) && al16(u) && al16(coef) && al16(coef2));
   // Full 512-frame tiles are one workgroup per CU in ONE round, every workgroup in the same phase at the same time: the second
@@ -1673,6 +1692,8 @@ int lasr::dwconv_fwd_bn(const void* y, const float* coef, const void* y2, const 
   const dim3 gridm((unsigned)cdiv(C, kCB), (unsigned)B, (unsigned)s.gz_d);
   DwBnIn bn;
   bn.y = (const bf16_t*)y; bn.y2 = (const bf16_t*)y2; bn.coef = coef; bn.coef2 = coef2; bn.out = (bf16_t*)out; bn.act = act;
+  memset(&bn.fin, 0, sizeof(bn.fin));
+  if (partials_of) LASR_TRY(bn_slice_in(partials_of, y2 ? 2 : 1, B * T, eps, momentum, &bn.fin));
   hipStream_t st = as_stream(stream);
   const int tok = prof_begin(LASR_PROF_DWCONV, st, 2.0 * (double)B * T * C * k, (double)B * T * C * (y2 ? 4 : 3) * 2);
   const uint32_t* taps = dw_taps_for(w, 0, C);

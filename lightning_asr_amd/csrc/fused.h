@@ -10,8 +10,15 @@ namespace lasr {
 //   u   = depthwise_conv(out, w)          (models/QuartNet.py:15-19 of the next unit)
 // coef / coef2: [2][C] (scale | shift) as lasr_bn_finalize_partials leaves them; y2 / coef2 null: no residual branch.
 // Returns 0 (launched), 1 (this shape takes no fused kernel: nothing was launched, run the two launches) or a negative error.
+// partials_of (null: coef / coef2 are final): the unit's lasr_bn_branch descriptions (one, or two with y2) when its finalize
+// was left to its consumer - every workgroup folds the coefficients of its 64 channels from the GEMM's partial sums in its prologue
+// (bn_slice.h) and one workgroup per 64 channels leaves coef / saved / stats / the running statistics in memory.
 int dwconv_fwd_bn(const void* y, const float* coef, const void* y2, const float* coef2, int act, const float* w, void* out, void* u,
-                  int64_t B, int64_t T, int64_t C, int k, void* stream);
+                  int64_t B, int64_t T, int64_t C, int k, void* stream, const lasr_bn_branch* partials_of = nullptr, float eps = 0.f,
+                  float momentum = 0.f);
+// norm.hip: the kernel argument of such a consumer (bn_slice.h) from the public branch descriptions
+struct BnSliceIn;
+int bn_slice_in(const lasr_bn_branch* branches, int n_branches, int64_t n_rows, float eps, float momentum, BnSliceIn* in);
 
 // Depthwise tap tables made ONCE per training step (round 4) instead of by every workgroup of every depthwise launch: per layer
 // [2 (flip)][C][kDwTapRow] packed bf16 pairs - the layout dwconv_s1_mfma_body keeps in LDS: row = TE[0..79] | TO[0..79] of the

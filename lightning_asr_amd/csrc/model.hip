@@ -532,8 +532,21 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
   // `pend` is the unit whose pass is still owed.  LASR_BN_DW_FUSE=0: always its own launch (A/B runs; the results are bit-identical).
   static const bool bn_dw_fuse = !(getenv("LASR_BN_DW_FUSE") && atoi(getenv("LASR_BN_DW_FUSE")) == 0);
   const Unit* pend = nullptr;
+  // The finalize of a plain / residual unit's BatchNorm statistics is left to the kernel that applies them - either consumer
+  // (the next unit's depthwise launch, or the channel-sliced apply pass) folds the coefficients of its own 64 channels from the GEMM's
+  // partial sums in its prologue.  Whether a unit's finalize is deferred is decided where its GEMM is issued, from the unit and the mode
+  // alone - never from which consumer will run.  `owed` is that unit (its partials stay in `scratch` until the next GEMM: nothing
+  // between a unit's GEMM and its consumer writes there).  LASR_BN_FWD_FINALIZE=0: the separate launch (bit-identical).
+  static const bool bn_fwd_finalize = !(getenv("LASR_BN_FWD_FINALIZE") && atoi(getenv("LASR_BN_FWD_FINALIZE")) == 0);
+  const Unit* owed = nullptr;
+  lasr_bn_branch owed_br[2];
   auto bn_act_of = [&](const Unit& v) -> int {
     ProfScope ps_bn(LASR_PROF_BN, stream, (double)N * v.co * dtype_size(dt) * (v.has_res ? 3 : 2));
+    if (owed == &v) {
+      owed = nullptr;
+      return lasr_bn_act_fwd_partials(owed_br, v.has_res ? 2 : 1, kBnEps, kBnMom, at(ws, v.o_y), v.has_res ? at(ws, v.o_y2) : nullptr,
+                                      at(ws, v.o_out), dt, B, T, v.co, v.act ? m->cfg.act : LASR_ACT_NONE, stream);
+    }
     const lasr_dropout drop = {m->drop_step, m->drop_seed, (uint32_t)(&v - m->units.data()), dropping ? m->drop_p : 0.f};
     return lasr_bn_act_fwd_drop(at(ws, v.o_y), atf(ws, v.o_coef), v.has_res ? at(ws, v.o_y2) : nullptr,
                                 v.has_res ? atf(ws, v.o_coef2) : nullptr, v.has_se ? atf(ws, v.o_se_scale) : nullptr, at(ws, v.o_out), dt, B,
@@ -566,8 +579,9 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
       if (pend) {
         fused = dwconv_fwd_bn(at(ws, pend->o_y), atf(ws, pend->o_coef), pend->has_res ? at(ws, pend->o_y2) : nullptr,
                               pend->has_res ? atf(ws, pend->o_coef2) : nullptr, pend->act ? m->cfg.act : LASR_ACT_NONE, params + u.w_dw,
-                              at(ws, pend->o_out), at(ws, u.o_u), B, T, u.ci, u.k, stream);
+                              at(ws, pend->o_out), at(ws, u.o_u), B, T, u.ci, u.k, stream, owed == pend ? owed_br : nullptr, kBnEps, kBnMom);
         if (fused < 0) return fused;
+        if (fused == 0) owed = nullptr;
         if (fused == 1) LASR_TRY(bn_act_of(*pend));     // a shape without the fused kernel: the two launches
         pend = nullptr;
       }
@@ -602,15 +616,21 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
         if (u.has_res)
           br[1] = {parts[1], tiles[1], params + u.bn_res.gamma, params + u.bn_res.beta, buffers + u.bn_res.rmean,
                    buffers + u.bn_res.rvar, atf(ws, u.o_coef2), atf(ws, u.o_saved2), stats2};
-        ProfScope ps(LASR_PROF_BN, stream, 0.0);
-        // SE units: the squeeze's per-utterance sums of y do not depend on the finalize - one launch for both (se_seqsum.h)
-        int merged = 1;
-        if (u.has_se) {
-          merged = bn_finalize_partials_seqsum(br, np, u.co, N, kBnEps, kBnMom, at(ws, u.o_y), dt, B, T, atf(ws, u.o_se_sum), stream);
-          if (merged < 0 || merged > 1) return merged;
-          se_sums_done = merged == 0;
+        if (bn_fwd_finalize && dt == LASR_BF16 && !u.has_se && !dropping && u.co % 64 == 0) {
+          owed = &u;                                      // the consumer pays (no launch, no bracket)
+          owed_br[0] = br[0];
+          owed_br[1] = br[u.has_res ? 1 : 0];
+        } else {
+          ProfScope ps(LASR_PROF_BN, stream, 0.0);
+          // SE units: the squeeze's per-utterance sums of y do not depend on the finalize - one launch for both (se_seqsum.h)
+          int merged = 1;
+          if (u.has_se) {
+            merged = bn_finalize_partials_seqsum(br, np, u.co, N, kBnEps, kBnMom, at(ws, u.o_y), dt, B, T, atf(ws, u.o_se_sum), stream);
+            if (merged < 0 || merged > 1) return merged;
+            se_sums_done = merged == 0;
+          }
+          if (merged == 1) LASR_TRY(lasr_bn_finalize_partials(br, np, u.co, N, kBnEps, kBnMom, stream));
         }
-        if (merged == 1) LASR_TRY(lasr_bn_finalize_partials(br, np, u.co, N, kBnEps, kBnMom, stream));
       } else {
         LASR_TRY(lasr_gemm_batch(pr, np, dt, dt, 0, 0, 1, scratch, p.scratch_bytes, stream));
         if (training) {   // (eval: every layer's coefficients were computed by one launch before the loop)

@@ -6,6 +6,7 @@
 #include "reduce_body.h"
 #include "se_seqsum.h"
 #include "fused.h"
+#include "bn_slice.h"
 #include "dropout.h"
 #include <algorithm>
 #include <string.h>
@@ -80,34 +81,7 @@ __global__ __launch_bounds__(256) void mask_lengths_cast_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------ BN finalize --------------
-__device__ __forceinline__ void bn_finalize_channel(float s, float q, int64_t c, const float* __restrict__ gamma,
-                                                    const float* __restrict__ beta, float* __restrict__ rmean,
-                                                    float* __restrict__ rvar, float* __restrict__ coef, float* __restrict__ saved,
-                                                    int64_t C, float n, float eps, float momentum, int training) {
-  float mean, var;
-  if (training) {
-    // sums arrive in f32; the subtraction is done in double to keep E[x^2]-E[x]^2 benign
-    const double m = (double)s / n;
-    double v = (double)q / n - m * m;
-    if (v < 0) v = 0;
-    mean = (float)m;
-    var = (float)v;
-    if (rmean) {
-      rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
-      const float unbiased = n > 1.f ? (float)(v * (double)n / ((double)n - 1.0)) : var;
-      rvar[c] = (1.f - momentum) * rvar[c] + momentum * unbiased;
-    }
-  } else {
-    mean = rmean[c];
-    var = rvar[c];
-  }
-  const float rstd = 1.0f / sqrtf(var + eps);
-  const float a = gamma[c] * rstd;
-  coef[c] = a;
-  coef[C + c] = beta[c] - mean * a;
-  if (saved) { saved[c] = mean; saved[C + c] = rstd; }
-}
-
+// (bn_finalize_channel: bn_slice.h)
 __global__ void bn_finalize_kernel(const float* __restrict__ stats, const float* __restrict__ gamma,
                                    const float* __restrict__ beta, float* __restrict__ rmean, float* __restrict__ rvar,
                                    float* __restrict__ coef, float* __restrict__ saved, int64_t C, float n, float eps,
@@ -130,32 +104,7 @@ __global__ __launch_bounds__(256) void bn_eval_coef_many_kernel(BnEvalMany a, fl
 }
 
 // ------------------------------------------------------------------ fixed-order partial sums ----
-// block = 32 columns x 8 partial lanes; each lane strides the partial rows with 4 independent sums.
-// Accumulation is f64: these sums are BatchNorm statistics and gradient reductions, and the
-// network's backward map amplifies relative noise in them by ~1e2-1e3 (measured), so f32 sums
-// of a few hundred partials cost visible gradient parity.
-// one partial lane's share of column c: rows pl, pl+8, ... in a fixed order.  The partials were written by the
-// previous kernel on other XCDs, so every load is a trip to the fabric: 16 rows are requested before the
-// first is added (a loop of 4 loads per trip exposed that latency ~16 times for 501 rows: 8.6 us per call).
-template <int LANES = 8>
-__device__ __forceinline__ double partial_lane_sum(const float* __restrict__ partials, int n_part, int64_t ncols, int64_t c, int pl) {
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  for (int p = pl; p < n_part; p += 16 * LANES) {
-    float v[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int r = p + LANES * i;
-      const float x = partials[(int64_t)min(r, n_part - 1) * ncols + c];   // clamped address, masked value: no branch around the load
-      v[i] = r < n_part ? x : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i += 4) {
-      a0 += (double)v[i]; a1 += (double)v[i + 1]; a2 += (double)v[i + 2]; a3 += (double)v[i + 3];
-    }
-  }
-  return (a0 + a1) + (a2 + a3);
-}
-
+// (partial_lane_sum: bn_slice.h)
 __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ partials, int n_part, int64_t ncols,
                                                               float* __restrict__ out0, int64_t split, float* __restrict__ out1) {
   __shared__ double s_acc[8][33];
@@ -176,12 +125,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
 // and the residual branch of a unit in ONE launch (blockIdx.y = branch): the fixed-order f64 column
 // reduction of reduce_partials_kernel and the arithmetic of bn_finalize_kernel, without the f32 round
 // trip of the statistics through HBM and without three of the four launches.
-struct BnBranch {
-  const float* partials; int n_part;
-  const float* gamma; const float* beta; float* rmean; float* rvar; float* coef; float* saved; float* stats;
-};
-struct BnBranch2 { BnBranch b[2]; };
-
+// (BnBranch / BnBranch2: bn_slice.h)
 __global__ __launch_bounds__(256) void bn_finalize_partials_kernel(BnBranch2 br, int64_t C, float n, float eps, float momentum) {
   // block = 16 channels x {sum, sumsq} = 32 columns x 8 partial lanes (the parallelism of reduce_partials_kernel)
   __shared__ double s_acc[8][33];
@@ -850,6 +794,79 @@ __global__ __launch_bounds__(512, WPE) void bn_bwd_apply_sliced_kernel(const bf1
   });
 }
 
+// ---- channel-sliced BN forward apply (bf16, plain / residual units without SE / dropout) -------------------------------------
+// The forward's "statistics -> apply, nothing in between": the unit's 1x1 GEMM leaves per-tile partial sums, and every workgroup
+// here - 64 channels x a chunk of rows, the backward pair's geometry - folds the coefficients of its own 64 channels from them in its
+// prologue (bn_slice_finalize: the finalize launch's arithmetic, so the same numbers), behind the loads of its first rows.  Row
+// chunk 0 leaves coef / saved / stats / the running statistics in memory for the backward.  The element arithmetic is
+// bn_act_fwd_kernel's, operation for operation.  block = 8 column threads (16 bytes each) x 64 row lanes, RB rows in flight.
+// WPE: waves per SIMD the register allocation leaves room for - with the residual branch the prologue's 64 partial loads in flight
+// beside the rows' need more than 128 registers (2: one workgroup per CU, as the backward's statistics pass).
+template <bool HAS2, int RB = 4, int WPE = HAS2 ? 2 : 4>
+__global__ __launch_bounds__(512, WPE) void bn_act_fwd_sliced_kernel(const bf16_t* __restrict__ y, const bf16_t* __restrict__ y2, BnSliceIn in,
+                                                                   bf16_t* __restrict__ out, int rows, int C, int act_rt, int rpc) {
+  __shared__ double s_acc[kBnSliceAccBytes / 8];
+  __shared__ __attribute__((aligned(16))) float s_tab[kBnSliceTabFloats];
+  constexpr int V = 8;
+  const int tid = threadIdx.x, cl = tid & 7, rl = tid >> 3;
+  const int c0 = blockIdx.x * kSlCh, c = c0 + cl * V;
+  const int r0 = blockIdx.y * rpc, r1 = min(r0 + rpc, rows);
+  uint4 ry[RB], rr[RB];
+  auto load_rows = [&](int base, uint4 (&dy_)[RB], uint4 (&dr_)[RB]) {
+#pragma unroll
+    for (int u = 0; u < RB; ++u) {
+      const uint32_t off = (uint32_t)min(base + rl + u * kSlLanes, rows - 1) * (uint32_t)C + (uint32_t)c;
+      dy_[u] = Vec<bf16_t>::raw(y + off);
+      if (HAS2) dr_[u] = Vec<bf16_t>::raw(y2 + off);
+    }
+  };
+  load_rows(r0, ry, rr);                                  // the chunk's first rows are on their way while the slice is finalized
+  bn_slice_finalize<HAS2>(in, C, c0, blockIdx.y == 0, s_acc, s_tab);
+  float a[V], b[V], a2[V], b2[V];
+  lds_vec8(s_tab + cl * V, a); lds_vec8(s_tab + kBnSliceCh + cl * V, b);
+  if (HAS2) { lds_vec8(s_tab + 4 * kBnSliceCh + cl * V, a2); lds_vec8(s_tab + 5 * kBnSliceCh + cl * V, b2); }
+  with_act(act_rt, [&](auto act_c) {
+  constexpr int act = decltype(act_c)::value;
+  for (int base = r0;;) {
+    const int nbase = base + RB * kSlLanes;
+    const bool more = nbase < r1;                         // workgroup-uniform
+    uint4 ny[RB], nr[RB];
+    if (more) load_rows(nbase, ny, nr);
+#pragma unroll
+    for (int u = 0; u < RB; ++u) {
+      const int r = base + rl + u * kSlLanes;
+      float v[V], w[V], o[V];
+      Vec<bf16_t>::unpack(ry[u], v);
+#pragma unroll
+      for (int j = 0; j < V; ++j) o[j] = fmaf(v[j], a[j], b[j]);
+      if (HAS2) {
+        Vec<bf16_t>::unpack(rr[u], w);
+#pragma unroll
+        for (int j = 0; j < V; ++j) o[j] += fmaf(w[j], a2[j], b2[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < V; ++j) o[j] = act_fwd(o[j], act);
+      if (r < r1) Vec<bf16_t>::store(out + (uint32_t)r * (uint32_t)C + (uint32_t)c, o);
+    }
+    if (!more) break;
+#pragma unroll
+    for (int u = 0; u < RB; ++u) { ry[u] = ny[u]; if (HAS2) rr[u] = nr[u]; }
+    base = nbase;
+  }
+  });
+}
+
+// rows per chunk of the sliced forward apply: 256 workgroups, one round of the chip - every workgroup re-reads its slice's partial sums,
+// so more of them only add L2 traffic (cfg2 rows, us per call at 256 / 512 workgroups: C = 512 plain 7.7 / 8.4, residual 10.7 / 15.3;
+// C = 1024 residual 18.6 / 20.8).  LASR_BN_FWD_SLICED=<n> sets the count.  At least one row per row lane in a chunk.
+static int bn_fwd_sliced_rpc(int64_t rows, int64_t C) {
+  static const int forced = getenv("LASR_BN_FWD_SLICED") ? atoi(getenv("LASR_BN_FWD_SLICED")) : 0;
+  const int target = forced > 0 ? forced : 256;
+  const int64_t slices = C / kSlCh;
+  const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>(target / slices, rows / kSlLanes));
+  return (int)cdiv(rows, nchunk);
+}
+
 // rows per chunk of the sliced pair for this shape (0: take the row-major kernels).  One 512-thread workgroup per CU (the
 // statistics kernel holds 222 registers per lane): 256 workgroups measured best at cfg2 (128: 2.339, 192: 2.298, 256: 2.262,
 // 384: 2.447, 512: 2.419 ms per step; row-major pair with its table launch: 2.372).  LASR_BN_SLICED=<n> sets the count, 0 disables.
@@ -1029,6 +1046,39 @@ extern "C" int lasr_bn_act_fwd_drop(const void* y, const float* coef, const void
 extern "C" int lasr_bn_act_fwd(const void* y, const float* coef, const void* y2, const float* coef2, const float* se_scale,
                                void* out, int dtype, int64_t B, int64_t T_, int64_t C, int act, void* stream) {
   return lasr_bn_act_fwd_drop(y, coef, y2, coef2, se_scale, out, dtype, B, T_, C, act, nullptr, stream);
+}
+
+// host side of BnSliceIn (bn_slice.h): the public branch descriptions of a unit whose finalize is left to its consumer
+int lasr::bn_slice_in(const lasr_bn_branch* branches, int n_branches, int64_t n_rows, float eps, float momentum, BnSliceIn* in) {
+  LASR_CHECK_ARG(branches && (n_branches == 1 || n_branches == 2) && n_rows > 0 && in, "bn_slice_in: bad argument");
+  for (int i = 0; i < 2; ++i) {
+    const lasr_bn_branch& q = branches[i < n_branches ? i : 0];
+    LASR_CHECK_ARG(q.partials && q.n_partials > 0 && q.gamma && q.beta && q.coef && (!q.running_mean || q.running_var),
+                   "bn_slice_in: null pointer");
+    in->br.b[i] = {q.partials, q.n_partials, q.gamma, q.beta, q.running_mean, q.running_var, q.coef, q.saved, q.stats};
+  }
+  in->nb = n_branches; in->n = (float)n_rows; in->eps = eps; in->momentum = momentum;
+  return 0;
+}
+
+extern "C" int lasr_bn_act_fwd_partials(const lasr_bn_branch* branches, int n_branches, float eps, float momentum, const void* y,
+                                        const void* y2, void* out, int dtype, int64_t B, int64_t T_, int64_t C, int act, void* stream) {
+  LASR_CHECK_ARG(y && out && n_branches == (y2 ? 2 : 1), "lasr_bn_act_fwd_partials: bad argument");
+  LASR_TRY(check_bn_shape("lasr_bn_act_fwd_partials", dtype, B, T_, C));
+  LASR_CHECK_SHAPE(dtype == LASR_BF16 && C % kSlCh == 0, "lasr_bn_act_fwd_partials: bf16 and C=%lld a multiple of 64 only", (long long)C);
+  LASR_CHECK_ARG(reinterpret_cast<uintptr_t>(y) % 16 == 0 && reinterpret_cast<uintptr_t>(y2) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0,
+                 "lasr_bn_act_fwd_partials: 16-byte alignment");
+  const int64_t rows = B * T_;
+  BnSliceIn in;
+  LASR_TRY(bn_slice_in(branches, n_branches, rows, eps, momentum, &in));
+  const int rpc = bn_fwd_sliced_rpc(rows, C);
+  const dim3 grid((unsigned)(C / kSlCh), (unsigned)cdiv(rows, rpc));
+  with_bool(y2 != nullptr, [&](auto h2) {
+    hipLaunchKernelGGL((bn_act_fwd_sliced_kernel<decltype(h2)::value>), grid, dim3(kSlThreads), 0, as_stream(stream), (const bf16_t*)y,
+                       (const bf16_t*)y2, in, (bf16_t*)out, (int)rows, (int)C, act, rpc);
+  });
+  LASR_LAUNCH_CHECK("bn_act_fwd_sliced_kernel");
+  return 0;
 }
 
 extern "C" size_t lasr_bn_bwd_workspace_bytes(int64_t B, int64_t T_, int64_t C) {
