@@ -222,6 +222,21 @@ class AudioParser:
         """one utterance's (rir_id, noise_id, noise_start, snr_cdb): after its speed factor, before its SpecAugment rectangle"""
         return self.wave_aug.draw(self.rand)
 
+    def perturbs(self, mask: bool) -> bool:
+        """a training batch with speed perturbation or noise / reverberation on: its clips are rewritten on the device before the
+        mel kernel sees them, so they carry no lead-in sample (a resampled row has no sample "before" it)"""
+        return bool(mask) and (bool(getattr(self, "speed_factors", None)) or getattr(self, "wave_aug", None) is not None)
+
+    def draw_speed_batch(self, n: int, mask: bool):
+        """one speed factor (index into ``speed_factors``) per utterance of a training batch, None when off or not training.  The
+        draws of a DataLoader batch are made in the main process, where the batch reaches the GPU (a worker's copy of `rand` is
+        not reseeded per worker): all factors, then all parameter words, then (``draw_aug_batch``) all rectangles"""
+        return [self.draw_speed() for _ in range(n)] if mask and getattr(self, "speed_factors", None) else None
+
+    def draw_wave_aug_batch(self, n: int, mask: bool):
+        """one (rir_id, noise_id, noise_start, snr_cdb) per utterance of a training batch, None when off or not training"""
+        return [self.draw_wave_aug() for _ in range(n)] if mask and getattr(self, "wave_aug", None) is not None else None
+
     def draw_spec_augment(self, n_time: int, freq_mask: Union[int, float] = 27, time_mask: Union[int, float] = 0.07):
         """(rect_x, w_x, rect_y, w_y) with the draw order of spec_augment (:97-122)."""
         if isinstance(freq_mask, float):
@@ -320,44 +335,53 @@ class AudioParser:
             st["buf"][k] = torch.empty(int(n * 1.25) + 1024, dtype=torch.float32).pin_memory()
         return st["buf"][k][:n]
 
-    def features(self, waves: Sequence[torch.Tensor], mask: bool, dither: bool = True, leads: Optional[Sequence[int]] = None,
-                 speed: Optional[Sequence[int]] = None, wave_aug: Optional[Sequence[tuple]] = None):
-        """list of (L_i,) f32 host waves -> (inputs, input_percentages) on the GPU: padded into a reused pinned buffer, ONE H2D
-        copy for the batch, then ``features_device``.  leads[i] = 1: waves[i] starts with a lead-in sample (``crop_raw``).
-        speed[i]: index into ``speed_factors`` - the uploaded batch is resampled on the device (f32 -> f32) first, and the
-        SpecAugment rectangles are drawn for the resampled lengths; such waves carry no lead-in sample.
-        wave_aug[i]: (rir_id, noise_id, noise_start, snr_cdb) - reverberation and noise on the device (f32 -> f32) directly after
-        the resampler; the lengths do not change; no lead-in sample either."""
+    @staticmethod
+    def check_no_lead(leads, speed, wave_aug) -> None:
+        """a wave that is resampled or augmented on the device has no sample "before" it: a lead-in sample is a caller error"""
+        kind = "a speed-perturbed" if speed is not None else "an augmented" if wave_aug is not None else None
+        if kind and leads is not None and any(int(l) for l in leads):
+            raise ValueError(kind + " wave cannot carry a lead-in sample")
+
+    def wave_chain(self, waves: Sequence[torch.Tensor], leads: Optional[Sequence[int]] = None, speed: Optional[Sequence[int]] = None,
+                   wave_aug: Optional[Sequence[tuple]] = None, device=None):
+        """list of (L_i,) f32 host waves -> (rows (B, L) f32 on the GPU, length words (B,) int32 on the host, samples per utterance):
+        padded into a reused pinned buffer, ONE H2D copy for the batch.  leads[i] = 1: waves[i] starts with a lead-in sample
+        (``crop_raw``), flagged in its length word and not counted as a sample.
+        speed[i]: index into ``speed_factors`` - the uploaded batch is resampled on the device (f32 -> f32), and every length is
+        the resampled one.  wave_aug[i]: (rir_id, noise_id, noise_start, snr_cdb) - reverberation and noise on the device
+        (f32 -> f32) directly after the resampler; the lengths do not change.  Such waves carry no lead-in sample."""
+        self.check_no_lead(leads, speed, wave_aug)
         B = len(waves)
         L = max(int(w.numel()) for w in waves)
         host = self._staging(B * L).view(B, L)
         host.zero_()
-        lens = torch.empty(B, dtype=torch.int32)
-        n_sig = torch.empty(B, dtype=torch.int32)
         for i, w in enumerate(waves):
             host[i, :w.numel()] = w.cpu() if w.is_cuda else w
-            ld = int(leads[i]) if leads is not None else 0
-            n_sig[i] = w.numel() - ld
-            lens[i] = (w.numel() - ld) | (_lib.LEN_LEAD if ld else 0)
-        dev = self.device
+        leads = [int(l) for l in leads] if leads is not None else [0] * B
+        n_out = [w.numel() - ld for w, ld in zip(waves, leads)]
+        lens = torch.tensor([n | (_lib.LEN_LEAD if ld else 0) for n, ld in zip(n_out, leads)], dtype=torch.int32)
+        dev = self.device if device is None else torch.device(device)     # where the rows go: the caller's device, else the parser's
         wave = host.to(dev, non_blocking=True)
         ev = torch.cuda.Event()
-        ev.record()
+        ev.record(torch.cuda.current_stream(dev))
         self._stage["ev"][self._stage["k"]] = ev
         if speed is not None:
-            if leads is not None and any(int(l) for l in leads):
-                raise ValueError("a speed-perturbed wave cannot carry a lead-in sample")
-            n_sig = torch.tensor([self.speed_out_len(int(n_sig[i]), int(speed[i])) for i in range(B)], dtype=torch.int32)
+            n_out = [self.speed_out_len(n, int(k)) for n, k in zip(n_out, speed)]
             wave, _ = self.speed_resampler()(wave, lens.to(dev), torch.tensor([int(k) for k in speed], dtype=torch.int32).to(dev),
-                                             L_out=max(int(n_sig.max()), 1))
-            lens = n_sig.clone()
+                                             L_out=max(max(n_out), 1))
+            lens = torch.tensor(n_out, dtype=torch.int32)
         if wave_aug is not None:
-            if leads is not None and any(int(l) for l in leads):
-                raise ValueError("an augmented wave cannot carry a lead-in sample")
             wave, _, _ = self.wave_aug.op()(wave, lens.to(dev), torch.tensor([list(p) for p in wave_aug], dtype=torch.int32).to(dev))
-        aug = self.draw_aug_batch(n_sig).to(dev) if mask else None
+        return wave, lens, n_out
+
+    def features(self, waves: Sequence[torch.Tensor], mask: bool, dither: bool = True, leads: Optional[Sequence[int]] = None,
+                 speed: Optional[Sequence[int]] = None, wave_aug: Optional[Sequence[tuple]] = None):
+        """list of (L_i,) f32 host waves -> (inputs, input_percentages) on the GPU: ``wave_chain``, the SpecAugment rectangles
+        drawn for the lengths it returns, then ``features_device``"""
+        wave, lens, n_out = self.wave_chain(waves, leads, speed, wave_aug)
+        aug = self.draw_aug_batch(n_out).to(self.device) if mask else None
         # Tmax = the frames of the longest UTTERANCE (a row's lead-in sample is not part of it: it emits no frame of its own)
-        return self.features_device(wave, lens.to(dev), aug, dither, logical_len=max(int(n_sig.max()), 1))
+        return self.features_device(wave, lens.to(self.device), aug, dither, logical_len=max(max(n_out), 1))
 
     def _act_dtype(self):
         return getattr(self, "act_dtype", torch.float32)
@@ -530,13 +554,10 @@ class LibriDataModule(LightningDataModule):
     def _collate_wave(self, batch, mask: bool) -> WaveBatch:
         waves = [b[0] for b in batch]
         leads = None
-        perturb = mask and (bool(getattr(self, "speed_perturb", None)) or getattr(self.audio_parser, "wave_aug", None) is not None)
         if mask and getattr(self, "train_crop", True):   # training-time random sub-sequence (data_module.py:158-159)
-            cr = [self.audio_parser.crop_raw(w.unsqueeze(0), weight=0.98, lead_in=not perturb) for w in waves]
+            ap = self.audio_parser
+            cr = [ap.crop_raw(w.unsqueeze(0), weight=0.98, lead_in=not ap.perturbs(mask)) for w in waves]
             waves, leads = [c[0][0] for c in cr], [c[1] for c in cr]
-        # (the speed factors themselves are drawn where the batch reaches the GPU, in the main process - on_after_batch_transfer /
-        #  HostWaveSource - next to the SpecAugment rectangles: a worker's copy of the parser's random.Random is not reseeded per
-        #  worker, so factors drawn here would repeat across workers)
         max_trans = max(len(b[1]) for b in batch)
         targets = torch.zeros(len(batch), max_trans, dtype=torch.int64)
         target_sizes = torch.zeros(len(batch), dtype=torch.int32)
@@ -556,16 +577,10 @@ class LibriDataModule(LightningDataModule):
     _collate_fn = _collate_eval
 
     def draw_speed_batch(self, n: int, mask: bool):
-        """one speed factor (index into ``speed_perturb``) per utterance of a training batch, None when off or not training"""
-        if not (mask and getattr(self, "speed_perturb", None)):
-            return None
-        return [self.audio_parser.draw_speed() for _ in range(n)]
+        return self.audio_parser.draw_speed_batch(n, mask)
 
     def draw_wave_aug_batch(self, n: int, mask: bool):
-        """one (rir_id, noise_id, noise_start, snr_cdb) per utterance of a training batch, None when off or not training"""
-        if not (mask and getattr(self.audio_parser, "wave_aug", None) is not None):
-            return None
-        return [self.audio_parser.draw_wave_aug() for _ in range(n)]
+        return self.audio_parser.draw_wave_aug_batch(n, mask)
 
     # ---- device half: ONE batched HIP mel call -> the reference's 5-tuple -------------------------
     def on_after_batch_transfer(self, batch, dataloader_idx=0):

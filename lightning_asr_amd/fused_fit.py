@@ -21,8 +21,9 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _lib, ops
-from .ingest import BatchProducer, DevBatch, DeviceFeeder, PinnedRing, SR, fast_ingest_ok
+from . import ops
+from .data_module import AudioParser, parse_speed_factors
+from .ingest import BatchProducer, DevBatch, DeviceFeeder, Layout, PinnedRing, SR, fast_ingest_ok
 from .step import GraphedTrainStep, TrainStep, graph_dp_enabled
 
 logger = logging.getLogger(__name__)
@@ -48,57 +49,26 @@ def fused_eligible(model, optimizer, scheduler) -> bool:
 
 
 class HostWaveSource:
-    """Fallback ingest for a custom dataset: the DataLoader's WaveBatch (ragged f32 waves) padded on the host and uploaded as f32.
-    With speed perturbation on (the parser holds ``speed_factors``) a training batch gets one factor per utterance here, in the
-    main process, and is resampled on the device, f32 -> f32, by the parser's ``ops.Resampler``; its lengths are then the resampled ones."""
+    """Fallback ingest for a custom dataset: the DataLoader's WaveBatch (ragged f32 waves) through ``AudioParser.wave_chain`` -
+    padded on the host, uploaded as f32 and, for a training batch of a parser that holds speed factors / a ``WaveAug``, resampled
+    and augmented on the device with one draw per utterance made here, in the main process.  No parser given (a custom
+    datamodule): a bare one of its own, which holds neither - nothing is drawn, the waves are only padded and uploaded."""
 
     def __init__(self, loader, device, limit: int, audio_parser=None):
-        self.loader, self.device, self.limit, self.ap = loader, torch.device(device), limit, audio_parser
+        self.loader, self.device, self.limit, self.ap = loader, torch.device(device), limit, audio_parser or AudioParser(device=device)
 
     def __iter__(self):
+        dev = self.device
         for k, batch in enumerate(self.loader):
             if k >= self.limit:
                 return
             waves, targets, sizes, paths, mask = batch
-            B, L = len(waves), max(int(w.numel()) for w in waves)
-            host = torch.zeros(B, L).pin_memory()
-            lens = torch.empty(B, dtype=torch.int32)
-            leads = getattr(batch, "leads", None)            # crop_raw's lead-in samples (crop after pre-emphasis, data_module.py:157-159)
-            n_real, longest = 0, 1
-            for i, w in enumerate(waves):
-                host[i, :w.numel()] = w
-                ld = int(leads[i]) if leads is not None else 0
-                lens[i] = (w.numel() - ld) | (_lib.LEN_LEAD if ld else 0)
-                n_real += w.numel() - ld
-                longest = max(longest, int(w.numel()) - ld)
-            db = DevBatch()
-            db.L, db.pitch = longest, L                      # T = the frames of the longest UTTERANCE; rows may be one lead-in sample wider
-            db.pcm = host.to(self.device, non_blocking=True)
-            db.speed = None
-            if mask and self.ap is not None and getattr(self.ap, "speed_factors", None):
-                db.speed = [self.ap.draw_speed() for _ in waves]
-                if leads is not None and any(int(l) for l in leads):
-                    raise ValueError("a speed-perturbed wave cannot carry a lead-in sample")
-                n_out = [self.ap.speed_out_len(int(w.numel()), int(k)) for w, k in zip(waves, db.speed)]
-                longest = L = max(max(n_out), 1)
-                db.pcm, _ = self.ap.speed_resampler()(db.pcm, lens.to(self.device),
-                                                      torch.tensor([int(k) for k in db.speed], dtype=torch.int32).to(self.device), L_out=L)
-                lens = torch.tensor(n_out, dtype=torch.int32)
-                n_real = sum(n_out)
-                db.L, db.pitch = longest, L
-            db.wave_aug = None
-            if mask and self.ap is not None and getattr(self.ap, "wave_aug", None) is not None:
-                # noise / reverberation: drawn here in the main process, after the speed factors; f32 -> f32, lengths unchanged
-                db.wave_aug = [self.ap.draw_wave_aug() for _ in waves]
-                if leads is not None and any(int(l) for l in leads):
-                    raise ValueError("an augmented wave cannot carry a lead-in sample")
-                db.pcm, _, _ = self.ap.wave_aug.op()(db.pcm, lens.to(self.device), torch.tensor([list(p) for p in db.wave_aug], dtype=torch.int32).to(self.device))
-            db.lens, db.sizes, db.targets = lens.to(self.device), sizes.to(self.device), targets.to(self.device)
-            db.aug = None
-            db.paths, db.B, db.ld, db.S, db.seconds = paths, B, L, targets.shape[1], float(n_real) / SR
-            db.ready, db.dslot, db.index, db.key = None, -1, k, (B, L, targets.shape[1], False)
-            db.mask, db.waited = mask, True
-            yield db
+            speed, wave_aug = self.ap.draw_speed_batch(len(waves), mask), self.ap.draw_wave_aug_batch(len(waves), mask)
+            pcm, lens, n_out = self.ap.wave_chain(waves, getattr(batch, "leads", None), speed, wave_aug, device=dev)
+            # L: T = the frames of the longest UTTERANCE; the rows may be one sample wider (crop_raw's lead-in sample)
+            yield DevBatch(pcm=pcm, lens=lens.to(dev), sizes=sizes.to(dev), targets=targets.to(dev), paths=paths, B=len(waves),
+                           S=targets.shape[1], L=max(max(n_out), 1), pitch=pcm.shape[1], ld=pcm.shape[1], seconds=float(sum(n_out)) / SR,
+                           index=k, mask=mask, speed=speed, wave_aug=wave_aug)
 
     def release(self, db) -> None:
         pass
@@ -116,14 +86,13 @@ class NativeSource:
         parser's ``speed_factors``; None = whatever the parser already holds, [] = off"""
         index_batches = list(index_batches)[:limit]
         if speed_perturb is not None:
-            from .data_module import parse_speed_factors
             audio_parser.speed_factors = parse_speed_factors(speed_perturb)
             audio_parser._speed_rs = None
         factors = list(getattr(audio_parser, "speed_factors", None) or [])
         wave_aug = mask and getattr(audio_parser, "wave_aug", None) is not None      # noise / reverberation: training batches only
         stretch = 1.0 / float(min(factors)) if factors else 1.0          # the slowest factor makes the longest clip
         cap = int(batch_size * (int(max_seconds * SR) + 64))
-        self.ring = PinnedRing(4, cap, ((10 if factors else 8) + (4 if wave_aug else 0)) * batch_size + 2 * batch_size * 256)
+        self.ring = PinnedRing(4, cap, Layout(batch_size, 256, mask, bool(factors), wave_aug).words)   # (a longer transcript grows its slot)
         self.feeder = DeviceFeeder(self.ring, device, n_slots=4, resampler=audio_parser.speed_resampler() if factors else None,
                                    stretch=stretch, augmenter=audio_parser.wave_aug.op() if wave_aug else None)
         self.producer = BatchProducer(dataset, index_batches, self.ring, mask, audio_parser, n_threads=n_threads, crop=crop,
@@ -228,9 +197,8 @@ class FusedLoop:
         steps = self.graph_steps + self.eager_steps + 1
         if self.seen[key] < 3 or self.seen[key] < 0.08 * steps or len(self.graphs) >= 16:
             return None
-        B, L, S, with_aug = key
-        g = GraphedTrainStep(self.ts, B, L, S, ragged=True, prefetch=True, want_logp=False, wave_dtype=cur.pcm.dtype,
-                             with_aug=with_aug, dither=self.dither, logical_len=cur.L)
+        g = GraphedTrainStep(self.ts, cur.B, cur.pitch, cur.S, ragged=True, prefetch=True, want_logp=False, wave_dtype=cur.pcm.dtype,
+                             with_aug=cur.aug is not None, dither=self.dither, logical_len=cur.L)
         self.graphs[key] = g
         try:
             g.targets.copy_(cur.targets)

@@ -24,6 +24,8 @@ from __future__ import annotations
 import ctypes as C
 import queue
 import threading
+from collections import namedtuple
+from dataclasses import dataclass
 from typing import Iterable, List, Optional, Sequence
 
 import numpy as np
@@ -68,20 +70,77 @@ def read_wav_batch(paths: Sequence[str], out: torch.Tensor, lens_out: torch.Tens
     return int(ld.value)
 
 
-class HostBatch:
-    """one batch on the host: PCM rows in ring slot ``slot`` + the packed metadata block"""
-    __slots__ = ("slot", "B", "ld", "S", "lens", "sizes", "aug", "targets", "meta", "meta_words", "paths", "mask", "seconds", "index",
-                 "speed", "wave_aug")
+# the regions of one metadata block as tensors (``Layout.views``): aug, params (B, 4), targets (B, S) int64; None for a region that is off
+MetaViews = namedtuple("MetaViews", "lens sizes aug targets raw_lens conv params")
 
 
-def _meta_layout(B: int, S: int, with_aug: bool, with_speed: bool = False, with_wave_aug: bool = False):
-    """int32 word offsets of [lens B][sizes B][aug 4B]...[targets B*S int64] inside the metadata block; with speed perturbation
-    [raw lens B][conversion B] follow the targets (``lens`` then holds the resampled lengths); with noise / reverberation the
-    parameter words [(rir_id, noise_id, noise_start, snr_cdb) B] come last"""
-    o_lens, o_sizes, o_aug = 0, B, 2 * B
-    o_tg = 2 * B + (4 * B if with_aug else 0)
-    o_tg += o_tg & 1                                  # int64 view needs an even word offset
-    return o_lens, o_sizes, o_aug, o_tg, o_tg + 2 * B * S + (2 * B if with_speed else 0) + (4 * B if with_wave_aug else 0)
+class Layout:
+    """int32 word offsets of the packed metadata block: [lens B][sizes B][aug 4B]...[targets B*S int64]; with speed perturbation
+    [raw_lens B][conv B] follow the targets (``lens`` then holds the resampled lengths); with noise / reverberation the parameter
+    words [params = (rir_id, noise_id, noise_start, snr_cdb) B] come last.  ``words`` is the length of the block; a region that
+    is off is empty and sits where it would begin.  ``views`` cuts a block, on the host or on the device, into the regions."""
+
+    def __init__(self, B: int, S: int, with_aug: bool, with_speed: bool = False, with_wave_aug: bool = False):
+        self.B, self.S, self.with_aug, self.with_speed, self.with_wave_aug = B, S, bool(with_aug), bool(with_speed), bool(with_wave_aug)
+        self.lens, self.sizes, self.aug = 0, B, 2 * B
+        o_tg = 2 * B + (4 * B if with_aug else 0)
+        self.targets = o_tg + (o_tg & 1)                  # int64 view needs an even word offset
+        self.raw_lens = self.targets + 2 * B * S
+        self.conv = self.raw_lens + (B if with_speed else 0)
+        self.params = self.conv + (B if with_speed else 0)
+        self.words = self.params + (4 * B if with_wave_aug else 0)
+
+    def views(self, meta: torch.Tensor) -> MetaViews:
+        B, S = self.B, self.S
+        return MetaViews(meta[self.lens:self.lens + B], meta[self.sizes:self.sizes + B],
+                         meta[self.aug:self.aug + 4 * B].view(B, 4) if self.with_aug else None,
+                         meta[self.targets:self.targets + 2 * B * S].view(torch.int64).view(B, S),
+                         meta[self.raw_lens:self.raw_lens + B] if self.with_speed else None,
+                         meta[self.conv:self.conv + B] if self.with_speed else None,
+                         meta[self.params:self.params + 4 * B].view(B, 4) if self.with_wave_aug else None)
+
+
+@dataclass(slots=True, kw_only=True, eq=False)
+class _Batch:
+    """what a batch is on either side of the H2D copy; built by keyword, a missing field is a TypeError"""
+    B: int
+    S: int
+    ld: int                               # row pitch the padding bookkeeping counts (the host reader's on the native route)
+    lens: torch.Tensor
+    sizes: torch.Tensor
+    targets: torch.Tensor
+    paths: List[str]
+    mask: bool
+    seconds: float
+    index: int
+    aug: Optional[torch.Tensor] = None    # SpecAugment rectangles (B, 4)
+    speed: Optional[list] = None          # per clip: index of its speed factor / its (rir_id, noise_id, noise_start, snr_cdb)
+    wave_aug: Optional[list] = None
+
+
+@dataclass(slots=True, kw_only=True, eq=False)
+class HostBatch(_Batch):
+    """one batch on the host: PCM rows in ring slot ``slot`` + the packed metadata block ``meta[:layout.words]``"""
+    slot: int
+    layout: Layout
+    meta: torch.Tensor
+
+
+@dataclass(slots=True, kw_only=True, eq=False)
+class DevBatch(_Batch):
+    """one batch resident in HBM, valid for the compute stream once ``ready`` has been waited on.  The rows of ``pcm`` are ``pitch``
+    samples wide; ``L`` is the logical length the frame count follows (the longest utterance, a lead-in sample not counted)"""
+    pcm: torch.Tensor
+    L: int
+    pitch: int
+    ready: Optional[torch.cuda.Event] = None        # native route only: the batch's H2D copies, and its device ring slot
+    dslot: int = -1
+    waited: bool = False
+
+    @property
+    def key(self) -> tuple:
+        """batches of equal key can replay one captured graph"""
+        return self.B, self.pitch, self.L, self.S, self.aug is not None
 
 
 class PinnedRing:
@@ -150,7 +209,6 @@ class BatchProducer(threading.Thread):
                 item = self.make(list(idx), slot, k)
                 if self.feeder is not None:
                     item = self.feeder.upload(item)
-                    item.mask = self.mask
                 if not self._put(item):
                     return
             self._put(None)
@@ -174,73 +232,49 @@ class BatchProducer(threading.Thread):
         paths = [ds.datasets[i]["audio_filepath"] for i in idx]
         ids = [self._ids(i) for i in idx]
         S = max(1, max(a.size for a in ids))
-        o_lens, o_sizes, o_aug, o_tg, words = _meta_layout(B, S, self.mask, self.speed, self.wave_aug)
-        ring.grow(slot, meta_words=words)
+        lay = Layout(B, S, self.mask, self.speed, self.wave_aug)
+        ring.grow(slot, meta_words=lay.words)
         meta = ring.meta[slot]
-        mnp = meta.numpy()                                   # shares the (pinned) memory
+        v = lay.views(meta)                                  # (a view's .numpy() shares the pinned memory)
         crop_u = np.random.uniform(0.0, 1.0, size=(B, 2)) if self.crop else None      # the two draws of sub_secquence per clip
-        lens = meta[o_lens:o_lens + B]
         while True:
-            try:
-                ld = read_wav_batch(paths, ring.pcm[slot], lens, crop_u, self.crop_weight, self.n_threads,
-                                    lead_in=self.crop and not self.speed and not self.wave_aug)
+            try:                                             # a clip that is resampled or augmented carries no lead-in sample
+                ld = read_wav_batch(paths, ring.pcm[slot], v.lens, crop_u, self.crop_weight, self.n_threads,
+                                    lead_in=self.crop and not (self.speed or self.wave_aug))
                 break
             except _lib.LasrError as e:
                 if "do not fit the buffer" not in str(e):
                     raise
                 ring.grow(slot, capacity=int(ring.pcm[slot].numel() * 1.5) + 8 * B)    # a file longer than its manifest duration
-        lens_np = mnp[o_lens:o_lens + B] & (_lib.LEN_LEAD - 1)       # (the device words keep their lead-in flags; the host counts samples)
-        mnp[o_sizes:o_sizes + B] = [a.size for a in ids]
-        tg_np = mnp[o_tg:o_tg + 2 * B * S].view(np.int64).reshape(B, S)
+        raw = v.lens.numpy() & (_lib.LEN_LEAD - 1)           # (the device words keep their lead-in flags; the host counts samples)
+        v.sizes.numpy()[:] = [a.size for a in ids]
+        tg_np = v.targets.numpy()
         tg_np[:] = 0
         for i, a in enumerate(ids):
             tg_np[i, :a.size] = a
-        aug = None
-        speed = wave_aug = None
-        if self.speed or self.wave_aug:
-            # per clip: its factor (after the crop's draws above), its noise / reverberation word, then - below - its SpecAugment
-            # rectangle for the RESAMPLED length.  The raw lengths and the conversions travel behind the targets, the parameter
-            # words behind them; `lens` becomes the host-known resampled length.
-            o_raw = o_tg + 2 * B * S
-            o_par = o_raw + (2 * B if self.speed else 0)
-            speed, wave_aug, rects = [] if self.speed else None, [] if self.wave_aug else None, []
-            for l in lens_np:
-                n_out = int(l)
-                if self.speed:
-                    speed.append(self.ap.draw_speed())
-                    n_out = self.ap.speed_out_len(int(l), speed[-1])
-                if self.wave_aug:
-                    wave_aug.append(self.ap.draw_wave_aug())
-                if self.mask:
-                    rects.append(self.ap.draw_spec_augment(1 + (n_out + 64) // 160))
-            if self.speed:
-                mnp[o_raw:o_raw + B] = lens_np
-                mnp[o_raw + B:o_raw + 2 * B] = speed
-                mnp[o_lens:o_lens + B] = [self.ap.speed_out_len(int(l), k) for l, k in zip(lens_np, speed)]
-                lens_np = mnp[o_lens:o_lens + B]
-            if self.wave_aug:
-                mnp[o_par:o_par + 4 * B] = np.asarray(wave_aug, dtype=np.int32).reshape(-1)
-            if self.mask:
-                mnp[o_aug:o_aug + 4 * B] = np.asarray(rects, dtype=np.int32).reshape(-1)
-                aug = meta[o_aug:o_aug + 4 * B].view(B, 4)
-        elif self.mask:     # spec_augment(27, 0.07) rectangles, drawn per clip in the reference's order (data_module.py:97-122,165)
-            draw = self.ap.draw_spec_augment
-            mnp[o_aug:o_aug + 4 * B] = np.asarray([draw(1 + (int(l) + 64) // 160) for l in lens_np], dtype=np.int32).reshape(-1)
-            aug = meta[o_aug:o_aug + 4 * B].view(B, 4)
-        hb = HostBatch()
-        hb.speed, hb.wave_aug = speed, wave_aug
-        hb.slot, hb.B, hb.ld, hb.S, hb.lens, hb.aug = slot, B, ld, S, lens, aug
-        hb.sizes = meta[o_sizes:o_sizes + B]
-        hb.targets = meta[o_tg:o_tg + 2 * B * S].view(torch.int64).view(B, S)
-        hb.meta, hb.meta_words, hb.paths, hb.mask, hb.index = meta, words, paths, self.mask, index
-        hb.seconds = float(lens_np.sum()) / SR
-        return hb
+        n_out, speed, wave_aug, rects = zip(*[self._draw_clip(int(l)) for l in raw])
+        if self.speed:                                       # `lens` becomes the host-known resampled length
+            v.raw_lens.numpy()[:], v.conv.numpy()[:], v.lens.numpy()[:] = raw, speed, n_out
+        if self.wave_aug:
+            v.params.numpy()[:] = wave_aug
+        if self.mask:
+            v.aug.numpy()[:] = rects
+        return HostBatch(slot=slot, B=B, ld=ld, S=S, layout=lay, meta=meta, lens=v.lens, sizes=v.sizes, aug=v.aug, targets=v.targets,
+                         paths=paths, mask=self.mask, seconds=float(sum(n_out)) / SR, index=index,
+                         speed=list(speed) if self.speed else None, wave_aug=list(wave_aug) if self.wave_aug else None)
 
-
-class DevBatch:
-    """one batch resident in HBM (views of a device ring slot), valid for the compute stream once ``ready`` has been waited on"""
-    __slots__ = ("pcm", "lens", "sizes", "aug", "targets", "paths", "B", "ld", "S", "seconds", "ready", "dslot", "index", "key", "mask", "waited",
-                 "L", "pitch", "speed", "wave_aug")
+    def _draw_clip(self, n: int):
+        """one clip of `n` samples, the native route's order of draws: speed factor (after the crop's draws), noise / reverberation
+        word, SpecAugment rectangle for the RESAMPLED length -> (that length, factor index, word, rectangle); None for what is off"""
+        k = word = rect = None
+        if self.speed:
+            k = self.ap.draw_speed()
+            n = self.ap.speed_out_len(n, k)
+        if self.wave_aug:
+            word = self.ap.draw_wave_aug()
+        if self.mask:
+            rect = self.ap.draw_spec_augment(1 + (n + 64) // 160)
+        return n, k, word, rect
 
 
 class DeviceFeeder:
@@ -310,9 +344,9 @@ class DeviceFeeder:
             raise RuntimeError("an augmented batch needs a DeviceFeeder built with an augmenter")
         if pitch < hb.ld and not perturbed:    # (cannot happen: ld = the longest row rounded up to 8 <= 160 (T - 1) + 96)
             L_log = pitch = hb.ld
-        n = hb.B * pitch
+        n, n_raw, words = hb.B * pitch, hb.B * hb.ld, hb.layout.words
         cs = self.copy_stream
-        if n > self.pcm[k].numel() or hb.meta_words > self.meta[k].numel():
+        if n > self.pcm[k].numel() or words > self.meta[k].numel():
             # A batch outgrew its slot.  The new block is allocated UNDER THE COPY STREAM: the caching allocator keeps one pool per
             # stream, so it cannot be a block the compute thread just freed with kernels still queued on the compute stream (the
             # H2D copy below is not ordered against that stream).  The outgrown block is parked while steps still in flight may be
@@ -321,17 +355,14 @@ class DeviceFeeder:
             # block of every slot until close()).
             idle = released is None or released.query()
             with torch.cuda.stream(cs):
-                if n > self.pcm[k].numel():
-                    if not idle:
-                        self._retired.append((self.pcm[k], released))
-                    self.pcm[k] = torch.empty(int(n * 1.25) + 64, dtype=torch.int16, device=self.device)
-                if hb.meta_words > self.meta[k].numel():
-                    if not idle:
-                        self._retired.append((self.meta[k], released))
-                    self.meta[k] = torch.empty(int(hb.meta_words * 1.5) + 64, dtype=torch.int32, device=self.device)
-        if perturbed and (self.stage[k] is None or self.stage[k].numel() < hb.B * hb.ld):
+                for blocks, need, room in ((self.pcm, n, 1.25), (self.meta, words, 1.5)):
+                    if need > blocks[k].numel():
+                        if not idle:
+                            self._retired.append((blocks[k], released))
+                        blocks[k] = torch.empty(int(need * room) + 64, dtype=blocks[k].dtype, device=self.device)
+        if perturbed and (self.stage[k] is None or self.stage[k].numel() < n_raw):
             with torch.cuda.stream(cs):         # only ever touched on the copy stream: its pool orders the old block's reuse
-                self.stage[k] = torch.empty(int(hb.B * hb.ld * 1.25) + 64, dtype=torch.int16, device=self.device)
+                self.stage[k] = torch.empty(int(n_raw * 1.25) + 64, dtype=torch.int16, device=self.device)
         if augmented:
             need = int(_lib.load().lasr_wave_augment_workspace_bytes(hb.B, pitch))
             if self.aug_ws is None or self.aug_ws.numel() < need or self.aug_out[0].numel() < hb.B:
@@ -343,42 +374,28 @@ class DeviceFeeder:
             self._retired = [(blk, ev_) for blk, ev_ in self._retired if not ev_.query()]
         if released is not None:
             cs.wait_event(released)             # the step that read this device slot has finished with it
+        rows = self.pcm[k][:n].view(hb.B, pitch)
         with torch.cuda.stream(cs):
-            src = self.ring.pcm[hb.slot][:hb.B * hb.ld]
+            src = self.ring.pcm[hb.slot][:n_raw]
             if perturbed:
-                self.stage[k][:hb.B * hb.ld].copy_(src, non_blocking=True)
+                self.stage[k][:n_raw].copy_(src, non_blocking=True)
             elif pitch == hb.ld:
                 self.pcm[k][:n].copy_(src, non_blocking=True)
             else:                               # rows at the host reader's pitch -> rows at the class pitch (the tail of a row is never read)
-                self.pcm[k][:n].view(hb.B, pitch)[:, :hb.ld].copy_(src.view(hb.B, hb.ld), non_blocking=True)
-            self.meta[k][:hb.meta_words].copy_(hb.meta[:hb.meta_words], non_blocking=True)
+                rows[:, :hb.ld].copy_(src.view(hb.B, hb.ld), non_blocking=True)
+            self.meta[k][:words].copy_(hb.meta[:words], non_blocking=True)
+            v = hb.layout.views(self.meta[k])   # the device block has the host block's layout
             if perturbed:                       # raw rows -> the slot's rows at the class pitch, whole rows defined (zeros past n_out)
-                o_raw = _meta_layout(hb.B, hb.S, hb.aug is not None, True)[3] + 2 * hb.B * hb.S
-                mk = self.meta[k]
-                self.resampler(self.stage[k][:hb.B * hb.ld].view(hb.B, hb.ld), mk[o_raw:o_raw + hb.B], mk[o_raw + hb.B:o_raw + 2 * hb.B],
-                               out=self.pcm[k][:n].view(hb.B, pitch), L_out=pitch, out_lens=mk[:hb.B])
+                self.resampler(self.stage[k][:n_raw].view(hb.B, hb.ld), v.raw_lens, v.conv, out=rows, L_out=pitch, out_lens=v.lens)
             if augmented:                       # directly after the resampler, in place: PCM16 -> PCM16, lengths unchanged
-                o_par = _meta_layout(hb.B, hb.S, hb.aug is not None, perturbed)[4]
-                mk, rows = self.meta[k], self.pcm[k][:n].view(hb.B, pitch)
-                self.augmenter(rows, mk[:hb.B], mk[o_par:o_par + 4 * hb.B].view(hb.B, 4), out=rows, out_lens=self.aug_out[0][:hb.B],
-                               stats=self.aug_out[1][:hb.B], workspace=self.aug_ws)
+                self.augmenter(rows, v.lens, v.params, out=rows, out_lens=self.aug_out[0][:hb.B], stats=self.aug_out[1][:hb.B],
+                               workspace=self.aug_ws)
             ev = torch.cuda.Event()
             ev.record(cs)
         self._done_q.put((ev, hb.slot))
-        B, S = hb.B, hb.S
-        o_lens, o_sizes, o_aug, o_tg, _ = _meta_layout(B, S, hb.aug is not None, perturbed, augmented)
-        m = self.meta[k]
-        db = DevBatch()
-        db.pcm = self.pcm[k][:n].view(B, pitch)
-        db.L, db.pitch = L_log, pitch
-        db.lens, db.sizes = m[o_lens:o_lens + B], m[o_sizes:o_sizes + B]
-        db.aug = m[o_aug:o_aug + 4 * B].view(B, 4) if hb.aug is not None else None
-        db.targets = m[o_tg:o_tg + 2 * B * S].view(torch.int64).view(B, S)
-        db.paths, db.B, db.ld, db.S, db.seconds, db.ready, db.dslot, db.index = hb.paths, B, hb.ld, S, hb.seconds, ev, k, hb.index
-        db.key = (B, pitch, S, hb.aug is not None)
-        db.waited = False
-        db.speed, db.wave_aug = hb.speed, hb.wave_aug
-        return db
+        return DevBatch(pcm=rows, lens=v.lens, sizes=v.sizes, targets=v.targets, paths=hb.paths, B=hb.B, S=hb.S, L=L_log, pitch=pitch,
+                        ld=hb.ld, seconds=hb.seconds, index=hb.index, mask=hb.mask, aug=v.aug, speed=hb.speed, wave_aug=hb.wave_aug,
+                        ready=ev, dslot=k)
 
     def release(self, db: DevBatch) -> None:
         """call after the last kernel that reads ``db`` has been enqueued on the current stream"""

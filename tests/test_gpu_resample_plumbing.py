@@ -200,7 +200,7 @@ def test_native_source_applies_speed_perturbation(dev, tmp_path):
         assert b["lens"].cpu().tolist() == n_out
         frames = 1 + (max(n_out) + 64) // 160
         assert b["L"] == 160 * (frames - 1) + 95 and b["pitch"] == b["L"] + 1 and b["pcm"].shape == (3, b["pitch"])
-        assert b["key"] == (3, b["pitch"], b["S"], True) and b["pcm"].dtype == torch.int16
+        assert b["key"] == (3, b["pitch"], b["L"], b["S"], True) and b["pcm"].dtype == torch.int16
         assert abs(b["seconds"] - sum(n_out) / 16000.0) < 1e-9
         rows = b["pcm"].cpu().numpy()
         for i in range(3):
@@ -234,7 +234,7 @@ def test_native_source_without_the_key_is_todays_batches(dev, tmp_path):
         assert x["speed"] is None and x["lens"].cpu().tolist() == ns
         assert x["aug"].cpu().tolist() == [list(twin.draw_spec_augment(1 + (n + 64) // 160)) for n in ns]
         frames = 1 + (max(ns) + 64) // 160
-        assert x["L"] == 160 * (frames - 1) + 95 and x["pitch"] == x["L"] + 1 and x["key"] == (3, x["pitch"], x["S"], True)
+        assert x["L"] == 160 * (frames - 1) + 95 and x["pitch"] == x["L"] + 1 and x["key"] == (3, x["pitch"], x["L"], x["S"], True)
         rows = x["pcm"].cpu().numpy()
         for i in range(3):
             assert np.array_equal(rows[i, :ns[i]], pcms[3 * bi + i])

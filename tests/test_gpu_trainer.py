@@ -288,6 +288,42 @@ def test_custom_dataset_and_overridden_step_keep_working(dev, tmp_path):
     assert tr.fused is None                                  # training_step -> loss.backward() -> Novograd.step
 
 
+def test_host_wave_source_keys_batches_by_their_logical_length(dev):
+    """rows of one width, a longest utterance of L or L - 1 samples (the widest row's lead-in sample): the two batches must not share
+    a captured graph - their keys differ - and each gets the frame count of its own L.  At a width of 16 001 both L give 101 frames;
+    at 15 936 the lead-in sample decides between 101 and 100."""
+    from lightning_asr_amd import ops
+    from lightning_asr_amd.data_module import AudioParser, WaveBatch
+    from lightning_asr_amd.fused_fit import HostWaveSource
+    assert [ops.mel_num_frames(n) for n in (16000, 16001, 15935, 15936)] == [101, 101, 100, 101]
+    g = torch.Generator().manual_seed(11)
+
+    def batch(numels, leads):
+        wb = WaveBatch(([0.1 * torch.randn(n, generator=g) for n in numels], torch.zeros(2, 3, dtype=torch.int64),
+                        torch.tensor([3, 2], dtype=torch.int32), ["a", "b"], False))
+        wb.leads = leads
+        return wb
+    # (row width, L): (16001, 16000), (16001, 16001), (15936, 15936), (15936, 15935)
+    batches = [batch([16001, 15999], [1, 0]), batch([16001, 16000], [0, 1]), batch([15936, 15000], [0, 1]), batch([15936, 15000], [1, 0])]
+    ap = AudioParser(device=str(dev))
+    got = list(HostWaveSource(batches, dev, 4, audio_parser=ap))
+    assert [(db.pitch, db.L) for db in got] == [(16001, 16000), (16001, 16001), (15936, 15936), (15936, 15935)]
+    assert [db.key for db in got] == [(2, db.pitch, db.L, 3, False) for db in got]
+    assert got[0].key != got[1].key and got[2].key != got[3].key
+    frames = [ap.features_device(db.pcm, db.lens, logical_len=db.L)[0].shape[3] for db in got]
+    assert frames == [ops.mel_num_frames(db.L) for db in got] == [101, 101, 101, 100]
+    for k, (db, wb) in enumerate(zip(got, batches)):
+        assert db.ready is None and db.dslot == -1 and db.aug is None and db.speed is None and db.wave_aug is None
+        assert tuple(db.pcm.shape) == (2, db.pitch) and db.ld == db.pitch and db.index == k and db.B == 2 and db.S == 3
+        assert db.lens.cpu().tolist() == [w.numel() - ld | (ld << 30) for w, ld in zip(wb[0], wb.leads)]
+        assert abs(db.seconds - sum(w.numel() - ld for w, ld in zip(wb[0], wb.leads)) / 16000.0) < 1e-9
+        for i, w in enumerate(wb[0]):
+            assert torch.equal(db.pcm[i, :w.numel()].cpu(), w) and not db.pcm[i, w.numel():].any()
+    # no parser given (a custom datamodule): the same batches, nothing drawn
+    for db, ref in zip(HostWaveSource(batches, dev, 4), got):
+        assert db.key == ref.key and torch.equal(db.pcm, ref.pcm) and torch.equal(db.lens, ref.lens)
+
+
 def test_rows_wider_than_the_longest_utterance_keep_the_reference_frame_count(dev, tmp_path):
     """The reference pads a batch to its longest FEATURE matrix (data_module.py:222-248): Tmax = 1 + (longest + 64) // 160.  Until
     round 5 Tmax followed the device rows' width - the longest row rounded up to 8 samples, lead-in sample included - which is one
@@ -339,6 +375,7 @@ def test_rows_wider_than_the_longest_utterance_keep_the_reference_frame_count(de
     prod = BatchProducer(DS(), [[0, 1]], ring, mask=False, audio_parser=None, n_threads=2, crop=False, feeder=feeder)
     db = feeder.upload(prod.make([0, 1], ring.free.get(), 0))
     assert db.pitch == 160 * 100 + 96 and db.L == 160 * 100 + 95 and tuple(db.pcm.shape) == (2, db.pitch) and db.key[1] == db.pitch
+    assert db.key == (2, db.pitch, db.L, db.S, False) and db.S == 2
     torch.cuda.current_stream().wait_event(db.ready)
     bft, _, frames, pct = ops.mel(db.pcm, db.lens, None, None, True, logical_len=db.L)
     feats = [R.parse_wave((x.float() / 32768.0).unsqueeze(0)) for _, x in files]

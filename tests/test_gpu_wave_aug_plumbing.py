@@ -147,7 +147,7 @@ def test_native_source_applies_noise_and_reverb(dev, tmp_path, speed):
         assert b["lens"].cpu().tolist() == n_out, "the lengths do not change"
         frames = 1 + (max(n_out) + 64) // 160
         assert b["L"] == 160 * (frames - 1) + 95 and b["pitch"] == b["L"] + 1 and b["pcm"].shape == (3, b["pitch"])
-        assert b["key"] == (3, b["pitch"], b["S"], True) and b["pcm"].dtype == torch.int16
+        assert b["key"] == (3, b["pitch"], b["L"], b["S"], True) and b["pcm"].dtype == torch.int16
         rows = b["pcm"].cpu().numpy()
         for i in range(3):
             x = pcms[3 * bi + i]
@@ -187,7 +187,7 @@ def test_without_the_keys_batches_and_library_calls_are_todays(dev, tmp_path, mo
         assert x["speed"] is None and x["wave_aug"] is None and x["lens"].cpu().tolist() == ns
         assert x["aug"].cpu().tolist() == [list(twin.draw_spec_augment(1 + (n + 64) // 160)) for n in ns]
         frames = 1 + (max(ns) + 64) // 160
-        assert x["L"] == 160 * (frames - 1) + 95 and x["pitch"] == x["L"] + 1 and x["key"] == (3, x["pitch"], x["S"], True)
+        assert x["L"] == 160 * (frames - 1) + 95 and x["pitch"] == x["L"] + 1 and x["key"] == (3, x["pitch"], x["L"], x["S"], True)
         rows = x["pcm"].cpu().numpy()
         for i in range(3):
             assert np.array_equal(rows[i, :ns[i]], pcms[3 * bi + i])

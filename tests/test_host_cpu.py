@@ -338,9 +338,10 @@ def test_batch_producer_fills_ring_slots(tmp_path):
     ref = (load_wav(ds.datasets[4]["audio_filepath"])[0] * 32768).to(torch.int16)
     assert torch.equal(pcm[1, :12000], ref) and not pcm[1, 12000:].any()
     # the packed metadata block holds the same values at the documented offsets
-    o_lens, o_sizes, o_aug, o_tg, words = ingest._meta_layout(3, 4, True)
-    assert hb.meta[o_lens:o_lens + 3].tolist() == [11000, 12000, 13000] and words == hb.meta_words
-    assert hb.meta[o_tg:o_tg + 24].view(torch.int64).view(3, 4)[2].tolist() == [0, 1, 2, 6]
+    lay = ingest.Layout(3, 4, True)
+    assert hb.meta[lay.lens:lay.lens + 3].tolist() == [11000, 12000, 13000] and lay.words == hb.layout.words
+    assert hb.meta[lay.targets:lay.targets + 24].view(torch.int64).view(3, 4)[2].tolist() == [0, 1, 2, 6]
+    assert lay.views(hb.meta).targets[2].tolist() == [0, 1, 2, 6] and lay.views(hb.meta).aug.data_ptr() == hb.aug.data_ptr()
 
 
 def test_batch_producer_hands_errors_to_the_consumer_and_grows_a_short_slot(tmp_path):
@@ -378,6 +379,71 @@ def test_batch_producer_hands_errors_to_the_consumer_and_grows_a_short_slot(tmp_
     assert ring.pcm[out[0].slot].numel() >= 2 * 20000
     out, _ = drain([[0, 1]], 2 * 20000 + 64)
     assert isinstance(out[-1], BaseException) and "cannot open" in str(out[-1])
+
+
+def _dev_batch_fields(**over):
+    import torch
+    z = torch.zeros(2, dtype=torch.int32)
+    f = dict(pcm=torch.zeros(2, 16001), lens=z, sizes=z, targets=torch.zeros(2, 3, dtype=torch.int64), paths=["a", "b"], B=2, S=3, L=16000,
+             pitch=16001, ld=16001, seconds=2.0, index=0, mask=True)
+    f.update(over)
+    return f
+
+
+def test_graph_key_holds_pitch_and_logical_length():
+    """rows of one width can hold a longest utterance of L or L - 1 samples (a lead-in sample): the frame count follows L, so such
+    batches must not share a captured graph; everything else equal, equal L means equal keys"""
+    import torch
+    from lightning_asr_amd.ingest import DevBatch
+    a, b, c = DevBatch(**_dev_batch_fields()), DevBatch(**_dev_batch_fields(L=16001)), DevBatch(**_dev_batch_fields(index=7, seconds=1.0))
+    assert a.key == (2, 16001, 16000, 3, False) and b.key == (2, 16001, 16001, 3, False)
+    assert a.key != b.key and a.key == c.key
+    d = DevBatch(**_dev_batch_fields(aug=torch.zeros(2, 4, dtype=torch.int32)))
+    assert d.key == (2, 16001, 16000, 3, True)
+    assert (a.ready, a.dslot, a.waited, a.aug, a.speed, a.wave_aug) == (None, -1, False, None, None, None)    # native-route fields default
+
+
+def test_batch_records_cannot_be_built_with_a_field_missing():
+    from lightning_asr_amd.ingest import DevBatch, HostBatch, Layout
+    for name in ("pcm", "lens", "sizes", "targets", "paths", "B", "S", "L", "pitch", "ld", "seconds", "index", "mask"):
+        f = _dev_batch_fields()
+        del f[name]
+        with pytest.raises(TypeError, match=name):
+            DevBatch(**f)
+    with pytest.raises(TypeError):
+        DevBatch(**_dev_batch_fields(no_such_field=1))
+    with pytest.raises(TypeError):
+        DevBatch()
+    f = _dev_batch_fields()
+    host = {k: f[k] for k in ("lens", "sizes", "targets", "paths", "B", "S", "ld", "seconds", "index", "mask")}
+    host.update(slot=0, layout=Layout(2, 3, False), meta=f["lens"])
+    assert HostBatch(**host).speed is None
+    for name in host:
+        with pytest.raises(TypeError, match=name):
+            HostBatch(**{k: v for k, v in host.items() if k != name})
+    with pytest.raises(AttributeError):
+        DevBatch(**f).no_such_field = 1
+
+
+def test_wave_chain_refuses_a_lead_in_sample_on_a_perturbed_wave():
+    """the one lead-in check of the f32 wave chain (AudioParser.wave_chain calls it first), without a device"""
+    from lightning_asr_amd.data_module import AudioParser
+    check = AudioParser.check_no_lead
+    with pytest.raises(ValueError, match="a speed-perturbed wave cannot carry a lead-in sample"):
+        check([0, 1], [0, 2], None)
+    with pytest.raises(ValueError, match="an augmented wave cannot carry a lead-in sample"):
+        check([1, 0], None, [(-1, -1, 0, 0)] * 2)
+    with pytest.raises(ValueError, match="a speed-perturbed wave cannot carry a lead-in sample"):
+        check([1, 0], [0, 0], [(-1, -1, 0, 0)] * 2)
+    check([0, 0], [0, 2], [(-1, -1, 0, 0)] * 2)               # no lead-in sample: fine
+    check(None, [0, 2], None)
+    check([1, 1], None, None)                                 # an unperturbed batch keeps its lead-in samples
+    ap = AudioParser.__new__(AudioParser)                     # the rule the collate follows: training batch, and either kind on
+    assert not ap.perturbs(True)
+    ap.speed_factors, ap.wave_aug = [1], None
+    assert ap.perturbs(True) and not ap.perturbs(False)
+    ap.speed_factors, ap.wave_aug = [], object()
+    assert ap.perturbs(True) and not ap.perturbs(False)
 
 
 def test_native_ingest_probes_the_manifest_before_it_takes_over(tmp_path):

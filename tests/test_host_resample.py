@@ -218,9 +218,10 @@ def test_batch_producer_draws_speed_factors(tmp_path):
     assert hb.speed == ks and hb.lens.tolist() == n_out and hb.aug.tolist() == rects
     assert n_out == [int(math.ceil(n / Fraction(str([0.9, 1.0, 1.1][k])))) for n, k in zip(ns, ks)]
     assert abs(hb.seconds - sum(n_out) / 16000.0) < 1e-9 and hb.ld == 10000
-    o_lens, o_sizes, o_aug, o_tg, words = ingest._meta_layout(3, hb.S, True, True)
-    assert words == hb.meta_words == ingest._meta_layout(3, hb.S, True)[4] + 6
-    o_raw = o_tg + 2 * 3 * hb.S
+    lay = ingest.Layout(3, hb.S, True, True)
+    assert lay.words == hb.layout.words == ingest.Layout(3, hb.S, True).words + 6
+    o_raw = lay.targets + 2 * 3 * hb.S
+    assert o_raw == lay.raw_lens and o_raw + 3 == lay.conv
     assert hb.meta[o_raw:o_raw + 3].tolist() == ns and hb.meta[o_raw + 3:o_raw + 6].tolist() == ks
     # the crop on: slices of the files, but never a lead-in sample (the flag would be a caller error on a resampled row)
     np.random.seed(0)
@@ -231,4 +232,4 @@ def test_batch_producer_draws_speed_factors(tmp_path):
     # off: the batch of before, and no speed record
     prod3 = ingest.BatchProducer(ds, [[0, 1, 2]], ring, mask=True, audio_parser=parser(3), n_threads=1, crop=False)
     hb3 = prod3.make([0, 1, 2], 0)
-    assert hb3.speed is None and hb3.lens.tolist() == ns and hb3.meta_words == ingest._meta_layout(3, hb3.S, True)[4]
+    assert hb3.speed is None and hb3.lens.tolist() == ns and hb3.layout.words == ingest.Layout(3, hb3.S, True).words

@@ -209,9 +209,11 @@ def test_batch_producer_draws_and_metadata(tmp_path):
             words.append(twin.draw_wave_aug())
             rects.append(list(twin.draw_spec_augment(1 + (n + 64) // 160)))
         assert hb.wave_aug == words and hb.lens.tolist() == n_out and hb.aug.tolist() == rects and hb.speed == (ks if speed else None)
-        base = ingest._meta_layout(3, hb.S, True, speed)[4]
-        assert hb.meta_words == ingest._meta_layout(3, hb.S, True, speed, True)[4] == base + 12
+        base = ingest.Layout(3, hb.S, True, speed).words
+        lay = ingest.Layout(3, hb.S, True, speed, True)
+        assert hb.layout.words == lay.words == base + 12 and lay.params == base
         assert hb.meta[base:base + 12].view(3, 4).tolist() == [list(w) for w in words]
+        assert lay.views(hb.meta).params.tolist() == [list(w) for w in words]
     # the crop on: never a lead-in sample
     np.random.seed(0)
     hb2 = ingest.BatchProducer(ds, [[0, 1, 2]], ring, mask=True, audio_parser=parser(3), n_threads=1, crop=True, wave_aug=True).make([0, 1, 2], 0)
@@ -220,14 +222,20 @@ def test_batch_producer_draws_and_metadata(tmp_path):
     blocks = []
     for kw, aug in ((dict(), False), (dict(wave_aug=True), False), (dict(wave_aug=False), True)):
         hb3 = ingest.BatchProducer(ds, [[0, 1, 2]], ring, mask=True, audio_parser=parser(9, aug=aug), n_threads=1, crop=False, **kw).make([0, 1, 2], 0)
-        assert hb3.wave_aug is None and hb3.speed is None and hb3.meta_words == ingest._meta_layout(3, hb3.S, True)[4]
-        blocks.append(hb3.meta[:hb3.meta_words].numpy().tobytes())
+        assert hb3.wave_aug is None and hb3.speed is None and hb3.layout.words == ingest.Layout(3, hb3.S, True).words
+        blocks.append(hb3.meta[:hb3.layout.words].numpy().tobytes())
     twin = parser(9, aug=False)
     rects = [list(twin.draw_spec_augment(1 + (n + 64) // 160)) for n in ns]
-    o_lens, o_sizes, o_aug, o_tg, words = ingest._meta_layout(3, 2, True)
-    want = np.zeros(words, dtype=np.int32)
-    want[o_lens:o_lens + 3], want[o_sizes:o_sizes + 3] = ns, [2, 2, 2]
-    want[o_aug:o_aug + 12] = np.asarray(rects, dtype=np.int32).reshape(-1)
-    want[o_tg:o_tg + 12].view(np.int64)[:] = [0, 1] * 3
+    lay = ingest.Layout(3, 2, True)
+    want = np.zeros(lay.words, dtype=np.int32)
+    want[lay.lens:lay.lens + 3], want[lay.sizes:lay.sizes + 3] = ns, [2, 2, 2]
+    want[lay.aug:lay.aug + 12] = np.asarray(rects, dtype=np.int32).reshape(-1)
+    want[lay.targets:lay.targets + 12].view(np.int64)[:] = [0, 1] * 3
     assert blocks[0] == blocks[1] == blocks[2] == want.tobytes()
-    assert ingest._meta_layout(5, 7, True) == (0, 5, 10, 30, 100) and ingest._meta_layout(5, 7, False, True) == (0, 5, 10, 10, 90)
+
+    def offsets(*a):
+        lay = ingest.Layout(*a)
+        return lay.lens, lay.sizes, lay.aug, lay.targets, lay.words, lay.raw_lens, lay.conv, lay.params
+    assert offsets(5, 7, True)[:5] == (0, 5, 10, 30, 100) and offsets(5, 7, False, True)[:5] == (0, 5, 10, 10, 90)
+    assert offsets(5, 7, False, True)[5:] == (80, 85, 90) and offsets(5, 7, True, False, True)[4:] == (120, 100, 100, 100)
+    assert offsets(5, 7, True, True, True) == (0, 5, 10, 30, 130, 100, 105, 110)

@@ -16,7 +16,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 from lightning_asr_amd import ops  # noqa: E402
 from lightning_asr_amd.data_module import AudioParser, MyAudioDataset  # noqa: E402
-from lightning_asr_amd.ingest import BatchProducer, DeviceFeeder, PinnedRing, SR  # noqa: E402
+from lightning_asr_amd.ingest import BatchProducer, DeviceFeeder, Layout, PinnedRing, SR  # noqa: E402
 
 
 def main():
@@ -35,7 +35,7 @@ def main():
     out = {}
     for nt in [int(x) for x in a.threads.split(",")]:
         idx = [list(range(i * a.batch, (i + 1) * a.batch)) for i in range(a.batches)]
-        ring = PinnedRing(4, a.batch * (int(10.0 * SR) + 64), 8 * a.batch + 2 * a.batch * 256)
+        ring = PinnedRing(4, a.batch * (int(10.0 * SR) + 64), Layout(a.batch, 256, True).words)
         feeder = DeviceFeeder(ring, dev, n_slots=4)
         prod = BatchProducer(ds, idx, ring, True, parser, n_threads=nt, feeder=feeder)
         dd = ops.DeviceDither(1, dev)
