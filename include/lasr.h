@@ -25,14 +25,15 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 108   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 109   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
                               105: lasr_ctc_align_workspace_bytes / lasr_ctc_align (CTC forced alignment)
                               106: lasr_arpa_load_words / lasr_arpa_lexicon_info / lasr_ctc_beam_decode_wlm (word-level LM)
                               107: lasr_resample_* (sample-rate conversion, speed perturbation)
-                              108: lasr_rir_bank_* / lasr_wave_augment* (noise and reverberation augmentation) */
+                              108: lasr_rir_bank_* / lasr_wave_augment* (noise and reverberation augmentation)
+                              109: lasr_edit_align_workspace_bytes / lasr_edit_align_batch (substitution/deletion/insertion alignment) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -687,6 +688,34 @@ int lasr_ctc_loss_lean(const void* logits, int64_t ldc, const float* row_stat, c
 int lasr_edit_distance_batch(const int32_t* hyp_tokens, const int32_t* hyp_lens, int64_t ld_hyp, const int64_t* ref_tokens,
                              const int32_t* ref_lens, int64_t ld_ref, int64_t B, int space_id, int32_t* dist, int32_t* ref_units,
                              int64_t* totals, void* stream);
+
+/* The alignment behind lasr_edit_distance_batch: which errors the distance is made of (what sclite, Kaldi's align-text and
+ * jiwer print; the reference reports the total only).  Inputs, units (token ids, or words through the same 64-bit hash) and
+ * limits are those of lasr_edit_distance_batch; dist / ref_units (B) i32 are bit-equal to what it writes.
+ *   An alignment is a script of LASR_EDIT_HIT (a hypothesis unit paired with an equal reference unit), LASR_EDIT_SUB (paired
+ *   with a different one), LASR_EDIT_DEL (a reference unit with no hypothesis unit), LASR_EDIT_INS (a hypothesis unit with no
+ *   reference unit).  Several scripts of minimum cost usually exist and their counts differ ("a b" against "b a": two
+ *   substitutions, or insertion + hit + deletion), so ONE is defined, in hypothesis / reference terms - not in terms of which
+ *   side the kernel happens to lay along the wave: with D[i][j] the distance of the first i hypothesis units to the first j
+ *   reference units, walk from (n_hyp, n_ref) back to (0, 0) and take at every cell the first that applies of
+ *     1. diagonal:  i > 0, j > 0 and D[i-1][j-1] + (h_i != r_j) == D[i][j]   (a hit or a substitution),
+ *     2. deletion:  j > 0 and D[i][j-1] + 1 == D[i][j],
+ *     3. insertion: D[i-1][j] + 1 == D[i][j];
+ *   the script is reported forwards, from the start of the utterance.
+ * counts (B, 4) i32 = hits, substitutions, deletions, insertions; ops (B, ld_ops) u8 = the script, LASR_EDIT_PAD past n_ops[b];
+ * n_ops (B) i32; ld_ops >= ld_hyp + ld_ref.
+ * totals (may be NULL): i64[6] += sums of dist, ref_units, hits, substitutions, deletions, insertions.
+ * confusion (may be NULL; token units only - LASR_E_ARG with space_id >= 0): (n_classes + 1) x (n_classes + 1) i32, += 1 at
+ *   [reference label][hypothesis label] for every op, index n_classes standing for "none" (row n_classes: insertions, column
+ *   n_classes: deletions, hits on the diagonal); an op with a token id outside [0, n_classes) is left out of the matrix.
+ * workspace: lasr_edit_align_workspace_bytes = B * min(ld_hyp, ld_ref) * 64 * 8 (one 2-bit back-pointer per DP cell, a u64 per
+ *   lane and DP row), rounded up to 256.  Nothing is allocated or synchronised; a refused call launches nothing.           */
+enum { LASR_EDIT_HIT = 0, LASR_EDIT_SUB = 1, LASR_EDIT_DEL = 2, LASR_EDIT_INS = 3, LASR_EDIT_PAD = 255 };
+size_t lasr_edit_align_workspace_bytes(int64_t B, int64_t ld_hyp, int64_t ld_ref);
+int lasr_edit_align_batch(const int32_t* hyp_tokens, const int32_t* hyp_lens, int64_t ld_hyp, const int64_t* ref_tokens,
+                          const int32_t* ref_lens, int64_t ld_ref, int64_t B, int space_id, int32_t* dist, int32_t* ref_units,
+                          int32_t* counts, uint8_t* ops, int64_t ld_ops, int32_t* n_ops, int64_t* totals, int32_t* confusion,
+                          int n_classes, void* workspace, size_t workspace_bytes, void* stream);
 
 /* One training step's logged scalars (train.py:79-81: self.log('train_loss', loss) / self.log('train_wer', wer), on_step +
  * on_epoch) folded into DEVICE accumulators, so logging costs no D2H per step: with wer = sum(dist) / sum(ref_units) of the batch

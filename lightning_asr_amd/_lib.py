@@ -155,6 +155,8 @@ SIGNATURES = {
     "lasr_ctc_lean_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "lasr_ctc_loss_lean": (_i32, [_p, _i64, _p, _p, _i32, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "lasr_edit_distance_batch": (_i32, [_p, _p, _i64, _p, _p, _i64, _i64, _i32, _p, _p, _p, _p]),
+    "lasr_edit_align_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "lasr_edit_align_batch": (_i32, [_p, _p, _i64, _p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _i32, _p, _sz, _p]),
     "lasr_step_metrics": (_i32, [_p, _p, _p, _i64, _p, _p]),
     "lasr_wav_info": (_i32, [C.c_char_p, C.POINTER(_i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lasr_wav_read_batch": (_i32, [_p, _i64, _p, C.c_double, _p, _i64, C.POINTER(_i64), _p, C.c_int32, _i32, _i32]),

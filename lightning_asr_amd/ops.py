@@ -670,6 +670,49 @@ def edit_distance_batch(tokens: torch.Tensor, n_tokens: torch.Tensor, targets: t
     return dist, units
 
 
+EDIT_HIT, EDIT_SUB, EDIT_DEL, EDIT_INS, EDIT_PAD = 0, 1, 2, 3, 255      # LASR_EDIT_* (include/lasr.h)
+
+
+class EditOps(NamedTuple):
+    dist: torch.Tensor           # (B,) i32 Levenshtein distance, bit-equal to edit_distance_batch
+    ref_units: torch.Tensor      # (B,) i32 reference units
+    counts: torch.Tensor         # (B, 4) i32 hits, substitutions, deletions, insertions
+    ops: torch.Tensor            # (B, T + S) u8 the script forwards (EDIT_HIT / SUB / DEL / INS), EDIT_PAD past n_ops
+    n_ops: torch.Tensor          # (B,) i32 length of the script
+
+
+def edit_ops_batch(tokens: torch.Tensor, n_tokens: torch.Tensor, targets: torch.Tensor, target_lens: torch.Tensor,
+                   space_id: int = -1, totals: Optional[torch.Tensor] = None, confusion: Optional[torch.Tensor] = None) -> EditOps:
+    """edit_distance_batch with the alignment behind the distance (include/lasr.h lasr_edit_align_batch: the canonical script -
+    diagonal before deletion before insertion, walking back from the end): same inputs, same dist / ref_units.  ``totals`` (6)
+    i64, if given, is incremented by the sums of dist, ref_units, hits, subs, dels, ins; ``confusion`` (n_classes + 1,
+    n_classes + 1) i32, token units only, is incremented at [reference label][hypothesis label], index n_classes = none.
+    One launch (two with totals), nothing synchronised."""
+    if tokens.dim() != 2 or tokens.dtype != torch.int32 or targets.dim() != 2 or targets.dtype != torch.int64 \
+            or targets.shape[0] != tokens.shape[0]:
+        raise ValueError("edit_ops_batch takes tokens (B, T) int32 and targets (B, S) int64")
+    B, T, S = tokens.shape[0], tokens.shape[1], targets.shape[1]
+    for name, t in (("n_tokens", n_tokens), ("target_lens", target_lens)):
+        if t.shape != (B,) or t.dtype != torch.int32:
+            raise ValueError("edit_ops_batch: %s must be (B,) int32" % name)
+    if totals is not None and (totals.dtype != torch.int64 or totals.numel() < 6):
+        raise TypeError("totals must hold 6 int64 values")
+    n_classes = 0
+    if confusion is not None:
+        if confusion.dim() != 2 or confusion.shape[0] != confusion.shape[1] or confusion.shape[0] < 2 or confusion.dtype != torch.int32:
+            raise TypeError("confusion must be a square (n_classes + 1, n_classes + 1) int32 matrix")
+        n_classes = confusion.shape[0] - 1
+    dev = tokens.device
+    out = EditOps(torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+                  torch.empty(B, 4, dtype=torch.int32, device=dev), torch.empty(B, T + S, dtype=torch.uint8, device=dev),
+                  torch.empty(B, dtype=torch.int32, device=dev))
+    nb = int(_lib.load().lasr_edit_align_workspace_bytes(B, T, S))
+    ws = _ws(nb, dev)
+    call("lasr_edit_align_batch", _p(tokens), _p(n_tokens), T, _p(targets), _p(target_lens), S, B, int(space_id), _p(out.dist),
+         _p(out.ref_units), _p(out.counts), _p(out.ops), T + S, _p(out.n_ops), _p(totals), _p(confusion), n_classes, _p(ws), nb, _stream())
+    return out
+
+
 def step_metrics(loss: torch.Tensor, dist: torch.Tensor, units: torch.Tensor, acc: torch.Tensor) -> None:
     """fold one step's loss and batch WER into the device accumulators acc (7 f64): see lasr_step_metrics"""
     if acc.dtype != torch.float64 or acc.numel() < 7:

@@ -2,6 +2,7 @@
 manifest evaluation, on the HIP path (mel front-end, eval-mode model forward, greedy CTC decode - or, with
 ``decoder="beam"``, the CTC prefix beam search of beam_search.py, fused with an n-gram LM when ``lm_path`` names a text ARPA
 file: a character LM, or - the labels having exactly one " ", as EN_LABELS has - a word LM with its lexicon).
+``error_report`` splits a manifest's WER / CER into substitutions, deletions and insertions (``ops.edit_ops_batch``: the aligned reference and hypothesis of every utterance, the most confused pairs).
 ``align`` / ``translate_timed`` / ``align_manifest`` add word timings: the CTC forced alignment of a known transcript (or of the decoder's own hypothesis) to the audio, ``ops.ctc_align`` + the record functions of align.py.
 
 The checkpoint is the PL-style dict the reference's ``ModelCheckpoint`` writes and ``Trainer`` here
@@ -14,6 +15,7 @@ import json
 import math
 import os
 import time
+from collections import Counter
 from typing import List, Optional, Tuple
 
 import torch
@@ -24,7 +26,7 @@ from .lightning_compat import Trainer
 from .train import LightingModule
 from . import ops
 from .beam_search import BeamSearchDecoderWithLM
-from .utils.asr_metrics import WER, word_error_rate
+from .utils.asr_metrics import WER, _alignment, _edit_ops, word_error_rate
 
 EN_LABELS = [" ", "'"] + [chr(ord("a") + i) for i in range(26)]
 
@@ -160,6 +162,93 @@ class AsrTranslator:
                          "path": batch[-1]})
         model.test_epoch_end(outs)
         return outs
+
+    # ------------------------------------------------------------------------------------------ error breakdown
+    @torch.no_grad()
+    def error_report(self, manifest: str, out_path: str, batch_size: int = 32, decoder: Optional[str] = None, top: int = 20) -> dict:
+        """evalute_manifest's loop with the alignment behind every distance (``ops.edit_ops_batch``: the canonical script of
+        include/lasr.h - diagonal before deletion before insertion).  Units are the model metric's: words, or characters for a
+        ``use_cer`` checkpoint.  Writes one JSON line per utterance to out_path - audio_filepath, ref, hyp, dist, hits, subs,
+        dels, ins, alignment = [[ref unit or null, hyp unit or null, op], ...] with op 0 hit / 1 substitution / 2 deletion /
+        3 insertion - and returns the summary: utterances, use_cer, dist, ref_units, hits, subs, dels, ins, wer, sub_rate,
+        del_rate, ins_rate, top_substitutions [[ref, hyp, count], ...], top_deletions [[ref, count], ...], top_insertions
+        [[hyp, count], ...] (the ``top`` most frequent of each).  The totals are accumulated on the device and read once; over
+        characters the confusion counts come from the device matrix, over words (hashes on the device) from the scripts."""
+        decoder = self.decoder if decoder is None else decoder
+        if decoder not in ("greedy", "beam"):
+            raise ValueError("decoder must be 'greedy' or 'beam', got %r" % (decoder,))
+        if self.resample:
+            self._require_16k(manifest, "error_report")
+        model = self.model
+        dev = model.encoder.native.device
+        dm = LibriDataModule(train_manifest=manifest, dev_manifest=manifest, test_manifest=manifest, dev_bs=batch_size, num_worker=0,
+                             labels=self.labels, device=str(dev), act_dtype=model.encoder.native.act_dtype)
+        trainer = Trainer(gpus=1, device=str(dev))
+        model.trainer = trainer
+        model.eval()
+        dm.trainer = trainer
+        dm.setup("test")
+        loader = dm.test_dataloader()
+        wer = model.wer
+        n_cls = len(self.labels)
+        totals = torch.zeros(6, dtype=torch.int64, device=dev)
+        confusion = torch.zeros(n_cls + 1, n_cls + 1, dtype=torch.int32, device=dev) if wer.use_cer and wer.device_ok else None
+        host_totals = [0] * 6
+        pairs = {1: Counter(), 2: Counter(), 3: Counter()}          # op -> Counter of (ref unit, hyp unit), from the scripts
+        records = []
+        for batch in trainer._eval_batches(loader, dm, len(loader)):
+            out, _, t_lengths, trans, trans_lengths = model._shared(batch)
+            if decoder == "beam":
+                tokens, n, _ = self.beam.search(out, t_lengths, 1)
+                tokens, n = tokens[:, 0, :].contiguous(), n[:, 0].clamp(min=0).contiguous()
+            else:
+                tokens, n = ops.greedy_decode(model.encoder.last_argmax.to(torch.int32).contiguous(), t_lengths.contiguous(), wer.blank_id)
+            t_np, n_np = tokens.cpu().numpy(), n.cpu().numpy()
+            hyps = ["".join(self.labels[int(c)] for c in t_np[b, :n_np[b]]) for b in range(t_np.shape[0])]
+            refs = wer.decode_reference(trans, trans_lengths)
+            scripts = None
+            if wer.device_path(tokens, trans):
+                res = ops.edit_ops_batch(tokens, n, trans.to(dev, torch.int64).contiguous(), trans_lengths.to(dev, torch.int32).contiguous(),
+                                         wer.space_id, totals, confusion)
+                script_np, len_np = res.ops.cpu().numpy(), res.n_ops.cpu().numpy()
+                scripts = [script_np[b, :len_np[b]].tolist() for b in range(len(hyps))]
+            for b, path in enumerate(batch[-1]):
+                h_units, r_units = (list(hyps[b]), list(refs[b])) if wer.use_cer else (hyps[b].split(), refs[b].split())
+                if scripts is None:
+                    script = _edit_ops(h_units, r_units)
+                    cnt = [script.count(k) for k in range(4)]
+                    for k, v in enumerate([cnt[1] + cnt[2] + cnt[3], len(r_units)] + cnt):
+                        host_totals[k] += v
+                else:
+                    script = scripts[b]
+                alignment = _alignment(h_units, r_units, script)
+                if confusion is None or scripts is None:
+                    for r_u, h_u, op in alignment:
+                        if op:
+                            pairs[op][(r_u, h_u)] += 1
+                cnt = [script.count(k) for k in range(4)]
+                records.append({"audio_filepath": path, "ref": refs[b], "hyp": hyps[b], "dist": cnt[1] + cnt[2] + cnt[3], "hits": cnt[0],
+                                "subs": cnt[1], "dels": cnt[2], "ins": cnt[3], "alignment": alignment})
+        with open(out_path, "w", encoding="utf-8") as f:
+            for rec in records:
+                f.write(json.dumps(rec, ensure_ascii=False) + "\n")
+        if confusion is not None:                                    # one read of the device matrix: its non-zero cells
+            idx = confusion.nonzero().tolist()
+            for (r_i, h_i), v in zip(idx, confusion[confusion != 0].tolist()):
+                if r_i != h_i:
+                    op = 3 if r_i == n_cls else 2 if h_i == n_cls else 1
+                    pairs[op][(None if r_i == n_cls else self.labels[r_i], None if h_i == n_cls else self.labels[h_i])] += v
+        dist, units, hits, subs, dels, ins = [a + b for a, b in zip(totals.tolist(), host_totals)]
+
+        def ranked(op):
+            return sorted(pairs[op].items(), key=lambda kv: (-kv[1], str(kv[0][0]), str(kv[0][1])))[:max(int(top), 0)]
+
+        rate = (lambda v: v / units) if units else (lambda v: float("inf") if v else float("nan"))
+        return {"utterances": len(records), "use_cer": bool(wer.use_cer), "dist": dist, "ref_units": units, "hits": hits, "subs": subs,
+                "dels": dels, "ins": ins, "wer": rate(dist), "sub_rate": rate(subs), "del_rate": rate(dels), "ins_rate": rate(ins),
+                "top_substitutions": [[r_u, h_u, v] for (r_u, h_u), v in ranked(1)],
+                "top_deletions": [[r_u, v] for (r_u, _), v in ranked(2)],
+                "top_insertions": [[h_u, v] for (_, h_u), v in ranked(3)]}
 
     # ------------------------------------------------------------------------------------------ forced alignment
     def frame_seconds(self) -> float:
