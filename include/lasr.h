@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 109   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 110   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
@@ -33,7 +33,8 @@ extern "C" {
                               106: lasr_arpa_load_words / lasr_arpa_lexicon_info / lasr_ctc_beam_decode_wlm (word-level LM)
                               107: lasr_resample_* (sample-rate conversion, speed perturbation)
                               108: lasr_rir_bank_* / lasr_wave_augment* (noise and reverberation augmentation)
-                              109: lasr_edit_align_workspace_bytes / lasr_edit_align_batch (substitution/deletion/insertion alignment) */
+                              109: lasr_edit_align_workspace_bytes / lasr_edit_align_batch (substitution/deletion/insertion alignment)
+                              110: lasr_dwconv_plan (which depthwise kernel form and grid a shape takes; launches nothing) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -199,6 +200,25 @@ int lasr_dwconv_wgrad_partials(const void* x, const void* dy, int dtype, int64_t
 int lasr_dwconv_bwd_fused(const void* x, const void* dy, const float* w, const void* addend, void* dx, int dtype,
                           int64_t B, int64_t T, int64_t C, int k, void* workspace, size_t workspace_bytes,
                           int* n_partials, void* stream);
+/* Verification hook: the kernel forms and grids lasr_dwconv_fwd / lasr_dwconv_wgrad / lasr_dwconv_bwd_fused choose for a shape in
+ * this process (the LASR_DW* switches are read once per process), computed by the launchers' own dispatch code.  Launches nothing.
+ * Operands are taken as 16-byte aligned, the workspace as lasr_dwconv_wgrad_workspace_bytes sizes it.  Fields that do not apply to
+ * the chosen form are 0 (bwd_form: -1 for stride 2, which has no data-gradient form).  Same argument errors as the launchers. */
+enum { LASR_DW_FWD_STRIDED = 0, LASR_DW_FWD_F32 = 1, LASR_DW_FWD_MFMA = 2, LASR_DW_FWD_VALU = 3, LASR_DW_FWD_FMA = 4 };
+enum { LASR_DW_WGRAD_STRIDED = 0, LASR_DW_WGRAD_VALU = 1, LASR_DW_WGRAD_MFMA = 2 };
+enum { LASR_DW_BWD_TWO_LAUNCHES = 0, LASR_DW_BWD_TWO_KIND = 1, LASR_DW_BWD_UNI32 = 2, LASR_DW_BWD_UNI64 = 3 };
+typedef struct {
+  int32_t fwd_form;          /* LASR_DW_FWD_*: forward and (flip = 1) data gradient */
+  int32_t nks, nset, gz_d;   /* MFMA forward: 32-wide K steps, 256-frame sets per time tile (1 = half tiles), gridDim.z */
+  int32_t fwd_r;             /* strided forward: outputs per thread, 4 (64-frame tiles) or 8 */
+  int32_t wgrad_form;        /* LASR_DW_WGRAD_* */
+  int32_t zsplit;            /* MFMA weight gradient: time splits per utterance */
+  int32_t ts;                /* VALU stride-1 weight gradient: time splits per workgroup (1..3) */
+  int32_t bwd_form;          /* LASR_DW_BWD_*: what lasr_dwconv_bwd_fused launches */
+  int32_t bwd_gz, bwd_tiles; /* unified backward: workgroups per utterance and channel group, 256-frame tiles per utterance */
+  int32_t bwd_wgs, bwd_wgs_launched;   /* unified backward: workgroups with work, and gridDim.x (padded to groups of 16) */
+} lasr_dwconv_plan_info;
+int lasr_dwconv_plan(int64_t B, int64_t T, int64_t C, int k, int stride, int dtype, lasr_dwconv_plan_info* plan);
 
 /* lasr_gemm_batch that leaves each problem's BN partial sums UNREDUCED in the workspace (no split-K):
  * for every problem with stats != NULL, stat_partials[i] points at [stat_tiles[i]][2][N] f32 inside

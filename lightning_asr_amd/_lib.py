@@ -30,6 +30,17 @@ class WaveSrc(C.Structure):
 WAVE_F32, WAVE_PCM16 = 0, 1
 
 
+class DwconvPlan(C.Structure):
+    """lasr_dwconv_plan_info: the depthwise kernel forms and grids a shape takes (verification hook)"""
+    _fields_ = [(n, C.c_int32) for n in ("fwd_form", "nks", "nset", "gz_d", "fwd_r", "wgrad_form", "zsplit", "ts", "bwd_form", "bwd_gz",
+                                         "bwd_tiles", "bwd_wgs", "bwd_wgs_launched")]
+
+
+DW_FWD = ("strided", "f32", "mfma", "valu", "fma")
+DW_WGRAD = ("strided", "valu", "mfma")
+DW_BWD = ("two_launches", "two_kind", "uni32", "uni64")
+
+
 class ModelConfig(C.Structure):
     _fields_ = [("variant", C.c_int32), ("n_class", C.c_int32), ("in_c", C.c_int32),
                 ("mask", C.c_int32), ("act", C.c_int32), ("dtype", C.c_int32)]
@@ -70,6 +81,7 @@ SIGNATURES = {
     "lasr_gemm_multi_split_partials": (_i32, [_p, _i32, _i32, _p, _p, _p]),
     "lasr_dwconv_wgrad_partials": (_i32, [_p, _p, _i32, _i64, _i64, _i64, _i32, _i32, _p, _sz, _p, _p]),
     "lasr_dwconv_bwd_fused": (_i32, [_p, _p, _p, _p, _p, _i32, _i64, _i64, _i64, _i32, _p, _sz, _p, _p]),
+    "lasr_dwconv_plan": (_i32, [_i64, _i64, _i64, _i32, _i32, _i32, _p]),
     "lasr_gemm_batch_partials": (_i32, [_p, _i32, _i32, _i32, _i32, _i32, _p, _sz, _p, _p, _p]),
     "lasr_bn_finalize_partials": (_i32, [_p, _i32, _i64, _i64, C.c_float, C.c_float, _p]),
     "lasr_bn_act_fwd_partials": (_i32, [_p, _i32, C.c_float, C.c_float, _p, _p, _p, _i32, _i64, _i64, _i64, _i32, _p]),
@@ -217,3 +229,15 @@ def check(rc: int, what: str) -> None:
 def call(name: str, *args) -> None:
     """Call an int-returning entry point and raise on a non-zero status."""
     check(getattr(load(), name)(*args), name)
+
+
+def dwconv_plan(B: int, T: int, Cc: int, k: int, stride: int = 1, dtype: int = BF16) -> dict:
+    """lasr_dwconv_plan as a dict (the form codes of include/lasr.h by name): what the depthwise launchers choose for this shape
+    under this process's switches.  Launches nothing and needs no GPU."""
+    p = DwconvPlan()
+    call("lasr_dwconv_plan", B, T, Cc, k, stride, dtype, C.byref(p))
+    d = {n: int(getattr(p, n)) for n, _ in DwconvPlan._fields_}
+    d["fwd_form"] = DW_FWD[d["fwd_form"]]
+    d["wgrad_form"] = DW_WGRAD[d["wgrad_form"]]
+    d["bwd_form"] = DW_BWD[d["bwd_form"]] if d["bwd_form"] >= 0 else "none"
+    return d

@@ -515,7 +515,10 @@ __global__ __launch_bounds__(256) void dwconv_s1_bf16_kernel(const bf16_t* __res
 // Workgroup = 64 channels x one utterance (512-frame time tiles), 512 threads, wave = channel octet.
 namespace dwm {
 static constexpr int TT = 512;            // output frames per time tile (2 MFMA sets of 256)
-static constexpr int KWMAX = 128;         // input window per 16-frame block, max (k <= 101)
+static constexpr int KWMAX = 128;         // input window per 16-frame block, max: 15 + k + sh <= 128 holds for every odd k <= 113 (k = 113:
+                                          // sh = 0, exactly 128; 115: sh = 7).  The MFMA weight gradient's k + sh <= 112 ends at k = 111, so
+                                          // 113 pairs the MFMA forward with the VALU weight gradient and 115 ... 127 are all VALU
+                                          // (tests/test_gpu_dwconv.py walks 101 ... 127 bit for bit)
 static constexpr int TIN = TT - 16 + KWMAX;   // 624 staged frames at most
 static constexpr int LDI = 1296;          // bytes per channel row of the frame-contiguous image: a multiple of 16 (the B fragments are
                                           // 16-byte reads; at 1288 = 2 mod 32 dwords the 8-byte transposition writes were conflict-free but
@@ -1624,6 +1627,51 @@ static int with_dw_tile(const DwShape& s, F&& f) {
 }
 static bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
+// The stride-1 backward of a shape: which launch lasr_dwconv_bwd_fused makes, and the unified kernel's grid.
+enum { kDwBwdTwoLaunches = 0, kDwBwdTwoKind = 1, kDwBwdUni32 = 2, kDwBwdUni64 = 3 };
+struct DwBwdGrid {
+  int form;       // kDwBwd*
+  int cb;         // channels per workgroup of the unified kernel
+  int gx;         // channel groups
+  int gz;         // workgroups that share an utterance's time tiles
+  int n_tiles;    // 256-frame tiles per utterance
+  int total;      // workgroups with work
+  int launched;   // gridDim.x: `total` rounded up to whole groups of 16 (the kernel's workgroup-id permutation works on those)
+};
+// `ws_ok`: the caller's workspace holds the weight-gradient partials.  One launch needs BOTH MFMA forms (any VALU switch means the two
+// launches, each with its own fall-back).
+static DwBwdGrid dw_bwd_grid(const DwShape& s, int64_t B, int64_t T, int64_t C, int k, bool ws_ok) {
+  const DwSwitches& sw = dw_switches();
+  DwBwdGrid g{};
+  g.form = kDwBwdTwoLaunches;
+  if (sw.no_fused_bwd || !s.fwd || !s.wgrad || !ws_ok) return g;
+  // The unified kernel's weight gradient reads dY[u - m], m = 0..15, from the image it shares with the data gradient, whose first
+  // frame is t = tA - P (P = round-up-8(k/2)): the 15 frames in front of the tile are only there from P = 16 on, i.e. k >= 19.
+  // Narrower windows (none in the model, whose k start at 33) take the two-kind grid, whose weight-gradient workgroups stage
+  // their own dY image with a 16-frame lead.
+  const bool uni_ok = ((k / 2 + 7) & ~7) >= 16;
+  if (!(sw.uni == 64 || sw.uni == 32) || !uni_ok) {
+    g.form = kDwBwdTwoKind;
+    return g;
+  }
+  const bool u32 = sw.uni == 32 && s.nks <= 3;
+  g.form = u32 ? kDwBwdUni32 : kDwBwdUni64;
+  g.cb = u32 ? 32 : 64;
+  g.gx = (int)cdiv(C, g.cb);
+  g.n_tiles = (int)cdiv(T, (int64_t)dwu::TT);
+  const int want = u32 ? 400 : 200;                    // workgroups that fill the chip (two / one per CU)
+  g.gz = 1;
+  while (g.gz * 2 <= g.n_tiles && (int64_t)g.gx * B * g.gz < want) g.gz *= 2;
+  g.total = (int)(g.gx * B * g.gz);
+  g.launched = (g.total + 15) / 16 * 16;
+  return g;
+}
+// the strided forward: 64-frame tiles (R = 4 outputs per thread) when 128-frame tiles (R = 8) would not fill the chip
+// (first_cnn: 64 channels, stride 2)
+static bool dw_s2_small(int64_t B, int64_t Tout, int64_t C) { return cdiv(Tout, kTT) * cdiv(C, kCB) * B < 200; }
+// the f32 / VALU stride-1 weight gradient: time splits per workgroup (16 lane groups dealt as ceil(k/8) tap groups x ts splits)
+static int dw_wgrad_ts(int k) { return std::min(16 / ((k + 7) >> 3), 3); }
+
 extern "C" int lasr_dwconv_fwd(const void* x, const float* w, const void* addend, void* y, int dtype, int64_t B, int64_t Tin,
                                int64_t C, int k, int stride, int flip, void* stream) {
   LASR_CHECK_ARG(x && w && y, "lasr_dwconv_fwd: null pointer");
@@ -1661,8 +1709,7 @@ extern "C" int lasr_dwconv_fwd(const void* x, const float* w, const void* addend
       launch_lds(dwconv_s1_bf16_kernel, grid, dim3(256), sh1, st, (const bf16_t*)x, w, (const bf16_t*)addend, (bf16_t*)y, Tin, C, k, flip);
     }
   } else {
-    // 64-frame tiles when 128-frame tiles would not fill the chip (first_cnn: 64 channels, stride 2)
-    const bool small = (int64_t)grid.x * grid.y * grid.z < 200;
+    const bool small = dw_s2_small(B, Tout, C);
     const dim3 g2 = small ? dim3((unsigned)cdiv(Tout, 64), grid.y, grid.z) : grid;
     with_dtype(dtype, [&](auto t) {
       rc = with_int<4, 8>(small ? 4 : 8, [&](auto r) {
@@ -1731,6 +1778,8 @@ static int dwconv_wgrad_impl(const void* x, const void* dy, float* dw, int dtype
   LASR_CHECK_ARG(dtype == LASR_F32 || dtype == LASR_BF16, "lasr_dwconv_wgrad: bad dtype");
   LASR_CHECK_SHAPE(k >= 1 && k <= kMaxK && (k & 1) && (stride == 1 || stride == 2) && C % 4 == 0 && B > 0 && B < 65536 && Tin > 0,
                    "lasr_dwconv_wgrad: k=%d stride=%d C=%lld", k, stride, (long long)C);
+  LASR_CHECK_SHAPE(stride != 1 || (C % (int64_t)(16 / dtype_size(dtype)) == 0 && al16(x) && al16(dy)),
+                   "lasr_dwconv_wgrad: the stride-1 kernels load 16-byte channel vectors (C=%lld)", (long long)C);
   const int64_t Tout = conv_out_len(Tin, k, stride);
   if (workspace_bytes < lasr_dwconv_wgrad_workspace_bytes(B, Tout, C, k)) return fail(LASR_E_WORKSPACE, "lasr_dwconv_wgrad: workspace");
   hipStream_t st = as_stream(stream);
@@ -1750,8 +1799,7 @@ static int dwconv_wgrad_impl(const void* x, const void* dy, float* dw, int dtype
   dim3 grid((unsigned)n_chunks, (unsigned)cdiv(C, kCB), (unsigned)B);
   if (stride == 1) {
     const int ng = (k + 7) >> 3;
-    int ts = 16 / ng;
-    if (ts > 3) ts = 3;
+    const int ts = dw_wgrad_ts(k);
     const int WT = kSub * ts, kpad = ng * 8;
     size_t sh1 = (size_t)(WT + kpad + 8 + WT) * (kCB + (dtype_size(dtype) == 2 ? 8 : 0)) * dtype_size(dtype);   // padded rows
     const size_t red = (size_t)ts * kpad * kCB * sizeof(float);
@@ -1786,17 +1834,15 @@ extern "C" int lasr_dwconv_bwd_fused(const void* x, const void* dy, const float*
   LASR_CHECK_ARG(dtype == LASR_F32 || dtype == LASR_BF16, "lasr_dwconv_bwd_fused: bad dtype");
   LASR_CHECK_SHAPE(k >= 1 && k <= kMaxK && (k & 1) && C % 4 == 0 && B > 0 && B < 65536 && T > 0, "lasr_dwconv_bwd_fused: k=%d C=%lld", k,
                    (long long)C);
-  const DwSwitches& sw = dw_switches();
   const DwShape s = dw_shape(B, T, C, k, dtype, al16(x) && al16(dy));
-  // one launch needs BOTH MFMA forms (any VALU switch means the two launches, each with its own fall-back)
-  const bool ok = !sw.no_fused_bwd && s.fwd && s.wgrad && workspace_bytes >= lasr_dwconv_wgrad_workspace_bytes(B, T, C, k);
-  if (!ok) {
+  const DwBwdGrid g = dw_bwd_grid(s, B, T, C, k, workspace_bytes >= lasr_dwconv_wgrad_workspace_bytes(B, T, C, k));
+  if (g.form == kDwBwdTwoLaunches) {
     LASR_TRY(lasr_dwconv_wgrad_partials(x, dy, dtype, B, T, C, k, 1, workspace, workspace_bytes, n_partials, stream));
     return lasr_dwconv_fwd(dy, w, addend, dx, dtype, B, T, C, k, 1, 1, stream);
   }
   hipStream_t st = as_stream(stream);
-  if (sw.uni == 64 || sw.uni == 32) {
-    const bool u32 = sw.uni == 32 && s.nks <= 3;
+  if (g.form == kDwBwdUni32 || g.form == kDwBwdUni64) {
+    const bool u32 = g.form == kDwBwdUni32;
     DwUni u;
     u.x = (const bf16_t*)x; u.dy = (const bf16_t*)dy; u.w = w; u.addend = (const bf16_t*)addend; u.dx = (bf16_t*)dx;
     u.partials = reinterpret_cast<float*>(workspace);
@@ -1805,19 +1851,15 @@ extern "C" int lasr_dwconv_bwd_fused(const void* x, const void* dy, const float*
       const uint32_t* tp = dw_taps_for(w, 1, C);        // reversed taps: the second half of the layer's table
       u.taps = tp ? tp + (size_t)C * kDwTapRow : nullptr;
     }
-    const int cb = u32 ? 32 : 64;
-    u.gx = (int)cdiv(C, cb);
-    const int n_tiles = (int)cdiv(T, (int64_t)dwu::TT);
-    const int want = u32 ? 400 : 200;                  // workgroups that fill the chip (two / one per CU)
-    int gz = 1;
-    while (gz * 2 <= n_tiles && (int64_t)u.gx * B * gz < want) gz *= 2;
+    u.gx = g.gx;
+    const int gz = g.gz;
     u.gz = gz;
-    u.total = (int)(u.gx * B * gz);
+    u.total = g.total;
     const int tok = prof_begin(LASR_PROF_DWCONV, st, 4.0 * (double)B * T * C * k, (double)B * T * C * (addend ? 4 : 3) * 2);
     auto launch = [&](auto nks, auto waves) {
       with_bool((nt_loads_mask() & 4) != 0, [&](auto nt) {
         constexpr int N = decltype(nks)::value, W = decltype(waves)::value;
-        launch_lds(dwconv_bwd_uni_kernel<N, W, decltype(nt)::value>, dim3((unsigned)((u.total + 15) / 16 * 16)), dim3(64 * W),
+        launch_lds(dwconv_bwd_uni_kernel<N, W, decltype(nt)::value>, dim3((unsigned)g.launched), dim3(64 * W),
                    dwu::Cfg<N, W>::SMEM, st, u);
       });
     };
@@ -1847,5 +1889,33 @@ extern "C" int lasr_dwconv_bwd_fused(const void* x, const void* dy, const float*
   LASR_TRY(rc);
   LASR_LAUNCH_CHECK("dwconv_bwd_s1_mfma_kernel");
   *n_partials = (int)B * s.zsplit;
+  return 0;
+}
+
+// What the launchers above choose for a shape, from the same helpers (dw_shape, dw_bwd_grid, dw_s2_small, dw_wgrad_ts); launches
+// nothing.  Operands are taken as 16-byte aligned and the workspace as lasr_dwconv_wgrad_workspace_bytes sizes it.
+extern "C" int lasr_dwconv_plan(int64_t B, int64_t T, int64_t C, int k, int stride, int dtype, lasr_dwconv_plan_info* plan) {
+  LASR_CHECK_ARG(plan, "lasr_dwconv_plan: null pointer");
+  LASR_CHECK_ARG(dtype == LASR_F32 || dtype == LASR_BF16, "lasr_dwconv_plan: bad dtype");
+  LASR_CHECK_SHAPE(k >= 1 && k <= kMaxK && (k & 1) && (stride == 1 || stride == 2) && C % 4 == 0 && B > 0 && B < 65536 && T > 0,
+                   "lasr_dwconv_plan: k=%d stride=%d C=%lld", k, stride, (long long)C);
+  LASR_CHECK_SHAPE(stride != 1 || C % (int64_t)(16 / dtype_size(dtype)) == 0,
+                   "lasr_dwconv_plan: the stride-1 kernels load 16-byte channel vectors (C=%lld)", (long long)C);
+  memset(plan, 0, sizeof(*plan));
+  if (stride != 1) {
+    plan->fwd_form = LASR_DW_FWD_STRIDED;
+    plan->fwd_r = dw_s2_small(B, conv_out_len(T, k, stride), C) ? 4 : 8;
+    plan->wgrad_form = LASR_DW_WGRAD_STRIDED;
+    plan->bwd_form = -1;
+    return 0;
+  }
+  const DwShape s = dw_shape(B, T, C, k, dtype, true);
+  plan->fwd_form = dtype == LASR_F32 ? LASR_DW_FWD_F32 : s.fwd ? LASR_DW_FWD_MFMA : dw_switches().fma ? LASR_DW_FWD_FMA : LASR_DW_FWD_VALU;
+  if (s.fwd) { plan->nks = s.nks; plan->nset = s.nset; plan->gz_d = s.gz_d; }
+  plan->wgrad_form = s.wgrad ? LASR_DW_WGRAD_MFMA : LASR_DW_WGRAD_VALU;
+  if (s.wgrad) plan->zsplit = s.zsplit; else plan->ts = dw_wgrad_ts(k);
+  const DwBwdGrid g = dw_bwd_grid(s, B, T, C, k, true);
+  plan->bwd_form = g.form;
+  plan->bwd_gz = g.gz; plan->bwd_tiles = g.n_tiles; plan->bwd_wgs = g.total; plan->bwd_wgs_launched = g.launched;
   return 0;
 }
