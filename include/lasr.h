@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 110   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 111   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
@@ -34,7 +34,8 @@ extern "C" {
                               107: lasr_resample_* (sample-rate conversion, speed perturbation)
                               108: lasr_rir_bank_* / lasr_wave_augment* (noise and reverberation augmentation)
                               109: lasr_edit_align_workspace_bytes / lasr_edit_align_batch (substitution/deletion/insertion alignment)
-                              110: lasr_dwconv_plan (which depthwise kernel form and grid a shape takes; launches nothing) */
+                              110: lasr_dwconv_plan (which depthwise kernel form and grid a shape takes; launches nothing)
+                              111: lasr_vad_* / lasr_segment_gather (voice-activity segmentation of long recordings) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -845,6 +846,50 @@ int lasr_wave_augment(const void* rir_bank_dev, int64_t rir_bank_words, const vo
                       const int32_t* noise_clips, int n_clips, int64_t noise_total, const void* in, int in_dtype, int64_t in_pitch,
                       const int32_t* in_lens, const int32_t* params, void* out, int out_dtype, int64_t out_pitch, int64_t L,
                       int32_t* out_lens, double* stats, int64_t B, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- long recordings: voice-activity segmentation and the gather from segments to batch rows ---------------------------------
+ * One recording is one row.  Everything after the quantisation of a sample is integer arithmetic, so the result is exact in any
+ * summation order (DESIGN.md "Inference: long recordings"; lightning_asr_amd/csrc/segment.h has the host side):
+ *   q = the PCM16 sample, or clamp(rint(x * 32768), -32768, 32767) (half to even) of an f32 one
+ *   frame n = samples [160 n, 160 n + 160) of the row's len samples, F = ceil(len / 160);  E[n] = sum q^2 (64-bit)
+ *   lev[n] = 0 for E == 0, else 8 k + m + 1, k = floor(log2 E), m = the three bits of E below its leading one (0.376 dB a step)
+ *   floor = the max(1, ceil(F * floor_permille / 1000))-th smallest level;  base = min(max(floor, min_level), max_floor_level)
+ *   on = base + on_steps, off = base + off_steps;  a maximal run of lev >= off is speech iff one of its frames has lev >= on
+ *   close: a run that starts fewer than min_silence frames after the previous kept run's end is merged into it
+ *   open:  runs shorter than min_speech frames are then dropped
+ *   pad:   [max(0, s - pad), min(F, e + pad)); a run whose padded start is <= the previous padded end merges with it
+ *   split: while e - s > max_frames, cut at the first frame of lowest level in [s + max_frames / 2, s + max_frames)
+ *   segment = samples [160 s, min(160 e, len)), in time order.
+ * lasr_vad_params_from fills the struct from dB and seconds: steps = round(dB / (10 log10(2) / 8)); an absolute level = the level
+ * of round(160 * 32768^2 * 10^(dBFS / 10)); frames = round(seconds * 100), all half to even.  LASR_E_ARG: a value that is not
+ * finite, |dB| > 1000, a level above 0 dBFS, seconds outside [0, 1e6], and what lasr_vad_segment checks too: 0 <= off_steps <=
+ * on_steps, floor_permille in 1..1000, 0 <= min_level <= max_floor_level < LASR_VAD_LEVELS, max_frames >= 2, frame counts in [0, 2^30].
+ * lasr_vad_sweep: the frames (and runs) one workgroup takes per sweep of its passes - where the tests put their row lengths.
+ * lasr_vad_workspace_bytes(B, L): 0 and LASR_E_SHAPE for B > 65535 or L >= 2^31. */
+#define LASR_VAD_LEVELS 512
+typedef struct {
+  int32_t on_steps, off_steps, floor_permille, min_level, max_floor_level, min_silence, min_speech, pad, max_frames;
+} lasr_vad_params;
+int lasr_vad_params_from(double on_db, double off_db, int floor_permille, double min_level_db, double max_floor_db,
+                         double min_silence_s, double min_speech_s, double pad_s, double max_segment_s, lasr_vad_params* out);
+int64_t lasr_vad_sweep(void);
+size_t lasr_vad_workspace_bytes(int64_t B, int64_t L);
+/* B rows on `stream` (a memset and two launches); nothing is allocated or synchronised, so the call can be captured.
+ * wave: B rows of `pitch` elements (0 = L), LASR_WAVE_F32 or LASR_WAVE_PCM16; sample_lens (B) int32 plain sample counts, clamped to
+ * [0, L] (NULL = L).  segs (B, max_segments, 2) int32 = (start, end) in samples; n_segs (B) int32 = the TRUE count - when it exceeds
+ * max_segments only the first max_segments are written and the caller decides whether that is an error; rows of segs past the
+ * count are not touched.  floor_out (B) int32 = the noise floor level before its clamps (0 for an empty row), may be NULL.
+ * levels_out (B, ceil(L / 160)) uint16 = lev, 0 past a row's F, may be NULL (tests and diagnosis).  workspace:
+ * lasr_vad_workspace_bytes(B, L) bytes on the device, 16-byte aligned. */
+int lasr_vad_segment(const void* wave, int wave_dtype, int64_t pitch, const int32_t* sample_lens, int64_t B, int64_t L,
+                     const lasr_vad_params* params, int32_t* segs, int64_t max_segments, int32_t* n_segs, int32_t* floor_out,
+                     uint16_t* levels_out, void* workspace, size_t workspace_bytes, void* stream);
+/* table: (n, 3) int32 (row, start, end) in HOST memory, read before the call returns (up to 256 entries travel in the arguments of
+ * one launch).  out (n, out_pitch) in the input's dtype on the device: row i = samples [start, end) of source row `row` (rows of
+ * `pitch` elements), then zeros up to out_pitch; out_lens[i] = end - start.  The caller answers for row and end lying inside
+ * `wave`.  LASR_E_ARG: null pointer, row < 0, start < 0, end < start; LASR_E_SHAPE: a segment longer than out_pitch. */
+int lasr_segment_gather(const void* wave, int wave_dtype, int64_t pitch, const int32_t* table, int64_t n, void* out,
+                        int64_t out_pitch, int32_t* out_lens, void* stream);
 
 /* ---- data-parallel gradient exchange: RCCL over xGMI, called by the library itself ------------------------------
  * Replaces the NCCL all-reduce the reference gets from Lightning's DDP plugin (conf/conf.yaml:30-31 `accelerator: ddp`,

@@ -30,6 +30,12 @@ class WaveSrc(C.Structure):
 WAVE_F32, WAVE_PCM16 = 0, 1
 
 
+class VadParams(C.Structure):
+    """lasr_vad_params: the segmenter's integer parameters (level steps, levels, frames)"""
+    _fields_ = [(n, C.c_int32) for n in ("on_steps", "off_steps", "floor_permille", "min_level", "max_floor_level", "min_silence",
+                                         "min_speech", "pad", "max_frames")]
+
+
 class DwconvPlan(C.Structure):
     """lasr_dwconv_plan_info: the depthwise kernel forms and grids a shape takes (verification hook)"""
     _fields_ = [(n, C.c_int32) for n in ("fwd_form", "nks", "nset", "gz_d", "fwd_r", "wgrad_form", "zsplit", "ts", "bwd_form", "bwd_gz",
@@ -183,6 +189,11 @@ SIGNATURES = {
     "lasr_wave_augment_chunk": (_i64, []),
     "lasr_wave_augment_workspace_bytes": (_sz, [_i64, _i64]),
     "lasr_wave_augment": (_i32, [_p, _i64, _p, _i32, _p, _i32, _i64, _p, _i32, _i64, _p, _p, _p, _i32, _i64, _i64, _p, _p, _i64, _p, _sz, _p]),
+    "lasr_vad_params_from": (_i32, [C.c_double, C.c_double, _i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p]),
+    "lasr_vad_sweep": (_i64, []),
+    "lasr_vad_workspace_bytes": (_sz, [_i64, _i64]),
+    "lasr_vad_segment": (_i32, [_p, _i32, _i64, _p, _i64, _i64, _p, _p, _i64, _p, _p, _p, _p, _sz, _p]),
+    "lasr_segment_gather": (_i32, [_p, _i32, _i64, _p, _i64, _p, _i64, _p, _p]),
     "lasr_comm_timing": (_i32, [_p, _i32]),
     "lasr_comm_timing_collect": (_i32, [_p, _i32, _p, _p, C.POINTER(_i32), _p, C.POINTER(_i32)]),
     "lasr_comm_unique_id": (_i32, [_p, _sz]),

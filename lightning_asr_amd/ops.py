@@ -950,3 +950,105 @@ class WaveAugmenter:
              self.noise_total, wave.data_ptr(), code(wave.dtype), in_pitch, _p(lens), _p(params), out.data_ptr(), code(out_dtype),
              out_pitch, L, _p(out_lens), _p(stats), B, _p(ws), ws.numel(), _stream())
         return out[:, :L], out_lens, stats
+
+
+# ---- long recordings (csrc/segment.hip; DESIGN.md "Inference: long recordings") ---------------------------------------------
+class VadSegments(NamedTuple):
+    segs: torch.Tensor           # (B, max_segments, 2) i32 (start, end) in samples; rows past n_segs are not written
+    n_segs: torch.Tensor         # (B,) i32 the TRUE count: above max_segments only the first max_segments rows of segs are written
+    floor: torch.Tensor          # (B,) i32 the noise floor level, before its clamps
+    levels: Optional[torch.Tensor]   # (B, ceil(L / 160)) i16 frame levels 0..511 (the library's uint16), 0 past a row's frames, or None
+
+
+def vad_sweep() -> int:
+    """frames (and runs) one workgroup of the segmenter takes per sweep of its passes (where its tests put their row lengths)"""
+    return int(_lib.load().lasr_vad_sweep())
+
+
+def vad_params(on_db=12.0, off_db=6.0, floor_permille=100, min_level_db=-60.0, max_floor_db=-35.0, min_silence_s=0.3, min_speech_s=0.1,
+               pad_s=0.1, max_segment_s=16.0) -> "_lib.VadParams":
+    """the segmenter's integer parameters from dB and seconds (lasr_vad_params_from); LasrError for what its checks refuse"""
+    p = _lib.VadParams()
+    if not -2 ** 31 <= int(floor_permille) < 2 ** 31:
+        raise ValueError("vad_params: floor_permille must lie in 1..1000")
+    call("lasr_vad_params_from", float(on_db), float(off_db), int(floor_permille), float(min_level_db), float(max_floor_db),
+         float(min_silence_s), float(min_speech_s), float(pad_s), float(max_segment_s), ctypes.byref(p))
+    return p
+
+
+def _wave_rows(wave: torch.Tensor, who: str):
+    """a (B, L) f32 | int16 device tensor with contiguous rows -> (dtype code, row pitch)"""
+    if wave.dim() != 2 or wave.dtype not in (torch.float32, torch.int16) or not wave.is_cuda or (wave.shape[1] > 1 and wave.stride(1) != 1):
+        raise _lib.LasrError("%s: wave must be a (B, L) f32 or int16 device tensor with contiguous rows; there is no CPU path" % who)
+    B, L = wave.shape
+    pitch = wave.stride(0) if B > 1 else max(L, 1)
+    if pitch < L:
+        raise _lib.LasrError("%s: the rows of wave overlap" % who)
+    return (_lib.WAVE_F32 if wave.dtype == torch.float32 else _lib.WAVE_PCM16), pitch
+
+
+def vad_segments(wave: torch.Tensor, lens: Optional[torch.Tensor] = None, *, on_db=12.0, off_db=6.0, floor_permille=100,
+                 min_level_db=-60.0, max_floor_db=-35.0, min_silence_s=0.3, min_speech_s=0.1, pad_s=0.1, max_segment_s=16.0,
+                 max_segments=4096, return_levels=False) -> VadSegments:
+    """Energy voice-activity segmentation of recordings at 16 kHz, one per row: wave (L,) or (B, L) f32 | int16 on the device (rows
+    may be strided), lens (B) int32 samples per row (None = L).  A frame is 160 samples; its level is a quasi-log of its PCM16
+    energy (0.376 dB a step).  Speech is what rises ``on_db`` above the noise floor (the ``floor_permille``-th permille of the
+    row's levels, kept between ``min_level_db`` and ``max_floor_db`` dBFS) and everything around it down to ``off_db``; gaps shorter
+    than ``min_silence_s`` are closed, runs shorter than ``min_speech_s`` dropped, the rest padded by ``pad_s`` and cut at its
+    quietest frame wherever it is longer than ``max_segment_s``.  Integer arithmetic: exact, the same on every run.
+    No host synchronisation; a 1-D wave gives results without the batch dimension."""
+    one = wave.dim() == 1
+    w2 = wave.unsqueeze(0) if one else wave
+    code, pitch = _wave_rows(w2, "vad_segments")
+    B, L = w2.shape
+    dev = w2.device
+    if lens is not None and (lens.dtype != torch.int32 or lens.numel() != B or not lens.is_cuda):
+        raise _lib.LasrError("vad_segments: lens must be a (B,) int32 device tensor")
+    max_segments = int(max_segments)
+    if max_segments < 0:
+        raise ValueError("vad_segments: max_segments must not be negative")
+    p = vad_params(on_db, off_db, floor_permille, min_level_db, max_floor_db, min_silence_s, min_speech_s, pad_s, max_segment_s)
+    F = -(-L // 160)
+    segs = torch.empty(B, max_segments, 2, dtype=torch.int32, device=dev)
+    n_segs = torch.empty(B, dtype=torch.int32, device=dev)
+    floor = torch.empty(B, dtype=torch.int32, device=dev)
+    levels = torch.empty(B, F, dtype=torch.int16, device=dev) if return_levels else None
+    nb = int(_lib.load().lasr_vad_workspace_bytes(B, L))
+    if nb == 0 and B:
+        _lib.check(-1, "lasr_vad_workspace_bytes")
+    ws = _ws(nb, dev)
+    call("lasr_vad_segment", w2.data_ptr() if w2.numel() else None, code, pitch, _p(lens.contiguous()) if lens is not None else None, B, L,
+         ctypes.byref(p), segs.data_ptr() if max_segments else None, max_segments, _p(n_segs), _p(floor),
+         levels.data_ptr() if levels is not None and F else None, _p(ws), ws.numel(), _stream())
+    if one:
+        return VadSegments(segs[0], n_segs[0], floor[0], levels[0] if levels is not None else None)
+    return VadSegments(segs, n_segs, floor, levels)
+
+
+def gather_segments(wave: torch.Tensor, table, L_out: Optional[int] = None):
+    """wave (L,) or (B, L) f32 | int16 on the device; table: n rows of (row, start, end) - a HOST int tensor, array or list (a
+    device tensor is read back) -> (rows (n, L_out) of wave's dtype: samples [start, end) of the source row, then zeros;
+    lens (n,) int32 = end - start).  L_out defaults to the longest segment; a segment longer than L_out is a LasrError
+    (LASR_E_SHAPE), one outside its source row a ValueError.  One launch per 256 segments, no host synchronisation."""
+    w2 = wave.unsqueeze(0) if wave.dim() == 1 else wave
+    code, pitch = _wave_rows(w2, "gather_segments")
+    B, L = w2.shape
+    tab = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    tab = np.ascontiguousarray(tab.reshape(-1, 3)).astype(np.int64)
+    n = tab.shape[0]
+    bad = np.flatnonzero((tab[:, 0] < 0) | (tab[:, 0] >= B) | (tab[:, 1] < 0) | (tab[:, 2] < tab[:, 1]) | (tab[:, 2] > L))
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError("gather_segments: table[%d] = %s lies outside the (%d, %d) wave" % (i, tuple(int(v) for v in tab[i]), B, L))
+    if L_out is None:
+        L_out = int((tab[:, 2] - tab[:, 1]).max()) if n else 0
+    L_out = int(L_out)
+    if L_out < 0:
+        raise ValueError("gather_segments: L_out must not be negative")
+    out = torch.empty(n, L_out, dtype=w2.dtype, device=w2.device)
+    lens = torch.empty(n, dtype=torch.int32, device=w2.device)
+    tab32 = np.ascontiguousarray(tab.astype(np.int32))
+    if n:
+        call("lasr_segment_gather", w2.data_ptr(), code, pitch, tab32.ctypes.data, n, out.data_ptr() if L_out else None, L_out, _p(lens),
+             _stream())
+    return out, lens

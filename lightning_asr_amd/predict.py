@@ -3,6 +3,7 @@ manifest evaluation, on the HIP path (mel front-end, eval-mode model forward, gr
 ``decoder="beam"``, the CTC prefix beam search of beam_search.py, fused with an n-gram LM when ``lm_path`` names a text ARPA
 file: a character LM, or - the labels having exactly one " ", as EN_LABELS has - a word LM with its lexicon).
 ``error_report`` splits a manifest's WER / CER into substitutions, deletions and insertions (``ops.edit_ops_batch``: the aligned reference and hypothesis of every utterance, the most confused pairs).
+``translate_long`` takes a recording of any length: cut into utterances on the device (``ops.vad_segments``), decoded in batches, times relative to the recording.
 ``align`` / ``translate_timed`` / ``align_manifest`` add word timings: the CTC forced alignment of a known transcript (or of the decoder's own hypothesis) to the audio, ``ops.ctc_align`` + the record functions of align.py.
 
 The checkpoint is the PL-style dict the reference's ``ModelCheckpoint`` writes and ``Trainer`` here
@@ -29,6 +30,9 @@ from .beam_search import BeamSearchDecoderWithLM
 from .utils.asr_metrics import WER, _alignment, _edit_ops, word_error_rate
 
 EN_LABELS = [" ", "'"] + [chr(ord("a") + i) for i in range(26)]
+# the narrowest batch the model's forward takes is 33 feature frames (lasr_model_forward): 1 + (L + 64) // 160 >= 33.  A batch of
+# short segments is gathered into rows at least this wide; each row keeps its own length.
+MIN_ROW_SAMPLES = 160 * (33 - 1) - 64
 
 
 class AsrTranslator:
@@ -323,6 +327,106 @@ class AsrTranslator:
         if not text:
             return "", []
         return text, self._align_ids(out, self.text_to_ids(text), duration)
+
+    # ------------------------------------------------------------------------------------------ long recordings
+    def _segment_batch(self, wave: torch.Tensor, segs):
+        """segments [(start, end), ...] in samples of the (L,) device wave -> (log-probs (n, T', C), frames (n,) int32): one gather
+        into rows as wide as the longest of them (and no narrower than the model's shortest input), translate()'s feature chain on each row's own samples, the eval forward"""
+        width = max(max(int(e) - int(s) for s, e in segs), MIN_ROW_SAMPLES)
+        rows, lens = ops.gather_segments(wave, [(0, int(s), int(e)) for s, e in segs], width)
+        inputs, pct = self.audio_parser.features_device(rows, lens, None, True, logical_len=rows.shape[1])
+        out = self.model._encode(inputs, pct)
+        return out, ops.mask_lengths(pct.to(out.device, torch.float32).contiguous(), out.size(1))
+
+    def _decode_batch(self, out, t_lens) -> List[List[int]]:
+        """the translator's own decoder over a batch: label ids of every row's hypothesis"""
+        if self.decoder == "beam":
+            tokens, n, _ = self.beam.search(out, t_lens, 1)
+            tokens, n = tokens[:, 0, :], n[:, 0].clamp(min=0)
+        else:
+            tokens, n = ops.greedy_decode(self.model.encoder.last_argmax.to(torch.int32).contiguous(), t_lens.contiguous(), len(self.labels))
+        t_h, n_h = tokens.tolist(), n.tolist()
+        return [[int(c) for c in t_h[b][:n_h[b]]] for b in range(len(n_h))]
+
+    def _align_batch(self, out, t_lens, ids: List[List[int]], segs) -> List[Optional[List[dict]]]:
+        """one ops.ctc_align over a batch of segments: row b's label ids on its log-probs -> its word records with the times of the
+        RECORDING: offset by the segment's start, clipped to its end.  [] for a row without labels, None for one without an
+        alignment (a transcript too long for its segment)."""
+        S = max([len(i) for i in ids] + [0])
+        if S == 0:
+            return [[] for _ in ids]
+        logp = out.float().contiguous()
+        tg = torch.zeros(len(ids), S, dtype=torch.int64)
+        for b, i in enumerate(ids):
+            tg[b, :len(i)] = torch.tensor(i, dtype=torch.int64)
+        tl = torch.tensor([len(i) for i in ids], dtype=torch.int32)
+        al = ops.ctc_align(logp, tg.to(logp.device), t_lens.contiguous(), tl.to(logp.device), logp.shape[-1] - 1)
+        score, start, end, flp = al.score.tolist(), al.label_start.tolist(), al.label_end.tolist(), al.frame_logp.tolist()
+        secs, sr = self.frame_seconds(), float(self.audio_parser.sr)
+        recs: List[Optional[List[dict]]] = []
+        for b, i in enumerate(ids):
+            if not i:
+                recs.append([])
+                continue
+            if not math.isfinite(score[b]):
+                recs.append(None)
+                continue
+            t0, t1 = segs[b][0] / sr, segs[b][1] / sr
+            words = unit_records(i, start[b], end[b], flp[b], self.labels, secs, t1 - t0)
+            for w in words:
+                for r in [w] + w["labels"]:
+                    r["start"], r["end"] = min(r["start"] + t0, t1), min(r["end"] + t0, t1)
+            recs.append(words)
+        return recs
+
+    @torch.no_grad()
+    def translate_long(self, audio_path, batch_size: int = 32, timed: bool = True, resample: Optional[bool] = None, **vad) -> dict:
+        """A recording of any length -> {"text", "duration", "segments": [{"start", "end", "text", "words"}, ...]} in time order,
+        times in seconds of the recording.  The file is loaded once and cut into utterances on the device (``ops.vad_segments``;
+        ``**vad`` are its keywords: on_db, off_db, floor_permille, min_level_db, max_floor_db, min_silence_s, min_speech_s, pad_s,
+        max_segment_s, max_segments); the segments go through translate()'s chain in batches of at most ``batch_size``, longest
+        first (the first batch sizes the model's workspace), each normalised over its own frames, and are decoded by the
+        translator's own decoder.  timed: ``words`` = the forced alignment of each hypothesis (one ``ops.ctc_align`` per batch,
+        the records of ``align``); False: None.  ``text`` joins the segments' texts with " " when the vocabulary has a space
+        label, else with "".  An empty hypothesis stays a segment with "text": "" and "words": []; a recording without speech
+        gives "text": "" and "segments": [].  ValueError when the recording has more than ``max_segments`` segments."""
+        if isinstance(audio_path, str) and not os.path.exists(audio_path):
+            raise Exception("音频路径不存在 " + audio_path)
+        if int(batch_size) < 1:
+            raise ValueError("translate_long: batch_size must be at least 1")
+        if self._resample(resample):
+            y, rate = load_wav_rate(audio_path)
+            duration = y.shape[1] / float(rate)
+            y = self.audio_parser.resample_to_sr(y, rate)
+        else:
+            y = load_wav(audio_path)
+            duration = y.shape[1] / float(self.audio_parser.sr)
+        result = {"text": "", "duration": duration, "segments": []}
+        if y.shape[1] == 0:
+            return result
+        wave = y[0].to(self.device).contiguous()
+        found = ops.vad_segments(wave, **vad)
+        n = int(found.n_segs)                                            # the one read-back the host plans the batches from
+        if n > found.segs.shape[0]:
+            raise ValueError("translate_long: the recording has %d segments, more than max_segments=%d" % (n, found.segs.shape[0]))
+        if n == 0:
+            return result
+        segs = [tuple(s) for s in found.segs[:n].tolist()]
+        order = sorted(range(n), key=lambda i: segs[i][0] - segs[i][1])  # longest first; equal lengths in time order
+        sr = float(self.audio_parser.sr)
+        records: List[Optional[dict]] = [None] * n
+        for k in range(0, n, int(batch_size)):
+            idx = order[k:k + int(batch_size)]
+            batch = [segs[i] for i in idx]
+            out, t_lens = self._segment_batch(wave, batch)
+            ids = self._decode_batch(out, t_lens)
+            words = self._align_batch(out, t_lens, ids, batch) if timed else [None] * len(idx)
+            for j, i in enumerate(idx):
+                records[i] = {"start": segs[i][0] / sr, "end": segs[i][1] / sr, "text": "".join(self.labels[c] for c in ids[j]),
+                              "words": words[j]}
+        result["segments"] = records
+        result["text"] = (" " if " " in self.labels else "").join(r["text"] for r in records)
+        return result
 
     @torch.no_grad()
     def align_manifest(self, manifest: str, out_path: str, batch_size: int = 32) -> List[dict]:
