@@ -19,6 +19,11 @@ build/%.o: lightning_asr_amd/csrc/%.hip
 	@mkdir -p build
 	$(HIPCC) $(CXXFLAGS) -MMD -MP -MF build/$*.d -c $< -o $@
 
+# the widest LM + hotword search (33 candidates per thread) unrolls its candidate loop, so that the candidates stay in registers,
+# only above clang's default size limit for `#pragma unroll`.  The flag reaches every kernel of the file and changes none of the
+# others: profiles/beam_bias_kernel_resources.jsonl (tools/beam_kernel_resources.py) records each kernel with and without it
+build/ctc_beam.o: CXXFLAGS += -mllvm -pragma-unroll-threshold=32768
+
 -include $(OBJ:.o=.d)
 
 clean:

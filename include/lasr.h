@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 111   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 112   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
@@ -35,7 +35,8 @@ extern "C" {
                               108: lasr_rir_bank_* / lasr_wave_augment* (noise and reverberation augmentation)
                               109: lasr_edit_align_workspace_bytes / lasr_edit_align_batch (substitution/deletion/insertion alignment)
                               110: lasr_dwconv_plan (which depthwise kernel form and grid a shape takes; launches nothing)
-                              111: lasr_vad_* / lasr_segment_gather (voice-activity segmentation of long recordings) */
+                              111: lasr_vad_* / lasr_segment_gather (voice-activity segmentation of long recordings)
+                              112: lasr_hotword_* (phrase bank), lasr_ctc_beam_decode_bias / _lm_bias (hotword biasing) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -536,6 +537,72 @@ int lasr_ctc_beam_decode_wlm(const float* logp, const int32_t* lens, int64_t B, 
                              int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image, float alpha, float beta,
                              int32_t* tokens, int32_t* n_tokens, float* scores, float* am_scores, void* workspace,
                              size_t workspace_bytes, void* stream);
+
+/* Hotword biasing of the beam search (phrase boosting; DESIGN.md "Beam search with hotword biasing").  The caller hands over a
+ * bank of phrases; the search favours hypotheses that spell them.  No LM is involved or retrained.
+ *  Bank.  n_phrases phrases (0 is valid; at most 65 536), phrase i = labels[offsets[i] .. offsets[i+1]): 1..32 label ids in
+ *     [0, C), none the blank; weights[i] finite and > 0, in natural-log units per matched label.  Duplicates are allowed.
+ *  Automaton.  Over the trie of the phrases (at most 2^20 nodes, the root included) every node v carries depth(v); wmax(v), the
+ *     largest weight of a phrase through v; credit(v) = depth(v) * wmax(v), evaluated in f64 and stored as f32 (root: 0);
+ *     end(v): a phrase ends at v; leaf(v): end(v) and v has no child; keep(v): the credit of the deepest end node on the path
+ *     root..v, v included (0 if none); fail(v): the node of the longest proper suffix of v's string that is a trie node (the
+ *     root if none; fail(root) = root); max_credit: the largest credit of the bank (0 for an empty bank).
+ *  step(v, c) -> (v', delta).  If v has a child u by c: delta = credit(u) - credit(v).  Otherwise w = fail(v); while w is not
+ *     the root and has no child by c, w = fail(w); u = the child of w by c if it exists, else the root; delta = keep(v) -
+ *     credit(v) + credit(u): the provisional credit beyond the last completed phrase is given back, the suffix match is
+ *     credited.  v' = the root if leaf(u) (a completed phrase with no longer continuation is banked), else u.
+ *  bonus(prefix) = the sum of the deltas over the prefix's labels from the root; state(prefix) = the node reached;
+ *     final(prefix) = bonus(prefix) + keep(state) - credit(state): an unfinished match gives its provisional credit back at the
+ *     end of the utterance.  All three are functions of the prefix alone.  Arithmetic is f32, one rounding per step; with
+ *     weights that are multiples of 2^-k and small every value is exact.
+ *  Image.  Read-only and position-independent: a 64-byte header (its own magic, n_nodes, max_credit, the table size, C and the
+ *     blank), one 16-byte record per node (fail, credit, keep, flags) and an open-addressed hash (node, label) -> child, 16 bytes
+ *     per slot at load <= 1/2.  No table over nodes x C exists.  lightning_asr_amd/csrc/hotword_io.h holds the builder, the
+ *     layout and the one walker the host and the kernels both call.
+ * lasr_hotword_build: LASR_E_ARG for a null pointer (labels / offsets / weights may be NULL only when n_phrases is 0), a
+ * negative n_phrases, a blank outside [0, C), a label outside [0, C) or equal to the blank, an empty or over-long phrase or a
+ * weight that is not finite and > 0; LASR_E_FORMAT for too many phrases or trie nodes.  The message names the phrase index.
+ * lasr_hotword_info reports the phrases, the trie nodes (the root included), max_credit and the image size;
+ * lasr_hotword_write_image copies the image to host memory (LASR_E_WORKSPACE when `bytes` is too small);
+ * lasr_hotword_score is the host walk of labels[0 .. n) over the image: bonus, final and state of that prefix (any of the three
+ * may be NULL; LASR_E_ARG for a label that is the blank or outside [0, C)).  None of them does device work. */
+int lasr_hotword_build(const int32_t* labels, const int64_t* offsets /* n_phrases + 1 */, const float* weights, int n_phrases,
+                       int64_t C, int blank, void** handle);
+int lasr_hotword_info(const void* handle, int64_t* n_phrases, int64_t* n_nodes, float* max_credit, size_t* image_bytes);
+int lasr_hotword_write_image(const void* handle, void* host_dst, size_t bytes);
+void lasr_hotword_free(void* handle);
+int lasr_hotword_score(const void* handle, const int32_t* labels, int64_t n, float* bonus, float* final_bonus, int32_t* state);
+/* lasr_ctc_beam_decode with hotword biasing; bias_image is a device copy of a bank built for these C and blank.  Arguments,
+ * checks, workspace (lasr_ctc_beam_workspace_bytes), prune launch and ranges as lasr_ctc_beam_decode, and everything stated
+ * there holds (pruning, log_b / log_nb, merging, tie-break).  In addition:
+ *  - the beam is ranked by logaddexp(log_b, log_nb) + bonus(p); log_b / log_nb stay acoustic;
+ *  - an extension p -> p+c scores its acoustic value plus bonus(p) + delta(state(p), c); the "no new label" candidate keeps
+ *    bonus(p); a p+c that merges into a live entry is that entry with its own bonus (the bonus depends on the prefix alone, so
+ *    merging stays exact);
+ *  - end of utterance: each final entry's bonus is replaced by final(p), the <= beam_width entries are re-ranked by the new
+ *    score, ties by their order before, and n_best is cut from the new order.
+ * scores = acoustic + final(p); am_scores = the acoustic logaddexp; bias_scores = final(p); all (B, n_best) f32.  An empty
+ * slot holds -inf, -inf and 0.  An image whose header is not a hotword image for this C and blank yields empty slots
+ * (n_tokens -1) for every utterance.  An image of 0 phrases reproduces lasr_ctc_beam_decode bit for bit in tokens, n_tokens
+ * and scores.  LASR_E_ARG also for a null bias_image, am_scores or bias_scores.  Two launches on `stream`, nothing allocated
+ * or synchronised; deterministic. */
+int lasr_ctc_beam_decode_bias(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank, int beam_width,
+                              int cutoff_top_n, float cutoff_prob, int n_best, const void* bias_image, int32_t* tokens,
+                              int32_t* n_tokens, float* scores, float* am_scores, float* bias_scores, void* workspace,
+                              size_t workspace_bytes, void* stream);
+/* lasr_ctc_beam_decode_lm (character LM) with the same biasing: the emission term of its rule 1 becomes alpha * lm + beta +
+ * delta; the early cutoff becomes min_cutoff = score(beam_width-th) + logp[t][blank] - max(0, beta) - max_credit, score the
+ * fused score with bonus(p); end-of-utterance give-back and re-ranking as lasr_ctc_beam_decode_bias.  max_credit bounds what
+ * one step can add wherever keep(v) <= credit(v), which holds unless a phrase outweighs a longer one it is a prefix of by more
+ * than their lengths' ratio; the slack is part of the contract either way.  scores = the fused score with final(p) included;
+ * am_scores = lasr_ctc_beam_decode_lm's approx_ctc, computed from the fused score without the bias; bias_scores = final(p).  A
+ * wrong LM image or a wrong bias image yields empty slots.  An image of 0 phrases reproduces lasr_ctc_beam_decode_lm bit for
+ * bit.  The word-level search (lasr_ctc_beam_decode_wlm) has no biased form: its lexicon already confines it to LM words. */
+int lasr_ctc_beam_decode_lm_bias(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
+                                 int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image,
+                                 float alpha, float beta, const void* bias_image, int32_t* tokens, int32_t* n_tokens,
+                                 float* scores, float* am_scores, float* bias_scores, void* workspace, size_t workspace_bytes,
+                                 void* stream);
 
 /* ---------------------------------------------------------------- optimiser ----------------
  * scheduler/novograd.py:75-145 with betas=(0.8,0.5), eps=1e-8, no amsgrad/grad_averaging/luc

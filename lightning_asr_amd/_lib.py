@@ -122,6 +122,14 @@ SIGNATURES = {
     "lasr_arpa_lexicon_info": (_i32, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "lasr_ctc_beam_decode_wlm": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _p, _f32, _f32, _p, _p, _p, _p, _p, _sz,
                                         _p]),
+    "lasr_hotword_build": (_i32, [_p, _p, _p, _i32, _i64, _i32, C.POINTER(_p)]),
+    "lasr_hotword_info": (_i32, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_f32), C.POINTER(_sz)]),
+    "lasr_hotword_write_image": (_i32, [_p, _p, _sz]),
+    "lasr_hotword_free": (None, [_p]),
+    "lasr_hotword_score": (_i32, [_p, _p, _i64, C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_i32)]),
+    "lasr_ctc_beam_decode_bias": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "lasr_ctc_beam_decode_lm_bias": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _p, _f32, _f32, _p, _p, _p, _p, _p,
+                                            _p, _p, _sz, _p]),
     "lasr_novograd_workspace_bytes": (_sz, [_i64, _i64]),
     "lasr_novograd_step": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p, _f32, _f32, _f32, _f32, _f32, _p, _sz, _p]),
     "lasr_novograd_step_keep": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p, _f32, _f32, _f32, _f32, _f32, _p, _sz, _p]),

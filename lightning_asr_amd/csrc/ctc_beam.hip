@@ -570,6 +570,7 @@ extern "C" int lasr_ctc_beam_decode(const float* logp, const int32_t* lens, int6
 // lm(c | ctx(p)) = log10 p(longest stored (x_m .. x_1 c)) + sum of the backoffs of the longer stored contexts, found by a walk
 // leftward from c through the image's hash, one probe per word; the probes of a thread's candidates go out together.
 #include "arpa_io.h"
+#include "hotword_io.h"
 
 namespace lasr {
 namespace {
@@ -673,6 +674,98 @@ __device__ void lm_context_sums(const LmImg& m, int w, const int* ctx, float* cb
   }
 }
 
+// ------------------------------------------------------------------ hotword biasing ------------------------------------
+// lasr_ctc_beam_decode_bias / _lm_bias (include/lasr.h states the contract; hotword_io.h the automaton, its image and the
+// walker).  Each entry carries the automaton node of its prefix and bonus(prefix); like the LM bonus both depend on the prefix
+// alone, so merging stays exact.  step(root, c) of every kept label is resolved once per frame into LDS: most live entries sit
+// at the root and then cost no global probe per candidate.  The first probes of a thread's other candidates are loaded
+// together, kLmGroup at a time, and handed to the walker.  A survivor's step is walked again when its entry is written, so no
+// candidate carries its next node in registers.  A bank of no phrases (one node) switches every probe off.
+struct BiasImg {
+  host::HotwordView m;
+  bool ok, on;                // ok: a hotword image for these classes; on: it holds a phrase
+};
+
+__device__ __forceinline__ BiasImg bias_open(const void* image, int C, int blank) {
+  BiasImg b;
+  b.m = host::hotword_open(image, 0);
+  b.ok = b.m.ok && b.m.n_classes == (uint32_t)C && b.m.blank == (uint32_t)blank;
+  b.on = b.ok && b.m.n_nodes > 1;
+  return b;
+}
+
+struct BiasLds {
+  int state[2][kBeamMaxWidth];                           // automaton node of each entry's prefix (0: the root)
+  float bonus[2][kBeamMaxWidth];                         // bonus(prefix): the sum of its steps' deltas
+  int rchild[kBeamMaxTopN], rstate[kBeamMaxTopN];        // per kept label: the root's child by it (-1: none) and step(root, label)
+  float rdelta[kBeamMaxTopN];
+  float fin[kBeamMaxWidth], fin_am[kBeamMaxWidth], fin_b[kBeamMaxWidth];   // the re-ranked final scores
+};
+
+// step(root, c) of the kept label this thread fetched (tid < n): c = BeamFetch::pc before beam_fetch_frame publishes it
+__device__ __forceinline__ void bias_root_steps(const BiasImg& hw, BiasLds& s, int tid, int n, int c, int blank) {
+  if (tid >= n) return;
+  int child = -1, st = 0;
+  float d = 0.f;
+  if (hw.on && c != blank && c >= 0 && (uint32_t)c < hw.m.n_classes) {
+    child = host::hotword_child(hw.m, 0, c);
+    st = host::hotword_step(hw.m, 0, c, child, host::HotwordEdge{}, &d);
+  }
+  s.rchild[tid] = child; s.rstate[tid] = st; s.rdelta[tid] = d;
+}
+
+// the slot the walk of (entry p, label c) probes first: loaded ahead of bias_walk, for several candidates at once.  Held as
+// (key, child) so that a thread's group of them stays in registers.
+struct BiasFirst {
+  uint64_t key;
+  int32_t child;
+};
+
+__device__ __forceinline__ BiasFirst bias_first(const BiasImg& hw, const BiasLds& s, int cur, int p, int c) {
+  const int v = s.state[cur][p];
+  if (!hw.on || v == 0) return BiasFirst{host::kHotwordEmptyKey, -1};
+  const uint4 e = *reinterpret_cast<const uint4*>(&hw.m.edge[host::hotword_slot(hw.m, v, c)]);
+  return BiasFirst{(uint64_t)e.x | ((uint64_t)e.y << 32), (int32_t)e.z};
+}
+
+// step(state(p), kept[k] = c): the node p+c reaches; *delta = bonus(p+c) - bonus(p)
+__device__ __forceinline__ int bias_walk(const BiasImg& hw, const BiasLds& s, int cur, int p, int k, int c,
+                                         uint64_t first_key, int32_t first_child, float* delta) {
+  const int v = s.state[cur][p];
+  if (!hw.on) { *delta = 0.f; return 0; }
+  if (v == 0) { *delta = s.rdelta[k]; return s.rstate[k]; }
+  host::HotwordEdge first;
+  first.key = first_key; first.child = first_child; first.reserved = 0;
+  return host::hotword_step(hw.m, v, c, s.rchild[k], first, delta);
+}
+
+// End of utterance.  Thread tid < nbeam hands in its entry's final score f (final(p) included), the am_scores value and
+// final(p); the entries are ranked by f, ties by their order before, and (node, len) and the three values are written in the
+// new order: node / len into the other half of the beam, which is returned for beam_write_back.
+__device__ __forceinline__ int bias_rerank(BeamCore& core, BiasLds& s, int cur, int nbeam, int tid, float f, float am, float fb) {
+  if (tid < nbeam) core.score[tid] = f;
+  __syncthreads();
+  const int fin = cur ^ 1;
+  if (tid < nbeam) {
+    int rank = 0;
+    for (int r = 0; r < nbeam; ++r) {
+      const float g = core.score[r];
+      rank += g > f || (g == f && r < tid);
+    }
+    core.node[fin][rank] = core.node[cur][tid]; core.len[fin][rank] = core.len[cur][tid];
+    s.fin[rank] = f; s.fin_am[rank] = am; s.fin_b[rank] = fb;
+  }
+  return fin;
+}
+
+// after beam_write_back (whose barrier publishes fin / fin_am / fin_b): scores, am_scores and bias_scores of slot o
+__device__ __forceinline__ void bias_write_scores(const BiasLds& s, bool have, int tid, int64_t o, float* scores, float* am_scores,
+                                                  float* bias_scores) {
+  scores[o] = have ? s.fin[tid] : kNegInfB;
+  am_scores[o] = have ? s.fin_am[tid] : kNegInfB;
+  bias_scores[o] = have ? s.fin_b[tid] : 0.f;
+}
+
 // core.b / core.nb stay ACOUSTIC here and core.score is the fused score; the LM's share of an entry lives beside the core
 struct BeamLmLds {
   BeamCore core;
@@ -684,27 +777,42 @@ struct BeamLmLds {
   int kwid[kBeamMaxTopN];                                // LM word id of each kept label (-1: the blank, or not in the LM)
   int ctx_oov[kBeamMaxWidth];
 };
+// the same with hotword biasing: each entry's automaton node and bias bonus sit next to its LM bonus / term
+struct BeamLmBiasLds : BeamLmLds {
+  BiasLds hw;
+};
+static_assert(sizeof(BeamLmLds) < 64 * 1024 && sizeof(BeamLmBiasLds) < 64 * 1024, "static LDS of the LM search");
 
-template <int J>
+// kBias: lasr_ctc_beam_decode_lm_bias, the search with hotword biasing (bias_image, bias_scores).  Every statement of the
+// biasing is under `if constexpr (kBias)`: the kBias = false instantiation is the LM search alone.
+template <int J, bool kBias>
 __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
     const float* __restrict__ logp, const int32_t* __restrict__ kcls_g, const float* __restrict__ klp_g,
     const int32_t* __restrict__ kn_g, const int32_t* __restrict__ lens, int64_t T, int C, int blank, int W, int n_best,
     const void* __restrict__ image, float alpha, float beta, int2* __restrict__ trie_g, int32_t* __restrict__ tokens,
-    int32_t* __restrict__ n_tokens, float* __restrict__ scores, float* __restrict__ am_scores) {
-  __shared__ BeamLmLds s;
+    int32_t* __restrict__ n_tokens, float* __restrict__ scores, float* __restrict__ am_scores,
+    const void* __restrict__ bias_image, float* __restrict__ bias_scores) {
+  __shared__ std::conditional_t<kBias, BeamLmBiasLds, BeamLmLds> s;
   BeamCore& core = s.core;
   const int tid = threadIdx.x;
   const int64_t ub = blockIdx.x;
-  const LmImg lm = lm_open(image);
+  LmImg lm = lm_open(image);
+  BiasImg hw{};
+  if constexpr (kBias) {
+    hw = bias_open(bias_image, C, blank);
+    lm.ok = lm.ok && hw.ok;             // either image wrong: empty slots
+  }
   const int64_t L = !lm.ok ? 0 : lens ? min((int64_t)max(lens[ub], 0), T) : T;
   const int nctx = lm.nctx;
   int2* trie = trie_g + ub * (1 + T * (int64_t)W);
   BeamFetch pf{kcls_g + ub * T * kBeamMaxTopN, klp_g + ub * T * kBeamMaxTopN, kn_g + ub * T};
   const float* lrow = logp + ub * T * (int64_t)C;
-  const float cut_beta = fmaxf(0.f, beta);
+  float cut_beta = fmaxf(0.f, beta);
+  if constexpr (kBias) cut_beta += hw.m.max_credit;     // the early cutoff's slack for one step of the automaton
   beam_init_root(core, tid);
   if (tid == 0) {
     s.bonus[0][0] = 0.f; s.term[0][0] = 0.f;
+    if constexpr (kBias) { s.hw.state[0][0] = 0; s.hw.bonus[0][0] = 0.f; }
     int rc[kLmMaxCtx];
     float cb[kLmMaxCtx + 1];
     for (int d = 0; d < kLmMaxCtx; ++d) rc[d] = lm.bos;
@@ -721,6 +829,7 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
   for (int64_t t = 0; t < L; ++t) {
     const float lblank = pblank;        // the frame's unpruned blank log-prob (the early cutoff's reference)
     if (tid < pf.pn) s.kwid[tid] = (pf.pc != blank && pf.pc >= 0 && (uint32_t)pf.pc < lm.n_classes) ? lm.cls[pf.pc] : -1;
+    if constexpr (kBias) bias_root_steps(hw, s.hw, tid, pf.pn, pf.pc, blank);
     const int nk = beam_fetch_frame(core, pf, t, L, tid);
     if (t + 1 < L) pblank = lrow[(t + 1) * (int64_t)C + blank];
     __syncthreads();
@@ -731,7 +840,8 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
       const int last = core.last[cur][tid];
       const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
       s.ascore[tid] = as;
-      core.score[tid] = as + s.bonus[cur][tid];
+      if constexpr (kBias) core.score[tid] = as + (s.bonus[cur][tid] + s.hw.bonus[cur][tid]);
+      else core.score[tid] = as + s.bonus[cur][tid];
       int oov = 0;
       for (int d = 0; d < nctx; ++d) oov |= s.ctx[cur][d][tid] < 0;
       s.ctx_oov[tid] = oov;
@@ -768,14 +878,18 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
       int64_t g[kLmGroup];
       int mm[kLmGroup], pp[kLmGroup], wc[kLmGroup];
       bool act[kLmGroup], ext[kLmGroup];
+      uint64_t hkey[kBias ? kLmGroup : 1];
+      int32_t hchild[kBias ? kLmGroup : 1];
 #pragma unroll
       for (int u = 0; u < kLmGroup; ++u) {
         const int j = j0 + u;
         am[u] = kNegInfB; lpv[u] = 0.f; g[u] = 0; mm[u] = 0; pp[u] = 0; wc[u] = -1; act[u] = false; ext[u] = false;
+        if constexpr (kBias) { hkey[u] = host::kHotwordEmptyKey; hchild[u] = -1; }
         if (j >= J) continue;
         const int i = tid + j * kSearchThreads;
         if (i < nbeam) {
-          am[u] = lae(core.next_b[i], core.next_nb[i]) + s.bonus[cur][i];
+          if constexpr (kBias) am[u] = lae(core.next_b[i], core.next_nb[i]) + (s.bonus[cur][i] + s.hw.bonus[cur][i]);
+          else am[u] = lae(core.next_b[i], core.next_nb[i]) + s.bonus[cur][i];
         } else if (i < ncand) {
           const int q = i - nbeam, p = q / nk, k = q - p * nk;
           const int c = core.kcls[k];
@@ -784,6 +898,12 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
             am[u] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
             ext[u] = am[u] > kNegInfB;
             wc[u] = s.kwid[k];
+            if constexpr (kBias) {
+              if (ext[u]) {
+                const BiasFirst e = bias_first(hw, s.hw, cur, p, c);
+                hkey[u] = e.key; hchild[u] = e.child;
+              }
+            }
             if (ext[u] && wc[u] >= 0 && !s.ctx_oov[p]) {
               g[u] = wc[u];
               lpv[u] = lm.uni[wc[u]].x;
@@ -834,7 +954,13 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
             const bool oov = wc[u] < 0 || s.ctx_oov[p];
             const float lmv = oov ? kLmOov : (lpv[u] + s.cb[cur][mm[u]][p]) / kLmLogE;
             term[j] = alpha * lmv + beta;
-            sc = am[u] + (s.bonus[cur][p] + term[j]);
+            if constexpr (kBias) {
+              float hd;
+              bias_walk(hw, s.hw, cur, p, k, core.kcls[k], hkey[u], hchild[u], &hd);
+              sc = am[u] + ((s.bonus[cur][p] + term[j]) + (s.hw.bonus[cur][p] + hd));
+            } else {
+              sc = am[u] + (s.bonus[cur][p] + term[j]);
+            }
           }
         }
         comp[j] = ((uint64_t)desc_bits(sc) << 32) | key;
@@ -853,6 +979,7 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
       if (i < nbeam) {
         beam_keep_entry(core, cur, nxt, rank, i);
         s.bonus[nxt][rank] = s.bonus[cur][i]; s.term[nxt][rank] = s.term[cur][i];
+        if constexpr (kBias) { s.hw.state[nxt][rank] = s.hw.state[cur][i]; s.hw.bonus[nxt][rank] = s.hw.bonus[cur][i]; }
         for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[nxt][d][rank] = s.ctx[cur][d][i];
         for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[nxt][d][rank] = s.cb[cur][d][i];
       } else {
@@ -862,6 +989,12 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
         beam_new_entry(core, cur, nxt, rank, p, c, t, W, trie);
         core.nb[nxt][rank] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
         s.bonus[nxt][rank] = s.bonus[cur][p] + tm; s.term[nxt][rank] = tm;
+        if constexpr (kBias) {
+          float hd;
+          const BiasFirst e = bias_first(hw, s.hw, cur, p, c);
+          s.hw.state[nxt][rank] = bias_walk(hw, s.hw, cur, p, k, c, e.key, e.child, &hd);
+          s.hw.bonus[nxt][rank] = s.hw.bonus[cur][p] + hd;
+        }
         int nc[kLmMaxCtx];
         float cb[kLmMaxCtx + 1];
         const int w = s.kwid[k];
@@ -875,6 +1008,26 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
     nbeam = nsel;
     cur = nxt;
     __syncthreads();
+  }
+  if constexpr (kBias) {
+    // end of utterance: an unfinished match gives its provisional credit back, the final entries are re-ranked
+    float f = kNegInfB, am = kNegInfB, fb = 0.f;
+    if (lm.ok && tid < nbeam) {
+      const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
+      int cx[kLmMaxCtx];
+      float cb[kLmMaxCtx + 1];
+      for (int d = 0; d < kLmMaxCtx; ++d) cx[d] = s.ctx[cur][d][tid];
+      for (int d = 0; d <= kLmMaxCtx; ++d) cb[d] = s.cb[cur][d][tid];
+      float sent = lm_score_one(lm, lm.eos, cx, cb);
+      if (core.len[cur][tid] == 0) sent += lm_score_one(lm, lm.bos, cx, cb);
+      fb = s.hw.bonus[cur][tid] + (hw.on ? host::hotword_give_back(hw.m, s.hw.state[cur][tid]) : 0.f);
+      f = as + (s.bonus[cur][tid] + fb);
+      am = as - alpha * sent;
+    }
+    const int fin = bias_rerank(core, s.hw, cur, lm.ok ? nbeam : 0, tid, f, am, fb);
+    beam_write_back(core, fin, nbeam, n_best, T, trie, tokens + ub * (int64_t)n_best * T, n_tokens + ub * n_best, lm.ok, tid);
+    if (tid < n_best) bias_write_scores(s.hw, lm.ok && tid < nbeam, tid, ub * n_best + tid, scores, am_scores, bias_scores);
+    return;
   }
   beam_write_back(core, cur, nbeam, n_best, T, trie, tokens + ub * (int64_t)n_best * T, n_tokens + ub * n_best, lm.ok, tid);
   if (tid < n_best) {
@@ -898,6 +1051,150 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
   }
 }
 
+// lasr_ctc_beam_decode_bias: the LM-free search with hotword biasing.  core.b / core.nb stay ACOUSTIC, core.score is
+// logaddexp(b, nb) + bonus(prefix), what the beam is ranked by.  With a bank of no phrases every bonus is 0 and each score is
+// the expression beam_search_kernel evaluates, so the result is that kernel's bit for bit.
+struct BeamBiasLds {
+  BeamCore core;
+  float ascore[kBeamMaxWidth];                           // acoustic logaddexp(b, nb) of the current beam
+  BiasLds hw;
+};
+static_assert(sizeof(BeamBiasLds) < 64 * 1024, "static LDS of the biased search");
+
+template <int J>
+__global__ __launch_bounds__(kSearchThreads) void beam_search_bias_kernel(
+    const int32_t* __restrict__ kcls_g, const float* __restrict__ klp_g, const int32_t* __restrict__ kn_g,
+    const int32_t* __restrict__ lens, int64_t T, int C, int blank, int W, int n_best, const void* __restrict__ bias_image,
+    int2* __restrict__ trie_g, int32_t* __restrict__ tokens, int32_t* __restrict__ n_tokens, float* __restrict__ scores,
+    float* __restrict__ am_scores, float* __restrict__ bias_scores) {
+  __shared__ BeamBiasLds s;
+  BeamCore& core = s.core;
+  const int tid = threadIdx.x;
+  const int64_t ub = blockIdx.x;
+  const BiasImg hw = bias_open(bias_image, C, blank);
+  const int64_t L = !hw.ok ? 0 : lens ? min((int64_t)max(lens[ub], 0), T) : T;
+  int2* trie = trie_g + ub * (1 + T * (int64_t)W);
+  BeamFetch pf{kcls_g + ub * T * kBeamMaxTopN, klp_g + ub * T * kBeamMaxTopN, kn_g + ub * T};
+  beam_init_root(core, tid);
+  if (tid == 0) { s.hw.state[0][0] = 0; s.hw.bonus[0][0] = 0.f; }
+  int nbeam = 1, cur = 0;
+  if (L > 0) pf.request(0, tid);
+  for (int64_t t = 0; t < L; ++t) {
+    bias_root_steps(hw, s.hw, tid, pf.pn, pf.pc, blank);
+    const int nk = beam_fetch_frame(core, pf, t, L, tid);
+    __syncthreads();
+    // (1) per live prefix: scores, kept index of its last label and of the blank, its parent among the live entries
+    int lastk = -1, pr = -1;
+    float blp = kNegInfB;
+    if (tid < nbeam) {
+      const int last = core.last[cur][tid];
+      const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
+      s.ascore[tid] = as;
+      core.score[tid] = as + s.hw.bonus[cur][tid];
+      beam_lookup(core, cur, nbeam, nk, blank, tid, last, &lastk, &pr, &blp);
+    }
+    __syncthreads();
+    // (2) "no new label" candidates (acoustic), with the parent's extension by the last label folded in
+    if (tid < nbeam) {
+      float nbn = kNegInfB;
+      if (lastk >= 0) {
+        const float lc = core.klp[lastk];
+        nbn = lc + core.nb[cur][tid];
+        if (pr >= 0) {
+          nbn = lae(nbn, lc + (core.last[cur][tid] == core.last[cur][pr] ? core.b[cur][pr] : s.ascore[pr]));
+          atomicOr(&core.merged[pr], 1ull << lastk);
+        }
+      }
+      core.next_b[tid] = blp + s.ascore[tid];
+      core.next_nb[tid] = nbn;
+    }
+    __syncthreads();
+    // (3) candidates; only finite, unmerged, non-blank extensions are walked, the first probes of kLmGroup of them together
+    const int ncand = nbeam + nbeam * nk;
+    uint64_t comp[J];
+    uint64_t valid = 0;
+#pragma unroll
+    for (int j0 = 0; j0 < J; j0 += kLmGroup) {
+      float sc[kLmGroup];
+      uint32_t ck[kLmGroup];
+      int pp[kLmGroup], kk[kLmGroup];
+      bool ext[kLmGroup];
+      uint64_t hkey[kLmGroup];
+      int32_t hchild[kLmGroup];
+#pragma unroll
+      for (int u = 0; u < kLmGroup; ++u) {
+        const int j = j0 + u;
+        sc[u] = kNegInfB; ck[u] = 0; pp[u] = 0; kk[u] = 0; ext[u] = false; hkey[u] = host::kHotwordEmptyKey; hchild[u] = -1;
+        if (j >= J) continue;
+        const int i = tid + j * kSearchThreads;
+        if (i < nbeam) {
+          sc[u] = lae(core.next_b[i], core.next_nb[i]) + s.hw.bonus[cur][i];
+          ck[u] = (uint32_t)i << 14;
+        } else if (i < ncand) {
+          const int q = i - nbeam, p = q / nk, k = q - p * nk;
+          const int c = core.kcls[k];
+          pp[u] = p; kk[u] = k;
+          ck[u] = ((uint32_t)p << 14) | (uint32_t)(c + 1);
+          if (c != blank && !((core.merged[p] >> k) & 1ull)) {
+            sc[u] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
+            ext[u] = sc[u] > kNegInfB;
+            if (ext[u]) {
+              const BiasFirst e = bias_first(hw, s.hw, cur, p, c);
+              hkey[u] = e.key; hchild[u] = e.child;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kLmGroup; ++u) {
+        const int j = j0 + u;
+        if (j >= J) continue;
+        if (ext[u]) {
+          float hd;
+          bias_walk(hw, s.hw, cur, pp[u], kk[u], core.kcls[kk[u]], hkey[u], hchild[u], &hd);
+          sc[u] = sc[u] + (s.hw.bonus[cur][pp[u]] + hd);
+        }
+        comp[j] = ((uint64_t)desc_bits(sc[u]) << 32) | ck[u];
+        if (sc[u] > kNegInfB) valid |= 1ull << j;
+      }
+    }
+    // (4) select the W best, (5) compact and order them, write the next beam: the core fields, then the automaton's
+    uint64_t prefix, mask;
+    beam_select<J>(core, comp, valid, W, tid, &prefix, &mask);
+    const int nsel = beam_compact<J>(core, comp, valid, prefix, mask, W, tid, [](uint32_t, int) {});
+    const int nxt = cur ^ 1;
+    if (tid < nsel) {
+      const int rank = beam_rank(core, nsel, tid);
+      const int i = core.surv_i[tid];
+      if (i < nbeam) {
+        beam_keep_entry(core, cur, nxt, rank, i);
+        s.hw.state[nxt][rank] = s.hw.state[cur][i]; s.hw.bonus[nxt][rank] = s.hw.bonus[cur][i];
+      } else {
+        const int q = i - nbeam, p = q / nk, k = q - p * nk;
+        const int c = core.kcls[k];
+        beam_new_entry(core, cur, nxt, rank, p, c, t, W, trie);
+        core.nb[nxt][rank] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
+        float hd;
+        const BiasFirst e = bias_first(hw, s.hw, cur, p, c);
+        s.hw.state[nxt][rank] = bias_walk(hw, s.hw, cur, p, k, c, e.key, e.child, &hd);
+        s.hw.bonus[nxt][rank] = s.hw.bonus[cur][p] + hd;
+      }
+    }
+    nbeam = nsel;
+    cur = nxt;
+    __syncthreads();
+  }
+  // end of utterance: an unfinished match gives its provisional credit back, the final entries are re-ranked
+  float f = kNegInfB, am = kNegInfB, fb = 0.f;
+  if (hw.ok && tid < nbeam) {
+    am = lae(core.b[cur][tid], core.nb[cur][tid]);
+    fb = s.hw.bonus[cur][tid] + (hw.on ? host::hotword_give_back(hw.m, s.hw.state[cur][tid]) : 0.f);
+    f = am + fb;
+  }
+  const int fin = bias_rerank(core, s.hw, cur, hw.ok ? nbeam : 0, tid, f, am, fb);
+  beam_write_back(core, fin, nbeam, n_best, T, trie, tokens + ub * (int64_t)n_best * T, n_tokens + ub * n_best, hw.ok, tid);
+  if (tid < n_best) bias_write_scores(s.hw, hw.ok && tid < nbeam, tid, ub * n_best + tid, scores, am_scores, bias_scores);
+}
 
 // ================================================================== with a word n-gram LM and its lexicon ==============
 // lasr_ctc_beam_decode_wlm: the same search with a word-level scorer (include/lasr.h states the contract).  Each entry carries
@@ -1221,8 +1518,9 @@ extern "C" int lasr_ctc_beam_decode_lm(const float* logp, const int32_t* lens, i
   LASR_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "lasr_ctc_beam_decode_lm: alpha %g / beta %g not finite",
                  (double)alpha, (double)beta);
   auto search = [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
-    hipLaunchKernelGGL(beam_search_lm_kernel<decltype(j)::value>, grid, dim3(kSearchThreads), 0, st, logp, kc, kl, kn, lens, T,
-                       (int)C, blank, beam_width, n_best, lm_image, alpha, beta, trie, tokens, n_tokens, scores, am_scores);
+    hipLaunchKernelGGL((beam_search_lm_kernel<decltype(j)::value, false>), grid, dim3(kSearchThreads), 0, st, logp, kc, kl, kn, lens,
+                       T, (int)C, blank, beam_width, n_best, lm_image, alpha, beta, trie, tokens, n_tokens, scores, am_scores,
+                       (const void*)nullptr, (float*)nullptr);
   };
   return beam_launch(a, "beam_search_lm_kernel", search);
 }
@@ -1266,4 +1564,93 @@ extern "C" int lasr_ctc_beam_decode_wlm(const float* logp, const int32_t* lens, 
                        (int)C, blank, beam_width, n_best, lm_image, alpha, beta, trie, tokens, n_tokens, scores, am_scores);
   };
   return beam_launch(a, "beam_search_wlm_kernel", search);
+}
+
+// ------------------------------------------------------------------ hotword biasing: the C ABI -------------------------
+namespace lasr {
+namespace {
+
+struct HotwordHandle {
+  host::HotwordBank b;
+};
+
+}  // namespace
+}  // namespace lasr
+
+extern "C" int lasr_hotword_build(const int32_t* labels, const int64_t* offsets, const float* weights, int n_phrases, int64_t C,
+                                  int blank, void** handle) {
+  LASR_CHECK_ARG(handle, "lasr_hotword_build: null handle");
+  *handle = nullptr;
+  HotwordHandle* h = new HotwordHandle();
+  std::string err;
+  const int rc = host::hotword_build(labels, offsets, weights, n_phrases, C, blank, &h->b, &err);   // hotword_io.h (also built
+  if (rc != host::kHotwordOk) {                                                                      // under ASan / UBSan)
+    delete h;
+    return fail(rc == host::kHotwordErrFormat ? LASR_E_FORMAT : LASR_E_ARG, "lasr_hotword_build: %s", err.c_str());
+  }
+  *handle = h;
+  return 0;
+}
+
+extern "C" int lasr_hotword_info(const void* handle, int64_t* n_phrases, int64_t* n_nodes, float* max_credit, size_t* image_bytes) {
+  LASR_CHECK_ARG(handle, "lasr_hotword_info: null handle");
+  const host::HotwordBank& b = static_cast<const HotwordHandle*>(handle)->b;
+  if (n_phrases) *n_phrases = b.n_phrases;
+  if (n_nodes) *n_nodes = b.n_nodes;
+  if (max_credit) *max_credit = b.max_credit;
+  if (image_bytes) *image_bytes = b.image.size();
+  return 0;
+}
+
+extern "C" int lasr_hotword_write_image(const void* handle, void* host_dst, size_t bytes) {
+  LASR_CHECK_ARG(handle && host_dst, "lasr_hotword_write_image: null pointer");
+  const host::HotwordBank& b = static_cast<const HotwordHandle*>(handle)->b;
+  if (bytes < b.image.size())
+    return fail(LASR_E_WORKSPACE, "lasr_hotword_write_image: %zu < %zu bytes", bytes, b.image.size());
+  memcpy(host_dst, b.image.data(), b.image.size());
+  return 0;
+}
+
+extern "C" void lasr_hotword_free(void* handle) { delete static_cast<HotwordHandle*>(handle); }
+
+extern "C" int lasr_hotword_score(const void* handle, const int32_t* labels, int64_t n, float* bonus, float* final_bonus,
+                                  int32_t* state) {
+  LASR_CHECK_ARG(handle && (labels || n == 0) && n >= 0, "lasr_hotword_score: null pointer or negative length");
+  const host::HotwordBank& b = static_cast<const HotwordHandle*>(handle)->b;
+  std::string err;
+  const int rc = host::hotword_score(b.image.data(), b.image.size(), labels, n, bonus, final_bonus, state, &err);
+  if (rc != host::kHotwordOk) return fail(rc == host::kHotwordErrFormat ? LASR_E_FORMAT : LASR_E_ARG, "lasr_hotword_score: %s", err.c_str());
+  return 0;
+}
+
+extern "C" int lasr_ctc_beam_decode_bias(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
+                                         int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* bias_image,
+                                         int32_t* tokens, int32_t* n_tokens, float* scores, float* am_scores, float* bias_scores,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  const BeamArgs a{"lasr_ctc_beam_decode_bias", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
+                   workspace_bytes, stream};
+  LASR_TRY(beam_check_args(a, logp && bias_image && tokens && n_tokens && scores && am_scores && bias_scores && workspace));
+  auto search = [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
+    hipLaunchKernelGGL(beam_search_bias_kernel<decltype(j)::value>, grid, dim3(kSearchThreads), 0, st, kc, kl, kn, lens, T, (int)C,
+                       blank, beam_width, n_best, bias_image, trie, tokens, n_tokens, scores, am_scores, bias_scores);
+  };
+  return beam_launch(a, "beam_search_bias_kernel", search);
+}
+
+extern "C" int lasr_ctc_beam_decode_lm_bias(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
+                                            int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image,
+                                            float alpha, float beta, const void* bias_image, int32_t* tokens, int32_t* n_tokens,
+                                            float* scores, float* am_scores, float* bias_scores, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  const BeamArgs a{"lasr_ctc_beam_decode_lm_bias", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
+                   workspace_bytes, stream};
+  LASR_TRY(beam_check_args(a, logp && lm_image && bias_image && tokens && n_tokens && scores && am_scores && bias_scores && workspace));
+  LASR_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "lasr_ctc_beam_decode_lm_bias: alpha %g / beta %g not finite",
+                 (double)alpha, (double)beta);
+  auto search = [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
+    hipLaunchKernelGGL((beam_search_lm_kernel<decltype(j)::value, true>), grid, dim3(kSearchThreads), 0, st, logp, kc, kl, kn, lens, T,
+                       (int)C, blank, beam_width, n_best, lm_image, alpha, beta, trie, tokens, n_tokens, scores, am_scores, bias_image,
+                       bias_scores);
+  };
+  return beam_launch(a, "beam_search_lm_kernel (biased)", search);
 }

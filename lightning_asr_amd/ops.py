@@ -635,6 +635,138 @@ def ctc_beam_decode_lm(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: 
     return tokens, n, scores, am
 
 
+HOTWORD_MAX_LEN = 32          # lasr_hotword_build's ranges (include/lasr.h)
+HOTWORD_MAX_PHRASES = 65536
+
+
+class HotwordBank:
+    """A bank of phrases the beam search is biased towards (build_hotwords): the device image of its automaton, the number of
+    phrases and trie nodes (the root included) and max_credit, the largest credit a node carries.  The host handle behind
+    hotword_bonus is kept with the bank and freed with it."""
+
+    def __init__(self, image: torch.Tensor, n_phrases: int, n_nodes: int, max_credit: float, n_classes: int, blank: int, handle=None):
+        self.image = image
+        self.n_phrases, self.n_nodes = int(n_phrases), int(n_nodes)
+        self.max_credit = float(max_credit)
+        self.n_classes, self.blank = int(n_classes), int(blank)
+        self._handle = handle
+
+    def __del__(self):
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            try:
+                _lib.load().lasr_hotword_free(h)
+            except Exception:       # interpreter shutdown
+                pass
+
+    def __repr__(self):
+        return "HotwordBank(n_phrases=%d, n_nodes=%d, max_credit=%g, %d bytes on %s)" % (
+            self.n_phrases, self.n_nodes, self.max_credit, self.image.numel(), self.image.device)
+
+
+def build_hotwords(phrases, weights=2.0, *, n_classes: int, blank: int, device="cuda") -> HotwordBank:
+    """Build the biasing automaton of `phrases`, a list of label-id lists (1..32 ids in [0, n_classes), none the blank; an empty
+    list is a valid bank that biases nothing), and copy its image to `device`.  `weights`: one float for all phrases or one per
+    phrase, finite and > 0, in natural-log units per matched label.  The default 2.0 is a starting value: nobody has tuned it
+    on a trained model.  A bad phrase or weight raises ValueError naming the phrase index."""
+    import numpy as np
+    phrases = [list(p) for p in phrases]
+    n = len(phrases)
+    if isinstance(weights, (int, float)):
+        weights = [float(weights)] * n
+    weights = [float(w) for w in weights]
+    if len(weights) != n:
+        raise ValueError("%d weights for %d phrases" % (len(weights), n))
+    labels = np.asarray([c for p in phrases for c in p], dtype=np.int64)
+    if labels.size and (labels.min() < -2 ** 31 or labels.max() >= 2 ** 31):
+        raise ValueError("a label id outside the int32 range")
+    labels = np.ascontiguousarray(labels.astype(np.int32))
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum([len(p) for p in phrases], out=offsets[1:])
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32))
+    lib = _lib.load()
+    h = ctypes.c_void_p()
+    rc = lib.lasr_hotword_build(labels.ctypes.data if n else None, offsets.ctypes.data if n else None, w.ctypes.data if n else None,
+                                n, int(n_classes), int(blank), ctypes.byref(h))
+    if rc != 0:
+        raise ValueError(lib.lasr_last_error().decode(errors="replace"))
+    try:
+        n_p, n_nodes, mc, nb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_float(), ctypes.c_size_t()
+        call("lasr_hotword_info", h, ctypes.byref(n_p), ctypes.byref(n_nodes), ctypes.byref(mc), ctypes.byref(nb))
+        host = np.empty(int(nb.value), dtype=np.uint8)
+        call("lasr_hotword_write_image", h, host.ctypes.data, int(nb.value))
+        image = torch.from_numpy(host).to(device)
+    except Exception:
+        lib.lasr_hotword_free(h)
+        raise
+    return HotwordBank(image, n_p.value, n_nodes.value, mc.value, n_classes, blank, h)
+
+
+def hotword_bonus(bank: HotwordBank, ids):
+    """The host walk of the label sequence `ids` over `bank`: (bonus, final, state) of that prefix (include/lasr.h: bonus is what
+    the search adds while the prefix is live, final what it is worth at the end of the utterance, state the automaton node)."""
+    import numpy as np
+    if not isinstance(bank, HotwordBank) or not bank._handle:
+        raise TypeError("bank must be a HotwordBank (ops.build_hotwords)")
+    a = np.ascontiguousarray(np.asarray(list(ids), dtype=np.int32))
+    b, f, st = ctypes.c_float(), ctypes.c_float(), ctypes.c_int32()
+    lib = _lib.load()
+    rc = lib.lasr_hotword_score(bank._handle, a.ctypes.data if a.size else None, int(a.size), ctypes.byref(b), ctypes.byref(f),
+                                ctypes.byref(st))
+    if rc != 0:
+        raise ValueError(lib.lasr_last_error().decode(errors="replace"))
+    return b.value, f.value, st.value
+
+
+def ctc_beam_decode_biased(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: int, bank: HotwordBank, beam_width: int = 16,
+                           cutoff_top_n: int = 40, cutoff_prob: float = 1.0, n_best: int = 1, lm: Optional[ArpaLm] = None,
+                           alpha: Optional[float] = None, beta: Optional[float] = None):
+    """ctc_beam_decode (lm=None) or ctc_beam_decode_lm (a character-based `lm`) biased towards the phrases of `bank`
+    (build_hotwords).  Returns (tokens, n_tokens, scores, am_scores, bias_scores): scores are what the hypotheses are ranked by,
+    the acoustic (or LM-fused) score plus bias_scores, the phrase credit of each hypothesis; am_scores are the acoustic
+    log-scores without an LM and ctc_decoders' approx_ctc with one.  Argument checks as ctc_beam_decode / ctc_beam_decode_lm;
+    the bank must be built for logp's classes and blank and sit on its device.  A word-level LM raises NotImplementedError:
+    its lexicon already confines the search to the LM's words."""
+    who = "ctc_beam_decode_biased"
+    if logp.dtype == torch.float32 and logp.dim() == 3:
+        if not isinstance(bank, HotwordBank):
+            raise TypeError("bank must be a HotwordBank (ops.build_hotwords)")
+        if lm is not None and not isinstance(lm, ArpaLm):
+            raise TypeError("lm must be an ArpaLm (ops.load_arpa) or None")
+    B, T, Cc, cutoff_top_n = _beam_args(logp, lens, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, who)
+    if lm is not None and not lm.is_character_based():
+        raise NotImplementedError("hotword biasing of the word-level LM search is not implemented: its lexicon confines the "
+                                  "search to the LM's words")
+    if bank.n_classes != Cc or bank.blank != blank:
+        raise ValueError("the hotword bank was built for %d classes with blank %d; the log-probs have %d classes, blank %d"
+                         % (bank.n_classes, bank.blank, Cc, blank))
+    if bank.image.device != logp.device:
+        raise ValueError("the hotword image is on %s, the log-probs on %s" % (bank.image.device, logp.device))
+    nb = int(_lib.load().lasr_ctc_beam_workspace_bytes(B, T, Cc, beam_width, cutoff_top_n))
+    if nb == 0:
+        raise ValueError("%s: shape (%d, %d, %d) outside the kernel's range" % (who, B, T, Cc))
+    if lm is not None:
+        alpha = lm.alpha if alpha is None else float(alpha)
+        beta = lm.beta if beta is None else float(beta)
+        if not (math.isfinite(alpha) and math.isfinite(beta)):
+            raise ValueError("alpha %r / beta %r must be finite" % (alpha, beta))
+        if len(lm.vocab) != Cc - 1:
+            raise ValueError("the LM was loaded for %d labels; the log-probs have %d classes" % (len(lm.vocab), Cc))
+        if lm.image.device != logp.device:
+            raise ValueError("the LM image is on %s, the log-probs on %s" % (lm.image.device, logp.device))
+    tokens, n, scores = _beam_outputs(logp, n_best)
+    am, bias = torch.empty_like(scores), torch.empty_like(scores)
+    ws = _ws(nb, logp.device)
+    if lm is None:
+        call("lasr_ctc_beam_decode_bias", _p(logp), _p(lens), B, T, Cc, int(blank), int(beam_width), int(cutoff_top_n),
+             float(cutoff_prob), int(n_best), _p(bank.image), _p(tokens), _p(n), _p(scores), _p(am), _p(bias), _p(ws), nb, _stream())
+    else:
+        call("lasr_ctc_beam_decode_lm_bias", _p(logp), _p(lens), B, T, Cc, int(blank), int(beam_width), int(cutoff_top_n),
+             float(cutoff_prob), int(n_best), _p(lm.image), alpha, beta, _p(bank.image), _p(tokens), _p(n), _p(scores), _p(am),
+             _p(bias), _p(ws), nb, _stream())
+    return tokens, n, scores, am, bias
+
+
 # ---------------------------------------------------------------------------------- optimiser
 def novograd_workspace(n_tensors: int, n_elems: int, device) -> torch.Tensor:
     """a ZEROED workspace a caller keeps across novograd_step(ws=...) calls (every call leaves it zeroed)"""

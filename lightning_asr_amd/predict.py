@@ -38,12 +38,19 @@ MIN_ROW_SAMPLES = 160 * (33 - 1) - 64
 class AsrTranslator:
     def __init__(self, model_path: str, map_location: str = "cuda", lang: str = "en", labels: Optional[List[str]] = None,
                  verbose: bool = False, decoder: str = "greedy", beam_width: int = 16, cutoff_top_n: int = 40,
-                 cutoff_prob: float = 1.0, lm_path: Optional[str] = None, alpha: float = 1.0, beta: float = 1.0, resample: bool = False):
+                 cutoff_prob: float = 1.0, lm_path: Optional[str] = None, alpha: float = 1.0, beta: float = 1.0, resample: bool = False,
+                 hotwords=None, hotword_weight: float = 2.0):
         """model_path: a ``.ckpt`` written by the reference or by ``Trainer``; map_location must name a GPU
         ("cuda" / "cuda:0"): there is no CPU path.  ``labels`` overrides the language's vocabulary.
         decoder: "greedy" (argmax + CTC collapse, the default) or "beam" (CTC prefix beam search; with ``lm_path``, a text ARPA
         LM, fused with it: ``alpha`` weighs the LM, ``beta`` is the per-label bonus of a character LM and the per-word bonus
         of a word LM, under which only the LM's words are decoded).
+        hotwords: a list of ``str`` or ``(str, weight)`` the beam search is biased towards (names, product terms, contacts),
+        with or without a character LM; every beam path picks them up (``translate``, ``translate_nbest``, ``translate_timed``,
+        ``translate_long``, ``evalute_manifest`` and ``error_report`` with decoder="beam").  ``hotword_weight`` is the weight of a
+        phrase given without one, in natural-log units per matched label; the default 2.0 is a starting value: nobody has tuned
+        it on a trained model.  decoder="greedy" with hotwords raises ValueError, a word-level LM NotImplementedError;
+        ``set_hotwords`` swaps the bank later.
         resample: False (the default, the reference's behaviour) feeds a file's samples to the 16 kHz front-end whatever its
         sample rate; True converts a file of another rate on the device first (``ops.resample``) - ``translate``,
         ``translate_nbest``, ``align`` and ``translate_timed`` then hear it at its true speed and report its true times (each
@@ -51,6 +58,8 @@ class AsrTranslator:
         resample: with resample=True they refuse a manifest that holds a file of another rate."""
         if decoder not in ("greedy", "beam"):
             raise ValueError("decoder must be 'greedy' or 'beam', got %r" % (decoder,))
+        if hotwords and decoder != "beam":
+            raise ValueError("hotwords bias the beam search: decoder must be 'beam', got %r" % (decoder,))
         if labels is not None:
             self.labels = list(labels)
         elif lang == "en":
@@ -70,8 +79,15 @@ class AsrTranslator:
         self.decoder = decoder
         self.resample = bool(resample)
         self.beam = BeamSearchDecoderWithLM(self.labels, beam_width, alpha, beta, lm_path, 1, cutoff_prob=cutoff_prob,
-                                            cutoff_top_n=cutoff_top_n, device=str(map_location))
+                                            cutoff_top_n=cutoff_top_n, device=str(map_location), hotwords=hotwords,
+                                            hotword_weight=hotword_weight)
         self.model.eval()
+
+    def set_hotwords(self, hotwords, weight: Optional[float] = None) -> None:
+        """Swap the phrases the beam search is biased towards (``None`` or ``[]``: none); see ``__init__``"""
+        if hotwords and self.decoder != "beam":
+            raise ValueError("hotwords bias the beam search: the translator's decoder is %r" % (self.decoder,))
+        self.beam.set_hotwords(hotwords, weight)
 
     @torch.no_grad()
     def translate(self, audio_path, resample: Optional[bool] = None) -> str:
