@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 112   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 113   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
@@ -36,7 +36,8 @@ extern "C" {
                               109: lasr_edit_align_workspace_bytes / lasr_edit_align_batch (substitution/deletion/insertion alignment)
                               110: lasr_dwconv_plan (which depthwise kernel form and grid a shape takes; launches nothing)
                               111: lasr_vad_* / lasr_segment_gather (voice-activity segmentation of long recordings)
-                              112: lasr_hotword_* (phrase bank), lasr_ctc_beam_decode_bias / _lm_bias (hotword biasing) */
+                              112: lasr_hotword_* (phrase bank), lasr_ctc_beam_decode_bias / _lm_bias (hotword biasing)
+                              113: lasr_ctc_kws_workspace_bytes / lasr_ctc_kws (CTC keyword search: phrases with time spans) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -429,6 +430,46 @@ int lasr_ctc_align(const float* logp, const int64_t* targets, const int32_t* in_
                    int64_t B, int64_t T, int64_t C, int64_t S_max, int blank, float* score, int32_t* frame_state,
                    float* frame_logp, int32_t* label_start, int32_t* label_end, void* workspace, size_t workspace_bytes,
                    void* stream);
+
+/* CTC keyword search: where in each utterance is each of K phrases said, and how well?  The third member of the lattice family:
+ * a max-product walk like lasr_ctc_align's, with a free start and a free end.  One wave per (utterance, keyword) pair, the
+ * picking of the hits in the same launch, everything on `stream`; nothing is allocated or synchronised.
+ * logp (B, T, C) f32 log-probabilities, finite or -inf; in_lens (B) int32 clamped to [0, T], or NULL (= T); the keyword bank in the
+ * form lasr_hotword_build takes, but on the DEVICE: kw_labels int32 concatenated, kw_offsets (K + 1) int32 ascending offsets
+ * into it.  L_max in [1, LASR_KWS_MAX_LABELS] is the caller's bound on the longest phrase.  The device clamps every phrase start
+ * into [0, kw_offsets[K] - 1], every length into [1, min(L_max, labels left)] and every label into [0, C - 1], so that bad data
+ * cannot become an out-of-bounds access (kw_labels must hold at least one entry).
+ * For utterance b with Tb frames and a keyword with labels l_0 .. l_{L-1}:
+ *   States j = 0 .. 2L-2: even j is label l_{j/2}, odd j a blank between two labels; no leading or trailing blank (those are
+ *   the background's).  skip_ok(j) holds for even j >= 2 iff l_{j/2} != l_{j/2-1}.
+ *   Filler-normalised emission: m_t = max_c logp[b,t,c] (the blank included), e_t(j) = logp[b,t,cls(j)] - m_t, one f32
+ *   subtraction, so e_t(j) <= 0: a path's score is its log-likelihood ratio against the greedy path over the same frames.
+ *   Each state carries (v, s): an f32 score and the frame at which its path entered state 0.  Candidates at frame t: stay
+ *   (v,s)_{t-1}(j); step (v,s)_{t-1}(j-1) for j >= 1; skip (v,s)_{t-1}(j-2) if skip_ok(j); fresh (0, t) for j == 0 only.  The
+ *   best candidate has the larger v, on equal v the smaller s (ties go to the earliest start; a fresh start loses ties to
+ *   staying).  v_t(j) = best.v + e_t(j), one f32 add; s_t(j) = best.s.  Before t = 0 every state is dead.
+ *   End trace: E_t = v_t(2L-2), S_t = s_t(2L-2) (L = 1: state 0 is both ends).
+ * Hits of (b, k), t ascending, thr = (float)threshold * (float)L (one f32 multiply): frame t is a candidate iff E_t >= thr, its
+ * span [S_t, t+1), its score E_t.  One hit is pending.  A candidate whose start is below the pending hit's end overlaps it and
+ * replaces it iff its score >= the pending score (the later candidate wins ties); one that does not overlap emits the pending
+ * hit and becomes pending; the last pending hit is emitted at the end.  Emitting writes slot n only while n < max_hits but
+ * always counts: n_hits (B, K) may exceed max_hits (the convention of lasr_vad_segment's n_segs).  hit_span (B, K, max_hits, 2)
+ * int32, hit_score (B, K, max_hits) f32; unwritten slots hold (-1, -1) and 0.
+ * Best of each pair, whatever the threshold: best_score (B, K) = max_t E_t, on ties the latest t; best_span (B, K, 2) that
+ * frame's [S_t, t+1).  Dead states hold a finite sentinel: an end score not above -5e29 (a dead state, -inf, NaN) is not live;
+ * with no live end frame - always when Tb < L + (adjacent equal labels) - best_score is -inf and best_span (-1, -1).
+ * threshold must lie in (-1e6, 0] (else LASR_E_ARG), so a dead state never passes it.  Starts are outputs only, never an index.
+ * Emissions: where an utterance's rows fit LDS (C = 28; the predicate of the other lattice kernels, LASR_CTC_NO_LDS honoured)
+ * they are staged once per workgroup with the exact row maxima; otherwise (C = 4334) a pre-pass writes the row maxima (B x T
+ * f32) into the workspace and each lane gathers its class from global memory several frames ahead of the recursion.
+ * Before any launch: a null pointer LASR_E_ARG; L_max outside [1, 64], K < 1, max_hits < 1, blank outside [0, C) or T * C >=
+ * 2^31 LASR_E_SHAPE; a workspace below lasr_ctc_kws_workspace_bytes LASR_E_WORKSPACE. */
+#define LASR_KWS_MAX_LABELS 64
+size_t lasr_ctc_kws_workspace_bytes(int64_t B, int64_t T, int64_t K);
+int lasr_ctc_kws(const float* logp, const int32_t* in_lens, int64_t B, int64_t T, int64_t C, int blank,
+                 const int32_t* kw_labels, const int32_t* kw_offsets, int64_t K, int64_t L_max, float threshold, int max_hits,
+                 int32_t* n_hits, int32_t* hit_span, float* hit_score, float* best_score, int32_t* best_span, void* workspace,
+                 size_t workspace_bytes, void* stream);
 
 /* Greedy CTC collapse of argmax ids (B, T) int32 truncated to lens (B) (NULL = T):
  * tokens (B, T) int32, n_tokens (B) int32.   utils/asr_metrics.py:159-166                      */

@@ -458,6 +458,91 @@ def ctc_align(logp: torch.Tensor, targets: torch.Tensor, in_lens: Optional[torch
     return out
 
 
+KWS_MAX_LABELS = 64     # LASR_KWS_MAX_LABELS (include/lasr.h): the longest phrase of a keyword bank
+
+
+class KeywordBank:
+    """The phrases of a keyword search on the device (build_keywords): labels (sum of lengths,) i32 concatenated, offsets
+    (K + 1,) i32; lengths is the host copy of the phrase lengths, max_len the longest."""
+
+    def __init__(self, labels: torch.Tensor, offsets: torch.Tensor, lengths, n_classes: int, blank: int):
+        self.labels, self.offsets = labels, offsets
+        self.lengths = [int(n) for n in lengths]
+        self.n_phrases, self.max_len = len(self.lengths), max(self.lengths)
+        self.n_classes, self.blank = int(n_classes), int(blank)
+
+    def __repr__(self):
+        return "KeywordBank(n_phrases=%d, max_len=%d, on %s)" % (self.n_phrases, self.max_len, self.labels.device)
+
+
+class KeywordHits(NamedTuple):
+    n_hits: torch.Tensor         # (B, K) i32 hits of the pair; may exceed max_hits (the slots hold the first max_hits)
+    hit_span: torch.Tensor       # (B, K, max_hits, 2) i32 [start frame, end frame) in time order, (-1, -1) for unwritten slots
+    hit_score: torch.Tensor      # (B, K, max_hits) f32 log-likelihood ratio against the greedy path over the span, 0 if unwritten
+    best_score: torch.Tensor     # (B, K) f32 the best end score whatever the threshold, -inf when the phrase does not fit
+    best_span: torch.Tensor      # (B, K, 2) i32 its span, (-1, -1) with -inf
+
+
+def build_keywords(phrases_ids, *, n_classes: int, blank: int, device="cuda") -> KeywordBank:
+    """The bank of a keyword search from `phrases_ids`, a non-empty list of label-id lists (1..KWS_MAX_LABELS ids in
+    [0, n_classes), none the blank; duplicates are fine), uploaded to `device`.  A bad phrase raises ValueError naming its index,
+    before anything is uploaded."""
+    phrases = [[int(c) for c in p] for p in phrases_ids]
+    if not phrases:
+        raise ValueError("build_keywords: no phrase")
+    if not 0 <= int(blank) < int(n_classes):
+        raise ValueError("build_keywords: blank %d outside [0, %d)" % (blank, n_classes))
+    for i, p in enumerate(phrases):
+        if not p:
+            raise ValueError("build_keywords: phrase %d is empty" % i)
+        if len(p) > KWS_MAX_LABELS:
+            raise ValueError("build_keywords: phrase %d has %d labels; a keyword takes at most %d" % (i, len(p), KWS_MAX_LABELS))
+        for c in p:
+            if c == blank or not 0 <= c < n_classes:
+                raise ValueError("build_keywords: phrase %d holds the label %d: the blank or outside [0, %d)" % (i, c, n_classes))
+    lengths = [len(p) for p in phrases]
+    offsets = np.zeros(len(phrases) + 1, dtype=np.int32)
+    np.cumsum(lengths, out=offsets[1:])
+    labels = np.asarray([c for p in phrases for c in p], dtype=np.int32)
+    return KeywordBank(torch.from_numpy(labels).to(device), torch.from_numpy(offsets).to(device), lengths, n_classes, blank)
+
+
+def ctc_keyword_search(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: int, bank: KeywordBank, threshold: float = -2.0,
+                       max_hits: int = 8) -> KeywordHits:
+    """CTC keyword search (include/lasr.h lasr_ctc_kws): where in each row of logp (B, T, C) f32 is each phrase of `bank` said.
+    lens (B) i32 or None (= T).  A hit's score is the log-likelihood ratio of the phrase's best path against the greedy path
+    over the same frames (<= 0); a span is a hit when its score is at least threshold * (labels of the phrase), overlapping
+    spans of one phrase keep the best.  threshold in (-1e6, 0], in natural-log units per label; the default -2.0 is a
+    starting value: nobody has tuned it on a trained model (keyword_scores of AsrTranslator shows what a recording gives).  One
+    launch (two for a large vocabulary), nothing synchronised."""
+    if not isinstance(bank, KeywordBank):
+        raise TypeError("bank must be a KeywordBank (ops.build_keywords)")
+    if logp.dim() != 3 or logp.dtype != torch.float32:
+        raise ValueError("ctc_keyword_search takes (B, T, C) float32 log-probs")
+    B, T, Cc = logp.shape
+    if lens is not None and (lens.shape != (B,) or lens.dtype != torch.int32):
+        raise ValueError("ctc_keyword_search: lens must be (B,) int32")
+    if B < 1 or T < 1 or Cc < 2 or not 0 <= blank < Cc:
+        raise ValueError("ctc_keyword_search: shape (%d, %d, %d) with blank %d" % (B, T, Cc, blank))
+    if int(max_hits) < 1:
+        raise ValueError("ctc_keyword_search: max_hits must be at least 1")
+    if bank.n_classes != Cc or bank.blank != blank:
+        raise ValueError("the keyword bank was built for %d classes with blank %d; the log-probs have %d classes, blank %d"
+                         % (bank.n_classes, bank.blank, Cc, blank))
+    if logp.is_cuda and bank.labels.device != logp.device:
+        raise ValueError("the keyword bank is on %s, the log-probs on %s" % (bank.labels.device, logp.device))
+    K, dev = bank.n_phrases, logp.device
+    ptrs = [_p(logp), _p(lens), _p(bank.labels), _p(bank.offsets)]      # CPU tensors are refused here, before anything is allocated
+    out = KeywordHits(torch.empty(B, K, dtype=torch.int32, device=dev), torch.empty(B, K, int(max_hits), 2, dtype=torch.int32, device=dev),
+                      torch.empty(B, K, int(max_hits), dtype=torch.float32, device=dev), torch.empty(B, K, dtype=torch.float32, device=dev),
+                      torch.empty(B, K, 2, dtype=torch.int32, device=dev))
+    nb = int(_lib.load().lasr_ctc_kws_workspace_bytes(B, T, K))
+    ws = _ws(nb, dev)
+    call("lasr_ctc_kws", ptrs[0], ptrs[1], B, T, Cc, int(blank), ptrs[2], ptrs[3], K, bank.max_len, float(threshold), int(max_hits),
+         _p(out.n_hits), _p(out.hit_span), _p(out.hit_score), _p(out.best_score), _p(out.best_span), _p(ws), nb, _stream())
+    return out
+
+
 def greedy_decode(ids: torch.Tensor, lens: Optional[torch.Tensor], blank: int):
     B, T = ids.shape
     tokens = torch.empty(B, T, dtype=torch.int32, device=ids.device)

@@ -5,6 +5,7 @@ file: a character LM, or - the labels having exactly one " ", as EN_LABELS has -
 ``error_report`` splits a manifest's WER / CER into substitutions, deletions and insertions (``ops.edit_ops_batch``: the aligned reference and hypothesis of every utterance, the most confused pairs).
 ``translate_long`` takes a recording of any length: cut into utterances on the device (``ops.vad_segments``), decoded in batches, times relative to the recording.
 ``align`` / ``translate_timed`` / ``align_manifest`` add word timings: the CTC forced alignment of a known transcript (or of the decoder's own hypothesis) to the audio, ``ops.ctc_align`` + the record functions of align.py.
+``find_keywords`` / ``find_keywords_long`` / ``keyword_scores`` spot phrases in the frame posteriors with time spans and scores, without decoding: ``ops.ctc_keyword_search`` + the record functions of kws.py.
 
 The checkpoint is the PL-style dict the reference's ``ModelCheckpoint`` writes and ``Trainer`` here
 writes too: ``state_dict`` with the reference's key names (``encoder.encoder.block1.seq.0...``) and
@@ -22,6 +23,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from .align import frame_seconds, unit_records
+from .kws import hit_records, score_records, sort_records
 from .data_module import AudioParser, LibriDataModule, load_wav, load_wav_rate
 from .lightning_compat import Trainer
 from .train import LightingModule
@@ -443,6 +445,95 @@ class AsrTranslator:
         result["segments"] = records
         result["text"] = (" " if " " in self.labels else "").join(r["text"] for r in records)
         return result
+
+    # ------------------------------------------------------------------------------------------ keyword search
+    def _keyword_bank(self, keywords, who: str):
+        """keywords (list of str) -> (names, ops.KeywordBank for the model's classes on the translator's device)"""
+        if isinstance(keywords, str):
+            raise TypeError("%s: keywords is a list of str, not one str" % who)
+        names = [str(k) for k in keywords]
+        if not names:
+            raise ValueError("%s: no keyword" % who)
+        n_classes = len(self.labels) + 1                                 # the blank is the model's last class
+        return names, ops.build_keywords([self.text_to_ids(k) for k in names], n_classes=n_classes, blank=n_classes - 1,
+                                         device=self.device)
+
+    @torch.no_grad()
+    def find_keywords(self, audio_path, keywords, threshold: Optional[float] = None, max_hits: int = 8,
+                      resample: Optional[bool] = None) -> List[dict]:
+        """Where in one audio file is each of `keywords` (a list of str: names, wake words, terms) said?  One record per hit,
+        {"keyword", "start", "end", "score", "score_per_label", "confidence"}, sorted by start then keyword order, times in
+        seconds.  It searches the model's frame posteriors (``ops.ctc_keyword_search``) instead of the 1-best text, so an
+        occurrence off the best path is still found, with a score: the log-likelihood ratio of the phrase over its span against
+        the greedy path (0 = the phrase is the greedy path there).  A span is a hit when score >= threshold * (labels of the
+        keyword); threshold None is ``ops.ctc_keyword_search``'s default, -2.0 nat per label, a starting value nobody has tuned on a
+        trained model - ``keyword_scores`` shows what a recording gives.  Overlapping hits of one keyword keep the best; hits of
+        different keywords do not suppress each other.  At most ``max_hits`` hits per keyword are returned.  Works with either
+        decoder setting: nothing is decoded.  ValueError for a character outside the vocabulary and for an empty keyword."""
+        names, bank = self._keyword_bank(keywords, "find_keywords")
+        out, duration = self._encode_file(audio_path, resample)
+        logp = out.float().contiguous()
+        kw = {} if threshold is None else {"threshold": float(threshold)}
+        hits = ops.ctc_keyword_search(logp, None, bank.blank, bank, max_hits=int(max_hits), **kw)
+        return hit_records(names, bank.lengths, hits.n_hits[0].tolist(), hits.hit_span[0].tolist(), hits.hit_score[0].tolist(),
+                           self.frame_seconds(), duration)
+
+    @torch.no_grad()
+    def keyword_scores(self, audio_path, keywords, resample: Optional[bool] = None) -> List[dict]:
+        """For choosing a threshold: the best score of every keyword anywhere in the file, whatever the threshold, over its
+        labels - one {"keyword", "score_per_label", "start", "end"} per keyword in the order given (-inf and None times for a
+        keyword longer than the clip).  ``find_keywords`` with a threshold at or below a keyword's score_per_label reports it."""
+        names, bank = self._keyword_bank(keywords, "keyword_scores")
+        out, duration = self._encode_file(audio_path, resample)
+        hits = ops.ctc_keyword_search(out.float().contiguous(), None, bank.blank, bank, threshold=0.0, max_hits=1)
+        return score_records(names, bank.lengths, hits.best_score[0].tolist(), hits.best_span[0].tolist(), self.frame_seconds(), duration)
+
+    @torch.no_grad()
+    def find_keywords_long(self, audio_path, keywords, batch_size: int = 32, threshold: Optional[float] = None, max_hits: int = 8,
+                           resample: Optional[bool] = None, **vad) -> List[dict]:
+        """``find_keywords`` over a recording of any length: cut into utterances on the device as ``translate_long`` cuts it
+        (``**vad`` are ``ops.vad_segments``' keywords), the segments encoded in batches of at most ``batch_size``, longest first,
+        one keyword search per batch.  The records are ``find_keywords``', times in seconds of the RECORDING, sorted by start then
+        keyword order.  Speech outside every segment is not searched, and a phrase that straddles a cut between two segments is
+        not found.  ValueError when the recording has more than ``max_segments`` segments, and when a keyword has more than
+        ``max_hits`` hits in one segment (naming it): raise max_hits or the threshold."""
+        if isinstance(audio_path, str) and not os.path.exists(audio_path):
+            raise Exception("音频路径不存在 " + audio_path)
+        if int(batch_size) < 1:
+            raise ValueError("find_keywords_long: batch_size must be at least 1")
+        names, bank = self._keyword_bank(keywords, "find_keywords_long")
+        if self._resample(resample):
+            y, rate = load_wav_rate(audio_path)
+            y = self.audio_parser.resample_to_sr(y, rate)
+        else:
+            y = load_wav(audio_path)
+        if y.shape[1] == 0:
+            return []
+        wave = y[0].to(self.device).contiguous()
+        found = ops.vad_segments(wave, **vad)
+        n = int(found.n_segs)
+        if n > found.segs.shape[0]:
+            raise ValueError("find_keywords_long: the recording has %d segments, more than max_segments=%d" % (n, found.segs.shape[0]))
+        segs = [tuple(s) for s in found.segs[:n].tolist()]
+        order = sorted(range(n), key=lambda i: segs[i][0] - segs[i][1])  # longest first; equal lengths in time order
+        secs, sr = self.frame_seconds(), float(self.audio_parser.sr)
+        kw = {} if threshold is None else {"threshold": float(threshold)}
+        records: List[dict] = []
+        for k in range(0, n, int(batch_size)):
+            batch = [segs[i] for i in order[k:k + int(batch_size)]]
+            out, t_lens = self._segment_batch(wave, batch)
+            hits = ops.ctc_keyword_search(out.float().contiguous(), t_lens.contiguous(), bank.blank, bank, max_hits=int(max_hits), **kw)
+            n_hits, span, score = hits.n_hits.tolist(), hits.hit_span.tolist(), hits.hit_score.tolist()
+            for b, (s0, s1) in enumerate(batch):
+                for j, c in enumerate(n_hits[b]):
+                    if c > int(max_hits):
+                        raise ValueError("find_keywords_long: the keyword %r has %d hits in the segment %.2f-%.2f s, more than "
+                                         "max_hits=%d" % (names[j], c, s0 / sr, s1 / sr, int(max_hits)))
+                t0, t1 = s0 / sr, s1 / sr
+                for r in hit_records(names, bank.lengths, n_hits[b], span[b], score[b], secs, t1 - t0):
+                    r["start"], r["end"] = min(r["start"] + t0, t1), min(r["end"] + t0, t1)     # the recording's time, as _align_batch
+                    records.append(r)
+        return sort_records(records, names)
 
     @torch.no_grad()
     def align_manifest(self, manifest: str, out_path: str, batch_size: int = 32) -> List[dict]:
