@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 113   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 114   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
@@ -37,7 +37,8 @@ extern "C" {
                               110: lasr_dwconv_plan (which depthwise kernel form and grid a shape takes; launches nothing)
                               111: lasr_vad_* / lasr_segment_gather (voice-activity segmentation of long recordings)
                               112: lasr_hotword_* (phrase bank), lasr_ctc_beam_decode_bias / _lm_bias (hotword biasing)
-                              113: lasr_ctc_kws_workspace_bytes / lasr_ctc_kws (CTC keyword search: phrases with time spans) */
+                              113: lasr_ctc_kws_workspace_bytes / lasr_ctc_kws (CTC keyword search: phrases with time spans)
+                              114: lasr_grad_accumulate / lasr_grad_accumulate_ranges (gradient accumulation over micro-batches) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -662,6 +663,21 @@ int lasr_novograd_step_keep(float* params, const float* grads, float* exp_avg, f
                             const int64_t* offsets, int64_t n_tensors, int64_t n_elems, const float* lr, float beta1, float beta2,
                             float eps, float weight_decay, float grad_scale, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* Gradient accumulation (accumulate_grad_batches > 1; DESIGN 4, "Gradient accumulation"): acc[i] = acc[i] + g[i], a plain f32 add with one rounding
+ * per element - bit-equal to `acc + g` in torch, whatever the alignment.  Every backward of the plan overwrites its whole
+ * destination, so a window of K micro-batches backwards into a second flat buffer and adds it into the gradient the optimiser
+ * reads; the 1/K average is the grad_scale of lasr_novograd_step.
+ * lasr_grad_accumulate_ranges: [lo[i], hi[i]) are element offsets into BOTH buffers (host arrays, read before the call
+ * returns), e.g. the pieces of one all-reduce bucket: one launch for all of them.  The pieces must not overlap; hi == lo is an
+ * empty piece.  Each piece moves as a 4-byte head up to the first 16-byte boundary, 16-byte groups and a 4-byte tail; when
+ * acc + lo and g + lo are not congruent mod 16 bytes the whole piece moves by 4-byte accesses, so no offset has to be a
+ * multiple of 4.  One grid-strided launch of at most 2048 workgroups on `stream`; no workspace, no allocation, no
+ * synchronisation.  n == 0 / no non-empty piece: returns 0, nothing launched.  LASR_E_ARG: a null pointer, n < 0, lo < 0,
+ * lo > hi, n_ranges < 0 or above LASR_ACC_MAX_RANGES.  The buffers' lengths are the caller's to guard.                      */
+#define LASR_ACC_MAX_RANGES 8
+int lasr_grad_accumulate(float* acc, const float* g, int64_t n, void* stream);
+int lasr_grad_accumulate_ranges(float* acc, const float* g, const int64_t* lo, const int64_t* hi, int n_ranges, void* stream);
 
 /* roctx ranges (round 5; SURVEY 5 aux "tracing"): with LASR_ROCTX=1 in the environment the plan brackets its stages and units with
  * named ranges - "lasr:forward", "lasr:fwd <unit>", "lasr:head", "lasr:backward", "lasr:bwd <unit>", "lasr:wgrad flush", "lasr:reduce" -

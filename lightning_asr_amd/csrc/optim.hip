@@ -118,6 +118,44 @@ __global__ __launch_bounds__(256) void novograd_update_kernel(float* __restrict_
   }
 }
 
+// Gradient accumulation: acc[i] = acc[i] + g[i] over up to LASR_ACC_MAX_RANGES [lo, hi) pieces of two flat f32 buffers in ONE
+// launch (the pieces of an all-reduce bucket).  The host cuts every piece into a 4-byte head up to the first 16-byte boundary,
+// a body of 16-byte groups and a 4-byte tail, and numbers the "units" of all pieces consecutively: the body's groups first, then
+// the head's and the tail's single elements.  A piece whose two bases are not congruent mod 16 bytes is all single elements.
+// The table travels by value in the kernel arguments; the grid strides over the units.  One plain add per element, one rounding.
+struct AccRanges {
+  int64_t body[LASR_ACC_MAX_RANGES];   // element offset of the first 16-byte group
+  int64_t lo[LASR_ACC_MAX_RANGES];     // element offset of the piece
+  int64_t hi[LASR_ACC_MAX_RANGES];
+  int64_t nvec[LASR_ACC_MAX_RANGES];   // 16-byte groups
+  int64_t first[LASR_ACC_MAX_RANGES + 1];   // first unit of the piece; [n] = all units
+  int n;
+};
+
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, AccRanges r) {
+  const int64_t total = r.first[r.n];
+  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < total; u += (int64_t)gridDim.x * blockDim.x) {
+    int k = 0;
+    while (k + 1 < r.n && r.first[k + 1] <= u) ++k;
+    const int64_t q = u - r.first[k];
+    if (q < r.nvec[k]) {
+      const int64_t e = r.body[k] + 4 * q;
+      float4 a = *reinterpret_cast<const float4*>(acc + e);
+      const float4 b = *reinterpret_cast<const float4*>(g + e);
+      a.x = __fadd_rn(a.x, b.x);
+      a.y = __fadd_rn(a.y, b.y);
+      a.z = __fadd_rn(a.z, b.z);
+      a.w = __fadd_rn(a.w, b.w);
+      *reinterpret_cast<float4*>(acc + e) = a;
+    } else {
+      const int64_t s = q - r.nvec[k];                   // single elements: the head, then the tail
+      const int64_t head = r.body[k] - r.lo[k];
+      const int64_t e = s < head ? r.lo[k] + s : r.body[k] + 4 * r.nvec[k] + (s - head);
+      if (e < r.hi[k]) acc[e] = __fadd_rn(acc[e], g[e]);
+    }
+  }
+}
+
 // f32 -> bf16 copy of a flat buffer (weights for the bf16 MFMA kernels)
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ in, bf16_t* __restrict__ out, int64_t n) {
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
@@ -194,6 +232,51 @@ static int novograd_step_impl(float* params, const float* grads, float* exp_avg,
                      (int)n_tensors, denom, lr, beta1, weight_decay, grad_scale, n_elems);
   LASR_LAUNCH_CHECK("novograd_update_kernel");
   return 0;
+}
+
+extern "C" int lasr_grad_accumulate_ranges(float* acc, const float* g, const int64_t* lo, const int64_t* hi, int n_ranges, void* stream) {
+  LASR_CHECK_ARG(acc && g && lo && hi, "lasr_grad_accumulate_ranges: null pointer");
+  LASR_CHECK_ARG(n_ranges >= 0 && n_ranges <= LASR_ACC_MAX_RANGES, "lasr_grad_accumulate_ranges: %d ranges (at most %d)", n_ranges,
+                 LASR_ACC_MAX_RANGES);
+  for (int i = 0; i < n_ranges; ++i)
+    LASR_CHECK_ARG(lo[i] >= 0 && hi[i] >= lo[i], "lasr_grad_accumulate_ranges: range %d = [%lld, %lld)", i, (long long)lo[i], (long long)hi[i]);
+  AccRanges r;
+  r.n = 0;
+  r.first[0] = 0;
+  for (int i = 0; i < n_ranges; ++i) {
+    const int64_t len = hi[i] - lo[i];
+    if (len == 0) continue;
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(acc + lo[i]), pg = reinterpret_cast<uintptr_t>(g + lo[i]);
+    int64_t head = len, nvec = 0;                       // bases not congruent mod 16 bytes: the whole piece by single elements
+    if ((pa & 15) == (pg & 15) && (pa & 3) == 0) {
+      head = (int64_t)(((16 - (pa & 15)) & 15) >> 2);
+      if (head > len) head = len;
+      nvec = (len - head) >> 2;
+    }
+    const int k = r.n++;
+    r.lo[k] = lo[i];
+    r.hi[k] = hi[i];
+    r.body[k] = lo[i] + head;
+    r.nvec[k] = nvec;
+    r.first[k + 1] = r.first[k] + nvec + (len - 4 * nvec);
+  }
+  if (r.n == 0) return 0;
+  for (int k = r.n; k < LASR_ACC_MAX_RANGES; ++k) {
+    r.lo[k] = r.hi[k] = r.body[k] = r.nvec[k] = 0;
+    r.first[k + 1] = r.first[r.n];
+  }
+  int64_t blocks = cdiv(r.first[r.n], 256);
+  if (blocks > 256 * 8) blocks = 256 * 8;
+  hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), acc, g, r);
+  LASR_LAUNCH_CHECK("grad_accumulate_kernel");
+  return 0;
+}
+
+extern "C" int lasr_grad_accumulate(float* acc, const float* g, int64_t n, void* stream) {
+  LASR_CHECK_ARG(acc && g, "lasr_grad_accumulate: null pointer");
+  LASR_CHECK_ARG(n >= 0, "lasr_grad_accumulate: n=%lld", (long long)n);
+  const int64_t lo = 0;
+  return lasr_grad_accumulate_ranges(acc, g, &lo, &n, 1, stream);
 }
 
 extern "C" int lasr_cast_pad_f32_to_bf16(const float* in, void* out, int64_t rows, int64_t cols, int64_t ld_out, void* stream) {

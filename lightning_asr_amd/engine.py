@@ -56,6 +56,7 @@ class NativeModel:
         self.n_buffer = lib.lasr_model_buffer_elems(h)
         self.params = torch.zeros(self.n_param, dtype=torch.float32, device=self.device)
         self.grads = torch.zeros(self.n_param, dtype=torch.float32, device=self.device)
+        self._grads_micro: Optional[torch.Tensor] = None
         self.buffers = torch.zeros(max(self.n_buffer, 1), dtype=torch.float32, device=self.device)
         self.counters: Dict[str, torch.Tensor] = OrderedDict()   # num_batches_tracked (host side, int64)
         self._bump = 0          # training forwards replayed from a captured graph (num_batches_tracked is applied lazily)
@@ -78,6 +79,22 @@ class NativeModel:
             pass
 
     # ---- state --------------------------------------------------------------------------------
+    @property
+    def grads_micro(self) -> torch.Tensor:
+        """a second flat gradient buffer: where the backward of one micro-batch lands while ``grads`` holds the running sum of
+        its window (gradient accumulation; ops.grad_accumulate adds it in).  Allocated on first use: a run that never
+        accumulates never pays for it."""
+        if self._grads_micro is None:
+            self._grads_micro = torch.zeros(self.n_param, dtype=torch.float32, device=self.device)
+        return self._grads_micro
+
+    def _grad_dst(self, grads: Optional[torch.Tensor]) -> torch.Tensor:
+        if grads is None:
+            return self.grads
+        if grads.dtype != torch.float32 or grads.dim() != 1 or grads.numel() != self.n_param or grads.device != self.device:
+            raise ValueError("grads must be a flat float32 buffer of %d elements on %s" % (self.n_param, self.device))
+        return grads
+
     def param_infos(self) -> List[TensorInfo]:
         return [t for t in self.tensors if t.kind == 0]
 
@@ -279,15 +296,17 @@ class NativeModel:
             self._last_feats, self._last_logp = feats_btc, logp
         return logp, am
 
-    def backward(self, grad_logp: torch.Tensor) -> torch.Tensor:
-        """dL/d(log-probs) -> flat gradient buffer (views via ``view(t, self.grads)``)."""
+    def backward(self, grad_logp: torch.Tensor, grads: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dL/d(log-probs) -> flat gradient buffer (views via ``view(t, self.grads)``).  grads: another flat f32 buffer to
+        write the gradient to (every element overwritten) instead of ``self.grads``."""
+        dst = self._grad_dst(grads)
         if self._last_feats is None:
             raise RuntimeError("backward() needs a preceding training forward()")
         B, T_in, _ = self._last_feats.shape
         ws = self._ws
         call("lasr_model_backward", self._h, _p(self.params), _p(self._last_feats), _p(self._last_logp),
-             _p(grad_logp.contiguous()), B, T_in, _p(self.grads), _p(ws), ws.numel(), _stream())
-        return self.grads
+             _p(grad_logp.contiguous()), B, T_in, _p(dst), _p(ws), ws.numel(), _stream())
+        return dst
 
     def unit_names(self) -> List[str]:
         n = self._lib.lasr_model_num_units(self._h)
@@ -329,9 +348,11 @@ class NativeModel:
         return [(last, head), (first512, mid), (1, [(bounds[1], bounds[2])]), (0, [(bounds[0], bounds[1])])]
 
     def loss_backward_staged(self, feats_btc, pct, targets, tgt_lens, on_bucket, want_argmax: bool = True, n_buckets: Optional[int] = None,
-                             want_logp: bool = True):
+                             want_logp: bool = True, grads: Optional[torch.Tensor] = None):
         """loss_backward in stages; ``on_bucket(ranges)`` (ranges = [(lo, hi), ...] of the flat gradient) is called right after
-        the stage that finalises them has been enqueued (the data-parallel host starts that bucket's all-reduce there)."""
+        the stage that finalises them has been enqueued (the data-parallel host starts that bucket's all-reduce there).
+        grads: the flat f32 buffer the gradient is written to (default ``self.grads``)."""
+        dst = self._grad_dst(grads)
         B, T_in, _ = feats_btc.shape
         S = targets.shape[1]
         ws = self.workspace(B, T_in, S)
@@ -343,10 +364,10 @@ class NativeModel:
         sched = self.bucket_schedule(n_buckets)
         stop0, ranges0 = sched[0]
         call("lasr_model_loss_backward_partial", self._h, _p(self.params), _p(self.buffers), _p(feats_btc), _p(pct), _p(targets),
-             _p(tgt_lens), B, T_in, S, _p(logp), _p(loss), _p(nll), _p(am), _p(self.grads), _p(ws), ws.numel(), stop0, _stream())
+             _p(tgt_lens), B, T_in, S, _p(logp), _p(loss), _p(nll), _p(am), _p(dst), _p(ws), ws.numel(), stop0, _stream())
         on_bucket(ranges0)
         for stop, ranges in sched[1:]:
-            call("lasr_model_backward_continue", self._h, _p(self.params), _p(feats_btc), B, T_in, _p(self.grads), _p(ws), ws.numel(),
+            call("lasr_model_backward_continue", self._h, _p(self.params), _p(feats_btc), B, T_in, _p(dst), _p(ws), ws.numel(),
                  stop, _stream())
             on_bucket(ranges)
         for k in self.counters:
@@ -380,9 +401,12 @@ class NativeModel:
         self._last_feats, self._last_logp = feats_btc, logp
         return loss, nll, logp, am
 
-    def loss_backward(self, feats_btc, pct, targets, tgt_lens, want_argmax: bool = True, want_logp: bool = True):
+    def loss_backward(self, feats_btc, pct, targets, tgt_lens, want_argmax: bool = True, want_logp: bool = True,
+                      grads: Optional[torch.Tensor] = None):
         """forward + mean CTC + backward.  Returns (loss (1), nll (B), logp, argmax).  want_logp=False: logp is None when the
-        large-vocabulary head applies (bf16, C >= 256): no (B, T', C) f32 tensor is materialised."""
+        large-vocabulary head applies (bf16, C >= 256): no (B, T', C) f32 tensor is materialised.
+        grads: the flat f32 buffer the gradient is written to (default ``self.grads``)."""
+        dst = self._grad_dst(grads)
         B, T_in, _ = feats_btc.shape
         S = targets.shape[1]
         ws = self.workspace(B, T_in, S)
@@ -392,7 +416,7 @@ class NativeModel:
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         nll = torch.empty(B, dtype=torch.float32, device=self.device)
         call("lasr_model_loss_backward", self._h, _p(self.params), _p(self.buffers), _p(feats_btc), _p(pct), _p(targets),
-             _p(tgt_lens), B, T_in, S, _p(logp), _p(loss), _p(nll), _p(am), _p(self.grads), _p(ws), ws.numel(), _stream())
+             _p(tgt_lens), B, T_in, S, _p(logp), _p(loss), _p(nll), _p(am), _p(dst), _p(ws), ws.numel(), _stream())
         for k in self.counters:
             self.counters[k] += 1
         self._last_feats, self._last_logp = feats_btc, logp

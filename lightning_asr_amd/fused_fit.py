@@ -17,16 +17,25 @@ import logging
 import os
 import time
 from collections import deque
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import torch
 
 from . import ops
 from .data_module import AudioParser, parse_speed_factors
 from .ingest import BatchProducer, DevBatch, DeviceFeeder, Layout, PinnedRing, SR, fast_ingest_ok
-from .step import GraphedTrainStep, TrainStep, graph_dp_enabled
+from .step import GraphedTrainStep, TrainStep, check_accumulate, graph_dp_enabled
 
 logger = logging.getLogger(__name__)
+
+
+def window_roles(n_batches: int, K: int) -> List[bool]:
+    """``accumulate_grad_batches = K`` over an epoch of n_batches (Lightning 1.3): True where the optimiser steps - after every
+    K-th micro-batch and after the last batch of the epoch, whose window may be incomplete.  The one definition of the rule,
+    for the fused loop and the autograd loop."""
+    K = check_accumulate(K)
+    n = int(n_batches)
+    return [(i + 1) % K == 0 or i + 1 == n for i in range(n)]
 
 
 def fused_eligible(model, optimizer, scheduler) -> bool:
@@ -156,7 +165,8 @@ class FusedLoop:
         self.trainer, self.model, self.dm = trainer, model, datamodule
         self.native = model.encoder.native
         dev = self.native.device
-        self.ts = TrainStep.from_optimizer(self.native, optimizer, scheduler)
+        self.K = check_accumulate(getattr(trainer, "accumulate_grad_batches", 1))
+        self.ts = TrainStep.from_optimizer(self.native, optimizer, scheduler, accumulate=self.K)
         if scheduler is not None:
             self.ts.use_device_schedule()
         self.dither = ops.DeviceDither(int(torch.initial_seed()) ^ (0x9E3779B97F4A7C15 * (trainer.rank + 1)), dev)
@@ -181,11 +191,12 @@ class FusedLoop:
             return pf[1], pf[2]
         return self.ts.features(cur.pcm, cur.lens, self.dither, cur.aug, logical_len=cur.L)
 
-    def _graph_for(self, cur: DevBatch, nxt: DevBatch) -> Optional[GraphedTrainStep]:
+    def _graph_for(self, cur: DevBatch, nxt: DevBatch, boundary: bool = True) -> Optional[GraphedTrainStep]:
         key = cur.key
         if not self.use_graph or nxt is None or nxt.key != key or cur.pcm.dtype != nxt.pcm.dtype:
             return None
-        g = self.graphs.get(key)
+        gkey = (key, boundary)         # accumulate_grad_batches > 1: one graph per role of a shape (always "boundary" at K = 1)
+        g = self.graphs.get(gkey)
         if g is not None:
             return g if g.graph is not None else None
         self.seen[key] = self.seen.get(key, 0) + 1
@@ -198,8 +209,9 @@ class FusedLoop:
         if self.seen[key] < 3 or self.seen[key] < 0.08 * steps or len(self.graphs) >= 16:
             return None
         g = GraphedTrainStep(self.ts, cur.B, cur.pitch, cur.S, ragged=True, prefetch=True, want_logp=False, wave_dtype=cur.pcm.dtype,
-                             with_aug=cur.aug is not None, dither=self.dither, logical_len=cur.L)
-        self.graphs[key] = g
+                             with_aug=cur.aug is not None, dither=self.dither, logical_len=cur.L,
+                             role="boundary" if boundary else "accumulate")
+        self.graphs[gkey] = g
         try:
             g.targets.copy_(cur.targets)
             g.tgt_lens.copy_(cur.sizes)
@@ -215,7 +227,8 @@ class FusedLoop:
             return None
         return g
 
-    def step(self, cur: DevBatch, nxt: Optional[DevBatch], batch_idx: int):
+    def step(self, cur: DevBatch, nxt: Optional[DevBatch], batch_idx: int, boundary: bool = True):
+        """boundary (accumulate_grad_batches > 1): this micro-batch closes its window - the optimiser steps after it"""
         ts, native = self.ts, self.native
         stream = torch.cuda.current_stream()
         for b in (cur, nxt):          # once per batch: the compute stream is ordered behind the batch's H2D copies (issued two steps ahead)
@@ -229,7 +242,7 @@ class FusedLoop:
         if self.on_host_batch is not None:
             self.on_host_batch(cur)
         feats, pct = self._feats_for(cur)
-        g = self._graph_for(cur, nxt)
+        g = self._graph_for(cur, nxt, boundary)
         if g is not None:
             g.prime(feats, pct)
             loss, nll, _, am = g.step(nxt.pcm, cur.targets, cur.sizes, nxt.lens, nxt.aug)
@@ -245,7 +258,8 @@ class FusedLoop:
             nf = None
             if nxt is not None:
                 nf = native.arm_prefetch(nxt.pcm, nxt.lens, self.dither, nxt.aug, logical_len=nxt.L)
-            loss, nll, _, am = ts.step_features(feats, pct, cur.targets, cur.sizes, want_logp=False)
+            loss, nll, _, am = ts.step_features(feats, pct, cur.targets, cur.sizes, want_logp=False,
+                                                role="boundary" if boundary else "accumulate")
             self._pf = (nxt.index, nf[0], nf[1]) if nf is not None else None
             self.eager_steps += 1
         self.audio_seconds += cur.seconds
@@ -318,6 +332,7 @@ class FusedLoop:
                 b = next(it, None)
                 if b is not None:
                     window.append(b)
+            roles = window_roles(n_batches, self.K)      # True: the optimiser steps after this batch
             batch_idx = 0
             while window:
                 if tr.max_steps and tr.global_step >= tr.max_steps:
@@ -330,18 +345,21 @@ class FusedLoop:
                 c1 = time.thread_time()
                 if b is not None:
                     window.append(b)
-                self.step(cur, nxt, batch_idx)
+                # (the last batch of the epoch is a boundary also when the source ran dry before n_batches)
+                boundary = nxt is None or batch_idx >= len(roles) or roles[batch_idx]
+                self.step(cur, nxt, batch_idx, boundary)
                 self.ingest_wait_s += t1 - t0
                 self.host_step_s += time.perf_counter() - t1
                 self.host_cpu_s += time.thread_time() - c1
                 src.release(cur)
-                tr.global_step += 1
                 batch_idx += 1
-                if tr.log_every_n_steps and tr.global_step % tr.log_every_n_steps == 0:
-                    m = self.read_metrics()
-                    for k in ("train_loss", "train_wer"):
-                        if k + "_step" in m:
-                            tr.callback_metrics[k] = m[k + "_step"]
+                if boundary:         # trainer.global_step, max_steps and log_every_n_steps count optimiser steps
+                    tr.global_step += 1
+                    if tr.log_every_n_steps and tr.global_step % tr.log_every_n_steps == 0:
+                        m = self.read_metrics()
+                        for k in ("train_loss", "train_wer"):
+                            if k + "_step" in m:
+                                tr.callback_metrics[k] = m[k + "_step"]
                 if on_step is not None:
                     on_step(tr)
         finally:

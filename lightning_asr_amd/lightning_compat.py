@@ -147,8 +147,12 @@ class Trainer:
                  check_val_every_n_epoch: int = 1, limit_train_batches=1.0, limit_val_batches=1.0,
                  accelerator: Optional[str] = None, num_nodes: int = 1, default_root_dir: str = ".",
                  callbacks=None, logger=None, save_top_k: int = 3, monitor: str = "val_wer", max_steps: Optional[int] = None,
-                 device: Optional[str] = None, log_every_n_steps: int = 50, **ignored):
+                 device: Optional[str] = None, log_every_n_steps: int = 50, accumulate_grad_batches: int = 1, **ignored):
+        from .step import check_accumulate
         self.max_epochs, self.max_steps = max_epochs, max_steps
+        # train.py:244: K micro-batches per optimiser step, the gradient averaged over K; global_step, max_steps, the LR schedule and
+        # log_every_n_steps count optimiser steps (fused_fit.window_roles).  An int >= 1; Lightning's epoch -> K dict is not implemented
+        self.accumulate_grad_batches = check_accumulate(accumulate_grad_batches)
         self.log_every_n_steps = log_every_n_steps      # how often the fused loop reads its device-side metric accumulators
         self.callbacks = list(callbacks or [])          # objects with on_train_batch_end(trainer) / on_train_epoch_end(trainer)
         self.fused = None                               # the FusedLoop of the last fit (None: autograd route)
@@ -314,19 +318,27 @@ class Trainer:
                     if not k.endswith("_step"):
                         self._record(k, v)
             else:
+                from .fused_fit import window_roles
+                K = self.accumulate_grad_batches
+                roles = window_roles(n, K)           # True: the optimiser steps after this batch
+                opened = False                       # a window is open: its gradient is being summed in the parameters' .grad
                 for batch_idx, batch in enumerate(loader):
                     if batch_idx >= n or (self.max_steps and self.global_step >= self.max_steps):
                         break
                     batch = self._batch(batch, datamodule)
                     loss = model.training_step(batch, batch_idx)
-                    opt.zero_grad()
-                    loss.backward()
-                    if sync is not None:
-                        sync.all_reduce(native.grads)
-                    opt.step()
-                    if sched is not None:
-                        sched.step()
-                    self.global_step += 1
+                    if not opened:
+                        opt.zero_grad()
+                        opened = True
+                    (loss if K == 1 else loss / K).backward()      # a second backward of a window adds (models/_base.py)
+                    if roles[batch_idx]:
+                        if sync is not None:                       # no_sync on the other micro-batches
+                            sync.all_reduce(native.grads)
+                        opt.step()
+                        if sched is not None:
+                            sched.step()
+                        self.global_step += 1
+                        opened = False
                     on_step(self)
             rec = {"epoch": epoch, "global_step": self.global_step, "train_time_s": time.time() - t0,
                    "lr": opt.param_groups[0]["lr"]}

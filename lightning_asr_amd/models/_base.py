@@ -29,7 +29,14 @@ class _PlanFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_logp):
         m = ctx.module
-        m.native.backward(grad_logp)
+        if any(p.grad is not None for p in m._plist):
+            # torch semantics: a backward onto parameters that already hold a gradient ADDS to it (no zero_grad() since the last
+            # backward: gradient accumulation).  The plan overwrites its whole destination, so this micro-batch lands in the
+            # second flat buffer and one launch adds it into the gradient the parameters view.
+            m.native.backward(grad_logp, grads=m.native.grads_micro)
+            ops.grad_accumulate(m.native.grads, m.native.grads_micro)
+        else:
+            m.native.backward(grad_logp)
         # hand every parameter its view of the flat gradient buffer (no copies, optimiser stays flat)
         for p, t in zip(m._plist, m.native.param_infos()):
             p.grad = m.native.view(t, m.native.grads)

@@ -873,6 +873,40 @@ def novograd_step(params, grads, exp_avg, exp_avg_sq, offsets, lr_dev, beta1=0.8
          beta2, eps, weight_decay, grad_scale, _p(ws), nb, _stream())
 
 
+ACC_MAX_RANGES = 8          # LASR_ACC_MAX_RANGES
+
+
+def grad_accumulate(acc: torch.Tensor, g: torch.Tensor, ranges=None) -> None:
+    """``acc += g`` over two flat f32 GPU buffers of one size (bit-equal to torch's ``acc + g``), in one launch.  ranges:
+    [(lo, hi), ...] element offsets, at most ACC_MAX_RANGES pieces that do not overlap (the pieces of an all-reduce bucket);
+    None = the whole buffer."""
+    for t in (acc, g):
+        if t.dtype != torch.float32:
+            raise TypeError("grad_accumulate adds float32 buffers, got %s" % t.dtype)
+        if not t.is_cuda:
+            raise _lib.LasrError("liblasr ops need GPU tensors (got a %s tensor); there is no CPU fallback" % t.device)
+    if acc.dim() != 1 or g.dim() != 1 or acc.numel() != g.numel():
+        raise ValueError("grad_accumulate needs two flat buffers of one size, got %s and %s" % (tuple(acc.shape), tuple(g.shape)))
+    if acc.device != g.device:
+        raise ValueError("grad_accumulate: buffers on %s and %s" % (acc.device, g.device))
+    n = acc.numel()
+    if n == 0:
+        return
+    if ranges is None:
+        call("lasr_grad_accumulate", _p(acc), _p(g), n, _stream())
+        return
+    ranges = [(int(lo), int(hi)) for lo, hi in ranges]
+    if len(ranges) > ACC_MAX_RANGES:
+        raise ValueError("grad_accumulate takes at most %d ranges, got %d" % (ACC_MAX_RANGES, len(ranges)))
+    if any(lo < 0 or hi < lo or hi > n for lo, hi in ranges):
+        raise ValueError("grad_accumulate: a range outside [0, %d] or with lo > hi: %s" % (n, ranges))
+    if not ranges:
+        return
+    lo = (ctypes.c_int64 * len(ranges))(*[r[0] for r in ranges])
+    hi = (ctypes.c_int64 * len(ranges))(*[r[1] for r in ranges])
+    call("lasr_grad_accumulate_ranges", _p(acc), _p(g), lo, hi, len(ranges), _stream())
+
+
 def edit_distance_batch(tokens: torch.Tensor, n_tokens: torch.Tensor, targets: torch.Tensor, target_lens: torch.Tensor,
                         space_id: int = -1, totals: Optional[torch.Tensor] = None):
     """Levenshtein distance of every utterance on the device: tokens (B,T) i32 + n_tokens (B) i32 from greedy_decode,

@@ -48,7 +48,7 @@ class Novograd(Optimizer):
         return loss
 
     def zero_grad(self, set_to_none: bool = True):
-        # gradients live in the flat buffer and are fully overwritten by every backward
+        # gradients live in the flat buffer: the first backward after this overwrites it whole, further ones add (models/_base.py)
         for g in self.param_groups:
             for p in g["params"]:
                 p.grad = None

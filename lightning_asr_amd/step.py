@@ -30,14 +30,32 @@ def _roctx_on() -> bool:
     return _ROCTX
 
 
+def check_accumulate(k) -> int:
+    """``accumulate_grad_batches``: an int >= 1 (Lightning's epoch -> K dict is not implemented)"""
+    if isinstance(k, dict):
+        raise NotImplementedError("accumulate_grad_batches as a dict (epoch -> K) is not implemented: pass one int >= 1")
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError("accumulate_grad_batches has to be an int >= 1, got %r" % (k,))
+    return k
+
+
 class TrainStep:
     def __init__(self, model: NativeModel, learning_rate: float = 1e-2, weight_decay: float = 1e-3,
                  betas=(0.8, 0.5), eps: float = 1e-8, schedule: Optional[CosineAnnealingWarmupRestarts] = None,
-                 process_group=None, comm: Optional[Communicator] = None):
+                 process_group=None, comm: Optional[Communicator] = None, accumulate: int = 1):
         """comm: the library-owned RCCL communicator (lasr_comm_*).  Default for world > 1 on the nccl backend: one is built
         from the torch.distributed group (which then only bootstraps the unique id); ``LASR_COMM=torch`` keeps the gradient
-        exchange on torch.distributed (the only choice for gloo groups: CPU rehearsal, two ranks sharing a GPU in the tests)."""
+        exchange on torch.distributed (the only choice for gloo groups: CPU rehearsal, two ranks sharing a GPU in the tests).
+        accumulate: K = ``accumulate_grad_batches``.  K > 1: every call is one MICRO-step (forward, loss, backward into
+        ``model.grads_micro``, one launch that adds it into ``model.grads``); the K-th of a window - or one called with
+        ``last=True`` - is the boundary, which additionally all-reduces, steps the optimiser with grad_scale 1 / (K world),
+        steps the schedule and zeroes ``model.grads``, which is therefore zero between windows.  K = 1 is the step as it
+        always was: no second buffer, no extra launch."""
         self.model = model
+        self.accumulate = check_accumulate(accumulate)
+        self.micro = 0             # micro-batches already added into model.grads in the current window (K > 1)
+        if self.accumulate > 1:
+            model.grads.zero_()
         self.wd, self.betas, self.eps = weight_decay, betas, eps
         dev = model.device
         self.exp_avg = torch.zeros_like(model.params)
@@ -97,13 +115,14 @@ class TrainStep:
         return None
 
     @classmethod
-    def from_optimizer(cls, model: NativeModel, optimizer, schedule=None, process_group=None, comm: Optional[Communicator] = None):
+    def from_optimizer(cls, model: NativeModel, optimizer, schedule=None, process_group=None, comm: Optional[Communicator] = None,
+                       accumulate: int = 1):
         """The fused step over the state of a ``scheduler.novograd.Novograd`` (+ its ``CosineAnnealingWarmupRestarts``): the
         moments and the device learning rate ARE the optimizer's tensors, so ``optimizer.state_dict()`` / checkpoints / resume
         keep working while ``Trainer.fit`` drives this step instead of ``loss.backward(); optimizer.step()``."""
         g = optimizer.param_groups[0]
         ts = cls(model, learning_rate=float(g["lr"]), weight_decay=g["weight_decay"], betas=tuple(g["betas"]), eps=g["eps"],
-                 schedule=schedule, process_group=process_group, comm=comm)
+                 schedule=schedule, process_group=process_group, comm=comm, accumulate=accumulate)
         ts.exp_avg, ts.exp_avg_sq, ts.lr_dev = optimizer.exp_avg, optimizer.exp_avg_sq, optimizer.lr_dev
         ts.lr = float(g["lr"])
         ts.lr_dev.fill_(ts.lr)
@@ -150,7 +169,7 @@ class TrainStep:
         if getattr(self, "_opt_ws", None) is None:       # kept across steps: zeroed once, left zeroed by every step (no memset launch)
             self._opt_ws = ops.novograd_workspace(self.exp_avg_sq.numel(), m.params.numel(), m.device)
         ops.novograd_step(m.params, m.grads, self.exp_avg, self.exp_avg_sq, self.offsets, self.lr_dev, self.betas[0],
-                          self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world, ws=self._opt_ws)
+                          self.betas[1], self.eps, self.wd, grad_scale=1.0 / (self.accumulate * self.world), ws=self._opt_ws)
         if self.schedule is not None:
             if self._lr_state is not None and self.schedule.last_epoch != self._lr_epoch:
                 self.sync_device_schedule()                # the host schedule was loaded / reset since the last step
@@ -178,14 +197,65 @@ class TrainStep:
         self._lr_state = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(self.model.device)
         self._lr_epoch = int(sc.last_epoch)
 
-    def step_features(self, feats, pct, targets, tgt_lens, want_logp: bool = True):
+    def step_features(self, feats, pct, targets, tgt_lens, want_logp: bool = True, last: Optional[bool] = None,
+                      role: Optional[str] = None):
+        """last (accumulate > 1): None - the boundary follows the window counter ``self.micro``; True - this micro-batch closes
+        the window whatever it holds (the flush at the end of an epoch).  role: "accumulate" / "boundary" fixes the role
+        outright (a captured graph holds one role).  Both are ignored at accumulate = 1."""
+        if self.accumulate > 1:
+            if role not in (None, "accumulate", "boundary"):
+                raise ValueError("role has to be 'accumulate' or 'boundary', got %r" % (role,))
+            boundary = (role == "boundary") if role is not None else (bool(last) or self.micro + 1 >= self.accumulate)
+            body, args = self._micro_step, (feats, pct, targets, tgt_lens, want_logp, boundary)
+        else:
+            body, args = self._step_features, (feats, pct, targets, tgt_lens, want_logp)
         if _roctx_on():                      # LASR_ROCTX=1: "lasr:step" around the whole step (rocprofv3 --marker-trace)
             _lib.load().lasr_roctx_range_push(b"lasr:step")
             try:
-                return self._step_features(feats, pct, targets, tgt_lens, want_logp)
+                return body(*args)
             finally:
                 _lib.load().lasr_roctx_range_pop()
-        return self._step_features(feats, pct, targets, tgt_lens, want_logp)
+        return body(*args)
+
+    def _micro_step(self, feats, pct, targets, tgt_lens, want_logp: bool, boundary: bool):
+        """One micro-step of an accumulation window (accumulate > 1).  Two uniform roles: every micro-step ADDS its gradient to
+        ``model.grads`` (zero at the start of a window), the boundary also exchanges, steps and zeroes - so a batch shape
+        needs two captured graphs, not the three of "the first micro-batch overwrites"."""
+        m = self.model
+        gm = m.grads_micro
+        if self.overlap and (self.world > 1 or self.force_staged):
+            # data parallel: EVERY micro-step of a window takes the staged backward (the same kernels in the same split-K order
+            # throughout); each bucket is added into the running sum as soon as its stage is enqueued, and only the boundary
+            # hands it to the all-reduce right behind that add - the other micro-steps issue no collective (Lightning's no_sync)
+            works = []
+            if self.comm is not None:
+                def on_bucket(ranges):
+                    ops.grad_accumulate(m.grads, gm, ranges)
+                    if boundary:
+                        self.comm.all_reduce_ranges(m.grads, ranges)
+            else:
+                def on_bucket(ranges):
+                    ops.grad_accumulate(m.grads, gm, ranges)
+                    if boundary:
+                        works.extend(torch.distributed.all_reduce(m.grads[lo:hi], group=self.pg, async_op=True) for lo, hi in ranges)
+            loss, nll, logp, am = m.loss_backward_staged(feats, pct, targets, tgt_lens, on_bucket, want_logp=want_logp, grads=gm)
+            if boundary:
+                if self.comm is not None:
+                    self.comm.wait()
+                for w in works:
+                    w.wait()
+                self._reduced = True
+        else:
+            loss, nll, logp, am = m.loss_backward(feats, pct, targets, tgt_lens, want_logp=want_logp, grads=gm)
+            ops.grad_accumulate(m.grads, gm)
+            self._reduced = False
+        if boundary:
+            self.optimizer_step()          # (world > 1 and not staged: its one flat all-reduce, on the boundary only)
+            m.grads.zero_()
+            self.micro = 0
+        else:
+            self.micro += 1
+        return loss, nll, logp, am
 
     def _step_features(self, feats, pct, targets, tgt_lens, want_logp: bool = True):
         m = self.model
@@ -218,8 +288,9 @@ class TrainStep:
                      for t in (wave, sample_lens, dither, aug))
 
     def step(self, wave, targets, tgt_lens, sample_lens=None, dither=None, aug=None, prefetch_wave=None, prefetch_lens=None,
-             prefetch_dither=None, prefetch_aug=None, want_logp: bool = True, logical_len=None, prefetch_logical_len=None):
-        """One training step on `wave`.  prefetch_wave: the NEXT step's waveforms (already in HBM): their log-mel features are
+             prefetch_dither=None, prefetch_aug=None, want_logp: bool = True, logical_len=None, prefetch_logical_len=None,
+             last: Optional[bool] = None):
+        """One training step on `wave` (accumulate > 1: one micro-step; ``last`` as in ``step_features``).  prefetch_wave: the NEXT step's waveforms (already in HBM): their log-mel features are
         computed during this step in the grid of the CTC lattice kernel (32 busy workgroups, 224 idle CUs for ~0.1 ms) and
         picked up by the next call if it passes the same tensors - the data-loader prefetch of the reference's workers;
         every step still computes exactly one batch of features."""
@@ -232,7 +303,7 @@ class TrainStep:
         if prefetch_wave is not None:
             nf, npct = self.model.arm_prefetch(prefetch_wave, prefetch_lens, prefetch_dither, prefetch_aug, logical_len=prefetch_logical_len)
             nxt = (self._prefetch_key(prefetch_wave, prefetch_lens, prefetch_dither, prefetch_aug), nf, npct)
-        out = self.step_features(feats, pct, targets, tgt_lens, want_logp=want_logp)
+        out = self.step_features(feats, pct, targets, tgt_lens, want_logp=want_logp, last=last)
         self._prefetched = nxt
         return out
 
@@ -245,11 +316,12 @@ class GraphedTrainStep:
     ``step(next_wave, targets, tgt_lens)``: like the prefetching ``TrainStep.step`` - the replay trains on the features the
     PREVIOUS replay computed and computes the features of ``next_wave`` inside its CTC launch; ``targets`` belong to the batch
     being trained on.  prefetch=False: features and training step of the same ``wave`` in one replay.
-    Shapes are fixed at construction; one instance per (B, L, S)."""
+    Shapes are fixed at construction; one instance per (B, L, S) - and, over a ``TrainStep(accumulate > 1)``, per role: a graph
+    holds either the accumulate micro-step or the boundary micro-step (``role``; ignored at accumulate = 1)."""
 
     def __init__(self, ts: TrainStep, B: int, L: int, S: int, ragged: bool = False, prefetch: bool = True, want_logp: bool = False,
                  inputs=None, feats_in=None, feats_out=None, wave_dtype=torch.float32, with_aug: bool = False, dither=None,
-                 logical_len: Optional[int] = None):
+                 logical_len: Optional[int] = None, role: str = "boundary"):
         """inputs = (wave, sample_lens | None, targets, tgt_lens[, aug]): tensors already resident in HBM that the graph reads IN
         PLACE (``replay()`` then takes no data and nothing is copied); otherwise static buffers are allocated and ``step()``
         copies into them.  feats_in / feats_out = (feats, pct) pairs: the features this graph trains on and where it writes the
@@ -257,6 +329,9 @@ class GraphedTrainStep:
         wave_dtype: torch.float32 or torch.int16 (PCM); with_aug: a static (B, 4) SpecAugment block; dither: None, a static
         (B, L) noise tensor or an ``ops.DeviceDither`` (fresh noise per replay)."""
         self.ts, self.prefetch, self.want_logp = ts, prefetch, want_logp
+        if role not in ("accumulate", "boundary"):
+            raise ValueError("role has to be 'accumulate' or 'boundary', got %r" % (role,))
+        self.role = role if ts.accumulate > 1 else "boundary"
         self.logical_len = logical_len        # rows of L samples whose longest utterance has logical_len <= L (ops.mel): T follows it
         dev = ts.model.device
         self.bound = inputs is not None
@@ -279,13 +354,13 @@ class GraphedTrainStep:
         ts, m = self.ts, self.ts.model
         if self.prefetch:
             nf, npct = m.arm_prefetch(self.wave, self.lens, self.dither, self.aug, out=self.feats_out, logical_len=self.logical_len)
-            out = ts.step_features(self.F_cur, self.pct_cur, self.targets, self.tgt_lens, want_logp=self.want_logp)
+            out = ts.step_features(self.F_cur, self.pct_cur, self.targets, self.tgt_lens, want_logp=self.want_logp, role=self.role)
             if self.feats_out is None:
                 self.F_cur.copy_(nf)
                 self.pct_cur.copy_(npct)
             return out
         feats, pct = ts.features(self.wave, self.lens, self.dither, self.aug, logical_len=self.logical_len)
-        return ts.step_features(feats, pct, self.targets, self.tgt_lens, want_logp=self.want_logp)
+        return ts.step_features(feats, pct, self.targets, self.tgt_lens, want_logp=self.want_logp, role=self.role)
 
     def capture(self, first_wave: Optional[torch.Tensor] = None, first_lens: Optional[torch.Tensor] = None, warmup: int = 2,
                 first_aug: Optional[torch.Tensor] = None) -> None:
@@ -293,12 +368,15 @@ class GraphedTrainStep:
         with bound inputs + feats_in, or when ``prime()`` hands the features over).
         The eager warm-up passes and the capture pass leave the training state (parameters, BN buffers, optimiser moments,
         schedule, dither / dropout counters) exactly as it was - also when the capture fails: it is snapshotted before and
-        restored in a ``finally``."""
+        restored in a ``finally`` (accumulate > 1: the running gradient sum, the micro-batch buffer and the window counter too)."""
         ts, m = self.ts, self.ts.model
         if ts.world > 1 and not graph_dp_enabled():
             raise RuntimeError("graph capture of the data-parallel step (RCCL inside the graph) is switched off: LASR_GRAPH_DP=0")
         ts.use_device_schedule()
         dev_state = [m.params, m.buffers, ts.exp_avg, ts.exp_avg_sq, ts.lr_dev] + ([ts._lr_state] if ts._lr_state is not None else [])
+        if ts.accumulate > 1:
+            dev_state += [m.grads, m.grads_micro]
+        micro = ts.micro
         if hasattr(self.dither, "step"):
             dev_state.append(self.dither.step)
         if getattr(m, "drop_step", None) is not None:
@@ -345,7 +423,7 @@ class GraphedTrainStep:
                 ts.schedule.load_state_dict(sched_sd)
                 ts.lr = ts.schedule.lr
                 ts.schedule._publish()
-            ts.global_step, m._bump, ts._lr_epoch = gstep, bump, lr_epoch
+            ts.global_step, m._bump, ts._lr_epoch, ts.micro = gstep, bump, lr_epoch, micro
             m.counters.update(counters)
             ts._prefetched = None
             m.disarm_prefetch()
@@ -377,10 +455,15 @@ class GraphedTrainStep:
         return self.replay()
 
     def replay(self):
-        """one training step from the captured graph (inputs as they are in the bound / static buffers right now)"""
+        """one training step from the captured graph (inputs as they are in the bound / static buffers right now); an
+        accumulate-role graph counts a training forward and a micro-batch, but no optimiser step"""
         self.graph.replay()
         ts = self.ts
         ts.model.bump_counters(1)
+        if self.role == "accumulate":
+            ts.micro += 1
+            return self.out
+        ts.micro = 0
         if ts.schedule is not None:
             ts.lr = ts.schedule.step()
             ts._lr_epoch = ts.schedule.last_epoch

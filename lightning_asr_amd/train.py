@@ -81,7 +81,10 @@ class LightingModule(LightningModule):
     def configure_optimizers(self):
         self.print("设置学习率" + str(self.learning_rate))
         novo_optim = Novograd(self.parameters(), lr=self.learning_rate, weight_decay=self.weight_decay, betas=(0.8, 0.5))
-        lr_scheduler = CosineAnnealingWarmupRestarts(novo_optim, first_cycle_steps=self.total_epoch * len(self.train_dataloader()),
+        # the schedule counts OPTIMISER steps: ceil(batches / K) per epoch under accumulate_grad_batches = K (the last window of an
+        # epoch may be incomplete and still steps)
+        K = int(getattr(self.trainer, "accumulate_grad_batches", 1) or 1)
+        lr_scheduler = CosineAnnealingWarmupRestarts(novo_optim, first_cycle_steps=self.total_epoch * -(-len(self.train_dataloader()) // K),
                                                      cycle_mult=2, max_lr=self.learning_rate, min_lr=1e-4,
                                                      warmup_steps=self.warmup_steps, gamma=0.5)
         return [novo_optim], [{"scheduler": lr_scheduler, "interval": "step", "monitor": "val_loss"}]
@@ -195,7 +198,8 @@ def main(argv=None):
     trainer = Trainer(gpus=tran_cfg.get("gpus"), resume_from_checkpoint=tran_cfg.get("checkpoint"), accelerator=tran_cfg.get("accelerator"),
                       max_epochs=tran_cfg.get("total_epoch"), check_val_every_n_epoch=tran_cfg.get("check_val_every_n_epoch", 1),
                       num_nodes=tran_cfg.get("num_nodes"), default_root_dir=cfg.get("output_dir", "."),
-                      max_steps=tran_cfg.get("max_steps"), log_every_n_steps=tran_cfg.get("log_every_n_steps", 50))
+                      max_steps=tran_cfg.get("max_steps"), log_every_n_steps=tran_cfg.get("log_every_n_steps", 50),
+                      accumulate_grad_batches=tran_cfg.get("accumulate_grad_batches", 1))
     trainer.fit(model, datamodule=data_module)
     trainer.test(model, test_dataloaders=data_module.test_dataloader())
     return trainer
