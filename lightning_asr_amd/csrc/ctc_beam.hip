@@ -1,17 +1,27 @@
-// CTC prefix beam search without an external scorer: ctc_decoders' ctc_beam_search_decoder as used by the reference's
-// BeamSearchDecoderWithLM (beam_search.py:17-57) with lm_path=None.  Blank is an argument (C-1 in this project).
+// CTC prefix beam search: ctc_decoders' ctc_beam_search_decoder as used by the reference's BeamSearchDecoderWithLM
+// (beam_search.py:17-57), without a scorer, with a character or a word n-gram LM, with hotword biasing, or with the character
+// LM and hotwords together (include/lasr.h states each contract).  Blank is an argument (C-1 in this project).
 //
 // Two launches, no host synchronisation, no allocation:
 //   1. beam_prune_kernel: one wave per (utterance, frame).  Ranks the classes by (log-prob desc, id asc) with a radix select
 //      of the cutoff_top_n best (a direct 64-lane rank for C <= 64), applies cutoff_prob to the cumulative probability of
 //      that run and writes the kept (class, log-prob) list of the frame into the workspace.
-//   2. beam_search_kernel: one 256-thread workgroup per utterance, looping over its frames.  The beam (trie node, last
-//      label, length, prefix hash, log_b, log_nb) lives in LDS; the frame's candidates (one "no new label" entry per live
-//      prefix + one extension per (prefix, kept label)) live in registers, J per thread.  The beam_width best are found by
-//      an 8-bit radix select over (score, tie-break key) that stops as soon as the boundary bucket is taken whole; only the
-//      survivors are ordered (rank by counting).  New prefixes are appended to a parent-pointer trie in the workspace
-//      (at most beam_width nodes per frame) that is walked back once at the end.  Everything but the scoring of a frame's
-//      candidates is in the beam_* functions over BeamCore, which the LM-fused search further down calls as well.
+//   2. beam_search_kernel<J, Scorer>: one 256-thread workgroup per utterance, looping over its frames.  The beam (trie node,
+//      last label, length, prefix hash, ACOUSTIC log_b / log_nb) lives in LDS; the frame's candidates (one "no new label" entry
+//      per live prefix + one extension per (prefix, kept label)) live in registers, J per thread.  The beam_width best are
+//      found by an 8-bit radix select over (score, tie-break key) that stops as soon as the boundary bucket is taken whole;
+//      only the survivors are ordered (rank by counting).  New prefixes are appended to a parent-pointer trie in the workspace
+//      (at most beam_width nodes per frame) that is walked back once at the end.
+//
+// There is one frame loop, beam_search_kernel, over the beam_* phases on BeamCore; what a search adds to the acoustic score is
+// a Scorer policy: NullScorer, LmScorer<false / true> (character LM, without / with hotwords), BiasScorer (hotwords) and
+// WlmScorer (word LM and lexicon).  A new scorer provides: Args (its kernel arguments) and Lds (BeamCore first, its
+// per-survivor array right behind); open() (false: wrong image, every slot comes back empty); init_root() and begin_frame();
+// prefix_bonus() / prefix_extras(), what core.score holds beyond logaddexp(b, nb); kCutoff with logp / cut_slack for the early
+// cutoff; Group with clear / issue / chain / finish, the scoring of kLmGroup extensions whose probes are in flight together,
+// and the Carry a survivor takes through beam_compact (on_keep); keep_entry() / new_entry() for its per-entry fields;
+// final_scores() with kOuts, kRerank, fin() and extra_out() for the end of the utterance.  The body never re-associates the
+// sums a scorer returns: the parenthesisation of every score is part of the result.
 //
 // Prefix identity: p+c merges with a live entry q when q's parent prefix equals p and q's last label is c.  Entries carry a
 // 64-bit hash of their label sequence and of their parent's, so "q's parent equals p" is a hash compare; a trie node id
@@ -19,6 +29,8 @@
 #include <type_traits>
 
 #include "common.h"
+#include "arpa_io.h"
+#include "hotword_io.h"
 
 namespace lasr {
 namespace {
@@ -191,14 +203,14 @@ __global__ __launch_bounds__(64) void beam_prune_kernel(const float* __restrict_
   if (lane == 0) kn[frame] = keep;
 }
 
-// ------------------------------------------------------------------ the search ------------------------------------------
-// What a search keeps in LDS whether or not a language model scores the extensions.  The phases below (beam_init_root ..
-// beam_write_back) work on this alone; each search kernel owns its candidate scoring, steps (2)-(3), and its extra fields.
+// ------------------------------------------------------------------ the search: phases ----------------------------------
+// What every search keeps in LDS.  The phases below (beam_init_root .. beam_write_back) work on this alone; b / nb are always
+// ACOUSTIC, score is what the beam is ranked by.
 struct BeamCore {
   int node[2][kBeamMaxWidth], last[2][kBeamMaxWidth], len[2][kBeamMaxWidth];
   float b[2][kBeamMaxWidth], nb[2][kBeamMaxWidth];       // acoustic log_b / log_nb
   uint64_t h[2][kBeamMaxWidth], ph[2][kBeamMaxWidth];
-  float score[kBeamMaxWidth];             // what the current beam is ranked by: logaddexp(b, nb) (+ the LM bonus, if any)
+  float score[kBeamMaxWidth];             // what the current beam is ranked by: logaddexp(b, nb) (+ the scorer's bonus, if any)
   float next_b[kBeamMaxWidth], next_nb[kBeamMaxWidth];   // the "no new label" candidate of each live prefix
   unsigned long long merged[kBeamMaxWidth];              // bit k: p + kept[k] merged into a live entry
   uint64_t surv[kBeamMaxWidth];
@@ -207,7 +219,7 @@ struct BeamCore {
   uint32_t hist[256];
   uint32_t found[4];
   uint32_t nsel;
-  // last, and aligned so that the struct has no tail padding: a per-survivor array that a search places right behind its
+  // last, and aligned so that the struct has no tail padding: a per-survivor array that a scorer places right behind its
   // BeamCore is then 512 bytes from surv_i, and beam_compact's store and on_keep's go out as one paired LDS write
   alignas(8) int surv_i[kBeamMaxWidth];
 };
@@ -336,6 +348,30 @@ __device__ __forceinline__ void beam_new_entry(BeamCore& s, int cur, int nxt, in
   s.b[nxt][rank] = kNegInfB;
 }
 
+// End of utterance, for the scorers whose end term can change the order.  Thread tid < nbeam hands in its entry's N final
+// values, out[0] the score; the entries are ranked by it, ties by their order before, and (node, len) and the values are
+// written in the new order: node / len into the other half of the beam, which is returned for beam_write_back (whose barrier
+// publishes fin).
+template <int N>
+__device__ __forceinline__ int beam_final_rerank(BeamCore& core, float (&fin)[N][kBeamMaxWidth], int cur, int nbeam, int tid,
+                                                 const float (&out)[N]) {
+  if (tid < nbeam) core.score[tid] = out[0];
+  __syncthreads();
+  const int dst = cur ^ 1;
+  if (tid < nbeam) {
+    const float f = out[0];
+    int rank = 0;
+    for (int r = 0; r < nbeam; ++r) {
+      const float g = core.score[r];
+      rank += g > f || (g == f && r < tid);
+    }
+    core.node[dst][rank] = core.node[cur][tid]; core.len[dst][rank] = core.len[cur][tid];
+#pragma unroll
+    for (int n = 0; n < N; ++n) fin[n][rank] = out[n];
+  }
+  return dst;
+}
+
 // walks the trie back from each of the n_best final entries (none of them when !valid_all) into tok, this utterance's
 // (n_best, T) tokens, and writes the lengths; the slots past a hypothesis are -1, the length of an empty slot is -1
 __device__ __forceinline__ void beam_write_back(const BeamCore& s, int cur, int nbeam, int n_best, int64_t T, const int2* trie,
@@ -365,218 +401,57 @@ __device__ __forceinline__ void beam_write_back(const BeamCore& s, int cur, int 
   }
 }
 
-// the extension candidate (p, kept[k]) -> its score (-inf when it merged into a live entry or k is the blank)
-__device__ __forceinline__ float ext_score(const BeamCore& s, int cur, int p, int k, int blank) {
-  const int c = s.kcls[k];
-  if (c == blank || ((s.merged[p] >> k) & 1ull)) return kNegInfB;
-  return s.klp[k] + (c == s.last[cur][p] ? s.b[cur][p] : s.score[p]);
-}
-
-template <int J>
-__global__ __launch_bounds__(kSearchThreads) void beam_search_kernel(const int32_t* __restrict__ kcls_g,
-                                                                     const float* __restrict__ klp_g,
-                                                                     const int32_t* __restrict__ kn_g,
-                                                                     const int32_t* __restrict__ lens, int64_t T, int blank,
-                                                                     int W, int n_best, int2* __restrict__ trie_g,
-                                                                     int32_t* __restrict__ tokens, int32_t* __restrict__ n_tokens,
-                                                                     float* __restrict__ scores) {
-  __shared__ BeamCore s;
-  const int tid = threadIdx.x;
-  const int64_t ub = blockIdx.x;
-  const int64_t L = lens ? min((int64_t)max(lens[ub], 0), T) : T;
-  int2* trie = trie_g + ub * (1 + T * (int64_t)W);
-  BeamFetch pf{kcls_g + ub * T * kBeamMaxTopN, klp_g + ub * T * kBeamMaxTopN, kn_g + ub * T};
-  beam_init_root(s, tid);
-  int nbeam = 1, cur = 0;
-  if (L > 0) pf.request(0, tid);
-  for (int64_t t = 0; t < L; ++t) {
-    const int nk = beam_fetch_frame(s, pf, t, L, tid);
-    __syncthreads();
-    // (1) per live prefix: score, the kept index of its last label and of the blank, its parent among the live entries
-    int lastk = -1, pr = -1;
-    float blp = kNegInfB;
-    if (tid < nbeam) {
-      const int last = s.last[cur][tid];
-      s.score[tid] = lae(s.b[cur][tid], s.nb[cur][tid]);
-      beam_lookup(s, cur, nbeam, nk, blank, tid, last, &lastk, &pr, &blp);
-    }
-    __syncthreads();
-    // (2) the "no new label" candidate of each live prefix, with what its parent's extension by its last label adds
-    if (tid < nbeam) {
-      const float sc = s.score[tid];
-      float nbn = kNegInfB;
-      if (lastk >= 0) {
-        const float lc = s.klp[lastk];
-        nbn = lc + s.nb[cur][tid];
-        if (pr >= 0) {
-          nbn = lae(nbn, lc + (s.last[cur][tid] == s.last[cur][pr] ? s.b[cur][pr] : s.score[pr]));
-          atomicOr(&s.merged[pr], 1ull << lastk);
-        }
-      }
-      s.next_b[tid] = blp + sc;
-      s.next_nb[tid] = nbn;
-    }
-    __syncthreads();
-    // (3) candidates: i < nbeam "no new label" of entry i, then nbeam * nk extensions (p, k); composite = score desc, key asc
-    const int ncand = nbeam + nbeam * nk;
-    uint64_t comp[J];
-    uint64_t valid = 0;
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      const int i = tid + j * kSearchThreads;
-      float sc = kNegInfB;
-      uint32_t key = 0;
-      if (i < nbeam) {
-        sc = lae(s.next_b[i], s.next_nb[i]);
-        key = (uint32_t)i << 14;
-      } else if (i < ncand) {
-        const int q = i - nbeam, p = q / nk, k = q - p * nk;
-        sc = ext_score(s, cur, p, k, blank);
-        key = ((uint32_t)p << 14) | (uint32_t)(s.kcls[k] + 1);
-      }
-      comp[j] = ((uint64_t)desc_bits(sc) << 32) | key;
-      if (sc > kNegInfB) valid |= 1ull << j;
-    }
-    // (4) select the W best, (5) compact and order them, write the next beam (and the trie nodes of new prefixes)
-    uint64_t prefix, mask;
-    beam_select<J>(s, comp, valid, W, tid, &prefix, &mask);
-    const int nsel = beam_compact<J>(s, comp, valid, prefix, mask, W, tid, [](uint32_t, int) {});
-    const int nxt = cur ^ 1;
-    if (tid < nsel) {
-      const int rank = beam_rank(s, nsel, tid);
-      const int i = s.surv_i[tid];
-      if (i < nbeam) {
-        beam_keep_entry(s, cur, nxt, rank, i);
-      } else {
-        const int q = i - nbeam, p = q / nk, k = q - p * nk;
-        beam_new_entry(s, cur, nxt, rank, p, s.kcls[k], t, W, trie);
-        s.nb[nxt][rank] = ext_score(s, cur, p, k, blank);
-      }
-    }
-    nbeam = nsel;
-    cur = nxt;
-    __syncthreads();
-  }
-  beam_write_back(s, cur, nbeam, n_best, T, trie, tokens + ub * (int64_t)n_best * T, n_tokens + ub * n_best, true, tid);
-  if (tid < n_best) scores[ub * n_best + tid] = tid < nbeam ? lae(s.b[cur][tid], s.nb[cur][tid]) : kNegInfB;
-}
-
-bool beam_shape_ok(int64_t B, int64_t T, int64_t C, int W, int topn) {
-  return B >= 1 && T >= 1 && C >= 1 && C <= kBeamMaxClasses && W >= 1 && W <= kBeamMaxWidth && topn >= 1 &&
-         topn <= kBeamMaxTopN && B * T <= 0x7fffffffLL && 1 + T * (int64_t)W <= 0x7fffffffLL;
-}
-
-struct BeamWs {
-  size_t kcls, klp, kn, trie, total;
-};
-
-BeamWs beam_ws(int64_t B, int64_t T, int64_t W) {
-  BeamWs w;
-  const size_t frames = (size_t)(B * T);
-  w.kcls = 0;
-  w.klp = align_up(w.kcls + frames * kBeamMaxTopN * sizeof(int32_t), 256);
-  w.kn = align_up(w.klp + frames * kBeamMaxTopN * sizeof(float), 256);
-  w.trie = align_up(w.kn + frames * sizeof(int32_t), 256);
-  w.total = align_up(w.trie + (size_t)B * (size_t)(1 + T * W) * sizeof(int2), 256);
-  return w;
-}
-
-// the arguments both decoders take, as `who` (the exported function) received them
-struct BeamArgs {
-  const char* who;
-  const float* logp;
+// what every search is handed beside the prune launch's kept lists: the lengths, the shape, the trie and the outputs all share
+struct BeamIo {
   const int32_t* lens;
-  int64_t B, T, C;
-  int blank, beam_width, cutoff_top_n;
-  float cutoff_prob;
-  int n_best;
-  void* workspace;
-  size_t workspace_bytes;
-  void* stream;
+  int64_t T;
+  int C, blank, W, n_best;
+  int2* trie;
+  int32_t* tokens;
+  int32_t* n_tokens;
+  float* scores;
 };
 
-// the value checks both decoders make; ptrs_ok: every pointer the caller requires is set
-int beam_check_args(const BeamArgs& a, bool ptrs_ok) {
-  LASR_CHECK_ARG(ptrs_ok, "%s: null pointer", a.who);
-  LASR_CHECK_ARG(a.n_best >= 1 && a.n_best <= a.beam_width, "%s: n_best %d outside [1, beam_width %d]", a.who, a.n_best,
-                 a.beam_width);
-  LASR_CHECK_ARG(a.cutoff_prob > 0.f && a.cutoff_prob <= 1.f, "%s: cutoff_prob %g outside (0, 1]", a.who, (double)a.cutoff_prob);
-  LASR_CHECK_ARG(a.C >= 1 && a.blank >= 0 && a.blank < a.C, "%s: blank %d outside [0, C = %lld)", a.who, a.blank, (long long)a.C);
-  return 0;
-}
-
-// Checks the shape and the workspace, carves it, launches the prune kernel and then search(J, grid, stream, kc, kl, kn, trie)
-// with J, the candidates per thread, as a std::integral_constant: the caller launches its kernel's instantiation.
-template <class Search>
-int beam_launch(const BeamArgs& a, const char* search_name, Search search) {
-  LASR_CHECK_SHAPE(beam_shape_ok(a.B, a.T, a.C, a.beam_width, a.cutoff_top_n),
-                   "%s: B %lld T %lld C %lld beam_width %d cutoff_top_n %d outside the supported range "
-                   "(C <= %d, beam_width 1..%d, cutoff_top_n 1..%d)", a.who, (long long)a.B, (long long)a.T, (long long)a.C,
-                   a.beam_width, a.cutoff_top_n, kBeamMaxClasses, kBeamMaxWidth, kBeamMaxTopN);
-  const BeamWs w = beam_ws(a.B, a.T, a.beam_width);
-  if (a.workspace_bytes < w.total)
-    return fail(LASR_E_WORKSPACE, "%s: workspace %zu < %zu bytes", a.who, a.workspace_bytes, w.total);
-  char* ws = static_cast<char*>(a.workspace);
-  int32_t* kc = reinterpret_cast<int32_t*>(ws + w.kcls);
-  float* kl = reinterpret_cast<float*>(ws + w.klp);
-  int32_t* kn = reinterpret_cast<int32_t*>(ws + w.kn);
-  int2* trie = reinterpret_cast<int2*>(ws + w.trie);
-  hipStream_t st = as_stream(a.stream);
-  hipLaunchKernelGGL(beam_prune_kernel, dim3((unsigned)(a.B * a.T)), dim3(64), 0, st, a.logp, a.lens, a.T, (int)a.C,
-                     a.cutoff_top_n, a.cutoff_prob, kc, kl, kn);
-  LASR_LAUNCH_CHECK("beam_prune_kernel");
-  // candidates per frame: beam_width "no new label" entries + beam_width * kept labels, J per thread
-  const int K = (int)(a.C < a.cutoff_top_n ? a.C : a.cutoff_top_n);
-  const int per = (int)cdiv((int64_t)a.beam_width * (K + 1), kSearchThreads);
-  const dim3 grid((unsigned)a.B);
-  if (per <= 1) search(std::integral_constant<int, 1>{}, grid, st, kc, kl, kn, trie);
-  else if (per <= 2) search(std::integral_constant<int, 2>{}, grid, st, kc, kl, kn, trie);
-  else if (per <= 4) search(std::integral_constant<int, 4>{}, grid, st, kc, kl, kn, trie);
-  else if (per <= 8) search(std::integral_constant<int, 8>{}, grid, st, kc, kl, kn, trie);
-  else if (per <= 16) search(std::integral_constant<int, 16>{}, grid, st, kc, kl, kn, trie);
-  else search(std::integral_constant<int, 33>{}, grid, st, kc, kl, kn, trie);
-  LASR_LAUNCH_CHECK(search_name);
-  return 0;
-}
-
-}  // namespace
-}  // namespace lasr
-
-using namespace lasr;
-
-extern "C" size_t lasr_ctc_beam_workspace_bytes(int64_t B, int64_t T, int64_t C, int beam_width, int cutoff_top_n) {
-  if (!beam_shape_ok(B, T, C, beam_width, cutoff_top_n)) return 0;
-  return beam_ws(B, T, beam_width).total;
-}
-
-extern "C" int lasr_ctc_beam_decode(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
-                                    int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, int32_t* tokens,
-                                    int32_t* n_tokens, float* scores, void* workspace, size_t workspace_bytes, void* stream) {
-  const BeamArgs a{"lasr_ctc_beam_decode", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
-                   workspace_bytes, stream};
-  LASR_TRY(beam_check_args(a, logp && tokens && n_tokens && scores && workspace));
-  auto search = [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
-    hipLaunchKernelGGL(beam_search_kernel<decltype(j)::value>, grid, dim3(kSearchThreads), 0, st, kc, kl, kn, lens, T, blank,
-                       beam_width, n_best, trie, tokens, n_tokens, scores);
-  };
-  return beam_launch(a, "beam_search_kernel", search);
-}
-
-// ================================================================== with an n-gram LM ===================================
-// lasr_ctc_beam_decode_lm: the same search with ctc_decoders' character-based Scorer (include/lasr.h states the contract).
-// The prune launch is the one above.  The search keeps each entry's ACOUSTIC log_b / log_nb and beside them its LM bonus
-// (alpha * sum of lm + beta * labels, which depends on the prefix alone, so merging stays exact), its own emission term, the
-// LM word ids of its last N-1 labels and the backoff sums of its context chain.  An extension p -> p+c scores
-// lm(c | ctx(p)) = log10 p(longest stored (x_m .. x_1 c)) + sum of the backoffs of the longer stored contexts, found by a walk
-// leftward from c through the image's hash, one probe per word; the probes of a thread's candidates go out together.
-#include "arpa_io.h"
-#include "hotword_io.h"
-
-namespace lasr {
-namespace {
-
-constexpr int kLmMaxCtx = host::kArpaMaxOrder - 1;
 constexpr int kLmGroup = 4;                  // candidates per thread whose probes are in flight together
+
+// ------------------------------------------------------------------ no scorer -------------------------------------------
+// core.score is logaddexp(b, nb) itself: the acoustic score of a prefix and what it is ranked by are one array
+struct NoCarry {};
+
+struct NullScorer {
+  struct Args {};
+  struct Lds {
+    BeamCore core;
+  };
+  using Carry = NoCarry;
+  static constexpr Carry kNoCarry{};
+  static constexpr bool kScored = false, kCutoff = false, kRerank = false;
+  static constexpr int kOuts = 1;
+  static constexpr const char* kName = "beam_search_kernel";
+  struct Group {};
+  static bool args_set(const Args&) { return true; }
+  static __device__ __forceinline__ float* ascore(Lds& s) { return s.core.score; }
+  __device__ __forceinline__ float* extra_out(int) const { return nullptr; }
+  __device__ __forceinline__ bool open(const BeamIo&, const Args&) { return true; }
+  __device__ __forceinline__ void init_root(Lds&) const {}
+  __device__ __forceinline__ void begin_frame(Lds&, const BeamFetch&, int) const {}
+  __device__ __forceinline__ void clear(Group&, int) const {}
+  __device__ __forceinline__ void issue(const Lds&, Group&, int, int, int, int, int, float) const {}
+  __device__ __forceinline__ void chain(const Lds&, Group&, int, const int (&)[kLmGroup]) const {}
+  __device__ __forceinline__ float finish(const Lds&, Group&, int, int, int, int, int, float am, Carry*) const { return am; }
+  static __device__ __forceinline__ void on_keep(Lds&, uint32_t, Carry) {}
+  __device__ __forceinline__ void keep_entry(Lds&, int, int, int, int) const {}
+  __device__ __forceinline__ void new_entry(Lds&, int, int, int, int, int, int, int) const {}
+  __device__ __forceinline__ void final_scores(const Lds& s, int cur, int tid, float (&out)[kOuts]) const {
+    out[0] = lae(s.core.b[cur][tid], s.core.nb[cur][tid]);
+  }
+};
+
+// ------------------------------------------------------------------ n-gram LM images ------------------------------------
+// A character LM scores an extension p -> p+c by lm(c | ctx(p)) = log10 p(longest stored (x_m .. x_1 c)) + sum of the backoffs
+// of the longer stored contexts, found by a walk leftward from c through the image's hash, one probe per word.  An entry keeps
+// the LM word ids of its last N-1 labels (words, for the word LM) and the backoff sums of its context chain.
+constexpr int kLmMaxCtx = host::kArpaMaxOrder - 1;
 constexpr float kLmOov = -1000.f;            // ctc_decoders' OOV_SCORE (natural log, not converted)
 constexpr float kLmLogE = 0.4342944819f;     // ctc_decoders' NUM_FLT_LOGE: log10 -> natural log by division
 
@@ -674,13 +549,69 @@ __device__ void lm_context_sums(const LmImg& m, int w, const int* ctx, float* cb
   }
 }
 
+// An entry's context chain in LDS, for both LM scorers: S has ctx[2][kLmMaxCtx][] (LM ids of the last N-1 labels or words,
+// nearest first, -1 = OOV) and cb[2][kLmMaxCtx + 1][] (cb[j]: log10 backoffs of the stored contexts longer than j words).
+template <class S>
+__device__ __forceinline__ void lm_chain_load(const S& s, int cur, int i, int* cx, float* cb) {
+  for (int d = 0; d < kLmMaxCtx; ++d) cx[d] = s.ctx[cur][d][i];
+  for (int d = 0; d <= kLmMaxCtx; ++d) cb[d] = s.cb[cur][d][i];
+}
+template <class S>
+__device__ __forceinline__ void lm_chain_copy(S& s, int cur, int nxt, int rank, int i) {
+  for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[nxt][d][rank] = s.ctx[cur][d][i];
+  for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[nxt][d][rank] = s.cb[cur][d][i];
+}
+// cb holds nctx + 1 sums; the rest of an entry's is 0
+template <class S>
+__device__ __forceinline__ void lm_chain_store(S& s, int nxt, int rank, const int* cx, const float* cb, int nctx) {
+  for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[nxt][d][rank] = cx[d];
+  for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[nxt][d][rank] = d <= nctx ? cb[d] : 0.f;
+}
+// the root's chain: <s> in every position
+template <class S>
+__device__ __forceinline__ void lm_chain_root(S& s, const LmImg& lm, bool ok) {
+  int rc[kLmMaxCtx];
+  float cb[kLmMaxCtx + 1];
+  for (int d = 0; d < kLmMaxCtx; ++d) rc[d] = lm.bos;
+  for (int d = 0; d <= kLmMaxCtx; ++d) cb[d] = 0.f;
+  if (ok) lm_context_sums(lm, lm.bos, rc, cb);
+  lm_chain_store(s, 0, 0, rc, cb, lm.nctx);
+}
+// the chain of p + w: w joins p's context
+template <class S>
+__device__ __forceinline__ void lm_chain_push(const S& s, const LmImg& lm, int cur, int p, int w, int* nc, float* cb) {
+  nc[0] = w;
+  for (int d = 1; d < kLmMaxCtx; ++d) nc[d] = s.ctx[cur][d - 1][p];
+  lm_context_sums(lm, w, nc + 1, cb);
+}
+// ctc_decoders' sentence-end window of entry tid: </s> (and the <s> window of <s>^N </s> for an empty hypothesis)
+template <class S>
+__device__ __forceinline__ float lm_sentence_end(const S& s, const LmImg& lm, int cur, int tid) {
+  int cx[kLmMaxCtx];
+  float cb[kLmMaxCtx + 1];
+  lm_chain_load(s, cur, tid, cx, cb);
+  float sent = lm_score_one(lm, lm.eos, cx, cb);
+  if (s.core.len[cur][tid] == 0) sent += lm_score_one(lm, lm.bos, cx, cb);
+  return sent;
+}
+
+// the kernel arguments of the LM scorers (bias_image / bias_scores: LmScorer<true> alone)
+struct LmArgs {
+  const float* logp;
+  const void* image;
+  float alpha, beta;
+  float* am_scores;
+  const void* bias_image;
+  float* bias_scores;
+};
+
 // ------------------------------------------------------------------ hotword biasing ------------------------------------
-// lasr_ctc_beam_decode_bias / _lm_bias (include/lasr.h states the contract; hotword_io.h the automaton, its image and the
-// walker).  Each entry carries the automaton node of its prefix and bonus(prefix); like the LM bonus both depend on the prefix
-// alone, so merging stays exact.  step(root, c) of every kept label is resolved once per frame into LDS: most live entries sit
-// at the root and then cost no global probe per candidate.  The first probes of a thread's other candidates are loaded
-// together, kLmGroup at a time, and handed to the walker.  A survivor's step is walked again when its entry is written, so no
-// candidate carries its next node in registers.  A bank of no phrases (one node) switches every probe off.
+// hotword_io.h has the automaton, its image and the walker.  Each entry carries the automaton node of its prefix and
+// bonus(prefix); like the LM bonus both depend on the prefix alone, so merging stays exact.  step(root, c) of every kept label is
+// resolved once per frame into LDS: most live entries sit at the root and then cost no global probe per candidate.  The first
+// probes of a thread's other candidates are loaded together, kLmGroup at a time, and handed to the walker.  A survivor's step is
+// walked again when its entry is written, so no candidate carries its next node in registers.  A bank of no phrases (one node)
+// switches every probe off.
 struct BiasImg {
   host::HotwordView m;
   bool ok, on;                // ok: a hotword image for these classes; on: it holds a phrase
@@ -699,7 +630,7 @@ struct BiasLds {
   float bonus[2][kBeamMaxWidth];                         // bonus(prefix): the sum of its steps' deltas
   int rchild[kBeamMaxTopN], rstate[kBeamMaxTopN];        // per kept label: the root's child by it (-1: none) and step(root, label)
   float rdelta[kBeamMaxTopN];
-  float fin[kBeamMaxWidth], fin_am[kBeamMaxWidth], fin_b[kBeamMaxWidth];   // the re-ranked final scores
+  float fin[3][kBeamMaxWidth];                           // the re-ranked final score, am_scores and bias_scores values
 };
 
 // step(root, c) of the kept label this thread fetched (tid < n): c = BeamFetch::pc before beam_fetch_frame publishes it
@@ -739,470 +670,261 @@ __device__ __forceinline__ int bias_walk(const BiasImg& hw, const BiasLds& s, in
   return host::hotword_step(hw.m, v, c, s.rchild[k], first, delta);
 }
 
-// End of utterance.  Thread tid < nbeam hands in its entry's final score f (final(p) included), the am_scores value and
-// final(p); the entries are ranked by f, ties by their order before, and (node, len) and the three values are written in the
-// new order: node / len into the other half of the beam, which is returned for beam_write_back.
-__device__ __forceinline__ int bias_rerank(BeamCore& core, BiasLds& s, int cur, int nbeam, int tid, float f, float am, float fb) {
-  if (tid < nbeam) core.score[tid] = f;
-  __syncthreads();
-  const int fin = cur ^ 1;
-  if (tid < nbeam) {
-    int rank = 0;
-    for (int r = 0; r < nbeam; ++r) {
-      const float g = core.score[r];
-      rank += g > f || (g == f && r < tid);
-    }
-    core.node[fin][rank] = core.node[cur][tid]; core.len[fin][rank] = core.len[cur][tid];
-    s.fin[rank] = f; s.fin_am[rank] = am; s.fin_b[rank] = fb;
+// The hotword share of a search: BiasScorer is this alone, LmScorer<true> has it beside the character LM.
+struct BiasPart {
+  BiasImg hw;
+  struct Group {
+    uint64_t key[kLmGroup];
+    int32_t child[kLmGroup];
+  };
+  __device__ __forceinline__ void init_root(BiasLds& s) const { s.state[0][0] = 0; s.bonus[0][0] = 0.f; }
+  __device__ __forceinline__ void clear(Group& g, int u) const { g.key[u] = host::kHotwordEmptyKey; g.child[u] = -1; }
+  __device__ __forceinline__ void issue(const BiasLds& s, Group& g, int u, int cur, int p, int c) const {
+    const BiasFirst e = bias_first(hw, s, cur, p, c);
+    g.key[u] = e.key; g.child[u] = e.child;
   }
-  return fin;
-}
+  // bonus(p + c) - bonus(p) of the candidate whose first probe issue() loaded
+  __device__ __forceinline__ float delta(const BiasLds& s, const Group& g, int u, int cur, int p, int k, int c) const {
+    float hd;
+    bias_walk(hw, s, cur, p, k, c, g.key[u], g.child[u], &hd);
+    return hd;
+  }
+  __device__ __forceinline__ void keep_entry(BiasLds& s, int cur, int nxt, int rank, int i) const {
+    s.state[nxt][rank] = s.state[cur][i]; s.bonus[nxt][rank] = s.bonus[cur][i];
+  }
+  __device__ __forceinline__ void new_entry(BiasLds& s, int cur, int nxt, int rank, int p, int k, int c) const {
+    float hd;
+    const BiasFirst e = bias_first(hw, s, cur, p, c);
+    s.state[nxt][rank] = bias_walk(hw, s, cur, p, k, c, e.key, e.child, &hd);
+    s.bonus[nxt][rank] = s.bonus[cur][p] + hd;
+  }
+  // end of utterance: an unfinished match gives its provisional credit back
+  __device__ __forceinline__ float final_bonus(const BiasLds& s, int cur, int tid) const {
+    return s.bonus[cur][tid] + (hw.on ? host::hotword_give_back(hw.m, s.state[cur][tid]) : 0.f);
+  }
+};
 
-// after beam_write_back (whose barrier publishes fin / fin_am / fin_b): scores, am_scores and bias_scores of slot o
-__device__ __forceinline__ void bias_write_scores(const BiasLds& s, bool have, int tid, int64_t o, float* scores, float* am_scores,
-                                                  float* bias_scores) {
-  scores[o] = have ? s.fin[tid] : kNegInfB;
-  am_scores[o] = have ? s.fin_am[tid] : kNegInfB;
-  bias_scores[o] = have ? s.fin_b[tid] : 0.f;
-}
+// lasr_ctc_beam_decode_bias: core.score is logaddexp(b, nb) + bonus(prefix).  With a bank of no phrases every bonus is 0 and
+// each score is the expression NullScorer's search evaluates, so the result is that search's bit for bit.
+struct BiasScorer {
+  struct Args {
+    const void* bias_image;
+    float* am_scores;
+    float* bias_scores;
+  };
+  struct Lds {
+    BeamCore core;
+    float ascore[kBeamMaxWidth];                           // acoustic logaddexp(b, nb) of the current beam
+    BiasLds hw;
+  };
+  using Carry = NoCarry;
+  static constexpr Carry kNoCarry{};
+  static constexpr bool kScored = true, kCutoff = false, kRerank = true;
+  static constexpr int kOuts = 3;
+  static constexpr const char* kName = "beam_search_bias_kernel";
+  using Group = BiasPart::Group;
+  BiasPart bias;
+  Args a;
+  int blank;
+  static bool args_set(const Args& a) { return a.bias_image && a.am_scores && a.bias_scores; }
+  static __device__ __forceinline__ float* ascore(Lds& s) { return s.ascore; }
+  static __device__ __forceinline__ auto& fin(Lds& s) { return s.hw.fin; }
+  __device__ __forceinline__ float* extra_out(int n) const { return n == 1 ? a.am_scores : a.bias_scores; }
+  __device__ __forceinline__ bool open(const BeamIo& io, const Args& args) {
+    a = args; blank = io.blank;
+    bias.hw = bias_open(a.bias_image, io.C, io.blank);
+    return bias.hw.ok;
+  }
+  __device__ __forceinline__ void init_root(Lds& s) const { bias.init_root(s.hw); }
+  __device__ __forceinline__ void begin_frame(Lds& s, const BeamFetch& pf, int tid) const {
+    bias_root_steps(bias.hw, s.hw, tid, pf.pn, pf.pc, blank);
+  }
+  __device__ __forceinline__ float prefix_bonus(const Lds& s, int cur, int i) const { return s.hw.bonus[cur][i]; }
+  __device__ __forceinline__ void prefix_extras(Lds&, int, int) const {}
+  __device__ __forceinline__ void clear(Group& g, int u) const { bias.clear(g, u); }
+  __device__ __forceinline__ void issue(const Lds& s, Group& g, int u, int cur, int p, int, int c, float) const {
+    bias.issue(s.hw, g, u, cur, p, c);
+  }
+  __device__ __forceinline__ void chain(const Lds&, Group&, int, const int (&)[kLmGroup]) const {}
+  __device__ __forceinline__ float finish(const Lds& s, Group& g, int u, int cur, int p, int k, int c, float am, Carry*) const {
+    return am + (s.hw.bonus[cur][p] + bias.delta(s.hw, g, u, cur, p, k, c));
+  }
+  static __device__ __forceinline__ void on_keep(Lds&, uint32_t, Carry) {}
+  __device__ __forceinline__ void keep_entry(Lds& s, int cur, int nxt, int rank, int i) const {
+    bias.keep_entry(s.hw, cur, nxt, rank, i);
+  }
+  __device__ __forceinline__ void new_entry(Lds& s, int cur, int nxt, int rank, int p, int k, int c, int) const {
+    bias.new_entry(s.hw, cur, nxt, rank, p, k, c);
+  }
+  __device__ __forceinline__ void final_scores(const Lds& s, int cur, int tid, float (&out)[kOuts]) const {
+    const float am = lae(s.core.b[cur][tid], s.core.nb[cur][tid]);
+    const float fb = bias.final_bonus(s.hw, cur, tid);
+    out[0] = am + fb; out[1] = am; out[2] = fb;
+  }
+};
 
-// core.b / core.nb stay ACOUSTIC here and core.score is the fused score; the LM's share of an entry lives beside the core
+// ------------------------------------------------------------------ character n-gram LM (+ hotwords) -------------------
+// lasr_ctc_beam_decode_lm / _lm_bias: ctc_decoders' character-based Scorer.  Beside the acoustic log_b / log_nb an entry keeps
+// its LM bonus (alpha * sum of lm + beta * labels, which depends on the prefix alone, so merging stays exact), its own emission
+// term and its context chain; the probes of a thread's kLmGroup candidates go out together.  kBias: the hotword share
+// (BiasPart) beside it; every statement of the biasing is under `if constexpr (kBias)`.
 struct BeamLmLds {
   BeamCore core;
   float surv_t[kBeamMaxWidth];                           // emission term of a surviving extension (beside core.surv_i)
   float bonus[2][kBeamMaxWidth], term[2][kBeamMaxWidth]; // alpha * sum lm + beta * labels; the last label's own term
-  int ctx[2][kLmMaxCtx][kBeamMaxWidth];                  // LM word ids of the last N-1 labels, nearest first (-1 = OOV)
-  float cb[2][kLmMaxCtx + 1][kBeamMaxWidth];             // cb[j]: log10 backoffs of the stored contexts longer than j words
+  int ctx[2][kLmMaxCtx][kBeamMaxWidth];
+  float cb[2][kLmMaxCtx + 1][kBeamMaxWidth];
   float ascore[kBeamMaxWidth];                           // acoustic logaddexp(b, nb) of the current beam
   int kwid[kBeamMaxTopN];                                // LM word id of each kept label (-1: the blank, or not in the LM)
   int ctx_oov[kBeamMaxWidth];
 };
-// the same with hotword biasing: each entry's automaton node and bias bonus sit next to its LM bonus / term
 struct BeamLmBiasLds : BeamLmLds {
   BiasLds hw;
 };
-static_assert(sizeof(BeamLmLds) < 64 * 1024 && sizeof(BeamLmBiasLds) < 64 * 1024, "static LDS of the LM search");
 
-// kBias: lasr_ctc_beam_decode_lm_bias, the search with hotword biasing (bias_image, bias_scores).  Every statement of the
-// biasing is under `if constexpr (kBias)`: the kBias = false instantiation is the LM search alone.
-template <int J, bool kBias>
-__global__ __launch_bounds__(kSearchThreads) void beam_search_lm_kernel(
-    const float* __restrict__ logp, const int32_t* __restrict__ kcls_g, const float* __restrict__ klp_g,
-    const int32_t* __restrict__ kn_g, const int32_t* __restrict__ lens, int64_t T, int C, int blank, int W, int n_best,
-    const void* __restrict__ image, float alpha, float beta, int2* __restrict__ trie_g, int32_t* __restrict__ tokens,
-    int32_t* __restrict__ n_tokens, float* __restrict__ scores, float* __restrict__ am_scores,
-    const void* __restrict__ bias_image, float* __restrict__ bias_scores) {
-  __shared__ std::conditional_t<kBias, BeamLmBiasLds, BeamLmLds> s;
-  BeamCore& core = s.core;
-  const int tid = threadIdx.x;
-  const int64_t ub = blockIdx.x;
-  LmImg lm = lm_open(image);
-  BiasImg hw{};
-  if constexpr (kBias) {
-    hw = bias_open(bias_image, C, blank);
-    lm.ok = lm.ok && hw.ok;             // either image wrong: empty slots
+template <bool kBias>
+struct LmScorer {
+  using Args = LmArgs;
+  using Lds = std::conditional_t<kBias, BeamLmBiasLds, BeamLmLds>;
+  using Carry = float;                                   // the extension's emission term
+  static constexpr Carry kNoCarry = 0.f;
+  static constexpr bool kScored = true, kCutoff = true, kRerank = kBias;
+  static constexpr int kOuts = kBias ? 3 : 2;
+  static constexpr const char* kName = kBias ? "beam_search_lm_kernel (biased)" : "beam_search_lm_kernel";
+  struct Group {
+    float lpv[kLmGroup];
+    int64_t g[kLmGroup];
+    int mm[kLmGroup], wc[kLmGroup];
+    bool act[kLmGroup];
+    std::conditional_t<kBias, BiasPart::Group, NoCarry> hw;
+  };
+  LmImg lm;
+  BiasPart bias;
+  Args a;
+  const float* logp;
+  int blank;
+  static bool args_set(const Args& a) { return a.image && a.am_scores && (!kBias || (a.bias_image && a.bias_scores)); }
+  static __device__ __forceinline__ float* ascore(Lds& s) { return s.ascore; }
+  static __device__ __forceinline__ auto& fin(Lds& s) { return s.hw.fin; }
+  __device__ __forceinline__ float* extra_out(int n) const { return n == 1 ? a.am_scores : a.bias_scores; }
+  __device__ __forceinline__ bool open(const BeamIo& io, const Args& args) {
+    a = args; logp = args.logp; blank = io.blank;
+    lm = lm_open(a.image);
+    if constexpr (kBias) {
+      bias.hw = bias_open(a.bias_image, io.C, io.blank);
+      lm.ok = lm.ok && bias.hw.ok;          // either image wrong: empty slots
+    }
+    return lm.ok;
   }
-  const int64_t L = !lm.ok ? 0 : lens ? min((int64_t)max(lens[ub], 0), T) : T;
-  const int nctx = lm.nctx;
-  int2* trie = trie_g + ub * (1 + T * (int64_t)W);
-  BeamFetch pf{kcls_g + ub * T * kBeamMaxTopN, klp_g + ub * T * kBeamMaxTopN, kn_g + ub * T};
-  const float* lrow = logp + ub * T * (int64_t)C;
-  float cut_beta = fmaxf(0.f, beta);
-  if constexpr (kBias) cut_beta += hw.m.max_credit;     // the early cutoff's slack for one step of the automaton
-  beam_init_root(core, tid);
-  if (tid == 0) {
+  // the early cutoff's slack: one label's beta, and with hotwords one step of the automaton
+  __device__ __forceinline__ float cut_slack() const {
+    float slack = fmaxf(0.f, a.beta);
+    if constexpr (kBias) slack += bias.hw.m.max_credit;
+    return slack;
+  }
+  __device__ __forceinline__ void init_root(Lds& s) const {
     s.bonus[0][0] = 0.f; s.term[0][0] = 0.f;
-    if constexpr (kBias) { s.hw.state[0][0] = 0; s.hw.bonus[0][0] = 0.f; }
-    int rc[kLmMaxCtx];
-    float cb[kLmMaxCtx + 1];
-    for (int d = 0; d < kLmMaxCtx; ++d) rc[d] = lm.bos;
-    if (lm.ok) lm_context_sums(lm, lm.bos, rc, cb);
-    for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[0][d][0] = lm.bos;
-    for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[0][d][0] = lm.ok ? cb[d] : 0.f;
+    if constexpr (kBias) bias.init_root(s.hw);
+    lm_chain_root(s, lm, lm.ok);
   }
-  int nbeam = 1, cur = 0;
-  float pblank = 0.f;
-  if (L > 0) {
-    pf.request(0, tid);
-    pblank = lrow[blank];
-  }
-  for (int64_t t = 0; t < L; ++t) {
-    const float lblank = pblank;        // the frame's unpruned blank log-prob (the early cutoff's reference)
+  __device__ __forceinline__ void begin_frame(Lds& s, const BeamFetch& pf, int tid) const {
     if (tid < pf.pn) s.kwid[tid] = (pf.pc != blank && pf.pc >= 0 && (uint32_t)pf.pc < lm.n_classes) ? lm.cls[pf.pc] : -1;
-    if constexpr (kBias) bias_root_steps(hw, s.hw, tid, pf.pn, pf.pc, blank);
-    const int nk = beam_fetch_frame(core, pf, t, L, tid);
-    if (t + 1 < L) pblank = lrow[(t + 1) * (int64_t)C + blank];
-    __syncthreads();
-    // (1) per live prefix: scores, kept index of its last label and of the blank, its parent among the live entries
-    int lastk = -1, pr = -1;
-    float blp = kNegInfB;
-    if (tid < nbeam) {
-      const int last = core.last[cur][tid];
-      const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
-      s.ascore[tid] = as;
-      if constexpr (kBias) core.score[tid] = as + (s.bonus[cur][tid] + s.hw.bonus[cur][tid]);
-      else core.score[tid] = as + s.bonus[cur][tid];
-      int oov = 0;
-      for (int d = 0; d < nctx; ++d) oov |= s.ctx[cur][d][tid] < 0;
-      s.ctx_oov[tid] = oov;
-      beam_lookup(core, cur, nbeam, nk, blank, tid, last, &lastk, &pr, &blp);
+    if constexpr (kBias) bias_root_steps(bias.hw, s.hw, tid, pf.pn, pf.pc, blank);
+  }
+  __device__ __forceinline__ float prefix_bonus(const Lds& s, int cur, int i) const {
+    if constexpr (kBias) return s.bonus[cur][i] + s.hw.bonus[cur][i];
+    else return s.bonus[cur][i];
+  }
+  __device__ __forceinline__ void prefix_extras(Lds& s, int cur, int tid) const {
+    int oov = 0;
+    for (int d = 0; d < lm.nctx; ++d) oov |= s.ctx[cur][d][tid] < 0;
+    s.ctx_oov[tid] = oov;
+  }
+  __device__ __forceinline__ void clear(Group& g, int u) const {
+    g.lpv[u] = 0.f; g.g[u] = 0; g.mm[u] = 0; g.wc[u] = -1; g.act[u] = false;
+    if constexpr (kBias) bias.clear(g.hw, u);
+  }
+  __device__ __forceinline__ void issue(const Lds& s, Group& g, int u, int cur, int p, int k, int c, float) const {
+    g.wc[u] = s.kwid[k];
+    if constexpr (kBias) bias.issue(s.hw, g.hw, u, cur, p, c);
+    if (g.wc[u] >= 0 && !s.ctx_oov[p]) {
+      g.g[u] = g.wc[u];
+      g.lpv[u] = lm.uni[g.wc[u]].x;
+      g.act[u] = lm.nctx > 0;
     }
-    __syncthreads();
-    // the early cutoff: with a full beam, (p, c) contributes nothing where score(p) + logp[c] < min_cutoff
-    const float min_cutoff = nbeam == W ? core.score[W - 1] + lblank - cut_beta : kNegInfB;
-    // (2) "no new label" candidates (acoustic), with the parent's extension by the last label folded in
-    if (tid < nbeam) {
-      const float asc = s.ascore[tid];
-      float nbn = kNegInfB;
-      if (lastk >= 0) {
-        const float lc = core.klp[lastk];
-        if (!(core.score[tid] + lc < min_cutoff)) nbn = lc + core.nb[cur][tid];
-        if (pr >= 0) {
-          if (!(core.score[pr] + lc < min_cutoff))
-            nbn = lae(nbn, lc + (core.last[cur][tid] == core.last[cur][pr] ? core.b[cur][pr] : s.ascore[pr]));
-          atomicOr(&core.merged[pr], 1ull << lastk);
-        }
-      }
-      core.next_b[tid] = blp + asc;
-      core.next_nb[tid] = nbn;
-    }
-    __syncthreads();
-    // (3) candidates with fused scores; the LM probes of kLmGroup extensions per thread are issued together
-    const int ncand = nbeam + nbeam * nk;
-    uint64_t comp[J];
-    float term[J];
-    uint64_t valid = 0;
-#pragma unroll
-    for (int j0 = 0; j0 < J; j0 += kLmGroup) {
-      float am[kLmGroup], lpv[kLmGroup];
-      int64_t g[kLmGroup];
-      int mm[kLmGroup], pp[kLmGroup], wc[kLmGroup];
-      bool act[kLmGroup], ext[kLmGroup];
-      uint64_t hkey[kBias ? kLmGroup : 1];
-      int32_t hchild[kBias ? kLmGroup : 1];
+  }
+  // the group's walks leftward, one context word per round: every probe of a round is loaded before any is compared
+  __device__ __forceinline__ void chain(const Lds& s, Group& g, int cur, const int (&pp)[kLmGroup]) const {
+    for (int d = 0; d < lm.nctx; ++d) {
+      uint64_t key[kLmGroup];
+      uint32_t at[kLmGroup];
+      uint4 v[kLmGroup];
 #pragma unroll
       for (int u = 0; u < kLmGroup; ++u) {
-        const int j = j0 + u;
-        am[u] = kNegInfB; lpv[u] = 0.f; g[u] = 0; mm[u] = 0; pp[u] = 0; wc[u] = -1; act[u] = false; ext[u] = false;
-        if constexpr (kBias) { hkey[u] = host::kHotwordEmptyKey; hchild[u] = -1; }
-        if (j >= J) continue;
-        const int i = tid + j * kSearchThreads;
-        if (i < nbeam) {
-          if constexpr (kBias) am[u] = lae(core.next_b[i], core.next_nb[i]) + (s.bonus[cur][i] + s.hw.bonus[cur][i]);
-          else am[u] = lae(core.next_b[i], core.next_nb[i]) + s.bonus[cur][i];
-        } else if (i < ncand) {
-          const int q = i - nbeam, p = q / nk, k = q - p * nk;
-          const int c = core.kcls[k];
-          pp[u] = p;
-          if (c != blank && !((core.merged[p] >> k) & 1ull) && !(core.score[p] + core.klp[k] < min_cutoff)) {
-            am[u] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
-            ext[u] = am[u] > kNegInfB;
-            wc[u] = s.kwid[k];
-            if constexpr (kBias) {
-              if (ext[u]) {
-                const BiasFirst e = bias_first(hw, s.hw, cur, p, c);
-                hkey[u] = e.key; hchild[u] = e.child;
-              }
-            }
-            if (ext[u] && wc[u] >= 0 && !s.ctx_oov[p]) {
-              g[u] = wc[u];
-              lpv[u] = lm.uni[wc[u]].x;
-              act[u] = nctx > 0;
-            }
-          }
-        }
-      }
-      for (int d = 0; d < nctx; ++d) {
-        uint64_t key[kLmGroup];
-        uint32_t at[kLmGroup];
-        uint4 v[kLmGroup];
-#pragma unroll
-        for (int u = 0; u < kLmGroup; ++u) {
-          if (!act[u]) continue;
-          key[u] = ((uint64_t)g[u] << 32) | (uint32_t)s.ctx[cur][d][pp[u]];
-          at[u] = (uint32_t)lm_hash(key[u]) & lm.mask;
-          v[u] = lm.slot[at[u]];
-        }
-#pragma unroll
-        for (int u = 0; u < kLmGroup; ++u) {
-          if (!act[u]) continue;
-          uint4 hit;
-          const int64_t f = lm_probe_rest(lm, key[u], at[u], v[u], &hit);
-          if (f < 0) {
-            act[u] = false;
-          } else {
-            g[u] = f;
-            lpv[u] = __uint_as_float(hit.z);
-            mm[u] = d + 1;
-          }
-        }
+        if (!g.act[u]) continue;
+        key[u] = ((uint64_t)g.g[u] << 32) | (uint32_t)s.ctx[cur][d][pp[u]];
+        at[u] = (uint32_t)lm_hash(key[u]) & lm.mask;
+        v[u] = lm.slot[at[u]];
       }
 #pragma unroll
       for (int u = 0; u < kLmGroup; ++u) {
-        const int j = j0 + u;
-        if (j >= J) continue;
-        const int i = tid + j * kSearchThreads;
-        float sc = am[u];
-        uint32_t key = 0;
-        term[j] = 0.f;
-        if (i < nbeam) {
-          key = (uint32_t)i << 14;
-        } else if (i < ncand) {
-          const int q = i - nbeam, p = pp[u], k = q - p * nk;
-          key = ((uint32_t)p << 14) | (uint32_t)(core.kcls[k] + 1);
-          if (ext[u]) {
-            const bool oov = wc[u] < 0 || s.ctx_oov[p];
-            const float lmv = oov ? kLmOov : (lpv[u] + s.cb[cur][mm[u]][p]) / kLmLogE;
-            term[j] = alpha * lmv + beta;
-            if constexpr (kBias) {
-              float hd;
-              bias_walk(hw, s.hw, cur, p, k, core.kcls[k], hkey[u], hchild[u], &hd);
-              sc = am[u] + ((s.bonus[cur][p] + term[j]) + (s.hw.bonus[cur][p] + hd));
-            } else {
-              sc = am[u] + (s.bonus[cur][p] + term[j]);
-            }
-          }
+        if (!g.act[u]) continue;
+        uint4 hit;
+        const int64_t f = lm_probe_rest(lm, key[u], at[u], v[u], &hit);
+        if (f < 0) {
+          g.act[u] = false;
+        } else {
+          g.g[u] = f;
+          g.lpv[u] = __uint_as_float(hit.z);
+          g.mm[u] = d + 1;
         }
-        comp[j] = ((uint64_t)desc_bits(sc) << 32) | key;
-        if (sc > kNegInfB) valid |= 1ull << j;
       }
     }
-    // (4) select the W best, (5) compact and order them, write the next beam: the core fields, then the LM's
-    uint64_t prefix, mask;
-    beam_select<J>(core, comp, valid, W, tid, &prefix, &mask);
-    const int nsel =
-        beam_compact<J>(core, comp, valid, prefix, mask, W, tid, [&](uint32_t pos, int j) { s.surv_t[pos] = term[j]; });
-    const int nxt = cur ^ 1;
-    if (tid < nsel) {
-      const int rank = beam_rank(core, nsel, tid);
-      const int i = core.surv_i[tid];
-      if (i < nbeam) {
-        beam_keep_entry(core, cur, nxt, rank, i);
-        s.bonus[nxt][rank] = s.bonus[cur][i]; s.term[nxt][rank] = s.term[cur][i];
-        if constexpr (kBias) { s.hw.state[nxt][rank] = s.hw.state[cur][i]; s.hw.bonus[nxt][rank] = s.hw.bonus[cur][i]; }
-        for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[nxt][d][rank] = s.ctx[cur][d][i];
-        for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[nxt][d][rank] = s.cb[cur][d][i];
-      } else {
-        const int q = i - nbeam, p = q / nk, k = q - p * nk;
-        const int c = core.kcls[k];
-        const float tm = s.surv_t[tid];
-        beam_new_entry(core, cur, nxt, rank, p, c, t, W, trie);
-        core.nb[nxt][rank] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
-        s.bonus[nxt][rank] = s.bonus[cur][p] + tm; s.term[nxt][rank] = tm;
-        if constexpr (kBias) {
-          float hd;
-          const BiasFirst e = bias_first(hw, s.hw, cur, p, c);
-          s.hw.state[nxt][rank] = bias_walk(hw, s.hw, cur, p, k, c, e.key, e.child, &hd);
-          s.hw.bonus[nxt][rank] = s.hw.bonus[cur][p] + hd;
-        }
-        int nc[kLmMaxCtx];
-        float cb[kLmMaxCtx + 1];
-        const int w = s.kwid[k];
-        nc[0] = w;
-        for (int d = 1; d < kLmMaxCtx; ++d) nc[d] = s.ctx[cur][d - 1][p];
-        lm_context_sums(lm, w, nc + 1, cb);
-        for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[nxt][d][rank] = nc[d];
-        for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[nxt][d][rank] = d <= nctx ? cb[d] : 0.f;
-      }
-    }
-    nbeam = nsel;
-    cur = nxt;
-    __syncthreads();
   }
-  if constexpr (kBias) {
-    // end of utterance: an unfinished match gives its provisional credit back, the final entries are re-ranked
-    float f = kNegInfB, am = kNegInfB, fb = 0.f;
-    if (lm.ok && tid < nbeam) {
-      const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
-      int cx[kLmMaxCtx];
-      float cb[kLmMaxCtx + 1];
-      for (int d = 0; d < kLmMaxCtx; ++d) cx[d] = s.ctx[cur][d][tid];
-      for (int d = 0; d <= kLmMaxCtx; ++d) cb[d] = s.cb[cur][d][tid];
-      float sent = lm_score_one(lm, lm.eos, cx, cb);
-      if (core.len[cur][tid] == 0) sent += lm_score_one(lm, lm.bos, cx, cb);
-      fb = s.hw.bonus[cur][tid] + (hw.on ? host::hotword_give_back(hw.m, s.hw.state[cur][tid]) : 0.f);
-      f = as + (s.bonus[cur][tid] + fb);
-      am = as - alpha * sent;
-    }
-    const int fin = bias_rerank(core, s.hw, cur, lm.ok ? nbeam : 0, tid, f, am, fb);
-    beam_write_back(core, fin, nbeam, n_best, T, trie, tokens + ub * (int64_t)n_best * T, n_tokens + ub * n_best, lm.ok, tid);
-    if (tid < n_best) bias_write_scores(s.hw, lm.ok && tid < nbeam, tid, ub * n_best + tid, scores, am_scores, bias_scores);
-    return;
+  __device__ __forceinline__ float finish(const Lds& s, Group& g, int u, int cur, int p, int k, int c, float am, Carry* term) const {
+    const bool oov = g.wc[u] < 0 || s.ctx_oov[p];
+    const float lmv = oov ? kLmOov : (g.lpv[u] + s.cb[cur][g.mm[u]][p]) / kLmLogE;
+    *term = a.alpha * lmv + a.beta;
+    if constexpr (kBias) return am + ((s.bonus[cur][p] + *term) + (s.hw.bonus[cur][p] + bias.delta(s.hw, g.hw, u, cur, p, k, c)));
+    else return am + (s.bonus[cur][p] + *term);
   }
-  beam_write_back(core, cur, nbeam, n_best, T, trie, tokens + ub * (int64_t)n_best * T, n_tokens + ub * n_best, lm.ok, tid);
-  if (tid < n_best) {
-    const int64_t o = ub * n_best + tid;
-    if (lm.ok && tid < nbeam) {
-      const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
-      int cx[kLmMaxCtx];
-      float cb[kLmMaxCtx + 1];
-      for (int d = 0; d < kLmMaxCtx; ++d) cx[d] = s.ctx[cur][d][tid];
-      for (int d = 0; d <= kLmMaxCtx; ++d) cb[d] = s.cb[cur][d][tid];
-      // ctc_decoders' approx_ctc = fused - k beta - alpha sent_lm: the emission terms cancel, the </s> window remains (and the
-      // <s> window of <s>^N </s> for an empty hypothesis)
-      float sent = lm_score_one(lm, lm.eos, cx, cb);
-      if (core.len[cur][tid] == 0) sent += lm_score_one(lm, lm.bos, cx, cb);
-      scores[o] = as + s.bonus[cur][tid];
-      am_scores[o] = as - alpha * sent;
+  static __device__ __forceinline__ void on_keep(Lds& s, uint32_t pos, Carry term) { s.surv_t[pos] = term; }
+  __device__ __forceinline__ void keep_entry(Lds& s, int cur, int nxt, int rank, int i) const {
+    s.bonus[nxt][rank] = s.bonus[cur][i]; s.term[nxt][rank] = s.term[cur][i];
+    if constexpr (kBias) bias.keep_entry(s.hw, cur, nxt, rank, i);
+    lm_chain_copy(s, cur, nxt, rank, i);
+  }
+  __device__ __forceinline__ void new_entry(Lds& s, int cur, int nxt, int rank, int p, int k, int c, int tid) const {
+    const float tm = s.surv_t[tid];
+    s.bonus[nxt][rank] = s.bonus[cur][p] + tm; s.term[nxt][rank] = tm;
+    if constexpr (kBias) bias.new_entry(s.hw, cur, nxt, rank, p, k, c);
+    int nc[kLmMaxCtx];
+    float cb[kLmMaxCtx + 1];
+    lm_chain_push(s, lm, cur, p, s.kwid[k], nc, cb);
+    lm_chain_store(s, nxt, rank, nc, cb, lm.nctx);
+  }
+  // ctc_decoders' approx_ctc = fused - k beta - alpha sent_lm: the emission terms cancel, the sentence-end window remains
+  __device__ __forceinline__ void final_scores(const Lds& s, int cur, int tid, float (&out)[kOuts]) const {
+    const float as = lae(s.core.b[cur][tid], s.core.nb[cur][tid]);
+    const float sent = lm_sentence_end(s, lm, cur, tid);
+    if constexpr (kBias) {
+      const float fb = bias.final_bonus(s.hw, cur, tid);
+      out[0] = as + (s.bonus[cur][tid] + fb);
+      out[2] = fb;
     } else {
-      scores[o] = kNegInfB;
-      am_scores[o] = kNegInfB;
+      out[0] = as + s.bonus[cur][tid];
     }
+    out[1] = as - a.alpha * sent;
   }
-}
-
-// lasr_ctc_beam_decode_bias: the LM-free search with hotword biasing.  core.b / core.nb stay ACOUSTIC, core.score is
-// logaddexp(b, nb) + bonus(prefix), what the beam is ranked by.  With a bank of no phrases every bonus is 0 and each score is
-// the expression beam_search_kernel evaluates, so the result is that kernel's bit for bit.
-struct BeamBiasLds {
-  BeamCore core;
-  float ascore[kBeamMaxWidth];                           // acoustic logaddexp(b, nb) of the current beam
-  BiasLds hw;
 };
-static_assert(sizeof(BeamBiasLds) < 64 * 1024, "static LDS of the biased search");
 
-template <int J>
-__global__ __launch_bounds__(kSearchThreads) void beam_search_bias_kernel(
-    const int32_t* __restrict__ kcls_g, const float* __restrict__ klp_g, const int32_t* __restrict__ kn_g,
-    const int32_t* __restrict__ lens, int64_t T, int C, int blank, int W, int n_best, const void* __restrict__ bias_image,
-    int2* __restrict__ trie_g, int32_t* __restrict__ tokens, int32_t* __restrict__ n_tokens, float* __restrict__ scores,
-    float* __restrict__ am_scores, float* __restrict__ bias_scores) {
-  __shared__ BeamBiasLds s;
-  BeamCore& core = s.core;
-  const int tid = threadIdx.x;
-  const int64_t ub = blockIdx.x;
-  const BiasImg hw = bias_open(bias_image, C, blank);
-  const int64_t L = !hw.ok ? 0 : lens ? min((int64_t)max(lens[ub], 0), T) : T;
-  int2* trie = trie_g + ub * (1 + T * (int64_t)W);
-  BeamFetch pf{kcls_g + ub * T * kBeamMaxTopN, klp_g + ub * T * kBeamMaxTopN, kn_g + ub * T};
-  beam_init_root(core, tid);
-  if (tid == 0) { s.hw.state[0][0] = 0; s.hw.bonus[0][0] = 0.f; }
-  int nbeam = 1, cur = 0;
-  if (L > 0) pf.request(0, tid);
-  for (int64_t t = 0; t < L; ++t) {
-    bias_root_steps(hw, s.hw, tid, pf.pn, pf.pc, blank);
-    const int nk = beam_fetch_frame(core, pf, t, L, tid);
-    __syncthreads();
-    // (1) per live prefix: scores, kept index of its last label and of the blank, its parent among the live entries
-    int lastk = -1, pr = -1;
-    float blp = kNegInfB;
-    if (tid < nbeam) {
-      const int last = core.last[cur][tid];
-      const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
-      s.ascore[tid] = as;
-      core.score[tid] = as + s.hw.bonus[cur][tid];
-      beam_lookup(core, cur, nbeam, nk, blank, tid, last, &lastk, &pr, &blp);
-    }
-    __syncthreads();
-    // (2) "no new label" candidates (acoustic), with the parent's extension by the last label folded in
-    if (tid < nbeam) {
-      float nbn = kNegInfB;
-      if (lastk >= 0) {
-        const float lc = core.klp[lastk];
-        nbn = lc + core.nb[cur][tid];
-        if (pr >= 0) {
-          nbn = lae(nbn, lc + (core.last[cur][tid] == core.last[cur][pr] ? core.b[cur][pr] : s.ascore[pr]));
-          atomicOr(&core.merged[pr], 1ull << lastk);
-        }
-      }
-      core.next_b[tid] = blp + s.ascore[tid];
-      core.next_nb[tid] = nbn;
-    }
-    __syncthreads();
-    // (3) candidates; only finite, unmerged, non-blank extensions are walked, the first probes of kLmGroup of them together
-    const int ncand = nbeam + nbeam * nk;
-    uint64_t comp[J];
-    uint64_t valid = 0;
-#pragma unroll
-    for (int j0 = 0; j0 < J; j0 += kLmGroup) {
-      float sc[kLmGroup];
-      uint32_t ck[kLmGroup];
-      int pp[kLmGroup], kk[kLmGroup];
-      bool ext[kLmGroup];
-      uint64_t hkey[kLmGroup];
-      int32_t hchild[kLmGroup];
-#pragma unroll
-      for (int u = 0; u < kLmGroup; ++u) {
-        const int j = j0 + u;
-        sc[u] = kNegInfB; ck[u] = 0; pp[u] = 0; kk[u] = 0; ext[u] = false; hkey[u] = host::kHotwordEmptyKey; hchild[u] = -1;
-        if (j >= J) continue;
-        const int i = tid + j * kSearchThreads;
-        if (i < nbeam) {
-          sc[u] = lae(core.next_b[i], core.next_nb[i]) + s.hw.bonus[cur][i];
-          ck[u] = (uint32_t)i << 14;
-        } else if (i < ncand) {
-          const int q = i - nbeam, p = q / nk, k = q - p * nk;
-          const int c = core.kcls[k];
-          pp[u] = p; kk[u] = k;
-          ck[u] = ((uint32_t)p << 14) | (uint32_t)(c + 1);
-          if (c != blank && !((core.merged[p] >> k) & 1ull)) {
-            sc[u] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
-            ext[u] = sc[u] > kNegInfB;
-            if (ext[u]) {
-              const BiasFirst e = bias_first(hw, s.hw, cur, p, c);
-              hkey[u] = e.key; hchild[u] = e.child;
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kLmGroup; ++u) {
-        const int j = j0 + u;
-        if (j >= J) continue;
-        if (ext[u]) {
-          float hd;
-          bias_walk(hw, s.hw, cur, pp[u], kk[u], core.kcls[kk[u]], hkey[u], hchild[u], &hd);
-          sc[u] = sc[u] + (s.hw.bonus[cur][pp[u]] + hd);
-        }
-        comp[j] = ((uint64_t)desc_bits(sc[u]) << 32) | ck[u];
-        if (sc[u] > kNegInfB) valid |= 1ull << j;
-      }
-    }
-    // (4) select the W best, (5) compact and order them, write the next beam: the core fields, then the automaton's
-    uint64_t prefix, mask;
-    beam_select<J>(core, comp, valid, W, tid, &prefix, &mask);
-    const int nsel = beam_compact<J>(core, comp, valid, prefix, mask, W, tid, [](uint32_t, int) {});
-    const int nxt = cur ^ 1;
-    if (tid < nsel) {
-      const int rank = beam_rank(core, nsel, tid);
-      const int i = core.surv_i[tid];
-      if (i < nbeam) {
-        beam_keep_entry(core, cur, nxt, rank, i);
-        s.hw.state[nxt][rank] = s.hw.state[cur][i]; s.hw.bonus[nxt][rank] = s.hw.bonus[cur][i];
-      } else {
-        const int q = i - nbeam, p = q / nk, k = q - p * nk;
-        const int c = core.kcls[k];
-        beam_new_entry(core, cur, nxt, rank, p, c, t, W, trie);
-        core.nb[nxt][rank] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
-        float hd;
-        const BiasFirst e = bias_first(hw, s.hw, cur, p, c);
-        s.hw.state[nxt][rank] = bias_walk(hw, s.hw, cur, p, k, c, e.key, e.child, &hd);
-        s.hw.bonus[nxt][rank] = s.hw.bonus[cur][p] + hd;
-      }
-    }
-    nbeam = nsel;
-    cur = nxt;
-    __syncthreads();
-  }
-  // end of utterance: an unfinished match gives its provisional credit back, the final entries are re-ranked
-  float f = kNegInfB, am = kNegInfB, fb = 0.f;
-  if (hw.ok && tid < nbeam) {
-    am = lae(core.b[cur][tid], core.nb[cur][tid]);
-    fb = s.hw.bonus[cur][tid] + (hw.on ? host::hotword_give_back(hw.m, s.hw.state[cur][tid]) : 0.f);
-    f = am + fb;
-  }
-  const int fin = bias_rerank(core, s.hw, cur, hw.ok ? nbeam : 0, tid, f, am, fb);
-  beam_write_back(core, fin, nbeam, n_best, T, trie, tokens + ub * (int64_t)n_best * T, n_tokens + ub * n_best, hw.ok, tid);
-  if (tid < n_best) bias_write_scores(s.hw, hw.ok && tid < nbeam, tid, ub * n_best + tid, scores, am_scores, bias_scores);
-}
-
-// ================================================================== with a word n-gram LM and its lexicon ==============
-// lasr_ctc_beam_decode_wlm: the same search with a word-level scorer (include/lasr.h states the contract).  Each entry carries
-// the lexicon trie node of its unfinished word; p + c exists only where that node has a child c, p + space only where it is
-// a complete word, and the LM scores a word when the space after it is emitted.  What a prefix needs in every frame is
-// worked out once, when its entry is created: its node, the LM id of the word the node spells and `sterm`, the term the
-// space after that word adds (alpha * lm(word | context) + beta) - also the end-of-utterance term.  A frame then costs one
-// lexicon probe per (prefix, kept label) candidate, kLmGroup of them in flight per thread, and one n-gram chain per NEW prefix.
+// ------------------------------------------------------------------ word n-gram LM and its lexicon ---------------------
+// lasr_ctc_beam_decode_wlm: each entry carries the lexicon trie node of its unfinished word; p + c exists only where that node
+// has a child c, p + space only where it is a complete word, and the LM scores a word when the space after it is emitted.  What
+// a prefix needs in every frame is worked out once, when its entry is created: its node, the LM id of the word the node spells
+// and `sterm`, the term the space after that word adds (alpha * lm(word | context) + beta) - also the end-of-utterance term.  A
+// frame then costs one lexicon probe per (prefix, kept label) candidate, kLmGroup of them in flight per thread, and one n-gram
+// chain per NEW prefix.
 struct WlmImg {
   LmImg lm;
   const uint4* edge;          // ArpaLexEdge as (key lo, key hi, child, reserved)
@@ -1236,58 +958,154 @@ __device__ __forceinline__ int wlm_child_rest(const WlmImg& w, uint64_t key, uin
   }
 }
 
-// core.b / core.nb stay ACOUSTIC and core.score is the fused score, as in BeamLmLds
-struct BeamWlmLds {
-  BeamCore core;
-  int surv_n[kBeamMaxWidth];                             // lexicon node of a surviving extension (beside core.surv_i)
-  int lex[2][kBeamMaxWidth], wid[2][kBeamMaxWidth];      // trie node of the unfinished word; the LM word it spells, or -1
-  float bonus[2][kBeamMaxWidth], sterm[2][kBeamMaxWidth];// sum of the terms of the prefix's spaces; the next space's term
-  int ctx[2][kLmMaxCtx][kBeamMaxWidth];                  // LM ids of the last N-1 finished words, nearest first
-  float cb[2][kLmMaxCtx + 1][kBeamMaxWidth];             // cb[j]: log10 backoffs of the stored contexts longer than j words
-  float ascore[kBeamMaxWidth];                           // acoustic logaddexp(b, nb) of the current beam
-  float fin[kBeamMaxWidth], fin_am[kBeamMaxWidth];       // final fused score (end term included); the ranked acoustic scores
+struct WlmScorer {
+  using Args = LmArgs;
+  struct Lds {
+    BeamCore core;
+    int surv_n[kBeamMaxWidth];                             // lexicon node of a surviving extension (beside core.surv_i)
+    int lex[2][kBeamMaxWidth], wid[2][kBeamMaxWidth];      // trie node of the unfinished word; the LM word it spells, or -1
+    float bonus[2][kBeamMaxWidth], sterm[2][kBeamMaxWidth];// sum of the terms of the prefix's spaces; the next space's term
+    int ctx[2][kLmMaxCtx][kBeamMaxWidth];                  // the last N-1 finished words
+    float cb[2][kLmMaxCtx + 1][kBeamMaxWidth];
+    float ascore[kBeamMaxWidth];                           // acoustic logaddexp(b, nb) of the current beam
+    float fin[2][kBeamMaxWidth];                           // the re-ranked final score (end term included) and am_scores values
+  };
+  using Carry = int;                                       // the lexicon node the extension reaches
+  static constexpr Carry kNoCarry = -1;
+  static constexpr bool kScored = true, kCutoff = true, kRerank = true;
+  static constexpr int kOuts = 2;
+  static constexpr const char* kName = "beam_search_wlm_kernel";
+  struct Group {
+    float sc[kLmGroup];
+    uint64_t key[kLmGroup];
+    uint32_t at[kLmGroup];
+    uint4 v[kLmGroup];
+    int child[kLmGroup];
+    bool probe[kLmGroup];
+  };
+  WlmImg wl;
+  Args a;
+  const float* logp;
+  static bool args_set(const Args& a) { return a.image && a.am_scores; }
+  static __device__ __forceinline__ float* ascore(Lds& s) { return s.ascore; }
+  static __device__ __forceinline__ auto& fin(Lds& s) { return s.fin; }
+  __device__ __forceinline__ float* extra_out(int) const { return a.am_scores; }
+  __device__ __forceinline__ bool open(const BeamIo& io, const Args& args) {
+    a = args; logp = args.logp;
+    wl = wlm_open(a.image);
+    wl.lm.ok = wl.lm.ok && wl.space >= 0 && wl.space < io.C && wl.space != io.blank;
+    return wl.lm.ok;
+  }
+  __device__ __forceinline__ float cut_slack() const { return fmaxf(0.f, a.beta); }
+  __device__ __forceinline__ void init_root(Lds& s) const {
+    s.bonus[0][0] = 0.f; s.sterm[0][0] = 0.f; s.lex[0][0] = 0; s.wid[0][0] = -1;
+    lm_chain_root(s, wl.lm, wl.lm.ok);
+  }
+  __device__ __forceinline__ void begin_frame(Lds&, const BeamFetch&, int) const {}
+  __device__ __forceinline__ float prefix_bonus(const Lds& s, int cur, int i) const { return s.bonus[cur][i]; }
+  __device__ __forceinline__ void prefix_extras(Lds&, int, int) const {}
+  __device__ __forceinline__ void clear(Group& g, int u) const { g.sc[u] = kNegInfB; g.child[u] = -1; g.probe[u] = false; }
+  __device__ __forceinline__ void issue(const Lds& s, Group& g, int u, int cur, int p, int, int c, float am) const {
+    if (c == wl.space) {
+      if (s.wid[cur][p] >= 0) {              // the node is a complete word: the space scores it and returns to the root
+        g.child[u] = 0;
+        g.sc[u] = am + (s.bonus[cur][p] + s.sterm[cur][p]);
+      }
+    } else {
+      g.sc[u] = am + s.bonus[cur][p];
+      g.key[u] = ((uint64_t)(uint32_t)s.lex[cur][p] << 32) | (uint32_t)c;
+      g.at[u] = (uint32_t)lm_hash(g.key[u]) & wl.emask;
+      g.v[u] = wl.edge[g.at[u]];
+      g.probe[u] = true;
+    }
+  }
+  __device__ __forceinline__ void chain(const Lds&, Group&, int, const int (&)[kLmGroup]) const {}
+  __device__ __forceinline__ float finish(const Lds&, Group& g, int u, int, int, int, int, float, Carry* child) const {
+    if (g.probe[u]) {
+      g.child[u] = wlm_child_rest(wl, g.key[u], g.at[u], g.v[u]);
+      if (g.child[u] < 0) g.sc[u] = kNegInfB;      // no such word in the lexicon
+    }
+    *child = g.child[u];
+    return g.sc[u];
+  }
+  static __device__ __forceinline__ void on_keep(Lds& s, uint32_t pos, Carry child) { s.surv_n[pos] = child; }
+  __device__ __forceinline__ void keep_entry(Lds& s, int cur, int nxt, int rank, int i) const {
+    s.lex[nxt][rank] = s.lex[cur][i]; s.wid[nxt][rank] = s.wid[cur][i];
+    s.bonus[nxt][rank] = s.bonus[cur][i]; s.sterm[nxt][rank] = s.sterm[cur][i];
+    lm_chain_copy(s, cur, nxt, rank, i);
+  }
+  __device__ __forceinline__ void new_entry(Lds& s, int cur, int nxt, int rank, int p, int, int c, int tid) const {
+    int nc[kLmMaxCtx];
+    float cb[kLmMaxCtx + 1];
+    if (c == wl.space) {
+      // the word of p's node is finished: it joins the context, the trie state returns to the root
+      lm_chain_push(s, wl.lm, cur, p, s.wid[cur][p], nc, cb);
+      s.lex[nxt][rank] = 0; s.wid[nxt][rank] = -1;
+      s.bonus[nxt][rank] = s.bonus[cur][p] + s.sterm[cur][p]; s.sterm[nxt][rank] = 0.f;
+    } else {
+      const int node = s.surv_n[tid];
+      const int w = wl.node_word[node];
+      lm_chain_load(s, cur, p, nc, cb);
+      s.lex[nxt][rank] = node; s.wid[nxt][rank] = w;
+      s.bonus[nxt][rank] = s.bonus[cur][p];
+      s.sterm[nxt][rank] = w >= 0 ? a.alpha * lm_score_one(wl.lm, w, nc, cb) + a.beta : 0.f;
+    }
+    lm_chain_store(s, nxt, rank, nc, cb, wl.lm.nctx);
+  }
+  // end of utterance: an unfinished last word is scored (OOV_SCORE where the node is no complete word)
+  __device__ __forceinline__ void final_scores(const Lds& s, int cur, int tid, float (&out)[kOuts]) const {
+    const float as = lae(s.core.b[cur][tid], s.core.nb[cur][tid]);
+    float f = as + s.bonus[cur][tid];
+    if (s.core.len[cur][tid] > 0 && s.core.last[cur][tid] != wl.space)
+      f += s.wid[cur][tid] >= 0 ? s.sterm[cur][tid] : a.alpha * kLmOov + a.beta;
+    out[0] = f; out[1] = as;
+  }
 };
-static_assert(sizeof(BeamWlmLds) < 64 * 1024, "static LDS of the word-LM search");
 
-template <int J>
-__global__ __launch_bounds__(kSearchThreads) void beam_search_wlm_kernel(
-    const float* __restrict__ logp, const int32_t* __restrict__ kcls_g, const float* __restrict__ klp_g,
-    const int32_t* __restrict__ kn_g, const int32_t* __restrict__ lens, int64_t T, int C, int blank, int W, int n_best,
-    const void* __restrict__ image, float alpha, float beta, int2* __restrict__ trie_g, int32_t* __restrict__ tokens,
-    int32_t* __restrict__ n_tokens, float* __restrict__ scores, float* __restrict__ am_scores) {
-  __shared__ BeamWlmLds s;
+static_assert(sizeof(BeamLmBiasLds) < 64 * 1024 && sizeof(WlmScorer::Lds) < 64 * 1024, "static LDS of the widest searches");
+
+// ------------------------------------------------------------------ the search: one frame loop -------------------------
+// The kept lists come as kernel parameters of their own, const and __restrict__, not inside BeamIo: only so does the compiler
+// know that a frame's trie stores leave them alone, and the next frame's count, which every thread reads, is prefetched by a
+// scalar load.  As a vector load it is waited for on the spot, and the kept list's prefetch with it.
+template <int J, class Scorer>
+__global__ __launch_bounds__(kSearchThreads) void beam_search_kernel(const int32_t* __restrict__ kcls_g,
+                                                                     const float* __restrict__ klp_g,
+                                                                     const int32_t* __restrict__ kn_g, const BeamIo io,
+                                                                     const typename Scorer::Args sargs) {
+  __shared__ typename Scorer::Lds s;
   BeamCore& core = s.core;
+  float* const asc = Scorer::ascore(s);     // acoustic logaddexp(b, nb) of the current beam: core.score itself without a scorer
   const int tid = threadIdx.x;
   const int64_t ub = blockIdx.x;
-  const WlmImg wl = wlm_open(image);
-  const LmImg& lm = wl.lm;
-  const bool ok = lm.ok && wl.space >= 0 && wl.space < C && wl.space != blank;
-  const int64_t L = !ok ? 0 : lens ? min((int64_t)max(lens[ub], 0), T) : T;
-  const int nctx = lm.nctx, space = wl.space;
-  int2* trie = trie_g + ub * (1 + T * (int64_t)W);
+  const int64_t T = io.T;
+  const int blank = io.blank, W = io.W, n_best = io.n_best;
+  Scorer sc;
+  const bool ok = sc.open(io, sargs);       // a wrong image: no frames, empty slots
+  const int64_t L = !ok ? 0 : io.lens ? min((int64_t)max(io.lens[ub], 0), T) : T;
+  int2* trie = io.trie + ub * (1 + T * (int64_t)W);
   BeamFetch pf{kcls_g + ub * T * kBeamMaxTopN, klp_g + ub * T * kBeamMaxTopN, kn_g + ub * T};
-  const float* lrow = logp + ub * T * (int64_t)C;
-  const float cut_beta = fmaxf(0.f, beta);
   beam_init_root(core, tid);
-  if (tid == 0) {
-    s.bonus[0][0] = 0.f; s.sterm[0][0] = 0.f; s.lex[0][0] = 0; s.wid[0][0] = -1;
-    int rc[kLmMaxCtx];
-    float cb[kLmMaxCtx + 1];
-    for (int d = 0; d < kLmMaxCtx; ++d) rc[d] = lm.bos;
-    if (ok) lm_context_sums(lm, lm.bos, rc, cb);
-    for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[0][d][0] = lm.bos;
-    for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[0][d][0] = ok ? cb[d] : 0.f;
-  }
+  if (tid == 0) sc.init_root(s);
   int nbeam = 1, cur = 0;
-  float pblank = 0.f;
+  // the early cutoff's reference, the frame's unpruned blank log-prob, is fetched a frame ahead like the kept list
+  [[maybe_unused]] const float* lrow = nullptr;
+  [[maybe_unused]] float pblank = 0.f, cut_slack = 0.f;
+  if constexpr (Scorer::kCutoff) {
+    lrow = sc.logp + ub * T * (int64_t)io.C;
+    cut_slack = sc.cut_slack();
+  }
   if (L > 0) {
     pf.request(0, tid);
-    pblank = lrow[blank];
+    if constexpr (Scorer::kCutoff) pblank = lrow[blank];
   }
   for (int64_t t = 0; t < L; ++t) {
-    const float lblank = pblank;        // the frame's unpruned blank log-prob (the early cutoff's reference)
+    [[maybe_unused]] const float lblank = pblank;
+    sc.begin_frame(s, pf, tid);
     const int nk = beam_fetch_frame(core, pf, t, L, tid);
-    if (t + 1 < L) pblank = lrow[(t + 1) * (int64_t)C + blank];
+    if constexpr (Scorer::kCutoff) {
+      if (t + 1 < L) pblank = lrow[(t + 1) * (int64_t)io.C + blank];
+    }
     __syncthreads();
     // (1) per live prefix: scores, kept index of its last label and of the blank, its parent among the live entries
     int lastk = -1, pr = -1;
@@ -1295,162 +1113,225 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_wlm_kernel(
     if (tid < nbeam) {
       const int last = core.last[cur][tid];
       const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
-      s.ascore[tid] = as;
-      core.score[tid] = as + s.bonus[cur][tid];
+      asc[tid] = as;
+      if constexpr (Scorer::kScored) {
+        core.score[tid] = as + sc.prefix_bonus(s, cur, tid);
+        sc.prefix_extras(s, cur, tid);
+      }
       beam_lookup(core, cur, nbeam, nk, blank, tid, last, &lastk, &pr, &blp);
     }
     __syncthreads();
-    const float min_cutoff = nbeam == W ? core.score[W - 1] + lblank - cut_beta : kNegInfB;
-    // (2) "no new label" candidates (acoustic), with the parent's extension by the last label folded in: a live prefix
-    // came through the lexicon, so that extension exists
+    // the early cutoff: with a full beam, (p, c) contributes nothing where score(p) + logp[c] < min_cutoff
+    [[maybe_unused]] float min_cutoff = kNegInfB;
+    if constexpr (Scorer::kCutoff) min_cutoff = nbeam == W ? core.score[W - 1] + lblank - cut_slack : kNegInfB;
+    auto cut = [&](int p, float lc) {
+      if constexpr (Scorer::kCutoff) return core.score[p] + lc < min_cutoff;
+      else return false;
+    };
+    // (2) "no new label" candidates (acoustic), with the parent's extension by the last label folded in
     if (tid < nbeam) {
-      const float asc = s.ascore[tid];
+      const float as = asc[tid];
       float nbn = kNegInfB;
       if (lastk >= 0) {
         const float lc = core.klp[lastk];
-        if (!(core.score[tid] + lc < min_cutoff)) nbn = lc + core.nb[cur][tid];
+        if (!cut(tid, lc)) nbn = lc + core.nb[cur][tid];
         if (pr >= 0) {
-          if (!(core.score[pr] + lc < min_cutoff))
-            nbn = lae(nbn, lc + (core.last[cur][tid] == core.last[cur][pr] ? core.b[cur][pr] : s.ascore[pr]));
+          if (!cut(pr, lc)) nbn = lae(nbn, lc + (core.last[cur][tid] == core.last[cur][pr] ? core.b[cur][pr] : asc[pr]));
           atomicOr(&core.merged[pr], 1ull << lastk);
         }
       }
-      core.next_b[tid] = blp + asc;
+      core.next_b[tid] = blp + as;
       core.next_nb[tid] = nbn;
     }
     __syncthreads();
-    // (3) candidates with fused scores; the lexicon probes of kLmGroup extensions per thread are issued together
+    // (3) candidates: i < nbeam "no new label" of entry i, then nbeam * nk extensions (p, k); composite = score desc, key
+    // asc.  The scorer's probes of kLmGroup extensions per thread are issued together, then consumed.
     const int ncand = nbeam + nbeam * nk;
     uint64_t comp[J];
-    int child[J];
+    typename Scorer::Carry carry[J];
     uint64_t valid = 0;
 #pragma unroll
     for (int j0 = 0; j0 < J; j0 += kLmGroup) {
-      float sc[kLmGroup];
-      uint64_t key[kLmGroup];
-      uint32_t at[kLmGroup], ck[kLmGroup];
-      uint4 v[kLmGroup];
-      bool probe[kLmGroup];
+      typename Scorer::Group g;
+      float am[kLmGroup];
+      uint32_t ck[kLmGroup];
+      int pp[kLmGroup], kk[kLmGroup];
+      bool ext[kLmGroup];
 #pragma unroll
       for (int u = 0; u < kLmGroup; ++u) {
         const int j = j0 + u;
-        sc[u] = kNegInfB; ck[u] = 0; probe[u] = false;
+        am[u] = kNegInfB; ck[u] = 0; pp[u] = 0; kk[u] = 0; ext[u] = false;
+        sc.clear(g, u);
         if (j >= J) continue;
-        child[j] = -1;
         const int i = tid + j * kSearchThreads;
         if (i < nbeam) {
-          sc[u] = lae(core.next_b[i], core.next_nb[i]) + s.bonus[cur][i];
+          am[u] = lae(core.next_b[i], core.next_nb[i]);
+          if constexpr (Scorer::kScored) am[u] = am[u] + sc.prefix_bonus(s, cur, i);
           ck[u] = (uint32_t)i << 14;
         } else if (i < ncand) {
           const int q = i - nbeam, p = q / nk, k = q - p * nk;
           const int c = core.kcls[k];
+          pp[u] = p; kk[u] = k;
           ck[u] = ((uint32_t)p << 14) | (uint32_t)(c + 1);
-          if (c != blank && !((core.merged[p] >> k) & 1ull) && !(core.score[p] + core.klp[k] < min_cutoff)) {
-            const float am = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
-            if (c == space) {
-              if (s.wid[cur][p] >= 0) {            // the node is a complete word: the space scores it and returns to the root
-                child[j] = 0;
-                sc[u] = am + (s.bonus[cur][p] + s.sterm[cur][p]);
-              }
-            } else if (am > kNegInfB) {
-              sc[u] = am + s.bonus[cur][p];
-              key[u] = ((uint64_t)(uint32_t)s.lex[cur][p] << 32) | (uint32_t)c;
-              at[u] = (uint32_t)lm_hash(key[u]) & wl.emask;
-              v[u] = wl.edge[at[u]];
-              probe[u] = true;
-            }
+          if (c != blank && !((core.merged[p] >> k) & 1ull) && !cut(p, core.klp[k])) {
+            am[u] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : asc[p]);
+            ext[u] = am[u] > kNegInfB;        // only finite, unmerged, non-blank extensions go to the scorer
+            if (ext[u]) sc.issue(s, g, u, cur, p, k, c, am[u]);
           }
         }
       }
+      sc.chain(s, g, cur, pp);
 #pragma unroll
       for (int u = 0; u < kLmGroup; ++u) {
         const int j = j0 + u;
         if (j >= J) continue;
-        if (probe[u]) {
-          child[j] = wlm_child_rest(wl, key[u], at[u], v[u]);
-          if (child[j] < 0) sc[u] = kNegInfB;      // no such word in the lexicon
-        }
-        comp[j] = ((uint64_t)desc_bits(sc[u]) << 32) | ck[u];
-        if (sc[u] > kNegInfB) valid |= 1ull << j;
+        float v = am[u];
+        carry[j] = Scorer::kNoCarry;
+        if (ext[u]) v = sc.finish(s, g, u, cur, pp[u], kk[u], core.kcls[kk[u]], am[u], &carry[j]);
+        comp[j] = ((uint64_t)desc_bits(v) << 32) | ck[u];
+        if (v > kNegInfB) valid |= 1ull << j;
       }
     }
-    // (4) select the W best, (5) compact and order them, write the next beam: the core fields, then the lexicon's and the LM's
+    // (4) select the W best, (5) compact and order them, write the next beam: the core fields, then the scorer's
     uint64_t prefix, mask;
     beam_select<J>(core, comp, valid, W, tid, &prefix, &mask);
-    const int nsel =
-        beam_compact<J>(core, comp, valid, prefix, mask, W, tid, [&](uint32_t pos, int j) { s.surv_n[pos] = child[j]; });
+    const int nsel = beam_compact<J>(core, comp, valid, prefix, mask, W, tid,
+                                     [&](uint32_t pos, int j) { Scorer::on_keep(s, pos, carry[j]); });
     const int nxt = cur ^ 1;
     if (tid < nsel) {
       const int rank = beam_rank(core, nsel, tid);
       const int i = core.surv_i[tid];
       if (i < nbeam) {
         beam_keep_entry(core, cur, nxt, rank, i);
-        s.lex[nxt][rank] = s.lex[cur][i]; s.wid[nxt][rank] = s.wid[cur][i];
-        s.bonus[nxt][rank] = s.bonus[cur][i]; s.sterm[nxt][rank] = s.sterm[cur][i];
-        for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[nxt][d][rank] = s.ctx[cur][d][i];
-        for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[nxt][d][rank] = s.cb[cur][d][i];
+        sc.keep_entry(s, cur, nxt, rank, i);
       } else {
         const int q = i - nbeam, p = q / nk, k = q - p * nk;
         const int c = core.kcls[k];
         beam_new_entry(core, cur, nxt, rank, p, c, t, W, trie);
-        core.nb[nxt][rank] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : s.ascore[p]);
-        int nc[kLmMaxCtx];
-        float cb[kLmMaxCtx + 1];
-        if (c == space) {
-          // the word of p's node is finished: it joins the context, the trie state returns to the root
-          const int w = s.wid[cur][p];
-          nc[0] = w;
-          for (int d = 1; d < kLmMaxCtx; ++d) nc[d] = s.ctx[cur][d - 1][p];
-          lm_context_sums(lm, w, nc + 1, cb);
-          for (int d = nctx + 1; d <= kLmMaxCtx; ++d) cb[d] = 0.f;
-          s.lex[nxt][rank] = 0; s.wid[nxt][rank] = -1;
-          s.bonus[nxt][rank] = s.bonus[cur][p] + s.sterm[cur][p]; s.sterm[nxt][rank] = 0.f;
-        } else {
-          const int node = s.surv_n[tid];
-          const int w = wl.node_word[node];
-          for (int d = 0; d < kLmMaxCtx; ++d) nc[d] = s.ctx[cur][d][p];
-          for (int d = 0; d <= kLmMaxCtx; ++d) cb[d] = s.cb[cur][d][p];
-          s.lex[nxt][rank] = node; s.wid[nxt][rank] = w;
-          s.bonus[nxt][rank] = s.bonus[cur][p];
-          s.sterm[nxt][rank] = w >= 0 ? alpha * lm_score_one(lm, w, nc, cb) + beta : 0.f;
-        }
-        for (int d = 0; d < kLmMaxCtx; ++d) s.ctx[nxt][d][rank] = nc[d];
-        for (int d = 0; d <= kLmMaxCtx; ++d) s.cb[nxt][d][rank] = cb[d];
+        core.nb[nxt][rank] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : asc[p]);
+        sc.new_entry(s, cur, nxt, rank, p, k, c, tid);
       }
     }
     nbeam = nsel;
     cur = nxt;
     __syncthreads();
   }
-  // end of utterance: an unfinished last word is scored (OOV_SCORE where the node is no complete word), then the final
-  // entries are re-ranked by a counting rank, ties by their order before the term, into the other half of the beam
-  if (tid < nbeam) {
-    const float as = lae(core.b[cur][tid], core.nb[cur][tid]);
-    float f = as + s.bonus[cur][tid];
-    if (core.len[cur][tid] > 0 && core.last[cur][tid] != space)
-      f += s.wid[cur][tid] >= 0 ? s.sterm[cur][tid] : alpha * kLmOov + beta;
-    s.ascore[tid] = as;
-    core.score[tid] = f;
+  // end of utterance: the scorer's final values of each entry, re-ranked where its end term can change the order
+  const bool have = ok && tid < nbeam;
+  float out[Scorer::kOuts];
+#pragma unroll
+  for (int n = 0; n < Scorer::kOuts; ++n) out[n] = n < 2 ? kNegInfB : 0.f;      // an empty slot: scores -inf, bias_scores 0
+  int src = cur;
+  if constexpr (Scorer::kRerank) {
+    if (have) sc.final_scores(s, cur, tid, out);
+    src = beam_final_rerank(core, Scorer::fin(s), cur, ok ? nbeam : 0, tid, out);
   }
-  __syncthreads();
-  const int fin = cur ^ 1;
-  if (tid < nbeam) {
-    const float f = core.score[tid];
-    int rank = 0;
-    for (int r = 0; r < nbeam; ++r) {
-      const float g = core.score[r];
-      rank += g > f || (g == f && r < tid);
-    }
-    core.node[fin][rank] = core.node[cur][tid]; core.len[fin][rank] = core.len[cur][tid];
-    s.fin[rank] = f; s.fin_am[rank] = s.ascore[tid];
-  }
-  beam_write_back(core, fin, nbeam, n_best, T, trie, tokens + ub * (int64_t)n_best * T, n_tokens + ub * n_best, ok, tid);
+  beam_write_back(core, src, nbeam, n_best, T, trie, io.tokens + ub * (int64_t)n_best * T, io.n_tokens + ub * n_best, ok, tid);
   if (tid < n_best) {
     const int64_t o = ub * n_best + tid;
-    const bool have = ok && tid < nbeam;
-    scores[o] = have ? s.fin[tid] : kNegInfB;
-    am_scores[o] = have ? s.fin_am[tid] : kNegInfB;
+    if constexpr (Scorer::kRerank) {
+#pragma unroll
+      for (int n = 0; n < Scorer::kOuts; ++n)
+        if (have) out[n] = Scorer::fin(s)[n][tid];
+    } else {
+      if (have) sc.final_scores(s, cur, tid, out);
+    }
+    io.scores[o] = out[0];
+#pragma unroll
+    for (int n = 1; n < Scorer::kOuts; ++n) sc.extra_out(n)[o] = out[n];
   }
+}
+
+// ------------------------------------------------------------------ host side -------------------------------------------
+bool beam_shape_ok(int64_t B, int64_t T, int64_t C, int W, int topn) {
+  return B >= 1 && T >= 1 && C >= 1 && C <= kBeamMaxClasses && W >= 1 && W <= kBeamMaxWidth && topn >= 1 &&
+         topn <= kBeamMaxTopN && B * T <= 0x7fffffffLL && 1 + T * (int64_t)W <= 0x7fffffffLL;
+}
+
+struct BeamWs {
+  size_t kcls, klp, kn, trie, total;
+};
+
+BeamWs beam_ws(int64_t B, int64_t T, int64_t W) {
+  BeamWs w;
+  const size_t frames = (size_t)(B * T);
+  w.kcls = 0;
+  w.klp = align_up(w.kcls + frames * kBeamMaxTopN * sizeof(int32_t), 256);
+  w.kn = align_up(w.klp + frames * kBeamMaxTopN * sizeof(float), 256);
+  w.trie = align_up(w.kn + frames * sizeof(int32_t), 256);
+  w.total = align_up(w.trie + (size_t)B * (size_t)(1 + T * W) * sizeof(int2), 256);
+  return w;
+}
+
+// the arguments every decoder takes, as `who` (the exported function) received them
+struct BeamArgs {
+  const char* who;
+  const float* logp;
+  const int32_t* lens;
+  int64_t B, T, C;
+  int blank, beam_width, cutoff_top_n;
+  float cutoff_prob;
+  int n_best;
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+};
+
+// the value checks every decoder makes; ptrs_ok: every pointer the caller requires is set
+int beam_check_args(const BeamArgs& a, bool ptrs_ok) {
+  LASR_CHECK_ARG(ptrs_ok, "%s: null pointer", a.who);
+  LASR_CHECK_ARG(a.n_best >= 1 && a.n_best <= a.beam_width, "%s: n_best %d outside [1, beam_width %d]", a.who, a.n_best,
+                 a.beam_width);
+  LASR_CHECK_ARG(a.cutoff_prob > 0.f && a.cutoff_prob <= 1.f, "%s: cutoff_prob %g outside (0, 1]", a.who, (double)a.cutoff_prob);
+  LASR_CHECK_ARG(a.C >= 1 && a.blank >= 0 && a.blank < a.C, "%s: blank %d outside [0, C = %lld)", a.who, a.blank, (long long)a.C);
+  return 0;
+}
+
+// Checks the shape and the workspace, carves it, launches the prune kernel and then search(J, grid, stream, kc, kl, kn, trie)
+// with J, the candidates per thread, as a std::integral_constant: the caller launches its kernel's instantiation.
+template <class Search>
+int beam_launch(const BeamArgs& a, const char* search_name, Search search) {
+  LASR_CHECK_SHAPE(beam_shape_ok(a.B, a.T, a.C, a.beam_width, a.cutoff_top_n),
+                   "%s: B %lld T %lld C %lld beam_width %d cutoff_top_n %d outside the supported range "
+                   "(C <= %d, beam_width 1..%d, cutoff_top_n 1..%d)", a.who, (long long)a.B, (long long)a.T, (long long)a.C,
+                   a.beam_width, a.cutoff_top_n, kBeamMaxClasses, kBeamMaxWidth, kBeamMaxTopN);
+  const BeamWs w = beam_ws(a.B, a.T, a.beam_width);
+  if (a.workspace_bytes < w.total)
+    return fail(LASR_E_WORKSPACE, "%s: workspace %zu < %zu bytes", a.who, a.workspace_bytes, w.total);
+  char* ws = static_cast<char*>(a.workspace);
+  int32_t* kc = reinterpret_cast<int32_t*>(ws + w.kcls);
+  float* kl = reinterpret_cast<float*>(ws + w.klp);
+  int32_t* kn = reinterpret_cast<int32_t*>(ws + w.kn);
+  int2* trie = reinterpret_cast<int2*>(ws + w.trie);
+  hipStream_t st = as_stream(a.stream);
+  hipLaunchKernelGGL(beam_prune_kernel, dim3((unsigned)(a.B * a.T)), dim3(64), 0, st, a.logp, a.lens, a.T, (int)a.C,
+                     a.cutoff_top_n, a.cutoff_prob, kc, kl, kn);
+  LASR_LAUNCH_CHECK("beam_prune_kernel");
+  // candidates per frame: beam_width "no new label" entries + beam_width * kept labels, J per thread
+  const int K = (int)(a.C < a.cutoff_top_n ? a.C : a.cutoff_top_n);
+  const int per = (int)cdiv((int64_t)a.beam_width * (K + 1), kSearchThreads);
+  const dim3 grid((unsigned)a.B);
+  if (per <= 1) search(std::integral_constant<int, 1>{}, grid, st, kc, kl, kn, trie);
+  else if (per <= 2) search(std::integral_constant<int, 2>{}, grid, st, kc, kl, kn, trie);
+  else if (per <= 4) search(std::integral_constant<int, 4>{}, grid, st, kc, kl, kn, trie);
+  else if (per <= 8) search(std::integral_constant<int, 8>{}, grid, st, kc, kl, kn, trie);
+  else if (per <= 16) search(std::integral_constant<int, 16>{}, grid, st, kc, kl, kn, trie);
+  else search(std::integral_constant<int, 33>{}, grid, st, kc, kl, kn, trie);
+  LASR_LAUNCH_CHECK(search_name);
+  return 0;
+}
+
+// What every exported decoder does after packing its arguments: the checks, then the two launches with Scorer's search.
+template <class Scorer>
+int beam_decode(const BeamArgs& a, const typename Scorer::Args& sargs, int32_t* tokens, int32_t* n_tokens, float* scores) {
+  LASR_TRY(beam_check_args(a, a.logp && tokens && n_tokens && scores && a.workspace && Scorer::args_set(sargs)));
+  if constexpr (std::is_same_v<typename Scorer::Args, LmArgs>)
+    LASR_CHECK_ARG(std::isfinite(sargs.alpha) && std::isfinite(sargs.beta), "%s: alpha %g / beta %g not finite", a.who,
+                   (double)sargs.alpha, (double)sargs.beta);
+  return beam_launch(a, Scorer::kName, [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
+    const BeamIo io{a.lens, a.T, (int)a.C, a.blank, a.beam_width, a.n_best, trie, tokens, n_tokens, scores};
+    hipLaunchKernelGGL((beam_search_kernel<decltype(j)::value, Scorer>), grid, dim3(kSearchThreads), 0, st, kc, kl, kn, io, sargs);
+  });
 }
 
 struct ArpaHandle {
@@ -1466,9 +1347,71 @@ int arpa_code(int rc) {
   }
 }
 
+struct HotwordHandle {
+  host::HotwordBank b;
+};
+
 }  // namespace
 }  // namespace lasr
 
+using namespace lasr;
+
+// ------------------------------------------------------------------ the C ABI: decoders ---------------------------------
+extern "C" size_t lasr_ctc_beam_workspace_bytes(int64_t B, int64_t T, int64_t C, int beam_width, int cutoff_top_n) {
+  if (!beam_shape_ok(B, T, C, beam_width, cutoff_top_n)) return 0;
+  return beam_ws(B, T, beam_width).total;
+}
+
+extern "C" size_t lasr_ctc_beam_lm_workspace_bytes(int64_t B, int64_t T, int64_t C, int beam_width, int cutoff_top_n) {
+  return lasr_ctc_beam_workspace_bytes(B, T, C, beam_width, cutoff_top_n);   // a scorer's own state is all in LDS
+}
+
+extern "C" int lasr_ctc_beam_decode(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
+                                    int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, int32_t* tokens,
+                                    int32_t* n_tokens, float* scores, void* workspace, size_t workspace_bytes, void* stream) {
+  const BeamArgs a{"lasr_ctc_beam_decode", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
+                   workspace_bytes, stream};
+  return beam_decode<NullScorer>(a, {}, tokens, n_tokens, scores);
+}
+
+extern "C" int lasr_ctc_beam_decode_lm(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
+                                       int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image,
+                                       float alpha, float beta, int32_t* tokens, int32_t* n_tokens, float* scores,
+                                       float* am_scores, void* workspace, size_t workspace_bytes, void* stream) {
+  const BeamArgs a{"lasr_ctc_beam_decode_lm", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
+                   workspace_bytes, stream};
+  return beam_decode<LmScorer<false>>(a, {logp, lm_image, alpha, beta, am_scores, nullptr, nullptr}, tokens, n_tokens, scores);
+}
+
+extern "C" int lasr_ctc_beam_decode_wlm(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
+                                        int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image,
+                                        float alpha, float beta, int32_t* tokens, int32_t* n_tokens, float* scores,
+                                        float* am_scores, void* workspace, size_t workspace_bytes, void* stream) {
+  const BeamArgs a{"lasr_ctc_beam_decode_wlm", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
+                   workspace_bytes, stream};
+  return beam_decode<WlmScorer>(a, {logp, lm_image, alpha, beta, am_scores, nullptr, nullptr}, tokens, n_tokens, scores);
+}
+
+extern "C" int lasr_ctc_beam_decode_bias(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
+                                         int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* bias_image,
+                                         int32_t* tokens, int32_t* n_tokens, float* scores, float* am_scores, float* bias_scores,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  const BeamArgs a{"lasr_ctc_beam_decode_bias", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
+                   workspace_bytes, stream};
+  return beam_decode<BiasScorer>(a, {bias_image, am_scores, bias_scores}, tokens, n_tokens, scores);
+}
+
+extern "C" int lasr_ctc_beam_decode_lm_bias(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
+                                            int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image,
+                                            float alpha, float beta, const void* bias_image, int32_t* tokens, int32_t* n_tokens,
+                                            float* scores, float* am_scores, float* bias_scores, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  const BeamArgs a{"lasr_ctc_beam_decode_lm_bias", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
+                   workspace_bytes, stream};
+  return beam_decode<LmScorer<true>>(a, {logp, lm_image, alpha, beta, am_scores, bias_image, bias_scores}, tokens, n_tokens, scores);
+}
+
+// ------------------------------------------------------------------ the C ABI: ARPA models ------------------------------
 extern "C" int lasr_arpa_load(const char* path, const char* const* vocab, int n_vocab, void** handle) {
   LASR_CHECK_ARG(path && handle && (vocab || n_vocab == 0) && n_vocab >= 0, "lasr_arpa_load: null pointer or negative n_vocab");
   *handle = nullptr;
@@ -1481,48 +1424,6 @@ extern "C" int lasr_arpa_load(const char* path, const char* const* vocab, int n_
   }
   *handle = h;
   return 0;
-}
-
-extern "C" int lasr_arpa_info(const void* handle, int* order, int* char_based, int64_t* n_ngrams, size_t* image_bytes) {
-  LASR_CHECK_ARG(handle, "lasr_arpa_info: null handle");
-  const host::ArpaModel& m = static_cast<const ArpaHandle*>(handle)->m;
-  if (order) *order = m.order;
-  if (char_based) *char_based = m.char_based ? 1 : 0;
-  if (n_ngrams) *n_ngrams = m.n_ngrams;
-  if (image_bytes) *image_bytes = m.image.size();
-  return 0;
-}
-
-extern "C" int lasr_arpa_write_image(const void* handle, void* host_dst, size_t bytes) {
-  LASR_CHECK_ARG(handle && host_dst, "lasr_arpa_write_image: null pointer");
-  const host::ArpaModel& m = static_cast<const ArpaHandle*>(handle)->m;
-  if (bytes < m.image.size())
-    return fail(LASR_E_WORKSPACE, "lasr_arpa_write_image: %zu < %zu bytes", bytes, m.image.size());
-  memcpy(host_dst, m.image.data(), m.image.size());
-  return 0;
-}
-
-extern "C" void lasr_arpa_free(void* handle) { delete static_cast<ArpaHandle*>(handle); }
-
-extern "C" size_t lasr_ctc_beam_lm_workspace_bytes(int64_t B, int64_t T, int64_t C, int beam_width, int cutoff_top_n) {
-  return lasr_ctc_beam_workspace_bytes(B, T, C, beam_width, cutoff_top_n);   // the LM search's own state is all in LDS
-}
-
-extern "C" int lasr_ctc_beam_decode_lm(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
-                                       int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image,
-                                       float alpha, float beta, int32_t* tokens, int32_t* n_tokens, float* scores,
-                                       float* am_scores, void* workspace, size_t workspace_bytes, void* stream) {
-  const BeamArgs a{"lasr_ctc_beam_decode_lm", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
-                   workspace_bytes, stream};
-  LASR_TRY(beam_check_args(a, logp && lm_image && tokens && n_tokens && scores && am_scores && workspace));
-  LASR_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "lasr_ctc_beam_decode_lm: alpha %g / beta %g not finite",
-                 (double)alpha, (double)beta);
-  auto search = [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
-    hipLaunchKernelGGL((beam_search_lm_kernel<decltype(j)::value, false>), grid, dim3(kSearchThreads), 0, st, logp, kc, kl, kn, lens,
-                       T, (int)C, blank, beam_width, n_best, lm_image, alpha, beta, trie, tokens, n_tokens, scores, am_scores,
-                       (const void*)nullptr, (float*)nullptr);
-  };
-  return beam_launch(a, "beam_search_lm_kernel", search);
 }
 
 extern "C" int lasr_arpa_load_words(const char* path, const char* const* vocab, int n_vocab, int space_id, void** handle) {
@@ -1540,6 +1441,16 @@ extern "C" int lasr_arpa_load_words(const char* path, const char* const* vocab, 
   return 0;
 }
 
+extern "C" int lasr_arpa_info(const void* handle, int* order, int* char_based, int64_t* n_ngrams, size_t* image_bytes) {
+  LASR_CHECK_ARG(handle, "lasr_arpa_info: null handle");
+  const host::ArpaModel& m = static_cast<const ArpaHandle*>(handle)->m;
+  if (order) *order = m.order;
+  if (char_based) *char_based = m.char_based ? 1 : 0;
+  if (n_ngrams) *n_ngrams = m.n_ngrams;
+  if (image_bytes) *image_bytes = m.image.size();
+  return 0;
+}
+
 extern "C" int lasr_arpa_lexicon_info(const void* handle, int64_t* n_lexicon_words, int64_t* n_nodes, int64_t* n_dropped_words) {
   LASR_CHECK_ARG(handle, "lasr_arpa_lexicon_info: null handle");
   const host::ArpaModel& m = static_cast<const ArpaHandle*>(handle)->m;
@@ -1550,33 +1461,18 @@ extern "C" int lasr_arpa_lexicon_info(const void* handle, int64_t* n_lexicon_wor
   return 0;
 }
 
-extern "C" int lasr_ctc_beam_decode_wlm(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
-                                        int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image,
-                                        float alpha, float beta, int32_t* tokens, int32_t* n_tokens, float* scores,
-                                        float* am_scores, void* workspace, size_t workspace_bytes, void* stream) {
-  const BeamArgs a{"lasr_ctc_beam_decode_wlm", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
-                   workspace_bytes, stream};
-  LASR_TRY(beam_check_args(a, logp && lm_image && tokens && n_tokens && scores && am_scores && workspace));
-  LASR_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "lasr_ctc_beam_decode_wlm: alpha %g / beta %g not finite",
-                 (double)alpha, (double)beta);
-  auto search = [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
-    hipLaunchKernelGGL(beam_search_wlm_kernel<decltype(j)::value>, grid, dim3(kSearchThreads), 0, st, logp, kc, kl, kn, lens, T,
-                       (int)C, blank, beam_width, n_best, lm_image, alpha, beta, trie, tokens, n_tokens, scores, am_scores);
-  };
-  return beam_launch(a, "beam_search_wlm_kernel", search);
+extern "C" int lasr_arpa_write_image(const void* handle, void* host_dst, size_t bytes) {
+  LASR_CHECK_ARG(handle && host_dst, "lasr_arpa_write_image: null pointer");
+  const host::ArpaModel& m = static_cast<const ArpaHandle*>(handle)->m;
+  if (bytes < m.image.size())
+    return fail(LASR_E_WORKSPACE, "lasr_arpa_write_image: %zu < %zu bytes", bytes, m.image.size());
+  memcpy(host_dst, m.image.data(), m.image.size());
+  return 0;
 }
 
-// ------------------------------------------------------------------ hotword biasing: the C ABI -------------------------
-namespace lasr {
-namespace {
+extern "C" void lasr_arpa_free(void* handle) { delete static_cast<ArpaHandle*>(handle); }
 
-struct HotwordHandle {
-  host::HotwordBank b;
-};
-
-}  // namespace
-}  // namespace lasr
-
+// ------------------------------------------------------------------ the C ABI: hotword banks ----------------------------
 extern "C" int lasr_hotword_build(const int32_t* labels, const int64_t* offsets, const float* weights, int n_phrases, int64_t C,
                                   int blank, void** handle) {
   LASR_CHECK_ARG(handle, "lasr_hotword_build: null handle");
@@ -1621,36 +1517,4 @@ extern "C" int lasr_hotword_score(const void* handle, const int32_t* labels, int
   const int rc = host::hotword_score(b.image.data(), b.image.size(), labels, n, bonus, final_bonus, state, &err);
   if (rc != host::kHotwordOk) return fail(rc == host::kHotwordErrFormat ? LASR_E_FORMAT : LASR_E_ARG, "lasr_hotword_score: %s", err.c_str());
   return 0;
-}
-
-extern "C" int lasr_ctc_beam_decode_bias(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
-                                         int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* bias_image,
-                                         int32_t* tokens, int32_t* n_tokens, float* scores, float* am_scores, float* bias_scores,
-                                         void* workspace, size_t workspace_bytes, void* stream) {
-  const BeamArgs a{"lasr_ctc_beam_decode_bias", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
-                   workspace_bytes, stream};
-  LASR_TRY(beam_check_args(a, logp && bias_image && tokens && n_tokens && scores && am_scores && bias_scores && workspace));
-  auto search = [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
-    hipLaunchKernelGGL(beam_search_bias_kernel<decltype(j)::value>, grid, dim3(kSearchThreads), 0, st, kc, kl, kn, lens, T, (int)C,
-                       blank, beam_width, n_best, bias_image, trie, tokens, n_tokens, scores, am_scores, bias_scores);
-  };
-  return beam_launch(a, "beam_search_bias_kernel", search);
-}
-
-extern "C" int lasr_ctc_beam_decode_lm_bias(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
-                                            int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const void* lm_image,
-                                            float alpha, float beta, const void* bias_image, int32_t* tokens, int32_t* n_tokens,
-                                            float* scores, float* am_scores, float* bias_scores, void* workspace,
-                                            size_t workspace_bytes, void* stream) {
-  const BeamArgs a{"lasr_ctc_beam_decode_lm_bias", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
-                   workspace_bytes, stream};
-  LASR_TRY(beam_check_args(a, logp && lm_image && bias_image && tokens && n_tokens && scores && am_scores && bias_scores && workspace));
-  LASR_CHECK_ARG(std::isfinite(alpha) && std::isfinite(beta), "lasr_ctc_beam_decode_lm_bias: alpha %g / beta %g not finite",
-                 (double)alpha, (double)beta);
-  auto search = [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
-    hipLaunchKernelGGL((beam_search_lm_kernel<decltype(j)::value, true>), grid, dim3(kSearchThreads), 0, st, logp, kc, kl, kn, lens, T,
-                       (int)C, blank, beam_width, n_best, lm_image, alpha, beta, trie, tokens, n_tokens, scores, am_scores, bias_image,
-                       bias_scores);
-  };
-  return beam_launch(a, "beam_search_lm_kernel (biased)", search);
 }

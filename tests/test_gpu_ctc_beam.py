@@ -101,6 +101,15 @@ def test_beam_large_vocabulary(dev):
     assert_matches(run(dev, x, None, W, 40, 1.0, 4), res, 4, T)
 
 
+def test_beam_widest_candidate_set(dev):
+    """C = 48 keeps cutoff_top_n = 40 classes: beam 128 then has 128 * 41 candidates per frame, the J = 33 search (the widest
+    rung), at the smallest vocabulary that reaches it"""
+    B, T, C, W, k = 2, 30, 48, 128, 40
+    assert W * (k + 1) > 16 * 256
+    x, res = oracle_case(B, T, C, W, k, 1.0, 4)
+    assert_matches(run(dev, x, None, W, k, 1.0, 4), res, 4, T)
+
+
 def test_beam_40s_utterance(dev):
     """one 40 s dev clip's worth of frames (T' = 2001) at beam 64"""
     T, C, W = 2001, 28, 64

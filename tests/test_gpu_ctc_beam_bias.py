@@ -260,6 +260,23 @@ def test_lm_bias_early_cutoff_decides(dev, en_lms):
     assert_matches(lm_run(dev, case, path, W, 40, 4, alpha, beta), res, 4, T)
 
 
+SYM47 = EN + [chr(ord("A") + i) for i in range(20)]               # 47 labels: C = 48, the smallest with 41 classes to keep
+
+
+# The LM + hotword search at the rungs test_lm_bias_matches_oracle (J = 2 and 16) leaves out: W 8, 32 and 64 on C = 28 are 1, 4
+# and 8 candidates per thread; C = 48 keeps cutoff_top_n = 40 labels, and W = 128 then has 128 * 41 candidates: J = 33.
+@pytest.mark.parametrize("vocab,order,W,alpha,beta", [(EN, 2, 8, 1.0, 1.0), (EN, 3, 32, 0.5, -0.5), (EN, 6, 64, 0.8, 1.5),
+                                                      (SYM47, 3, 128, 0.5, 0.5)], ids=["J1", "J4", "J8", "J33"])
+def test_lm_bias_every_other_rung(dev, en_lms, tmp_path, vocab, order, W, alpha, beta):
+    from lightning_asr_amd import ops
+    B, T, C = 2, 30, len(vocab) + 1
+    path = en_lms[order] if vocab is EN else S.write_arpa(tmp_path / "sym47.arpa", vocab, order, 400, seed=order)
+    lm = (vocab, LO.ArpaOracle.from_file(path), alpha, beta, (path, alpha, beta))
+    x, phrases, weights, res, _ = bias_case(C, B, T, W, 40, 1.0, 4, 2.0, lm=lm)
+    got = run(dev, x, None, phrases, weights, W, 40, 1.0, 4, ops.load_arpa(path, vocab, dev, alpha, beta))
+    assert_matches(got, res, 4, T)
+
+
 # ------------------------------------------------------------------------------------------------ determinism, capture, errors
 @pytest.mark.parametrize("with_lm", [False, True])
 def test_bias_deterministic_and_graph_capture(dev, en_lms, with_lm):

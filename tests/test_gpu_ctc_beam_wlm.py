@@ -185,6 +185,31 @@ def test_beam_wlm_widest_candidate_set(dev, en_lm):
     assert_matches(run(dev, x, None, EN_SP, path, W, k, 1.0, 8, 0.7, 1.0), res, 8, T)
 
 
+SYM47 = EN_SP + [chr(ord("A") + i) for i in range(19)]            # 47 labels: C = 48, the smallest with 41 classes to keep
+
+
+@pytest.fixture(scope="module")
+def sym47_lm(tmp_path_factory):
+    """a 3-gram over 2 000 random words of SYM47's 46 letters"""
+    words = WS.random_words(2000, SYM47[1:], 13, 1, 7)
+    path = tmp_path_factory.mktemp("wlm_sym47") / "sym2000.arpa"
+    sents = [words[i:i + 8] for i in range(0, len(words), 8)] + S.sentences(words, 1500, 5)
+    path.write_text(S.arpa_text(sents, 3), encoding="utf-8")
+    return words, str(path)
+
+
+# The rungs of the candidate ladder the cases above leave out (they run 1, 2, 4 and 16 candidates per thread): C = 29 at beam 64
+# has 64 * 30 candidates, J = 8; C = 48 keeps cutoff_top_n = 40 labels, and beam 128 then has 128 * 41, J = 33.
+@pytest.mark.parametrize("wide,W", [(False, 64), (True, 128)], ids=["J8", "J33"])
+def test_beam_wlm_every_other_rung(dev, en_lm, sym47_lm, wide, W):
+    vocab, (words, path) = (SYM47, sym47_lm) if wide else (EN_SP, en_lm)
+    B, T, k = 2, 30, 40
+    x, res, _, rejected, _ = wlm_case(vocab, words, path, B, T, W, k, 1.0, 4, 0.7, 1.0, seeds=tuple(range(8)), hot=10.0, n_words=(3, 6),
+                                      want=lambda x, out: scores_words(out[0]))
+    assert rejected > 0 and scores_words(res)
+    assert_matches(run(dev, x, None, vocab, path, W, k, 1.0, 4, 0.7, 1.0), res, 4, T)
+
+
 LONG_SEED = 1
 
 

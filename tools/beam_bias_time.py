@@ -7,7 +7,10 @@ this build's), else this build's.  With --lm the character-LM variant is timed a
 3-gram, tests/helpers/arpa_synth.py).  Calls are interleaved round by round (reference, then each bank), so that clock drift
 falls on all of them alike; inputs are peaky log-softmaxed normals (tools/beam_time.py).  One JSON line per case.
 
-    python tools/beam_bias_time.py [--reps N] [--parent PATH/liblasr.so] [--lm] [--out profiles/beam_bias_time.jsonl]"""
+    python tools/beam_bias_time.py [--reps N] [--parent PATH/liblasr.so] [--lm] [--out profiles/beam_bias_time.jsonl] [--dump F.npz]
+
+--dump saves every timed case's outputs (tokens, n_tokens, scores and, where the search has them, am_scores and bias_scores),
+as tools/beam_time.py does."""
 import argparse
 import ctypes
 import json
@@ -23,7 +26,7 @@ import torch  # noqa: E402
 
 import arpa_synth as S  # noqa: E402
 from lightning_asr_amd import _lib, ops  # noqa: E402
-from tools.beam_time import peaky  # noqa: E402
+from tools.beam_time import dump_case, peaky, save_dump  # noqa: E402
 
 EN = ["'"] + [chr(ord("a") + i) for i in range(26)]
 HAN = [chr(0x4E00 + i) for i in range(4333)]
@@ -75,11 +78,12 @@ def main():
     ap.add_argument("--parent", default=None)
     ap.add_argument("--lm", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dump", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda")
     ref = parent_decode(a.parent) if a.parent else ops.ctc_beam_decode
     tmp = tempfile.mkdtemp()
-    lines = []
+    lines, dump = [], {}
     for name, C, widths, vocab in (("c28", 28, (16, 128), EN), ("c4334", 4334, (16,), HAN)):
         B, T = 32, 501
         x = peaky(B, T, C, 1, dev)
@@ -103,6 +107,9 @@ def main():
                 for n, bank in banks.items():
                     fns["lm_bias_%d" % n] = lambda bank=bank: ops.ctc_beam_decode_biased(x, lens, C - 1, bank, W, 40, 1.0, 1, lm)
             t = interleaved(fns, a.reps)
+            if a.dump:
+                for k, f in fns.items():
+                    dump_case(dump, "%s.w%d.%s" % (name, W, k), f(), ("tokens", "n_tokens", "scores", "am_scores", "bias_scores"))
             out0 = ops.ctc_beam_decode_biased(x, lens, C - 1, banks[0], W, 40, 1.0, 1)
             same = all(torch.equal(u, v) for u, v in zip(out0[:3], ref(x, lens, C - 1, W, 40, 1.0, 1)))
             rec = {"shape": name, "B": B, "T": T, "C": C, "beam_width": W, "cutoff_top_n": 40, "reps": a.reps,
@@ -112,6 +119,8 @@ def main():
                    "ms_median": {k: round(v[0], 3) for k, v in t.items()}, "ms_min": {k: round(v[1], 3) for k, v in t.items()}}
             lines.append(rec)
             print(json.dumps(rec), flush=True)
+    if a.dump:
+        save_dump(a.dump, dump)
     if a.out:
         with open(a.out, "w") as f:
             for r in lines:

@@ -23,7 +23,12 @@ META = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment
 
 
 def short(name):
-    """beam_search_lm_kernel<33, true> from the mangled name"""
+    """beam_search_kernel<LmScorer<true>, J=33> from the mangled name (beam_search_lm_kernel<33, true> for a revision of the
+    file with one kernel per scorer)"""
+    m = re.search(r"\d+beam_search_kernelILi(\d+)E\w*?\d+([A-Za-z]+Scorer)(?:ILb([01])E)?", name)
+    if m:
+        scorer = m.group(2) + {"0": "<false>", "1": "<true>", None: ""}[m.group(3)]
+        return "beam_search_kernel<%s, J=%s>" % (scorer, m.group(1))
     m = re.search(r"\d+(beam_\w+?_kernel)(?:IL[ij](\d+)E(?:Lb([01])E)?E)?", name)
     if not m:
         return name
