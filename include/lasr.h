@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 114   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 115   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
@@ -38,7 +38,8 @@ extern "C" {
                               111: lasr_vad_* / lasr_segment_gather (voice-activity segmentation of long recordings)
                               112: lasr_hotword_* (phrase bank), lasr_ctc_beam_decode_bias / _lm_bias (hotword biasing)
                               113: lasr_ctc_kws_workspace_bytes / lasr_ctc_kws (CTC keyword search: phrases with time spans)
-                              114: lasr_grad_accumulate / lasr_grad_accumulate_ranges (gradient accumulation over micro-batches) */
+                              114: lasr_grad_accumulate / lasr_grad_accumulate_ranges (gradient accumulation over micro-batches)
+                              115: lasr_bn_tail / lasr_bn_side / lasr_se_side: the BN entry points take one record; the _drop twins are gone */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -256,83 +257,81 @@ typedef struct {
 } lasr_bn_branch;
 int lasr_bn_finalize_partials(const lasr_bn_branch* branches, int n_branches, int64_t C, int64_t n_rows, float eps,
                               float momentum, void* stream);
-/* lasr_bn_finalize_partials + lasr_bn_act_fwd (no SE scale) in ONE launch, bf16 and C a multiple of 64: workgroups of 64 channels x
- * a chunk of rows fold the coefficients of their own channels from the partial sums in their prologue (the finalize launch's
- * arithmetic in the same order: the same bits) and apply them; coef / saved / stats / the running statistics of `branches` are
- * written as lasr_bn_finalize_partials writes them.  n_branches = 2 with y2 (main, residual), 1 without; n_rows = B*T.      */
-int lasr_bn_act_fwd_partials(const lasr_bn_branch* branches, int n_branches, float eps, float momentum, const void* y,
-                             const void* y2, void* out, int dtype, int64_t B, int64_t T, int64_t C, int act, void* stream);
-
 /* nn.Dropout(p) of SeprationConv / last_cnn2 (models/QuartNet.py:26,38,149) folded into the BN-apply kernels as a counter-based
  * (Philox4x32-10) mask: forward and both backward passes regenerate it from (seed, *step, unit, element index); no mask tensor
  * exists.  step: device scalar holding the index of the current training forward (lasr_mask_lengths_step bumps it as the first
  * launch of a forward, so replayed graphs draw fresh masks); unit: distinct per layer.  A residual unit drops its MAIN branch
  * before the add (the Dropout at the end of its SeprationConv), first_cnn / last_cnn2 drop after the activation.  Kept
- * elements are scaled by 1/(1-p).  NULL descriptor or p = 0: off (the plain entry points).  lasr_dropout_mask writes the mask
- * itself (1 = kept) for verification against a CPU reference.                                                           */
+ * elements are scaled by 1/(1-p).  step = NULL or p = 0: off.  lasr_dropout_mask writes the mask itself (1 = kept) for
+ * verification against a CPU reference.                                                                                 */
 typedef struct { const uint64_t* step; uint64_t seed; uint32_t unit; float p; } lasr_dropout;
 int lasr_mask_lengths_step(const float* pct, int64_t B, int64_t T, int32_t* lens, uint64_t* step_counter, void* stream);
 int lasr_dropout_mask(const lasr_dropout* dropout, int64_t n, uint8_t* keep, void* stream);
-int lasr_bn_act_fwd_drop(const void* y, const float* coef, const void* y2, const float* coef2, const float* se_scale, void* out,
-                         int dtype, int64_t B, int64_t T, int64_t C, int act, const lasr_dropout* dropout, void* stream);
-int lasr_bn_act_bwd_stats_drop(const void* dout, const void* y, const float* coef, const float* saved, const void* y2,
-                               const float* coef2, const float* saved2, const float* se_scale, const float* se_grad, float* sums,
-                               float* sums2, int dtype, int64_t B, int64_t T, int64_t C, int act, const lasr_dropout* dropout,
-                               void* workspace, size_t workspace_bytes, void* stream);
-int lasr_se_bwd_drop(const void* dout, const void* y, const float* coef, const void* y2, const float* coef2, const float* scale,
-                     const float* hidden, const float* pooled, const float* W1, const float* W2, int dtype, int64_t B, int64_t T,
-                     int64_t C, int act, const lasr_dropout* dropout, float* seg, float* dW1, float* dW2, void* workspace,
-                     size_t workspace_bytes, void* stream);
-/* Backward of a ContextSE unit's  out = act(BN(y) * se + BN_res(y2))  (models/QuartNetContextSE.py:19-23,54-57) in TWO passes over
- * (dout, y, y2): per-utterance raw sums -> SE-scale gradient by algebra (gamma*sum(d*xhat) + beta*sum(d)) -> excite-MLP backward
- * (seg_out [B][C], dW1, dW2) -> BN-backward constants -> dy, dy2, dgamma, dbeta.  ysum [B][C] = sum_t y from lasr_seqsum.
- * Replaces lasr_se_bwd + lasr_bn_act_bwd_stats + lasr_bn_act_bwd_apply (three passes) for the SE units.                      */
-size_t lasr_bn_se_bwd_workspace_bytes(int64_t B, int64_t T, int64_t C);
-int lasr_bn_se_bwd(const void* dout, const void* y, const float* coef, const float* saved, const float* gamma, const float* beta,
-                   const void* y2, const float* coef2, const float* saved2, const float* gamma2, const float* se_scale,
-                   const float* se_hidden, const float* se_pooled, const float* ysum, const float* W1, const float* W2,
-                   const int32_t* row_lens, void* dy, void* dy2, float* dgamma, float* dbeta, float* dgamma2, float* dbeta2,
-                   float* dW1, float* dW2, float* seg_out, int dtype, int64_t B, int64_t T, int64_t C, int act,
-                   const lasr_dropout* dropout, void* workspace, size_t workspace_bytes, void* stream);
-int lasr_bn_act_bwd_apply_drop(const void* dout, const void* y, const float* coef, const float* saved, const float* gamma,
-                               const void* y2, const float* coef2, const float* saved2, const float* gamma2,
-                               const float* se_scale, const float* se_grad, const float* sums, const float* sums2,
-                               const int32_t* row_lens, void* dy, void* dy2, float* dgamma, float* dbeta, float* dgamma2,
-                               float* dbeta2, int dtype, int64_t B, int64_t T, int64_t C, int act, const lasr_dropout* dropout,
-                               void* workspace, size_t workspace_bytes, void* stream);
 
-/* out = act( (y*coef_a + coef_b) * se_scale[b][c] + (y2*coef2_a + coef2_b) )
- * y2/coef2 (residual branch) and se_scale ([B][C] f32) may be NULL.
- * (BN-apply + SE scale + residual add + ReLU: models/QuartNet.py:35-37,74-77; ContextSE :55) */
-int lasr_bn_act_fwd(const void* y, const float* coef, const void* y2, const float* coef2,
-                    const float* se_scale, void* out, int dtype, int64_t B, int64_t T, int64_t C, int act,
-                    void* stream);
+/* The tail every conv unit ends in,  out = act( BN(y) * se_scale[b][c] + BN_res(y2) )  with optional dropout and length masking
+ * (BN-apply + SE scale + residual add + ReLU: models/QuartNet.py:35-37,74-77; ContextSE :55), described ONCE: the forward and every
+ * backward entry point below take this record and read the fields they need (a field an entry point does not list is ignored).
+ * "No residual branch" is res.y == NULL and nothing else: the other fields of `res` are then not looked at.                   */
+typedef struct {                 /* one BatchNorm branch of the tail */
+  const void* y;                 /* pre-BN tensor [B][T][C] in `dtype` */
+  const float* coef;             /* [2][C] scale | shift, as lasr_bn_finalize leaves them */
+  const float* saved;            /* [2][C] mean | rstd                                          (backward) */
+  const float* gamma;            /* [C]                                                         (backward apply) */
+  const float* beta;             /* [C]                                                         (lasr_bn_se_bwd, main only) */
+  float* sums;                   /* reduced [2][C] sums between stats and apply; NULL: fused hand-over through the workspace */
+  void* dy;                      /* [B][T][C] gradient of y                                     (backward apply) */
+  float* dgamma; float* dbeta;   /* [C] parameter gradients                                     (backward apply) */
+} lasr_bn_side;
+typedef struct {
+  int dtype; int act;            /* LASR_F32 / LASR_BF16 of y, y2, dout, dy, out; LASR_ACT_* */
+  int64_t B, T, C;
+  lasr_bn_side main, res;
+  const void* dout;              /* [B][T][C] gradient of out                                   (backward) */
+  const float* se_scale;         /* [B][C] f32, may be NULL: no SE scale */
+  const float* se_grad;          /* [B][C] f32, may be NULL: extra per-(b,c) gradient added to d*se (SE pooled path) */
+  const int32_t* row_lens;       /* (B), may be NULL: rows t >= row_lens[b] of main.dy are zeroed (`res` is never masked) */
+  lasr_dropout dropout;          /* step == NULL or p == 0: off */
+} lasr_bn_tail;
+int lasr_bn_act_fwd(const lasr_bn_tail* tail, void* out, void* stream);   /* reads y, coef of both sides, se_scale, dropout */
+/* lasr_bn_finalize_partials + lasr_bn_act_fwd (no SE scale, no dropout) in ONE launch, bf16 and C a multiple of 64: workgroups of
+ * 64 channels x a chunk of rows fold the coefficients of their own channels from the partial sums in their prologue (the finalize
+ * launch's arithmetic in the same order: the same bits) and apply them; coef / saved / stats / the running statistics of `branches`
+ * are written as lasr_bn_finalize_partials writes them.  Of the record only y of both sides, dtype, act and the shape are read;
+ * n_branches = 2 with res.y (main, residual), 1 without; n_rows = B*T.                                                        */
+int lasr_bn_act_fwd_partials(const lasr_bn_branch* branches, int n_branches, float eps, float momentum, const lasr_bn_tail* tail,
+                             void* out, void* stream);
 
-/* Backward of the above + BatchNorm backward, two passes over the activations:
- * pass 1 (stats): d = dout * act'(.) ; sums[0..C) = sum d*se, [C..2C) = sum d*se*yhat for branch 1
- *                 and the same for branch 2 in sums2 (se=1 there); yhat = (y-mean)*rstd.
+/* Backward of the tail + BatchNorm backward, two passes over the activations:
+ * pass 1 (stats): d = dout * act'(.) ; main.sums[0..C) = sum d*se, [C..2C) = sum d*se*yhat for branch 1
+ *                 and the same for branch 2 in res.sums (se=1 there); yhat = (y-mean)*rstd.
  * pass 2 (apply): dy = gamma*rstd * (d*se - s1/n - yhat*s2/n), rows t >= row_lens[b] zeroed for
  *                 branch 1 only (the residual branch is never masked, models/QuartNet.py:75).
  * The pre-activation is rebuilt from y/y2 and the coefficients, so the forward output is not read.
  * dgamma = s2, dbeta = s1 are written by pass 2 (f32, may be NULL).
  * se_grad ([B][C] f32, may be NULL): extra per-(b,c) gradient added to d*se (SE pooled path).
- * Fused hand-over: call stats with sums = sums2 = NULL and apply with sums = sums2 = NULL and the SAME
- * workspace (lasr_bn_bwd_workspace_bytes): the per-block partial sums stay in the workspace and pass 2
- * reduces them while folding its per-channel constants (one launch less, no f32 round trip).   */
+ * Fused hand-over: call stats and apply with main.sums = res.sums = NULL and the SAME workspace
+ * (lasr_bn_bwd_workspace_bytes): the per-block partial sums stay in the workspace and pass 2
+ * reduces them while folding its per-channel constants (one launch less, no f32 round trip).
+ * stats reads dout, y / coef / saved of both sides, se_scale, se_grad, dropout and writes sums; apply reads gamma, sums, row_lens
+ * as well and writes dy, dgamma, dbeta of both sides.                                           */
 size_t lasr_bn_bwd_workspace_bytes(int64_t B, int64_t T, int64_t C);
-int lasr_bn_act_bwd_stats(const void* dout, const void* y, const float* coef,
-                          const float* saved, const void* y2, const float* coef2, const float* saved2,
-                          const float* se_scale, const float* se_grad, float* sums, float* sums2, int dtype,
-                          int64_t B, int64_t T, int64_t C, int act, void* workspace, size_t workspace_bytes,
-                          void* stream);
-int lasr_bn_act_bwd_apply(const void* dout, const void* y, const float* coef,
-                          const float* saved, const float* gamma, const void* y2, const float* coef2,
-                          const float* saved2, const float* gamma2, const float* se_scale,
-                          const float* se_grad, const float* sums, const float* sums2,
-                          const int32_t* row_lens, void* dy, void* dy2, float* dgamma, float* dbeta,
-                          float* dgamma2, float* dbeta2, int dtype, int64_t B, int64_t T, int64_t C, int act,
-                          void* workspace, size_t workspace_bytes, void* stream);
+int lasr_bn_act_bwd_stats(const lasr_bn_tail* tail, void* workspace, size_t workspace_bytes, void* stream);
+int lasr_bn_act_bwd_apply(const lasr_bn_tail* tail, void* workspace, size_t workspace_bytes, void* stream);
 size_t lasr_bn_bwd_apply_workspace_bytes(int64_t C);   /* folded per-channel constants, 10*C f32 */
+
+/* The excite MLP of a ContextSE unit (models/QuartNetContextSE.py:8-23), as its backward takes it: hidden (B,C/8), pooled (B,C) from
+ * lasr_se_fwd, ysum (B,C) = sum_t y from lasr_seqsum (lasr_bn_se_bwd only), W1 (C/8,C), W2 (C,C/8); outputs seg (B,C), dW1, dW2. */
+typedef struct {
+  const float* hidden; const float* pooled; const float* ysum; const float* W1; const float* W2;
+  float* seg; float* dW1; float* dW2;
+} lasr_se_side;
+/* Backward of a ContextSE unit's  out = act(BN(y) * se + BN_res(y2))  (models/QuartNetContextSE.py:19-23,54-57) in TWO passes over
+ * (dout, y, y2): per-utterance raw sums -> SE-scale gradient by algebra (gamma*sum(d*xhat) + beta*sum(d)) -> excite-MLP backward
+ * (se->seg [B][C], dW1, dW2) -> BN-backward constants -> dy, dy2, dgamma, dbeta.  se->seg takes the place of tail->se_grad, and
+ * the sums go through the workspace.  Replaces lasr_se_bwd + lasr_bn_act_bwd_stats + lasr_bn_act_bwd_apply (three passes) for the
+ * SE units.                                                                                                                  */
+size_t lasr_bn_se_bwd_workspace_bytes(int64_t B, int64_t T, int64_t C);
+int lasr_bn_se_bwd(const lasr_bn_tail* tail, const lasr_se_side* se, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- SE + BiLSTM context --------
  * models/QuartNetContextSE.py:8-23,55  SELayer(reduction=8, no bias): s = sigmoid(W2 relu(W1 mean_T(BN(y)))),
@@ -342,13 +341,12 @@ int lasr_seqsum(const void* x, int dtype, int64_t B, int64_t T, int64_t C, float
 /* pooled (B,C) = coef_a*sums/T + coef_b ; hidden (B,C/8) = relu(W1 pooled) ; scale (B,C) = sigmoid(W2 hidden) */
 int lasr_se_fwd(const float* sums, const float* coef, const float* W1, const float* W2, int64_t B, int64_t T, int64_t C,
                 float* pooled, float* hidden, float* scale, void* stream);
-/* Backward of the excite path: seg (B,C) = gradient reaching every frame of the BN output through the pooled
- * mean (feed it to lasr_bn_act_bwd_* as se_grad), dW1 (C/8,C), dW2 (C,C/8).  C a multiple of 32; the whole batch is
- * handled by two launches whose per-workgroup tables (B x C/8 floats and change) must fit 64 KB of LDS (B <= ~200 at C = 512). */
+/* Backward of the excite path: se->seg (B,C) = gradient reaching every frame of the BN output through the pooled
+ * mean (feed it to lasr_bn_act_bwd_* as se_grad), dW1 (C/8,C), dW2 (C,C/8).  Of the tail (lasr_bn_tail, above) it reads dout, y and
+ * coef of both sides, se_scale (required) and dropout.  C a multiple of 32; the whole batch is handled by two launches whose
+ * per-workgroup tables (B x C/8 floats and change) must fit 64 KB of LDS (B <= ~200 at C = 512). */
 size_t lasr_se_bwd_workspace_bytes(int64_t B, int64_t C);
-int lasr_se_bwd(const void* dout, const void* y, const float* coef, const void* y2, const float* coef2, const float* scale,
-                const float* hidden, const float* pooled, const float* W1, const float* W2, int dtype, int64_t B, int64_t T,
-                int64_t C, int act, float* seg, float* dW1, float* dW2, void* workspace, size_t workspace_bytes, void* stream);
+int lasr_se_bwd(const lasr_bn_tail* tail, const lasr_se_side* se, void* workspace, size_t workspace_bytes, void* stream);
 
 /* models/QuartNetContext.py:171-173,186-199: pack_padded_sequence -> nn.LSTM(256, 40, bidirectional) ->
  * pad_packed_sequence.  gx_f/gx_r (B,T,160) f32 = x W_ih^T per direction (lasr_gemm; biases are added here),

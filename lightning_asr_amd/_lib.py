@@ -21,6 +21,23 @@ class Dropout(C.Structure):
     _fields_ = [("step", C.c_void_p), ("seed", C.c_uint64), ("unit", C.c_uint32), ("p", C.c_float)]
 
 
+class BnSide(C.Structure):
+    """lasr_bn_side: one BatchNorm branch of a unit's tail (device pointers; an unset field is NULL)"""
+    _fields_ = [(n, C.c_void_p) for n in ("y", "coef", "saved", "gamma", "beta", "sums", "dy", "dgamma", "dbeta")]
+
+
+class BnTail(C.Structure):
+    """lasr_bn_tail: out = act(BN(y) * se_scale + BN_res(y2)) with optional dropout and length masking; res.y NULL = no residual"""
+    _fields_ = [("dtype", C.c_int), ("act", C.c_int), ("B", C.c_int64), ("T", C.c_int64), ("C", C.c_int64),
+                ("main", BnSide), ("res", BnSide), ("dout", C.c_void_p), ("se_scale", C.c_void_p), ("se_grad", C.c_void_p),
+                ("row_lens", C.c_void_p), ("dropout", Dropout)]
+
+
+class SeSide(C.Structure):
+    """lasr_se_side: the excite MLP of a ContextSE unit as its backward takes it"""
+    _fields_ = [(n, C.c_void_p) for n in ("hidden", "pooled", "ysum", "W1", "W2", "seg", "dW1", "dW2")]
+
+
 class WaveSrc(C.Structure):
     """lasr_wave_src: samples (f32 or int16 PCM) + explicit dither noise or (seed, device step counter) for generated noise"""
     _fields_ = [("wave", C.c_void_p), ("wave_dtype", C.c_int32), ("dither", C.c_void_p), ("dither_seed", C.c_uint64),
@@ -77,10 +94,10 @@ SIGNATURES = {
     "lasr_gemm_batch": (_i32, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _sz, _p]),
     "lasr_bn_finalize": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _f32, _i32, _p]),
     "lasr_bn_eval_coef_many": (_i32, [_p, _i32, _f32, _p]),
-    "lasr_bn_act_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i64, _i64, _i32, _p]),
+    "lasr_bn_act_fwd": (_i32, [_p, _p, _p]),
     "lasr_bn_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64]),
-    "lasr_bn_act_bwd_stats": (_i32, [_p] * 11 + [_i32, _i64, _i64, _i64, _i32, _p, _sz, _p]),
-    "lasr_bn_act_bwd_apply": (_i32, [_p] * 20 + [_i32, _i64, _i64, _i64, _i32, _p, _sz, _p]),
+    "lasr_bn_act_bwd_stats": (_i32, [_p, _p, _sz, _p]),
+    "lasr_bn_act_bwd_apply": (_i32, [_p, _p, _sz, _p]),
     "lasr_bn_bwd_apply_workspace_bytes": (_sz, [_i64]),
     "lasr_reduce_many": (_i32, [_p, _i32, _p]),
     "lasr_gemm_batch_split_partials": (_i32, [_p, _i32, _i32, _i32, _i32, _i32, _p, _sz, _p, _p, _p]),
@@ -90,11 +107,11 @@ SIGNATURES = {
     "lasr_dwconv_plan": (_i32, [_i64, _i64, _i64, _i32, _i32, _i32, _p]),
     "lasr_gemm_batch_partials": (_i32, [_p, _i32, _i32, _i32, _i32, _i32, _p, _sz, _p, _p, _p]),
     "lasr_bn_finalize_partials": (_i32, [_p, _i32, _i64, _i64, C.c_float, C.c_float, _p]),
-    "lasr_bn_act_fwd_partials": (_i32, [_p, _i32, C.c_float, C.c_float, _p, _p, _p, _i32, _i64, _i64, _i64, _i32, _p]),
+    "lasr_bn_act_fwd_partials": (_i32, [_p, _i32, C.c_float, C.c_float, _p, _p, _p]),
     "lasr_seqsum": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _p]),
     "lasr_se_fwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p]),
     "lasr_se_bwd_workspace_bytes": (_sz, [_i64, _i64]),
-    "lasr_se_bwd": (_i32, [_p] * 10 + [_i32, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
+    "lasr_se_bwd": (_i32, [_p, _p, _p, _sz, _p]),
     "lasr_bilstm_saved_bytes": (_sz, [_i64, _i64]),
     "lasr_bilstm_fwd": (_i32, [_p] * 9 + [_i64, _i64, _p, _i32, _i64, _i64, _p, _p]),
     "lasr_bilstm_bwd_workspace_bytes": (_sz, [_i64]),
@@ -170,12 +187,8 @@ SIGNATURES = {
     "lasr_model_backward_continue": (_i32, [_p, _p, _p, _i64, _i64, _p, _p, _sz, _i64, _p]),
     "lasr_mask_lengths_step": (_i32, [_p, _i64, _i64, _p, _p, _p]),
     "lasr_dropout_mask": (_i32, [_p, _i64, _p, _p]),
-    "lasr_bn_act_fwd_drop": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i64, _i64, _i32, _p, _p]),
-    "lasr_bn_act_bwd_stats_drop": (_i32, [_p] * 11 + [_i32, _i64, _i64, _i64, _i32, _p, _p, _sz, _p]),
-    "lasr_bn_act_bwd_apply_drop": (_i32, [_p] * 20 + [_i32, _i64, _i64, _i64, _i32, _p, _p, _sz, _p]),
-    "lasr_se_bwd_drop": (_i32, [_p] * 10 + [_i32, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _sz, _p]),
     "lasr_bn_se_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64]),
-    "lasr_bn_se_bwd": (_i32, [_p] * 26 + [_i32, _i64, _i64, _i64, _i32, _p, _p, _sz, _p]),
+    "lasr_bn_se_bwd": (_i32, [_p, _p, _p, _sz, _p]),
     "lasr_model_set_dropout": (_i32, [_p, _f32, C.c_uint64, _p]),
     "lasr_lr_schedule_state_bytes": (_sz, []),
     "lasr_lr_schedule_init": (_i32, [_p, _sz, _i64, C.c_double, C.c_double, C.c_double, _i64, C.c_double, _i64, _i64, _i64, _i64]),

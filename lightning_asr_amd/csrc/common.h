@@ -178,8 +178,15 @@ struct SeBwdBn {            // the BN side of the fused form (partials == nullpt
   float inv_n; float* tab; float* dgamma; float* dbeta; float* dgamma2; float* dbeta2;
 };
 size_t se_bwd_work_bytes(int64_t B, int64_t C);
-int launch_se_bwd(const float* ds, const SeBwdBn* bn, const float* scale, const float* hidden, const float* pooled, const float* W1,
-                  const float* W2, int64_t B, int64_t T_, int64_t C, float* seg, float* dW1, float* dW2, void* work, hipStream_t st);
+int launch_se_bwd(const float* ds, const SeBwdBn* bn, const lasr_bn_tail& t, const lasr_se_side& se, void* work, hipStream_t st);
+
+// norm.hip: the pointer rules of a lasr_bn_tail, once for every entry point that takes one.  `need`: which fields of a side the
+// entry point reads or writes besides y and coef; the residual side is looked at only when res.y is set (and never needs beta).
+// kBnSums: sums are optional, but reduced sums of the main side need those of the residual side.
+enum { kBnSaved = 1, kBnGamma = 2, kBnBeta = 4, kBnDy = 8, kBnDparams = 16, kBnDout = 32, kBnSeScale = 64, kBnSums = 128 };
+int check_bn_ptrs(const char* who, const lasr_bn_tail* t, int need);
+// the one rule for "no residual branch": without res.y no kernel sees a pointer of that side
+inline lasr_bn_side res_side(const lasr_bn_tail& t) { return t.res.y ? t.res : lasr_bn_side{}; }
 
 // pass 2a: per-channel constants of the backward apply, folded once by C threads:
 //   dy = G*d1 + Bc*y + Cc   with G = gamma*rstd, Bc = -G*rstd*s2/n, Cc = G*(mean*rstd*s2/n - s1/n)

@@ -1725,8 +1725,11 @@ extern "C" int lasr_dwconv_fwd(const void* x, const float* w, const void* addend
   return 0;
 }
 
-int lasr::dwconv_fwd_bn(const void* y, const float* coef, const void* y2, const float* coef2, int act, const float* w, void* out, void* u,
-                        int64_t B, int64_t T, int64_t C, int k, void* stream, const lasr_bn_branch* partials_of, float eps, float momentum) {
+int lasr::dwconv_fwd_bn(const lasr_bn_tail& t, const float* w, void* out, void* u, int k, void* stream, const lasr_bn_branch* partials_of,
+                        float eps, float momentum) {
+  const void *y = t.main.y, *y2 = res_side(t).y;
+  const float *coef = t.main.coef, *coef2 = res_side(t).coef;
+  const int64_t B = t.B, T = t.T, C = t.C;
   LASR_CHECK_ARG(y && coef && w && out && u && (!y2 || coef2), "dwconv_fwd_bn: null pointer");
   LASR_CHECK_SHAPE(!partials_of || C % kCB == 0, "dwconv_fwd_bn: a consumer-side finalize needs C=%lld a multiple of 64", (long long)C);
   if (k < 1 || k > kMaxK || !(k & 1) || C < 8 || T <= 0 || B <= 0 || B >= 65536) return 1;
@@ -1738,7 +1741,7 @@ int lasr::dwconv_fwd_bn(const void* y, const float* coef, const void* y2, const 
   if (!s.fwd || (s.nset == 2 && !full_too)) return 1;
   const dim3 gridm((unsigned)cdiv(C, kCB), (unsigned)B, (unsigned)s.gz_d);
   DwBnIn bn;
-  bn.y = (const bf16_t*)y; bn.y2 = (const bf16_t*)y2; bn.coef = coef; bn.coef2 = coef2; bn.out = (bf16_t*)out; bn.act = act;
+  bn.y = (const bf16_t*)y; bn.y2 = (const bf16_t*)y2; bn.coef = coef; bn.coef2 = coef2; bn.out = (bf16_t*)out; bn.act = t.act;
   memset(&bn.fin, 0, sizeof(bn.fin));
   if (partials_of) LASR_TRY(bn_slice_in(partials_of, y2 ? 2 : 1, B * T, eps, momentum, &bn.fin));
   hipStream_t st = as_stream(stream);

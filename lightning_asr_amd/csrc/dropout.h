@@ -21,6 +21,20 @@ struct DropArgs {
   float inv_keep;                   // 1 / (1 - p)
 };
 
+// public descriptor -> kernel arguments (step == null or p = 0: dropout off)
+inline DropArgs make_drop(const lasr_dropout& d) {
+  DropArgs a;
+  a.step = nullptr; a.seed = 0; a.unit = 0; a.thresh = 0; a.inv_keep = 1.f;
+  if (d.step && d.p > 0.f) {
+    a.step = reinterpret_cast<const unsigned long long*>(d.step);
+    a.seed = d.seed; a.unit = d.unit;
+    const float p = d.p < 0.999f ? d.p : 0.999f;
+    a.thresh = (uint32_t)(p * 65536.f + 0.5f);
+    a.inv_keep = 1.f / (1.f - (float)a.thresh / 65536.f);     // scale by the keep probability actually realised
+  }
+  return a;
+}
+
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
 #pragma unroll
   for (int r = 0; r < 10; ++r) {

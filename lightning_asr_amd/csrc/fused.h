@@ -8,14 +8,14 @@ namespace lasr {
 //   out = act(y a + b [+ y2 a2 + b2])     (bn_act_fwd_kernel's arithmetic: SeprationConv's BatchNorm, the block's residual add and
 //                                          ReLU, models/QuartNet.py:33-37,74-77 - bit-identical to the separate launch)
 //   u   = depthwise_conv(out, w)          (models/QuartNet.py:15-19 of the next unit)
-// coef / coef2: [2][C] (scale | shift) as lasr_bn_finalize_partials leaves them; y2 / coef2 null: no residual branch.
+// `t` is unit i's tail (lasr_bn_tail: y / coef of both sides, act and the shape are read; coef [2][C] (scale | shift) as
+// lasr_bn_finalize_partials leaves them; res.y null: no residual branch).
 // Returns 0 (launched), 1 (this shape takes no fused kernel: nothing was launched, run the two launches) or a negative error.
-// partials_of (null: coef / coef2 are final): the unit's lasr_bn_branch descriptions (one, or two with y2) when its finalize
+// partials_of (null: the coefficients are final): the unit's lasr_bn_branch descriptions (one, or two with res.y) when its finalize
 // was left to its consumer - every workgroup folds the coefficients of its 64 channels from the GEMM's partial sums in its prologue
 // (bn_slice.h) and one workgroup per 64 channels leaves coef / saved / stats / the running statistics in memory.
-int dwconv_fwd_bn(const void* y, const float* coef, const void* y2, const float* coef2, int act, const float* w, void* out, void* u,
-                  int64_t B, int64_t T, int64_t C, int k, void* stream, const lasr_bn_branch* partials_of = nullptr, float eps = 0.f,
-                  float momentum = 0.f);
+int dwconv_fwd_bn(const lasr_bn_tail& t, const float* w, void* out, void* u, int k, void* stream, const lasr_bn_branch* partials_of = nullptr,
+                  float eps = 0.f, float momentum = 0.f);
 // norm.hip: the kernel argument of such a consumer (bn_slice.h) from the public branch descriptions
 struct BnSliceIn;
 int bn_slice_in(const lasr_bn_branch* branches, int n_branches, int64_t n_rows, float eps, float momentum, BnSliceIn* in);
@@ -58,8 +58,9 @@ int head_tail(const float* gl, int64_t rows, int64_t C, void* gl_bf16, int64_t l
 // se.hip (round 5): the excite MLP (lasr_se_fwd's two launches) inside the BN + SE + residual add + activation pass, dealt over
 // (64-channel slab x utterance) workgroups that each recompute their utterance's hidden vector; bit-identical to the three launches.
 // 0 = launched, 1 = not taken (f32, dropout, odd shapes: the caller runs lasr_se_fwd + lasr_bn_act_fwd), negative = error
-int bn_se_act_fwd(const void* y, const float* coef, const void* y2, const float* coef2, const float* sums, const float* W1, const float* W2,
-                  void* out, float* pooled, float* hidden, float* scale, int dtype, int64_t B, int64_t T_, int64_t C, int act, void* stream);
+// Of the tail: y / coef of both sides, dtype, act and the shape (its se_scale is what `scale` receives).
+int bn_se_act_fwd(const lasr_bn_tail& t, const float* sums, const float* W1, const float* W2, void* out, float* pooled, float* hidden,
+                  float* scale, void* stream);
 
 // ctc.hip: the decoder GEMM's split-K reduction (+ bias) and lasr_log_softmax in one launch, for C <= 64 (log_softmax_split_on)
 bool log_softmax_split_on(int64_t C);

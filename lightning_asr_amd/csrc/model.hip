@@ -430,6 +430,29 @@ static inline const void* wptr(const lasr_model* m, const float* params, void* w
   return params + off;
 }
 
+// The tail of unit u, out = act(BN(y) * se + BN_res(y2)) with its dropout and length mask (lasr_bn_tail), as the forward, the
+// hand-over into the next depthwise launch, the SE fold and the backward take it: the one place that knows where a unit's
+// y / coef / saved, its BatchNorm parameters and their gradients live.  grads: null in a forward.  dropping: this step draws masks.
+// The backward adds what only it has: dout, dy of both sides and, under LASR_NO_FUSE, the reduced sums.
+static lasr_bn_tail unit_tail(const lasr_model* m, const Unit& u, const float* params, float* grads, void* ws, bool dropping) {
+  const Plan& p = m->plan;
+  lasr_bn_tail t = {};
+  t.dtype = m->cfg.dtype; t.act = u.act ? m->cfg.act : LASR_ACT_NONE;
+  t.B = p.B; t.T = p.T; t.C = u.co;
+  auto side = [&](size_t o_y, size_t o_coef, size_t o_saved, const BnRef& bn) {
+    lasr_bn_side s = {};
+    s.y = at(ws, o_y); s.coef = atf(ws, o_coef); s.saved = atf(ws, o_saved); s.gamma = params + bn.gamma; s.beta = params + bn.beta;
+    if (grads) { s.dgamma = grads + bn.gamma; s.dbeta = grads + bn.beta; }
+    return s;
+  };
+  t.main = side(u.o_y, u.o_coef, u.o_saved, u.bn);
+  if (u.has_res) t.res = side(u.o_y2, u.o_coef2, u.o_saved2, u.bn_res);
+  if (u.has_se) { t.se_scale = atf(ws, u.o_se_scale); t.se_grad = atf(ws, u.o_se_grad); }
+  if (u.masked) t.row_lens = reinterpret_cast<const int32_t*>(at(ws, p.o_lens));
+  t.dropout = {m->drop_step, m->drop_seed, (uint32_t)(&u - m->units.data()), dropping ? m->drop_p : 0.f};
+  return t;
+}
+
 // The step's depthwise tap tables (fused.h): made by the training forward's first launch, looked up by the depthwise host
 // functions while a model call is in progress on this thread.
 struct DwTapScope {
@@ -542,15 +565,12 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
   lasr_bn_branch owed_br[2];
   auto bn_act_of = [&](const Unit& v) -> int {
     ProfScope ps_bn(LASR_PROF_BN, stream, (double)N * v.co * dtype_size(dt) * (v.has_res ? 3 : 2));
+    const lasr_bn_tail tail = unit_tail(m, v, params, nullptr, ws, dropping);
     if (owed == &v) {
       owed = nullptr;
-      return lasr_bn_act_fwd_partials(owed_br, v.has_res ? 2 : 1, kBnEps, kBnMom, at(ws, v.o_y), v.has_res ? at(ws, v.o_y2) : nullptr,
-                                      at(ws, v.o_out), dt, B, T, v.co, v.act ? m->cfg.act : LASR_ACT_NONE, stream);
+      return lasr_bn_act_fwd_partials(owed_br, v.has_res ? 2 : 1, kBnEps, kBnMom, &tail, at(ws, v.o_out), stream);
     }
-    const lasr_dropout drop = {m->drop_step, m->drop_seed, (uint32_t)(&v - m->units.data()), dropping ? m->drop_p : 0.f};
-    return lasr_bn_act_fwd_drop(at(ws, v.o_y), atf(ws, v.o_coef), v.has_res ? at(ws, v.o_y2) : nullptr,
-                                v.has_res ? atf(ws, v.o_coef2) : nullptr, v.has_se ? atf(ws, v.o_se_scale) : nullptr, at(ws, v.o_out), dt, B,
-                                T, v.co, v.act ? m->cfg.act : LASR_ACT_NONE, dropping ? &drop : nullptr, stream);
+    return lasr_bn_act_fwd(&tail, at(ws, v.o_out), stream);
   };
   RoctxRange rr_fwd(training ? "lasr:forward (training)" : "lasr:forward (eval)");
   for (size_t ui = 0; ui < m->units.size(); ++ui) {
@@ -577,9 +597,8 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
     if (u.has_dw) {
       int fused = 1;
       if (pend) {
-        fused = dwconv_fwd_bn(at(ws, pend->o_y), atf(ws, pend->o_coef), pend->has_res ? at(ws, pend->o_y2) : nullptr,
-                              pend->has_res ? atf(ws, pend->o_coef2) : nullptr, pend->act ? m->cfg.act : LASR_ACT_NONE, params + u.w_dw,
-                              at(ws, pend->o_out), at(ws, u.o_u), B, T, u.ci, u.k, stream, owed == pend ? owed_br : nullptr, kBnEps, kBnMom);
+        fused = dwconv_fwd_bn(unit_tail(m, *pend, params, nullptr, ws, dropping), params + u.w_dw, at(ws, pend->o_out), at(ws, u.o_u), u.k,
+                              stream, owed == pend ? owed_br : nullptr, kBnEps, kBnMom);
         if (fused < 0) return fused;
         if (fused == 0) owed = nullptr;
         if (fused == 1) LASR_TRY(bn_act_of(*pend));     // a shape without the fused kernel: the two launches
@@ -649,9 +668,8 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
       if (!se_sums_done) LASR_TRY(lasr_seqsum(at(ws, u.o_y), dt, B, T, u.co, atf(ws, u.o_se_sum), stream));
       int folded = 1;
       if (training && !dropping && !no_fuse())   // round 5: the excite MLP inside the apply pass (one launch instead of three)
-        folded = bn_se_act_fwd(at(ws, u.o_y), atf(ws, u.o_coef), u.has_res ? at(ws, u.o_y2) : nullptr, u.has_res ? atf(ws, u.o_coef2) : nullptr,
-                               atf(ws, u.o_se_sum), params + u.w_se1, params + u.w_se2, at(ws, u.o_out), atf(ws, u.o_se_pool),
-                               atf(ws, u.o_se_hid), atf(ws, u.o_se_scale), dt, B, T, u.co, u.act ? m->cfg.act : LASR_ACT_NONE, stream);
+        folded = bn_se_act_fwd(unit_tail(m, u, params, nullptr, ws, dropping), atf(ws, u.o_se_sum), params + u.w_se1, params + u.w_se2,
+                               at(ws, u.o_out), atf(ws, u.o_se_pool), atf(ws, u.o_se_hid), atf(ws, u.o_se_scale), stream);
       if (folded < 0 || folded > 1) return folded;
       se_applied = folded == 0;
       if (!se_applied)
@@ -806,47 +824,30 @@ static int backward_from_glogits(lasr_model* m, const float* params, const void*
     const void* x_in = ui > 0 ? at(ws, m->units[ui - 1].o_out) : feats;
     if (u.ctx_before) x_in = at(ws, p.o_cat);
     const int64_t Tx = ui > 0 ? T : T_in;
-    const int act = u.act ? m->cfg.act : LASR_ACT_NONE;
     void* dout = at(ws, p.o_g[cur]);
     // weight-gradient GEMMs batched per stage (the multi-problem kernel loads 16-byte operand rows)
     const bool defer_w = defer && dt == LASR_BF16 && u.co % 8 == 0 && u.ci % 8 == 0;
     void* dy = defer_w ? at(ws, u.o_dy) : at(ws, p.o_d1);
     void* dy2 = u.has_res ? (defer_w ? at(ws, u.o_dy2) : at(ws, p.o_d2)) : nullptr;
-    const float* se_scale = u.has_se ? atf(ws, u.o_se_scale) : nullptr;
-    const float* se_grad = u.has_se ? atf(ws, u.o_se_grad) : nullptr;
-    const lasr_dropout drop = {m->drop_step, m->drop_seed, (uint32_t)ui, m->drop_p};   // the masks of this step's forward
-    const lasr_dropout* dq = m->drop_p > 0.f ? &drop : nullptr;
+    lasr_bn_tail tail = unit_tail(m, u, params, grads, ws, true);   // (dropping: the masks of this step's forward, off at p = 0)
+    tail.dout = dout; tail.main.dy = dy; tail.res.dy = dy2;
     static const bool se_unfused = getenv("LASR_SE_UNFUSED_BWD") != nullptr;    // A/B switch: the three-pass form
     const bool se_fused = u.has_se && !se_unfused && !no_fuse();
     {   // BatchNorm (+ activation, residual add, SE) backward of the unit: two passes over (dout, y[, y2]), writes dy[, dy2]
     ProfScope ps_bn(LASR_PROF_BN, stream, (double)N * u.co * dtype_size(dt) * (u.has_res ? 8 : 5));
+    lasr_se_side se = {};
+    if (u.has_se)
+      se = {atf(ws, u.o_se_hid), atf(ws, u.o_se_pool), atf(ws, u.o_se_sum), params + u.w_se1, params + u.w_se2,
+            atf(ws, u.o_se_grad), grads + u.w_se1, grads + u.w_se2};
     if (se_fused) {
       // SE units: statistics, SE-scale gradient, excite-MLP backward and BN apply in two passes over (dout, y, y2)
-      LASR_TRY(lasr_bn_se_bwd(dout, at(ws, u.o_y), atf(ws, u.o_coef), atf(ws, u.o_saved), params + u.bn.gamma, params + u.bn.beta,
-                              u.has_res ? at(ws, u.o_y2) : nullptr, u.has_res ? atf(ws, u.o_coef2) : nullptr,
-                              u.has_res ? atf(ws, u.o_saved2) : nullptr, u.has_res ? params + u.bn_res.gamma : nullptr, se_scale,
-                              atf(ws, u.o_se_hid), atf(ws, u.o_se_pool), atf(ws, u.o_se_sum), params + u.w_se1, params + u.w_se2,
-                              u.masked ? lens : nullptr, dy, dy2, grads + u.bn.gamma, grads + u.bn.beta,
-                              u.has_res ? grads + u.bn_res.gamma : nullptr, u.has_res ? grads + u.bn_res.beta : nullptr, grads + u.w_se1,
-                              grads + u.w_se2, atf(ws, u.o_se_grad), dt, B, T, u.co, act, dq, scratch, sb, stream));
+      LASR_TRY(lasr_bn_se_bwd(&tail, &se, scratch, sb, stream));
     } else {
-    if (u.has_se)
-      LASR_TRY(lasr_se_bwd_drop(dout, at(ws, u.o_y), atf(ws, u.o_coef), u.has_res ? at(ws, u.o_y2) : nullptr,
-                                u.has_res ? atf(ws, u.o_coef2) : nullptr, se_scale, atf(ws, u.o_se_hid), atf(ws, u.o_se_pool), params + u.w_se1,
-                                params + u.w_se2, dt, B, T, u.co, act, dq, atf(ws, u.o_se_grad), grads + u.w_se1, grads + u.w_se2, scratch, sb,
-                                stream));
+    if (u.has_se) LASR_TRY(lasr_se_bwd(&tail, &se, scratch, sb, stream));
     // fused hand-over: pass 2 reduces pass 1's partial sums (LASR_NO_FUSE=1 keeps the separate reductions, for A/B runs)
-    float* fsum = no_fuse() ? atf(ws, p.o_sums) : nullptr;
-    float* fsum2 = no_fuse() ? atf(ws, p.o_sums2) : nullptr;
-    LASR_TRY(lasr_bn_act_bwd_stats_drop(dout, at(ws, u.o_y), atf(ws, u.o_coef), atf(ws, u.o_saved), u.has_res ? at(ws, u.o_y2) : nullptr,
-                                        u.has_res ? atf(ws, u.o_coef2) : nullptr, u.has_res ? atf(ws, u.o_saved2) : nullptr, se_scale,
-                                        se_grad, fsum, fsum2, dt, B, T, u.co, act, dq, scratch, sb, stream));
-    LASR_TRY(lasr_bn_act_bwd_apply_drop(dout, at(ws, u.o_y), atf(ws, u.o_coef), atf(ws, u.o_saved), params + u.bn.gamma,
-                                        u.has_res ? at(ws, u.o_y2) : nullptr, u.has_res ? atf(ws, u.o_coef2) : nullptr,
-                                        u.has_res ? atf(ws, u.o_saved2) : nullptr, u.has_res ? params + u.bn_res.gamma : nullptr, se_scale,
-                                        se_grad, fsum, fsum2, u.masked ? lens : nullptr, dy, dy2,
-                                        grads + u.bn.gamma, grads + u.bn.beta, u.has_res ? grads + u.bn_res.gamma : nullptr,
-                                        u.has_res ? grads + u.bn_res.beta : nullptr, dt, B, T, u.co, act, dq, scratch, sb, stream));
+    if (no_fuse()) { tail.main.sums = atf(ws, p.o_sums); if (u.has_res) tail.res.sums = atf(ws, p.o_sums2); }
+    LASR_TRY(lasr_bn_act_bwd_stats(&tail, scratch, sb, stream));
+    LASR_TRY(lasr_bn_act_bwd_apply(&tail, scratch, sb, stream));
     }
     }
     // weight gradients of the main and residual 1x1: dW[co][ci] = dy^T gin, dWr = dy2^T x  (one split-K launch)

@@ -856,11 +856,23 @@ __global__ __launch_bounds__(512, WPE) void bn_act_fwd_sliced_kernel(const bf16_
   });
 }
 
+// A/B switches of the channel-sliced kernels, read once per process (the measurements behind each default stand where it is used)
+struct BnSwitches {
+  static int env_int(const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
+  const int sliced = env_int("LASR_BN_SLICED", 256);          // backward pair: workgroups per pass, 0 = the row-major kernels
+  const int apply_split = env_int("LASR_BN_APPLY_SPLIT", 2);  // backward apply: its chunks per chunk of the statistics pass
+  const int fwd_sliced = env_int("LASR_BN_FWD_SLICED", 0);    // forward apply: workgroups, 0 = the default of 256
+};
+static const BnSwitches& bn_switches() {
+  static const BnSwitches s;
+  return s;
+}
+
 // rows per chunk of the sliced forward apply: 256 workgroups, one round of the chip - every workgroup re-reads its slice's partial sums,
 // so more of them only add L2 traffic (cfg2 rows, us per call at 256 / 512 workgroups: C = 512 plain 7.7 / 8.4, residual 10.7 / 15.3;
 // C = 1024 residual 18.6 / 20.8).  LASR_BN_FWD_SLICED=<n> sets the count.  At least one row per row lane in a chunk.
 static int bn_fwd_sliced_rpc(int64_t rows, int64_t C) {
-  static const int forced = getenv("LASR_BN_FWD_SLICED") ? atoi(getenv("LASR_BN_FWD_SLICED")) : 0;
+  const int forced = bn_switches().fwd_sliced;
   const int target = forced > 0 ? forced : 256;
   const int64_t slices = C / kSlCh;
   const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>(target / slices, rows / kSlLanes));
@@ -871,7 +883,7 @@ static int bn_fwd_sliced_rpc(int64_t rows, int64_t C) {
 // statistics kernel holds 222 registers per lane): 256 workgroups measured best at cfg2 (128: 2.339, 192: 2.298, 256: 2.262,
 // 384: 2.447, 512: 2.419 ms per step; row-major pair with its table launch: 2.372).  LASR_BN_SLICED=<n> sets the count, 0 disables.
 static int bn_sliced_rpc(int dtype, int64_t rows, int64_t C, bool se, bool drop, int per_utt, bool reduced_sums) {
-  static const int target = getenv("LASR_BN_SLICED") ? atoi(getenv("LASR_BN_SLICED")) : 256;
+  const int target = bn_switches().sliced;
   if (target <= 0 || dtype != LASR_BF16 || se || drop || per_utt || reduced_sums || C % kSlCh != 0 || rows < 4096) return 0;
   const int64_t slices = C / kSlCh;
   // at least one row per row lane in a chunk: the partial rows ([nchunk][4][C]) then also fit the workspace the row-major pair
@@ -884,42 +896,12 @@ static int bn_sliced_rpc(int dtype, int64_t rows, int64_t C, bool se, bool drop,
 
 using namespace lasr;
 
-extern "C" int lasr_bn_act_bwd_stats_drop(const void* dout, const void* y, const float* coef, const float* saved, const void* y2,
-                                          const float* coef2, const float* saved2, const float* se_scale, const float* se_grad,
-                                          float* sums, float* sums2, int dtype, int64_t B, int64_t T_, int64_t C, int act,
-                                          const lasr_dropout* dropout, void* workspace, size_t workspace_bytes, void* stream);
-extern "C" int lasr_bn_act_bwd_apply_drop(const void* dout, const void* y, const float* coef, const float* saved,
-                                          const float* gamma, const void* y2, const float* coef2, const float* saved2,
-                                          const float* gamma2, const float* se_scale, const float* se_grad, const float* sums,
-                                          const float* sums2, const int32_t* row_lens, void* dy, void* dy2, float* dgamma,
-                                          float* dbeta, float* dgamma2, float* dbeta2, int dtype, int64_t B, int64_t T_, int64_t C,
-                                          int act, const lasr_dropout* dropout, void* workspace, size_t workspace_bytes, void* stream);
-
-static int bn_bwd_stats_impl(const void* dout, const void* y, const float* coef, const float* saved, const void* y2,
-                             const float* coef2, const float* saved2, const float* se_scale, const float* se_grad,
-                             float* sums, float* sums2, int dtype, int64_t B, int64_t T_, int64_t C, int act,
-                             const lasr_dropout* dropout, void* workspace, size_t workspace_bytes, void* stream, int per_utt);
-
 // dtype x HAS2 x SE x DROP - the template head of the three row-slab kernels - as four tags inside f
 template <typename F>
 static void with_bn_variant(int dtype, bool has2, bool se, bool drop, F&& f) {
   with_dtype(dtype, [&](auto t) {
     with_bool(has2, [&](auto h2) { with_bool(se, [&](auto s) { with_bool(drop, [&](auto d) { f(t, h2, s, d); }); }); });
   });
-}
-
-// public descriptor -> kernel arguments (p = 0 or a null descriptor: dropout off)
-static DropArgs make_drop(const lasr_dropout* d) {
-  DropArgs a;
-  a.step = nullptr; a.seed = 0; a.unit = 0; a.thresh = 0; a.inv_keep = 1.f;
-  if (d && d->step && d->p > 0.f) {
-    a.step = reinterpret_cast<const unsigned long long*>(d->step);
-    a.seed = d->seed; a.unit = d->unit;
-    const float p = d->p < 0.999f ? d->p : 0.999f;
-    a.thresh = (uint32_t)(p * 65536.f + 0.5f);
-    a.inv_keep = 1.f / (1.f - (float)a.thresh / 65536.f);     // scale by the keep probability actually realised
-  }
-  return a;
 }
 
 extern "C" int lasr_bct_to_btc(const float* in, void* out, int dtype, int64_t B, int64_t C, int64_t T_, void* stream) {
@@ -986,7 +968,7 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(DropArgs d, int64_t n
 }  // namespace lasr
 extern "C" int lasr_dropout_mask(const lasr_dropout* dropout, int64_t n, uint8_t* keep, void* stream) {
   LASR_CHECK_ARG(dropout && keep && n > 0 && n < ((int64_t)1 << 34), "lasr_dropout_mask: bad argument");
-  hipLaunchKernelGGL(lasr::dropout_mask_kernel, dim3((unsigned)cdiv(cdiv(n, 8), 256)), dim3(256), 0, as_stream(stream), make_drop(dropout), n, keep);
+  hipLaunchKernelGGL(lasr::dropout_mask_kernel, dim3((unsigned)cdiv(cdiv(n, 8), 256)), dim3(256), 0, as_stream(stream), make_drop(*dropout), n, keep);
   LASR_LAUNCH_CHECK("dropout_mask_kernel");
   return 0;
 }
@@ -1026,26 +1008,40 @@ static int check_bn_shape(const char* who, int dtype, int64_t B, int64_t T_, int
   return 0;
 }
 
-extern "C" int lasr_bn_act_fwd_drop(const void* y, const float* coef, const void* y2, const float* coef2, const float* se_scale,
-                                    void* out, int dtype, int64_t B, int64_t T_, int64_t C, int act, const lasr_dropout* dropout,
-                                    void* stream) {
-  LASR_CHECK_ARG(y && coef && out && (!y2 || coef2), "lasr_bn_act_fwd: null pointer");
-  LASR_TRY(check_bn_shape("lasr_bn_act_fwd", dtype, B, T_, C));
-  const DropArgs da = make_drop(dropout);
-  const int64_t rows = B * T_;
-  const size_t shmem = (size_t)4 * C * sizeof(float);
-  with_bn_variant(dtype, y2 != nullptr, se_scale != nullptr, da.step != nullptr, [&](auto t, auto h2, auto se, auto drop) {
-    using T = typename decltype(t)::type;
+// ---- lasr_bn_tail (include/lasr.h): checked once per entry point, unpacked into the kernels' argument lists -------------------------
+static bool bn_side_ok(const lasr_bn_side& s, int need) {
+  return s.coef && (!(need & kBnSaved) || s.saved) && (!(need & kBnGamma) || s.gamma) && (!(need & kBnBeta) || s.beta) &&
+         (!(need & kBnDy) || s.dy) && (!(need & kBnDparams) || (s.dgamma && s.dbeta));
+}
+int lasr::check_bn_ptrs(const char* who, const lasr_bn_tail* t, int need) {
+  LASR_CHECK_ARG(t && t->main.y && bn_side_ok(t->main, need) && (!(need & kBnDout) || t->dout) && (!(need & kBnSeScale) || t->se_scale),
+                 "%s: null pointer", who);
+  LASR_CHECK_ARG(!t->res.y || (bn_side_ok(t->res, need & ~kBnBeta) && (!(need & kBnSums) || t->res.sums || !t->main.sums)),
+                 "%s: branch-2 pointers", who);
+  return 0;
+}
+// `buf`: the entry point's output or workspace
+static int check_bn_tail(const char* who, const lasr_bn_tail* t, int need, const void* buf) {
+  LASR_TRY(check_bn_ptrs(who, t, need));
+  LASR_CHECK_ARG(buf, "%s: null pointer", who);
+  return check_bn_shape(who, t->dtype, t->B, t->T, t->C);
+}
+
+extern "C" int lasr_bn_act_fwd(const lasr_bn_tail* tail, void* out, void* stream) {
+  LASR_TRY(check_bn_tail("lasr_bn_act_fwd", tail, 0, out));
+  const lasr_bn_tail& t = *tail;
+  const lasr_bn_side r = res_side(t);
+  const DropArgs da = make_drop(t.dropout);
+  const int64_t rows = t.B * t.T;
+  const size_t shmem = (size_t)4 * t.C * sizeof(float);
+  with_bn_variant(t.dtype, r.y != nullptr, t.se_scale != nullptr, da.step != nullptr, [&](auto e, auto h2, auto se, auto drop) {
+    using T = typename decltype(e)::type;
     hipLaunchKernelGGL((bn_act_fwd_kernel<T, h2.value, se.value, drop.value>), dim3((unsigned)cdiv(rows, kFwdSlabRows)), dim3(256), shmem,
-                       as_stream(stream), (const T*)y, coef, (const T*)y2, coef2, se_scale, (T*)out, (int)rows, (int)T_, (int)C, act, da);
+                       as_stream(stream), (const T*)t.main.y, t.main.coef, (const T*)r.y, r.coef, t.se_scale, (T*)out, (int)rows, (int)t.T,
+                       (int)t.C, t.act, da);
   });
   LASR_LAUNCH_CHECK("bn_act_fwd_kernel");
   return 0;
-}
-
-extern "C" int lasr_bn_act_fwd(const void* y, const float* coef, const void* y2, const float* coef2, const float* se_scale,
-                               void* out, int dtype, int64_t B, int64_t T_, int64_t C, int act, void* stream) {
-  return lasr_bn_act_fwd_drop(y, coef, y2, coef2, se_scale, out, dtype, B, T_, C, act, nullptr, stream);
 }
 
 // host side of BnSliceIn (bn_slice.h): the public branch descriptions of a unit whose finalize is left to its consumer
@@ -1061,21 +1057,22 @@ int lasr::bn_slice_in(const lasr_bn_branch* branches, int n_branches, int64_t n_
   return 0;
 }
 
-extern "C" int lasr_bn_act_fwd_partials(const lasr_bn_branch* branches, int n_branches, float eps, float momentum, const void* y,
-                                        const void* y2, void* out, int dtype, int64_t B, int64_t T_, int64_t C, int act, void* stream) {
-  LASR_CHECK_ARG(y && out && n_branches == (y2 ? 2 : 1), "lasr_bn_act_fwd_partials: bad argument");
-  LASR_TRY(check_bn_shape("lasr_bn_act_fwd_partials", dtype, B, T_, C));
-  LASR_CHECK_SHAPE(dtype == LASR_BF16 && C % kSlCh == 0, "lasr_bn_act_fwd_partials: bf16 and C=%lld a multiple of 64 only", (long long)C);
+extern "C" int lasr_bn_act_fwd_partials(const lasr_bn_branch* branches, int n_branches, float eps, float momentum, const lasr_bn_tail* tail,
+                                        void* out, void* stream) {
+  LASR_CHECK_ARG(tail && tail->main.y && out && n_branches == (tail->res.y ? 2 : 1), "lasr_bn_act_fwd_partials: bad argument");
+  const void *y = tail->main.y, *y2 = tail->res.y;
+  const int64_t C = tail->C, rows = tail->B * tail->T;
+  LASR_TRY(check_bn_shape("lasr_bn_act_fwd_partials", tail->dtype, tail->B, tail->T, C));
+  LASR_CHECK_SHAPE(tail->dtype == LASR_BF16 && C % kSlCh == 0, "lasr_bn_act_fwd_partials: bf16 and C=%lld a multiple of 64 only", (long long)C);
   LASR_CHECK_ARG(reinterpret_cast<uintptr_t>(y) % 16 == 0 && reinterpret_cast<uintptr_t>(y2) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0,
                  "lasr_bn_act_fwd_partials: 16-byte alignment");
-  const int64_t rows = B * T_;
   BnSliceIn in;
   LASR_TRY(bn_slice_in(branches, n_branches, rows, eps, momentum, &in));
   const int rpc = bn_fwd_sliced_rpc(rows, C);
   const dim3 grid((unsigned)(C / kSlCh), (unsigned)cdiv(rows, rpc));
   with_bool(y2 != nullptr, [&](auto h2) {
     hipLaunchKernelGGL((bn_act_fwd_sliced_kernel<decltype(h2)::value>), grid, dim3(kSlThreads), 0, as_stream(stream), (const bf16_t*)y,
-                       (const bf16_t*)y2, in, (bf16_t*)out, (int)rows, (int)C, act, rpc);
+                       (const bf16_t*)y2, in, (bf16_t*)out, (int)rows, (int)C, tail->act, rpc);
   });
   LASR_LAUNCH_CHECK("bn_act_fwd_sliced_kernel");
   return 0;
@@ -1086,145 +1083,128 @@ extern "C" size_t lasr_bn_bwd_workspace_bytes(int64_t B, int64_t T_, int64_t C) 
   return (size_t)cdiv(B * T_, kRowsPerBlock) * 4 * C * sizeof(float) + (size_t)10 * C * sizeof(float);
 }
 
-extern "C" int lasr_bn_act_bwd_stats(const void* dout, const void* y, const float* coef, const float* saved, const void* y2,
-                                     const float* coef2, const float* saved2, const float* se_scale, const float* se_grad,
-                                     float* sums, float* sums2, int dtype, int64_t B, int64_t T_, int64_t C, int act,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
-  return lasr_bn_act_bwd_stats_drop(dout, y, coef, saved, y2, coef2, saved2, se_scale, se_grad, sums, sums2, dtype, B, T_, C, act, nullptr,
-                                    workspace, workspace_bytes, stream);
-}
-
-extern "C" int lasr_bn_act_bwd_stats_drop(const void* dout, const void* y, const float* coef, const float* saved, const void* y2,
-                                          const float* coef2, const float* saved2, const float* se_scale, const float* se_grad,
-                                          float* sums, float* sums2, int dtype, int64_t B, int64_t T_, int64_t C, int act,
-                                          const lasr_dropout* dropout, void* workspace, size_t workspace_bytes, void* stream) {
-  return bn_bwd_stats_impl(dout, y, coef, saved, y2, coef2, saved2, se_scale, se_grad, sums, sums2, dtype, B, T_, C, act, dropout, workspace,
-                           workspace_bytes, stream, 0);
-}
-
-// per_utt = 1: partials [B * ceil(T/32)][4][C] of the raw sums, one workgroup per (utterance, 32-frame slab) (see the kernel)
-static int bn_bwd_stats_impl(const void* dout, const void* y, const float* coef, const float* saved, const void* y2,
-                             const float* coef2, const float* saved2, const float* se_scale, const float* se_grad,
-                             float* sums, float* sums2, int dtype, int64_t B, int64_t T_, int64_t C, int act,
-                             const lasr_dropout* dropout, void* workspace, size_t workspace_bytes, void* stream, int per_utt) {
-  const DropArgs da = make_drop(dropout);
-  LASR_CHECK_ARG(dout && y && coef && saved && workspace, "lasr_bn_act_bwd_stats: null pointer");
-  LASR_CHECK_ARG(!y2 || (coef2 && saved2 && (sums2 || !sums)), "lasr_bn_act_bwd_stats: branch-2 pointers");
-  LASR_TRY(check_bn_shape("lasr_bn_act_bwd_stats", dtype, B, T_, C));
-  const int64_t rows = B * T_;
-  const int nblk = per_utt ? (int)(B * cdiv(T_, kRowsPerBlock)) : (int)cdiv(rows, kRowsPerBlock);
-  if (workspace_bytes < (size_t)nblk * 4 * C * sizeof(float)) return fail(LASR_E_WORKSPACE, "lasr_bn_act_bwd_stats: workspace");
-  if (const int rpc = bn_sliced_rpc(dtype, rows, C, se_scale != nullptr, da.step != nullptr, per_utt, sums != nullptr)) {
+// Pass 1 of a checked tail into `partials`: [ceil(B*T/32)][4][C], or per_utt = 1: [B * ceil(T/32)][4][C] of the raw sums, one
+// workgroup per (utterance, 32-frame slab) (see the kernel)
+static int bn_bwd_stats_impl(const lasr_bn_tail& t, float* partials, void* stream, int per_utt) {
+  const lasr_bn_side &m = t.main, r = res_side(t);
+  const DropArgs da = make_drop(t.dropout);
+  const int64_t C = t.C, rows = t.B * t.T;
+  const int nblk = per_utt ? (int)(t.B * cdiv(t.T, kRowsPerBlock)) : (int)cdiv(rows, kRowsPerBlock);
+  if (const int rpc = bn_sliced_rpc(t.dtype, rows, C, t.se_scale != nullptr, da.step != nullptr, per_utt, m.sums != nullptr)) {
     const dim3 grid((unsigned)(C / kSlCh), (unsigned)cdiv(rows, rpc));
-    float* partials = reinterpret_cast<float*>(workspace);
-    with_bool(y2 != nullptr, [&](auto h2) {
+    with_bool(r.y != nullptr, [&](auto h2) {
       with_bool((nt_loads_mask() & 1) != 0, [&](auto nt) {
         hipLaunchKernelGGL((bn_bwd_stats_sliced_kernel<decltype(h2)::value, false, decltype(nt)::value>), grid, dim3(kSlThreads), 0,
-                           as_stream(stream), (const bf16_t*)dout, (const bf16_t*)y, coef, saved, (const bf16_t*)y2, coef2, saved2, nullptr,
-                           partials, (int)rows, (int)C, act, rpc);
+                           as_stream(stream), (const bf16_t*)t.dout, (const bf16_t*)m.y, m.coef, m.saved, (const bf16_t*)r.y, r.coef, r.saved,
+                           nullptr, partials, (int)rows, (int)C, t.act, rpc);
       });
     });
     LASR_LAUNCH_CHECK("bn_bwd_stats_sliced_kernel");
     return 0;
   }
-  const int cv = (int)(C / (dtype == LASR_F32 ? 4 : 8));
+  const int cv = (int)(C / (t.dtype == LASR_F32 ? 4 : 8));
   const int col_threads = cv < 256 ? cv : 256;
   const int row_lanes = 256 / col_threads;
   const size_t shmem = (size_t)row_lanes * 4 * C * sizeof(float);
   LASR_CHECK_SHAPE(shmem <= 64 * 1024, "lasr_bn_act_bwd_stats: C too large for LDS staging");
-  float* partials = reinterpret_cast<float*>(workspace);
-  with_bn_variant(dtype, y2 != nullptr, se_scale != nullptr, da.step != nullptr, [&](auto t, auto h2, auto se, auto drop) {
-    using T = typename decltype(t)::type;
+  with_bn_variant(t.dtype, r.y != nullptr, t.se_scale != nullptr, da.step != nullptr, [&](auto e, auto h2, auto se, auto drop) {
+    using T = typename decltype(e)::type;
     hipLaunchKernelGGL((bn_bwd_stats_kernel<T, h2.value, se.value, drop.value>), dim3(nblk), dim3(256), shmem, as_stream(stream),
-                       (const T*)dout, (const T*)y, coef, saved, (const T*)y2, coef2, saved2, se_scale, se_grad, partials, (int)rows,
-                       (int)T_, (int)C, act, da, per_utt);
+                       (const T*)t.dout, (const T*)m.y, m.coef, m.saved, (const T*)r.y, r.coef, r.saved, t.se_scale, t.se_grad, partials,
+                       (int)rows, (int)t.T, (int)C, t.act, da, per_utt);
   });
   LASR_LAUNCH_CHECK("bn_bwd_stats_kernel");
-  if (!sums) return 0;   // partials stay in the workspace for lasr_bn_act_bwd_apply(sums = NULL)
-  return launch_reduce_partials(partials, nblk, 4 * C, sums, 2 * C, sums2, as_stream(stream));
+  if (!m.sums) return 0;   // partials stay in the workspace for lasr_bn_act_bwd_apply(sums = NULL)
+  return launch_reduce_partials(partials, nblk, 4 * C, m.sums, 2 * C, r.sums, as_stream(stream));
+}
+
+extern "C" int lasr_bn_act_bwd_stats(const lasr_bn_tail* tail, void* workspace, size_t workspace_bytes, void* stream) {
+  LASR_TRY(check_bn_tail("lasr_bn_act_bwd_stats", tail, kBnDout | kBnSaved | kBnSums, workspace));
+  if (workspace_bytes < (size_t)cdiv(tail->B * tail->T, kRowsPerBlock) * 4 * tail->C * sizeof(float))
+    return fail(LASR_E_WORKSPACE, "lasr_bn_act_bwd_stats: workspace");
+  return bn_bwd_stats_impl(*tail, reinterpret_cast<float*>(workspace), stream, 0);
 }
 
 extern "C" size_t lasr_bn_bwd_apply_workspace_bytes(int64_t C) { return (size_t)10 * C * sizeof(float); }
 
-extern "C" int lasr_bn_act_bwd_apply(const void* dout, const void* y, const float* coef, const float* saved,
-                                     const float* gamma, const void* y2, const float* coef2, const float* saved2,
-                                     const float* gamma2, const float* se_scale, const float* se_grad, const float* sums,
-                                     const float* sums2, const int32_t* row_lens, void* dy, void* dy2, float* dgamma,
-                                     float* dbeta, float* dgamma2, float* dbeta2, int dtype, int64_t B, int64_t T_, int64_t C,
-                                     int act, void* workspace, size_t workspace_bytes, void* stream) {
-  return lasr_bn_act_bwd_apply_drop(dout, y, coef, saved, gamma, y2, coef2, saved2, gamma2, se_scale, se_grad, sums, sums2, row_lens, dy, dy2,
-                                    dgamma, dbeta, dgamma2, dbeta2, dtype, B, T_, C, act, nullptr, workspace, workspace_bytes, stream);
+// Pass 2 of the channel-sliced pair from the statistics pass's partial rows (chunks of rpc rows) in the workspace
+static int launch_bn_bwd_apply_sliced(const lasr_bn_tail& t, int rpc, const float* partials, hipStream_t st) {
+  const lasr_bn_side &m = t.main, r = res_side(t);
+  const int64_t C = t.C, rows = t.B * t.T;
+  const int nchunk = (int)cdiv(rows, rpc);          // partial rows of the statistics pass
+  // The apply pass takes row chunks HALF as long as the statistics pass (LASR_BN_APPLY_SPLIT = 2; 1: the same chunks): 512
+  // workgroups with one row in flight per thread in 121 registers, so two are resident per CU and their load, arithmetic and
+  // store phases interleave - against one round of 256 workgroups that are all in the same phase at the same time.  Measured in
+  // the cfg2 step, one call: split 1 / 2 / 3 / 4 = 2.228 / 2.191 / 2.220 / 2.235 ms.  (The statistics pass does not gain from the
+  // same treatment: 2.219 with both split against 2.198.)  The arithmetic per element is unchanged.
+  const int asplit = bn_switches().apply_split;
+  // rb = rows in flight per thread, wpe = workgroups per CU the kernel is bounded for: (1, 4) on the half chunks, (2, 2) on whole ones
+  auto launch = [&](auto rb, auto wpe, int rows_per_chunk) {
+    const dim3 grid((unsigned)(C / kSlCh), (unsigned)cdiv(rows, rows_per_chunk));
+    with_bool(r.y != nullptr, [&](auto h2) {
+      with_bool((nt_loads_mask() & 2) != 0, [&](auto nt) {
+        constexpr bool H2 = decltype(h2)::value, NT = decltype(nt)::value;
+        hipLaunchKernelGGL((bn_bwd_apply_sliced_kernel<H2, false, decltype(rb)::value, decltype(wpe)::value, NT>), grid, dim3(kSlThreads),
+                           0, st, (const bf16_t*)t.dout, (const bf16_t*)m.y, (const bf16_t*)r.y, partials, nchunk, nullptr, nullptr, nullptr,
+                           m.coef, m.saved, m.gamma, r.coef, r.saved, r.gamma, 1.0f / (float)rows, t.row_lens, (bf16_t*)m.dy,
+                           (bf16_t*)r.dy, m.dgamma, m.dbeta, r.dgamma, r.dbeta, (int)rows, (int)t.T, (int)C, t.act, rows_per_chunk);
+      });
+    });
+  };
+  const int rpc2 = asplit > 1 ? (int)cdiv(rows, (int64_t)nchunk * asplit) : rpc;
+  if (asplit > 1 && rpc2 >= kSlLanes) launch(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{}, rpc2);
+  else launch(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, rpc);
+  LASR_LAUNCH_CHECK("bn_bwd_apply_sliced_kernel");
+  return 0;
 }
 
-extern "C" int lasr_bn_act_bwd_apply_drop(const void* dout, const void* y, const float* coef, const float* saved,
-                                          const float* gamma, const void* y2, const float* coef2, const float* saved2,
-                                          const float* gamma2, const float* se_scale, const float* se_grad, const float* sums,
-                                          const float* sums2, const int32_t* row_lens, void* dy, void* dy2, float* dgamma,
-                                          float* dbeta, float* dgamma2, float* dbeta2, int dtype, int64_t B, int64_t T_, int64_t C,
-                                          int act, const lasr_dropout* dropout, void* workspace, size_t workspace_bytes, void* stream) {
-  const DropArgs da = make_drop(dropout);
-  LASR_CHECK_ARG(dout && y && coef && saved && gamma && dy && workspace, "lasr_bn_act_bwd_apply: null pointer");
-  LASR_CHECK_ARG(!y2 || (coef2 && saved2 && gamma2 && (sums2 || !sums) && dy2), "lasr_bn_act_bwd_apply: branch-2 pointers");
-  LASR_TRY(check_bn_shape("lasr_bn_act_bwd_apply", dtype, B, T_, C));
-  const int64_t rows = B * T_;
-  hipStream_t st = as_stream(stream);
-  if (const int rpc = bn_sliced_rpc(dtype, rows, C, se_scale != nullptr, da.step != nullptr, 0, sums != nullptr)) {
-    if (workspace_bytes < lasr_bn_bwd_workspace_bytes(B, T_, C)) return fail(LASR_E_WORKSPACE, "lasr_bn_act_bwd_apply: workspace");
-    LASR_CHECK_ARG(dgamma && dbeta && (!y2 || (dgamma2 && dbeta2)), "lasr_bn_act_bwd_apply: parameter-gradient pointers");
-    const int nchunk = (int)cdiv(rows, rpc);          // partial rows of the statistics pass
-    const float* partials = reinterpret_cast<const float*>(workspace);
-    // The apply pass takes row chunks HALF as long as the statistics pass (LASR_BN_APPLY_SPLIT = 2; 1: the same chunks): 512
-    // workgroups with one row in flight per thread in 121 registers, so two are resident per CU and their load, arithmetic and
-    // store phases interleave - against one round of 256 workgroups that are all in the same phase at the same time.  Measured in
-    // the cfg2 step, one call: split 1 / 2 / 3 / 4 = 2.228 / 2.191 / 2.220 / 2.235 ms.  (The statistics pass does not gain from the
-    // same treatment: 2.219 with both split against 2.198.)  The arithmetic per element is unchanged.
-    static const int asplit = getenv("LASR_BN_APPLY_SPLIT") ? atoi(getenv("LASR_BN_APPLY_SPLIT")) : 2;
-    // rb = rows in flight per thread, wpe = workgroups per CU the kernel is bounded for: (1, 4) on the half chunks, (2, 2) on whole ones
-    auto launch = [&](auto rb, auto wpe, int rows_per_chunk) {
-      const dim3 grid((unsigned)(C / kSlCh), (unsigned)cdiv(rows, rows_per_chunk));
-      with_bool(y2 != nullptr, [&](auto h2) {
-        with_bool((nt_loads_mask() & 2) != 0, [&](auto nt) {
-          constexpr bool H2 = decltype(h2)::value, NT = decltype(nt)::value;
-          hipLaunchKernelGGL((bn_bwd_apply_sliced_kernel<H2, false, decltype(rb)::value, decltype(wpe)::value, NT>), grid, dim3(kSlThreads),
-                             0, st, (const bf16_t*)dout, (const bf16_t*)y, (const bf16_t*)y2, partials, nchunk, nullptr, nullptr, nullptr,
-                             coef, saved, gamma, coef2, saved2, gamma2, 1.0f / (float)rows, row_lens, (bf16_t*)dy, (bf16_t*)dy2, dgamma,
-                             dbeta, dgamma2, dbeta2, (int)rows, (int)T_, (int)C, act, rows_per_chunk);
-        });
-      });
-    };
-    const int rpc2 = asplit > 1 ? (int)cdiv(rows, (int64_t)nchunk * asplit) : rpc;
-    if (asplit > 1 && rpc2 >= kSlLanes) launch(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{}, rpc2);
-    else launch(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, rpc);
-    LASR_LAUNCH_CHECK("bn_bwd_apply_sliced_kernel");
-    return 0;
-  }
-  float* tab;
-  if (sums) {
-    if (workspace_bytes < lasr_bn_bwd_apply_workspace_bytes(C)) return fail(LASR_E_WORKSPACE, "lasr_bn_act_bwd_apply: workspace");
-    tab = reinterpret_cast<float*>(workspace);
-    hipLaunchKernelGGL(bn_bwd_table_kernel, dim3((unsigned)cdiv(C, 256)), dim3(256), 0, st, coef, saved, gamma, sums, y2 ? coef2 : nullptr,
-                       saved2, gamma2, sums2, 1.0f / (float)rows, (int)C, tab, dgamma, dbeta, dgamma2, dbeta2);
-    LASR_LAUNCH_CHECK("bn_bwd_table_kernel");
-  } else {
-    // the workspace of the preceding lasr_bn_act_bwd_stats(sums = NULL): unreduced partials, then room for the table
-    if (workspace_bytes < lasr_bn_bwd_workspace_bytes(B, T_, C)) return fail(LASR_E_WORKSPACE, "lasr_bn_act_bwd_apply: workspace");
-    const int nblk = (int)cdiv(rows, kRowsPerBlock);
-    const float* partials = reinterpret_cast<const float*>(workspace);
-    tab = reinterpret_cast<float*>(workspace) + (size_t)nblk * 4 * C;
-    hipLaunchKernelGGL(bn_bwd_table_partials_kernel, dim3((unsigned)cdiv(C, 8)), dim3(1024), 0, st, partials, nblk, coef, saved, gamma,
-                       y2 ? coef2 : nullptr, saved2, gamma2, 1.0f / (float)rows, (int)C, tab, dgamma, dbeta, dgamma2, dbeta2);
-    LASR_LAUNCH_CHECK("bn_bwd_table_partials_kernel");
-  }
-  const size_t shmem = (size_t)10 * C * sizeof(float);
-  LASR_CHECK_SHAPE(shmem <= 64 * 1024, "lasr_bn_act_bwd_apply: C too large for the LDS coefficient table");
-  with_bn_variant(dtype, y2 != nullptr, se_scale != nullptr, da.step != nullptr, [&](auto t, auto h2, auto se, auto drop) {
-    using T = typename decltype(t)::type;
+// Pass 2 of the row-major pair from the folded table: dy = G*(d*se + se_grad) + Bc*y + Cc, dy2 = G2*d + ...  (lasr_bn_act_bwd_apply and
+// lasr_bn_se_bwd)
+static int launch_bn_bwd_apply(const char* who, const lasr_bn_tail& t, const float* tab, hipStream_t st) {
+  const lasr_bn_side r = res_side(t);
+  const DropArgs da = make_drop(t.dropout);
+  const int64_t rows = t.B * t.T;
+  const size_t shmem = (size_t)10 * t.C * sizeof(float);
+  LASR_CHECK_SHAPE(shmem <= 64 * 1024, "%s: C too large for the LDS coefficient table", who);
+  with_bn_variant(t.dtype, r.y != nullptr, t.se_scale != nullptr, da.step != nullptr, [&](auto e, auto h2, auto se, auto drop) {
+    using T = typename decltype(e)::type;
     hipLaunchKernelGGL((bn_bwd_apply_kernel<T, h2.value, se.value, drop.value>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem,
-                       st, (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, se_grad, row_lens, (T*)dy, (T*)dy2, (int)rows, (int)T_,
-                       (int)C, act, da);
+                       st, (const T*)t.dout, (const T*)t.main.y, (const T*)r.y, tab, t.se_scale, t.se_grad, t.row_lens, (T*)t.main.dy,
+                       (T*)r.dy, (int)rows, (int)t.T, (int)t.C, t.act, da);
   });
   LASR_LAUNCH_CHECK("bn_bwd_apply_kernel");
   return 0;
+}
+
+extern "C" int lasr_bn_act_bwd_apply(const lasr_bn_tail* tail, void* workspace, size_t workspace_bytes, void* stream) {
+  LASR_TRY(check_bn_tail("lasr_bn_act_bwd_apply", tail, kBnDout | kBnSaved | kBnGamma | kBnDy | kBnSums, workspace));
+  const lasr_bn_tail& t = *tail;
+  const lasr_bn_side &m = t.main, r = res_side(t);
+  const int64_t C = t.C, rows = t.B * t.T;
+  hipStream_t st = as_stream(stream);
+  if (const int rpc = bn_sliced_rpc(t.dtype, rows, C, t.se_scale != nullptr, make_drop(t.dropout).step != nullptr, 0, m.sums != nullptr)) {
+    if (workspace_bytes < lasr_bn_bwd_workspace_bytes(t.B, t.T, C)) return fail(LASR_E_WORKSPACE, "lasr_bn_act_bwd_apply: workspace");
+    LASR_CHECK_ARG(m.dgamma && m.dbeta && (!r.y || (r.dgamma && r.dbeta)), "lasr_bn_act_bwd_apply: parameter-gradient pointers");
+    return launch_bn_bwd_apply_sliced(t, rpc, reinterpret_cast<const float*>(workspace), st);
+  }
+  float* tab;
+  if (m.sums) {
+    if (workspace_bytes < lasr_bn_bwd_apply_workspace_bytes(C)) return fail(LASR_E_WORKSPACE, "lasr_bn_act_bwd_apply: workspace");
+    tab = reinterpret_cast<float*>(workspace);
+    hipLaunchKernelGGL(bn_bwd_table_kernel, dim3((unsigned)cdiv(C, 256)), dim3(256), 0, st, m.coef, m.saved, m.gamma, m.sums, r.coef,
+                       r.saved, r.gamma, r.sums, 1.0f / (float)rows, (int)C, tab, m.dgamma, m.dbeta, r.dgamma, r.dbeta);
+    LASR_LAUNCH_CHECK("bn_bwd_table_kernel");
+  } else {
+    // the workspace of the preceding lasr_bn_act_bwd_stats(sums = NULL): unreduced partials, then room for the table
+    if (workspace_bytes < lasr_bn_bwd_workspace_bytes(t.B, t.T, C)) return fail(LASR_E_WORKSPACE, "lasr_bn_act_bwd_apply: workspace");
+    const int nblk = (int)cdiv(rows, kRowsPerBlock);
+    const float* partials = reinterpret_cast<const float*>(workspace);
+    tab = reinterpret_cast<float*>(workspace) + (size_t)nblk * 4 * C;
+    hipLaunchKernelGGL(bn_bwd_table_partials_kernel, dim3((unsigned)cdiv(C, 8)), dim3(1024), 0, st, partials, nblk, m.coef, m.saved, m.gamma,
+                       r.coef, r.saved, r.gamma, 1.0f / (float)rows, (int)C, tab, m.dgamma, m.dbeta, r.dgamma, r.dbeta);
+    LASR_LAUNCH_CHECK("bn_bwd_table_partials_kernel");
+  }
+  return launch_bn_bwd_apply("lasr_bn_act_bwd_apply", t, tab, st);
 }
 
 extern "C" size_t lasr_bn_se_bwd_workspace_bytes(int64_t B, int64_t T_, int64_t C) {
@@ -1235,17 +1215,17 @@ extern "C" size_t lasr_bn_se_bwd_workspace_bytes(int64_t B, int64_t T_, int64_t 
 
 // Backward of a ContextSE unit's  out = act(BN(y) * se + BN_res(y2))  (models/QuartNetContextSE.py:19-23,54-57) in TWO passes over
 // (dout, y, y2) instead of three: per-utterance raw sums -> ds (SE scale gradient) by algebra -> excite-MLP backward (seg, dW1,
-// dW2) -> BN-backward constants -> apply.  ysum [B][C] = sum_t y of the forward (lasr_seqsum).  seg_out [B][C] is also returned.
-extern "C" int lasr_bn_se_bwd(const void* dout, const void* y, const float* coef, const float* saved, const float* gamma, const float* beta,
-                              const void* y2, const float* coef2, const float* saved2, const float* gamma2, const float* se_scale,
-                              const float* se_hidden, const float* se_pooled, const float* ysum, const float* W1, const float* W2,
-                              const int32_t* row_lens, void* dy, void* dy2, float* dgamma, float* dbeta, float* dgamma2, float* dbeta2,
-                              float* dW1, float* dW2, float* seg_out, int dtype, int64_t B, int64_t T_, int64_t C, int act,
-                              const lasr_dropout* dropout, void* workspace, size_t workspace_bytes, void* stream) {
-  LASR_CHECK_ARG(dout && y && coef && saved && gamma && beta && se_scale && se_hidden && se_pooled && ysum && W1 && W2 && dy && dgamma &&
-                     dbeta && dW1 && dW2 && seg_out && workspace, "lasr_bn_se_bwd: null pointer");
-  LASR_CHECK_ARG(!y2 || (coef2 && saved2 && gamma2 && dy2 && dgamma2 && dbeta2), "lasr_bn_se_bwd: branch-2 pointers");
-  LASR_TRY(check_bn_shape("lasr_bn_se_bwd", dtype, B, T_, C));
+// dW2) -> BN-backward constants -> apply.  se.ysum [B][C] = sum_t y of the forward (lasr_seqsum).  se.seg [B][C] is also returned.
+extern "C" int lasr_bn_se_bwd(const lasr_bn_tail* tail, const lasr_se_side* se_side, void* workspace, size_t workspace_bytes, void* stream) {
+  LASR_TRY(check_bn_tail("lasr_bn_se_bwd", tail, kBnDout | kBnSeScale | kBnSaved | kBnGamma | kBnBeta | kBnDy | kBnDparams, workspace));
+  LASR_CHECK_ARG(se_side && se_side->hidden && se_side->pooled && se_side->ysum && se_side->W1 && se_side->W2 && se_side->seg &&
+                     se_side->dW1 && se_side->dW2, "lasr_bn_se_bwd: null pointer");
+  const lasr_se_side& se = *se_side;
+  lasr_bn_tail t = *tail;      // the sums go through the workspace, and pass 1 takes the raw sums: se.seg joins in pass 2
+  t.main.sums = t.res.sums = nullptr;
+  t.se_grad = nullptr;
+  const lasr_bn_side &m = t.main, r = res_side(t);
+  const int64_t B = t.B, T_ = t.T, C = t.C;
   if (workspace_bytes < lasr_bn_se_bwd_workspace_bytes(B, T_, C)) return fail(LASR_E_WORKSPACE, "lasr_bn_se_bwd: workspace");
   hipStream_t st = as_stream(stream);
   const int nslab = (int)cdiv(T_, kRowsPerBlock);
@@ -1257,54 +1237,41 @@ extern "C" int lasr_bn_se_bwd(const void* dout, const void* y, const float* coef
   void* se_work = w;
   // channel-sliced form: one workgroup per (64 channels, utterance) in both passes - the statistics pass then leaves the
   // per-utterance sums themselves (nslab = 1: nothing for the excite backward to fold)
-  static const bool se_sliced_off = getenv("LASR_BN_SLICED") && atoi(getenv("LASR_BN_SLICED")) <= 0;
-  const bool sliced = !se_sliced_off && dtype == LASR_BF16 && !(dropout && dropout->step && dropout->p > 0.f) && C % kSlCh == 0 &&
+  const bool sliced = bn_switches().sliced > 0 && t.dtype == LASR_BF16 && !make_drop(t.dropout).step && C % kSlCh == 0 &&
                       B * (C / kSlCh) >= 128 && T_ >= 64;
+  // the BN side of the excite backward (se.hip): fold -> ds -> excite-MLP backward (seg, dW1, dW2) -> BN-backward constants, two launches
+  auto excite_bwd = [&](int slabs) {
+    SeBwdBn bn;
+    bn.partials = partials; bn.nslab = slabs; bn.gamma = m.gamma; bn.beta = m.beta; bn.ysum = se.ysum;
+    bn.coef = m.coef; bn.saved = m.saved; bn.coef2 = r.coef; bn.saved2 = r.saved; bn.gamma2 = r.gamma;
+    bn.inv_n = 1.0f / (float)(B * T_); bn.tab = tab; bn.dgamma = m.dgamma; bn.dbeta = m.dbeta; bn.dgamma2 = r.dgamma; bn.dbeta2 = r.dbeta;
+    return launch_se_bwd(nullptr, &bn, t, se, se_work, st);
+  };
   if (sliced) {
     const dim3 grid((unsigned)(C / kSlCh), (unsigned)B);
-    with_bool(y2 != nullptr, [&](auto h2) {
-      hipLaunchKernelGGL((bn_bwd_stats_sliced_kernel<h2.value, true>), grid, dim3(kSlThreads), 0, st, (const bf16_t*)dout, (const bf16_t*)y,
-                         coef, saved, (const bf16_t*)y2, coef2, saved2, se_scale, partials, (int)(B * T_), (int)C, act, (int)T_);
+    with_bool(r.y != nullptr, [&](auto h2) {
+      hipLaunchKernelGGL((bn_bwd_stats_sliced_kernel<h2.value, true>), grid, dim3(kSlThreads), 0, st, (const bf16_t*)t.dout, (const bf16_t*)m.y,
+                         m.coef, m.saved, (const bf16_t*)r.y, r.coef, r.saved, t.se_scale, partials, (int)(B * T_), (int)C, t.act, (int)T_);
     });
     LASR_LAUNCH_CHECK("bn_bwd_stats_sliced_kernel");
-    SeBwdBn bn;
-    bn.partials = partials; bn.nslab = 1; bn.gamma = gamma; bn.beta = beta; bn.ysum = ysum;
-    bn.coef = coef; bn.saved = saved; bn.coef2 = y2 ? coef2 : nullptr; bn.saved2 = saved2; bn.gamma2 = gamma2;
-    bn.inv_n = 1.0f / (float)(B * T_); bn.tab = tab; bn.dgamma = dgamma; bn.dbeta = dbeta; bn.dgamma2 = dgamma2; bn.dbeta2 = dbeta2;
-    LASR_TRY(launch_se_bwd(nullptr, &bn, se_scale, se_hidden, se_pooled, W1, W2, B, T_, C, seg_out, dW1, dW2, se_work, st));
-    // (the apply pass stays on whole-utterance chunks here: the half-utterance form of lasr_bn_act_bwd_apply_drop needs the SE
+    LASR_TRY(excite_bwd(1));
+    // (the apply pass stays on whole-utterance chunks here: the half-utterance form of lasr_bn_act_bwd_apply needs the SE
     //  constants in 128 registers, spills 9 of them and measured 3.80 against 3.78 ms per cfg4 step)
-    with_bool(y2 != nullptr, [&](auto h2) {
-      hipLaunchKernelGGL((bn_bwd_apply_sliced_kernel<h2.value, true>), grid, dim3(kSlThreads), 0, st, (const bf16_t*)dout, (const bf16_t*)y,
-                         (const bf16_t*)y2, nullptr, 0, tab, se_scale, seg_out, coef, saved, gamma, coef2, saved2, gamma2, 0.f, row_lens,
-                         (bf16_t*)dy, (bf16_t*)dy2, dgamma, dbeta, dgamma2, dbeta2, (int)(B * T_), (int)T_, (int)C, act, (int)T_);
+    with_bool(r.y != nullptr, [&](auto h2) {
+      hipLaunchKernelGGL((bn_bwd_apply_sliced_kernel<h2.value, true>), grid, dim3(kSlThreads), 0, st, (const bf16_t*)t.dout, (const bf16_t*)m.y,
+                         (const bf16_t*)r.y, nullptr, 0, tab, t.se_scale, se.seg, m.coef, m.saved, m.gamma, r.coef, r.saved, r.gamma, 0.f,
+                         t.row_lens, (bf16_t*)m.dy, (bf16_t*)r.dy, m.dgamma, m.dbeta, r.dgamma, r.dbeta, (int)(B * T_), (int)T_, (int)C, t.act,
+                         (int)T_);
     });
     LASR_LAUNCH_CHECK("bn_bwd_apply_sliced_kernel");
     return 0;
   }
   // pass 1: raw per-(utterance, slab) sums (the SE scale enters the pre-activation z only)
-  LASR_TRY(bn_bwd_stats_impl(dout, y, coef, saved, y2, coef2, saved2, se_scale, nullptr, nullptr, nullptr, dtype, B, T_, C, act, dropout,
-                             partials, (size_t)B * nslab * 4 * C * sizeof(float), stream, 1));
-  // fold -> ds -> excite-MLP backward (seg, dW1, dW2) -> BN-backward constants: two launches (se.hip)
-  SeBwdBn bn;
-  bn.partials = partials; bn.nslab = nslab; bn.gamma = gamma; bn.beta = beta; bn.ysum = ysum;
-  bn.coef = coef; bn.saved = saved; bn.coef2 = y2 ? coef2 : nullptr; bn.saved2 = saved2; bn.gamma2 = gamma2;
-  bn.inv_n = 1.0f / (float)(B * T_); bn.tab = tab; bn.dgamma = dgamma; bn.dbeta = dbeta; bn.dgamma2 = dgamma2; bn.dbeta2 = dbeta2;
-  LASR_TRY(launch_se_bwd(nullptr, &bn, se_scale, se_hidden, se_pooled, W1, W2, B, T_, C, seg_out, dW1, dW2, se_work, st));
+  LASR_TRY(bn_bwd_stats_impl(t, partials, stream, 1));
+  LASR_TRY(excite_bwd(nslab));
   // pass 2: dy = G*(d*se + seg) + Bc*y + Cc, dy2 = G2*d + ...
-  const DropArgs da = make_drop(dropout);
-  const int64_t rows = B * T_;
-  const size_t shmem = (size_t)10 * C * sizeof(float);
-  LASR_CHECK_SHAPE(shmem <= 64 * 1024, "lasr_bn_se_bwd: C too large for the LDS coefficient table");
-  // (SE is always on here; the dispatcher's SE = false kernels are the ones lasr_bn_act_bwd_apply_drop launches)
-  with_bn_variant(dtype, y2 != nullptr, true, da.step != nullptr, [&](auto t, auto h2, auto se, auto drop) {
-    using T = typename decltype(t)::type;
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, h2.value, se.value, drop.value>), dim3((unsigned)cdiv(rows, kSlabRows)), dim3(256), shmem,
-                       st, (const T*)dout, (const T*)y, (const T*)y2, tab, se_scale, seg_out, row_lens, (T*)dy, (T*)dy2, (int)rows, (int)T_,
-                       (int)C, act, da);
-  });
-  LASR_LAUNCH_CHECK("bn_bwd_apply_kernel");
-  return 0;
+  t.se_grad = se.seg;
+  return launch_bn_bwd_apply("lasr_bn_se_bwd", t, tab, st);
 }
 
 extern "C" int lasr_bn_eval_coef_many(const lasr_bn_eval_desc* descs, int n_descs, float eps, void* stream) {

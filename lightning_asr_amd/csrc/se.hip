@@ -332,9 +332,13 @@ __global__ __launch_bounds__(256) void bn_se_act_fwd_kernel(const bf16_t* __rest
 // out = act((a y + b) * sigmoid(W2 relu(W1 (a mean_T(y) + b))) [+ a2 y2 + b2]) with pooled / hidden / scale left for the backward:
 // the excite MLP of lasr_se_fwd and lasr_bn_act_fwd(se_scale) in one launch.  0 = launched, 1 = this shape / dtype keeps the three
 // launches (nothing was launched), negative = error.
-int bn_se_act_fwd(const void* y, const float* coef, const void* y2, const float* coef2, const float* sums, const float* W1, const float* W2,
-                  void* out, float* pooled, float* hidden, float* scale, int dtype, int64_t B, int64_t T_, int64_t C, int act, void* stream) {
+int bn_se_act_fwd(const lasr_bn_tail& t, const float* sums, const float* W1, const float* W2, void* out, float* pooled, float* hidden,
+                  float* scale, void* stream) {
   static const bool off = getenv("LASR_SE_FWD_FOLD") && atoi(getenv("LASR_SE_FWD_FOLD")) == 0;
+  const void *y = t.main.y, *y2 = res_side(t).y;
+  const float *coef = t.main.coef, *coef2 = res_side(t).coef;
+  const int dtype = t.dtype, act = t.act;
+  const int64_t B = t.B, T_ = t.T, C = t.C;
   const int64_t H = C / 8;
   const size_t smem = (size_t)(C + H + 64 * (H + 1) + 64) * sizeof(float);
   if (off || dtype != LASR_BF16 || C % 64 != 0 || C < 64 || C > 4096 || smem > 64 * 1024 || B >= 65536 || T_ < 1 || T_ >= (1 << 30) ||
@@ -623,8 +627,9 @@ size_t se_bwd_work_bytes(int64_t B, int64_t C) {
          align_up((size_t)cdiv(B, kSeUtt) * C * (C / 8) * sizeof(float), 256);
 }
 
-int launch_se_bwd(const float* ds, const SeBwdBn* bn, const float* scale, const float* hidden, const float* pooled, const float* W1,
-                  const float* W2, int64_t B, int64_t T_, int64_t C, float* seg, float* dW1, float* dW2, void* work, hipStream_t st) {
+int launch_se_bwd(const float* ds, const SeBwdBn* bn, const lasr_bn_tail& t, const lasr_se_side& se, void* work, hipStream_t st) {
+  const int64_t B = t.B, T_ = t.T, C = t.C;
+  const float* scale = t.se_scale;
   const int H = (int)(C / 8);
   if (C % 32 != 0 || se_pool_smem(B, H) > 64 * 1024 || se_hidden_smem(H) > 64 * 1024 || B >= 65536 * kSeUtt)
     return fail(LASR_E_SHAPE, "lasr_se_bwd: C=%lld B=%lld (C a multiple of 32; the batch's excite vectors must fit 64 KB of LDS)",
@@ -639,13 +644,13 @@ int launch_se_bwd(const float* ds, const SeBwdBn* bn, const float* scale, const 
   const bool fused = bn && bn->partials;
   hipLaunchKernelGGL(se_bwd_hidden_kernel, dim3((unsigned)nchunk, (unsigned)ngroup), dim3(256), se_hidden_smem(H), st, ds,
                      fused ? bn->partials : nullptr, fused ? bn->nslab : 0, fused ? bn->gamma : nullptr, fused ? bn->beta : nullptr, scale,
-                     hidden, W2, (int)B, (int)C, H, P, dW2_part, dh_part);
+                     se.hidden, se.W2, (int)B, (int)C, H, P, dW2_part, dh_part);
   LASR_LAUNCH_CHECK("se_bwd_hidden_kernel");
   SeBwdBn b2;
   if (fused) b2 = *bn;
   else { memset(&b2, 0, sizeof(b2)); }
-  hipLaunchKernelGGL(se_bwd_pool_kernel, dim3((unsigned)(C / kSeC2)), dim3(512), se_pool_smem(B, H), st, dh_part, nchunk, hidden, pooled, W1,
-                     scale, P, dW2_part, ngroup, (int)B, (int)T_, (int)C, H, seg, dW1, dW2, b2);
+  hipLaunchKernelGGL(se_bwd_pool_kernel, dim3((unsigned)(C / kSeC2)), dim3(512), se_pool_smem(B, H), st, dh_part, nchunk, se.hidden, se.pooled, se.W1,
+                     scale, P, dW2_part, ngroup, (int)B, (int)T_, (int)C, H, se.seg, se.dW1, se.dW2, b2);
   LASR_LAUNCH_CHECK("se_bwd_pool_kernel");
   return 0;
 }
@@ -688,47 +693,28 @@ extern "C" size_t lasr_se_bwd_workspace_bytes(int64_t B, int64_t C) {
   return align_up((size_t)B * C * sizeof(float), 256) + se_bwd_work_bytes(B, C);
 }
 
-extern "C" int lasr_se_bwd_drop(const void* dout, const void* y, const float* coef, const void* y2, const float* coef2, const float* scale,
-                                const float* hidden, const float* pooled, const float* W1, const float* W2, int dtype, int64_t B, int64_t T_,
-                                int64_t C, int act, const lasr_dropout* dropout, float* seg, float* dW1, float* dW2, void* workspace,
-                                size_t workspace_bytes, void* stream);
-extern "C" int lasr_se_bwd(const void* dout, const void* y, const float* coef, const void* y2, const float* coef2, const float* scale,
-                           const float* hidden, const float* pooled, const float* W1, const float* W2, int dtype, int64_t B, int64_t T_,
-                           int64_t C, int act, float* seg, float* dW1, float* dW2, void* workspace, size_t workspace_bytes,
-                           void* stream) {
-  return lasr_se_bwd_drop(dout, y, coef, y2, coef2, scale, hidden, pooled, W1, W2, dtype, B, T_, C, act, nullptr, seg, dW1, dW2, workspace,
-                          workspace_bytes, stream);
-}
-
-extern "C" int lasr_se_bwd_drop(const void* dout, const void* y, const float* coef, const void* y2, const float* coef2, const float* scale,
-                                const float* hidden, const float* pooled, const float* W1, const float* W2, int dtype, int64_t B, int64_t T_,
-                                int64_t C, int act, const lasr_dropout* dropout, float* seg, float* dW1, float* dW2, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-  DropArgs da;
-  da.step = nullptr; da.seed = 0; da.unit = 0; da.thresh = 0; da.inv_keep = 1.f;
-  if (dropout && dropout->step && dropout->p > 0.f) {    // (same conversion as norm.hip's make_drop)
-    da.step = reinterpret_cast<const unsigned long long*>(dropout->step);
-    da.seed = dropout->seed; da.unit = dropout->unit;
-    const float p = dropout->p < 0.999f ? dropout->p : 0.999f;
-    da.thresh = (uint32_t)(p * 65536.f + 0.5f);
-    da.inv_keep = 1.f / (1.f - (float)da.thresh / 65536.f);
-  }
-  LASR_CHECK_ARG(dout && y && coef && scale && hidden && pooled && W1 && W2 && seg && dW1 && dW2 && workspace, "lasr_se_bwd: null pointer");
-  LASR_CHECK_ARG(!y2 || coef2, "lasr_se_bwd: residual coefficients");
-  LASR_CHECK_ARG(dtype == LASR_F32 || dtype == LASR_BF16, "lasr_se_bwd: bad dtype");
+extern "C" int lasr_se_bwd(const lasr_bn_tail* tail, const lasr_se_side* se, void* workspace, size_t workspace_bytes, void* stream) {
+  LASR_TRY(check_bn_ptrs("lasr_se_bwd", tail, kBnDout | kBnSeScale));
+  LASR_CHECK_ARG(se && se->hidden && se->pooled && se->W1 && se->W2 && se->seg && se->dW1 && se->dW2 && workspace, "lasr_se_bwd: null pointer");
+  const lasr_bn_tail& t = *tail;
+  const int64_t B = t.B, T_ = t.T, C = t.C;
+  LASR_CHECK_ARG(t.dtype == LASR_F32 || t.dtype == LASR_BF16, "lasr_se_bwd: bad dtype");
   LASR_CHECK_SHAPE(B > 0 && B < 65536 && T_ > 0 && C >= 8 && C % 8 == 0 && C <= 8192, "lasr_se_bwd: C=%lld", (long long)C);
   if (workspace_bytes < lasr_se_bwd_workspace_bytes(B, C)) return fail(LASR_E_WORKSPACE, "lasr_se_bwd: workspace");
+  const DropArgs da = make_drop(t.dropout);
+  const void* y2 = res_side(t).y;
+  const float* coef2 = res_side(t).coef;
   char* w = reinterpret_cast<char*>(workspace);
   float* ds = reinterpret_cast<float*>(w);
   void* work = w + align_up((size_t)B * C * sizeof(float), 256);
   dim3 grid((unsigned)cdiv(C, 64), (unsigned)B);
   hipStream_t st = as_stream(stream);
-  if (dtype == LASR_F32)
-    hipLaunchKernelGGL(se_bwd_reduce_kernel<float>, grid, dim3(256), 0, st, (const float*)dout, (const float*)y, coef, (const float*)y2,
-                       coef2, scale, T_, C, act, ds, da);
+  if (t.dtype == LASR_F32)
+    hipLaunchKernelGGL(se_bwd_reduce_kernel<float>, grid, dim3(256), 0, st, (const float*)t.dout, (const float*)t.main.y, t.main.coef,
+                       (const float*)y2, coef2, t.se_scale, T_, C, t.act, ds, da);
   else
-    hipLaunchKernelGGL(se_bwd_reduce_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)dout, (const bf16_t*)y, coef,
-                       (const bf16_t*)y2, coef2, scale, T_, C, act, ds, da);
+    hipLaunchKernelGGL(se_bwd_reduce_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)t.dout, (const bf16_t*)t.main.y, t.main.coef,
+                       (const bf16_t*)y2, coef2, t.se_scale, T_, C, t.act, ds, da);
   LASR_LAUNCH_CHECK("se_bwd_reduce_kernel");
-  return launch_se_bwd(ds, nullptr, scale, hidden, pooled, W1, W2, B, T_, C, seg, dW1, dW2, work, st);
+  return launch_se_bwd(ds, nullptr, t, *se, work, st);
 }

@@ -321,10 +321,25 @@ def gemm_bn_fused(xs, ws_, bns, row_lens=None, rows_per_seq: int = 0, eps: float
     return ys, coefs, saveds, stats
 
 
-def bn_act(y, coef, y2=None, coef2=None, se_scale=None, act: str = "relu") -> torch.Tensor:
+def _bn_tail(y, main, res=None, act: str = "relu", **fields) -> _lib.BnTail:
+    """lasr_bn_tail (include/lasr.h) from tensors.  y (B,T,C): the main branch's pre-BN tensor, which also fixes dtype and shape;
+    main / res: the other lasr_bn_side fields by name (coef, saved, gamma, sums, dy, ...), res with its own y, or None / y None
+    without a residual branch; fields: dout, se_scale, se_grad, row_lens.  A None tensor is NULL.  The record holds the tensors,
+    so they live as long as it does."""
     B, T, Cc = y.shape
+    t = _lib.BnTail(dtype=_dt(y), act=ACT[act], B=B, T=T, C=Cc)
+    t.tensors = []
+    for rec, named in ((t.main, dict(main, y=y)), (t.res, res if res and res.get("y") is not None else {}), (t, fields)):
+        for name, tensor in named.items():
+            setattr(rec, name, _p(tensor))
+            t.tensors.append(tensor)
+    return t
+
+
+def bn_act(y, coef, y2=None, coef2=None, se_scale=None, act: str = "relu") -> torch.Tensor:
     out = torch.empty_like(y)
-    call("lasr_bn_act_fwd", _p(y), _p(coef), _p(y2), _p(coef2), _p(se_scale), _p(out), _dt(y), B, T, Cc, ACT[act], _stream())
+    tail = _bn_tail(y, dict(coef=coef), dict(y=y2, coef=coef2), act, se_scale=se_scale)
+    call("lasr_bn_act_fwd", ctypes.byref(tail), _p(out), _stream())
     return out
 
 
@@ -352,8 +367,9 @@ def se_bwd(dout, y, coef, scale, hidden, pooled, W1, W2, y2=None, coef2=None, ac
     dW2 = torch.empty(Cc, Cc // 8, dtype=torch.float32, device=dev)
     nb = int(_lib.load().lasr_se_bwd_workspace_bytes(B, Cc))
     ws = _ws(nb, dev)
-    call("lasr_se_bwd", _p(dout), _p(y), _p(coef), _p(y2), _p(coef2), _p(scale), _p(hidden), _p(pooled), _p(W1), _p(W2), _dt(y), B, T, Cc,
-         ACT[act], _p(seg), _p(dW1), _p(dW2), _p(ws), nb, _stream())
+    tail = _bn_tail(y, dict(coef=coef), dict(y=y2, coef=coef2), act, dout=dout, se_scale=scale)
+    se = _lib.SeSide(hidden=_p(hidden), pooled=_p(pooled), W1=_p(W1), W2=_p(W2), seg=_p(seg), dW1=_p(dW1), dW2=_p(dW2))
+    call("lasr_se_bwd", ctypes.byref(tail), ctypes.byref(se), _p(ws), nb, _stream())
     return seg, dW1, dW2
 
 
@@ -368,15 +384,15 @@ def bn_act_bwd(dout, y, coef, saved, gamma, y2=None, coef2=None, saved2=None, ga
     ws = _ws(nb, dev)
     if fused:
         sums = sums2 = None
-    call("lasr_bn_act_bwd_stats", _p(dout), _p(y), _p(coef), _p(saved), _p(y2), _p(coef2), _p(saved2), _p(se_scale),
-         _p(se_grad), _p(sums), _p(sums2), _dt(y), B, T, Cc, ACT[act], _p(ws), nb, _stream())
     dy = torch.empty_like(y)
     dy2 = torch.empty_like(y) if y2 is not None else None
     dg, db = (torch.empty(Cc, dtype=torch.float32, device=dev) for _ in range(2))
     dg2, db2 = ((torch.empty(Cc, dtype=torch.float32, device=dev) for _ in range(2)) if y2 is not None else (None, None))
-    call("lasr_bn_act_bwd_apply", _p(dout), _p(y), _p(coef), _p(saved), _p(gamma), _p(y2), _p(coef2), _p(saved2), _p(gamma2),
-         _p(se_scale), _p(se_grad), _p(sums), _p(sums2), _p(row_lens), _p(dy), _p(dy2), _p(dg), _p(db), _p(dg2), _p(db2),
-         _dt(y), B, T, Cc, ACT[act], _p(ws), ws.numel(), _stream())
+    tail = _bn_tail(y, dict(coef=coef, saved=saved, gamma=gamma, sums=sums, dy=dy, dgamma=dg, dbeta=db),
+                    dict(y=y2, coef=coef2, saved=saved2, gamma=gamma2, sums=sums2, dy=dy2, dgamma=dg2, dbeta=db2), act,
+                    dout=dout, se_scale=se_scale, se_grad=se_grad, row_lens=row_lens)
+    call("lasr_bn_act_bwd_stats", ctypes.byref(tail), _p(ws), nb, _stream())
+    call("lasr_bn_act_bwd_apply", ctypes.byref(tail), _p(ws), ws.numel(), _stream())
     return dy, dy2, dg, db, dg2, db2
 
 

@@ -74,13 +74,12 @@ def test_sliced_apply_from_partials_is_the_two_launches_bit_for_bit(dev, C, rows
                         brs = (_BnBranch * 2)()
                         outs = [_branch(brs[i], parts[i], params[2 * i], params[2 * i + 1], rm[i], rv[i], C, dev) for i in range(nb)]
                         out = torch.full_like(y, float("nan"))
+                        tail = ops._bn_tail(y, dict(coef=outs[0][0]), dict(y=y2, coef=outs[1][0]) if has_res else None, act)
                         if form == "two":
                             call("lasr_bn_finalize_partials", brs, nb, C, rows, EPS, MOM, _stream())
-                            call("lasr_bn_act_fwd", _p(y), _p(outs[0][0]), _p(y2) if has_res else None, _p(outs[1][0]) if has_res else None,
-                                 None, _p(out), _lib.BF16, B, T, C, ops.ACT[act], _stream())
+                            call("lasr_bn_act_fwd", _lib.C.byref(tail), _p(out), _stream())
                         else:
-                            call("lasr_bn_act_fwd_partials", brs, nb, EPS, MOM, _p(y), _p(y2) if has_res else None, _p(out), _lib.BF16,
-                                 B, T, C, ops.ACT[act], _stream())
+                            call("lasr_bn_act_fwd_partials", brs, nb, EPS, MOM, _lib.C.byref(tail), _p(out), _stream())
                         torch.cuda.synchronize()
                         got[form] = {"out": out}
                         for i in range(nb):

@@ -60,6 +60,85 @@ def test_error_convention_and_no_cpu_fallback():
         NativeModel("plain", 28, device="cpu")
 
 
+class _HostTail:
+    """A fully populated lasr_bn_tail + lasr_se_side over small numpy buffers (host addresses, null stream: every call made with
+    it must be refused before anything is launched), and each record-taking entry point with the workspace bytes it asks for."""
+    B, T = 2, 3
+
+    def __init__(self, C=16, dtype=None):
+        from lightning_asr_amd import _lib
+        self.lib, self.C, B, T = _lib.load(), C, self.B, self.T
+        self.keep = []
+        self.tail = _lib.BnTail(dtype=_lib.BF16 if dtype is None else dtype, act=_lib.ACT_RELU, B=B, T=T, C=C)
+        for side in (self.tail.main, self.tail.res):
+            for name, _ in _lib.BnSide._fields_:
+                setattr(side, name, self.buf(B * T * C if name in ("y", "dy") else 2 * C))
+        for name in ("dout", "se_scale", "se_grad", "row_lens"):
+            setattr(self.tail, name, self.buf(B * T * C))
+        self.se = _lib.SeSide(**{name: self.buf(C * C) for name, _ in _lib.SeSide._fields_})
+        self.out = self.buf(B * T * C)
+        stats_bytes = self.lib.lasr_bn_bwd_workspace_bytes(B, T, C) - self.lib.lasr_bn_bwd_apply_workspace_bytes(C)   # the partials alone
+        self.entries = {     # name -> workspace bytes it needs (None: it takes no workspace)
+            "lasr_bn_act_fwd": None,
+            "lasr_bn_act_bwd_stats": stats_bytes,
+            "lasr_bn_act_bwd_apply": self.lib.lasr_bn_bwd_apply_workspace_bytes(C),      # (reduced sums are set)
+            "lasr_se_bwd": self.lib.lasr_se_bwd_workspace_bytes(B, C),
+            "lasr_bn_se_bwd": self.lib.lasr_bn_se_bwd_workspace_bytes(B, T, C),
+        }
+
+    def buf(self, n):
+        self.keep.append(np.zeros(max(int(n), 1), dtype=np.float32))
+        return self.keep[-1].ctypes.data
+
+    def call(self, name, short=0):
+        t, se, nb = ctypes.byref(self.tail), ctypes.byref(self.se), self.entries[name]
+        if nb is None:
+            rc = self.lib.lasr_bn_act_fwd(t, self.out, None)
+        else:
+            ws = self.buf(nb // 4 + 1)
+            args = (t, se) if name in ("lasr_se_bwd", "lasr_bn_se_bwd") else (t,)
+            rc = getattr(self.lib, name)(*args, ws, nb - short, None)
+        return rc, self.lib.lasr_last_error()
+
+
+BN_TAIL_ENTRIES = ("lasr_bn_act_fwd", "lasr_bn_act_bwd_stats", "lasr_bn_act_bwd_apply", "lasr_se_bwd", "lasr_bn_se_bwd")
+
+
+@pytest.mark.parametrize("name", BN_TAIL_ENTRIES)
+def test_bn_tail_record_is_validated_before_any_launch(name):
+    """The five entry points that take a lasr_bn_tail, called with host buffers: each bad record is refused with the library's own
+    code and message, so nothing is launched.  C is a late field of the record: reading it back in the message shows that the
+    ctypes layout and the C layout agree."""
+    E_ARG, E_SHAPE, E_WORKSPACE = -1, -2, -3
+    h = _HostTail(C=12)                                            # bf16 loads 8-channel vectors
+    assert h.lib.lasr_version() >= 115
+    rc, msg = h.call(name)
+    assert rc == E_SHAPE and b"C=12" in msg and name.encode() in msg, (rc, msg)
+    h = _HostTail()
+    h.tail.res.coef = None                                         # a residual branch (res.y) without its coefficients
+    rc, msg = h.call(name)
+    assert rc == E_ARG and b"branch-2 pointers" in msg, (rc, msg)
+    h = _HostTail()
+    h.tail.main.y = None
+    rc, msg = h.call(name)
+    assert rc == E_ARG and b"null pointer" in msg, (rc, msg)
+    h = _HostTail()
+    h.tail.res.y = None                                            # no residual branch: the rest of `res` is not looked at ...
+    h.tail.res.coef = h.tail.res.saved = h.tail.res.gamma = h.tail.res.dy = None
+    h.tail.C = 12
+    rc, msg = h.call(name)
+    assert rc == E_SHAPE and b"C=12" in msg, (rc, msg)             # ... so the call gets as far as the shape check
+    if h.entries[name] is not None:
+        rc, msg = _HostTail().call(name, short=1)
+        assert rc == E_WORKSPACE and b"workspace" in msg, (rc, msg)
+        h = _HostTail()
+        h.tail.main.sums = h.tail.res.sums = None                  # fused hand-over: apply then reads the partials from the workspace
+        if name == "lasr_bn_act_bwd_apply":
+            h.entries[name] = h.lib.lasr_bn_bwd_workspace_bytes(h.B, h.T, h.C)
+        rc, msg = h.call(name, short=1)
+        assert rc == E_WORKSPACE and b"workspace" in msg, (rc, msg)
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "lightning_asr_amd")
     for dirpath, _, files in os.walk(pkg):

@@ -32,17 +32,18 @@ if which in ("bn", "all"):
     y2 = torch.randn(B, T, C, device=dev).to(bf); out = torch.empty_like(x)
     coef = torch.randn(2 * C, device=dev); saved = torch.rand(2 * C, device=dev) + 0.5; gam = torch.ones(C, device=dev)
     lens = torch.full((B,), T, dtype=torch.int32, device=dev)
-    t = timeit(lambda: lib.lasr_bn_act_fwd(x.data_ptr(), coef.data_ptr(), y2.data_ptr(), coef.data_ptr(), None, out.data_ptr(), 1, B, T, C, 1, st()))
-    print("bn_act_fwd          : %6.1f us  (%.2f TB/s)" % (t, mb(3 * N * C * 2, t)))
+    from ctypes import byref
+    from lightning_asr_amd.ops import _bn_tail
     sums = torch.zeros(2 * C, device=dev); sums2 = torch.zeros(2 * C, device=dev)
-    nb = lib.lasr_bn_bwd_workspace_bytes(B, T, C); ws2 = torch.empty(nb, dtype=torch.uint8, device=dev)
-    t = timeit(lambda: lib.lasr_bn_act_bwd_stats(dy.data_ptr(), x.data_ptr(), coef.data_ptr(), saved.data_ptr(), y2.data_ptr(), coef.data_ptr(), saved.data_ptr(),
-                                                 None, None, sums.data_ptr(), sums2.data_ptr(), 1, B, T, C, 1, ws2.data_ptr(), nb, st()))
-    print("bn_bwd_stats(+reduce): %6.1f us  (%.2f TB/s)" % (t, mb(3 * N * C * 2, t)))
     d1 = torch.empty_like(x); d2 = torch.empty_like(x); dg = torch.empty(C, device=dev); db = torch.empty(C, device=dev)
-    t = timeit(lambda: lib.lasr_bn_act_bwd_apply(dy.data_ptr(), x.data_ptr(), coef.data_ptr(), saved.data_ptr(), gam.data_ptr(), y2.data_ptr(), coef.data_ptr(),
-                                                 saved.data_ptr(), gam.data_ptr(), None, None, sums.data_ptr(), sums2.data_ptr(), lens.data_ptr(), d1.data_ptr(),
-                                                 d2.data_ptr(), dg.data_ptr(), db.data_ptr(), dg.data_ptr(), db.data_ptr(), 1, B, T, C, 1, ws2.data_ptr(), nb, st()))
+    tail = byref(_bn_tail(x, dict(coef=coef, saved=saved, gamma=gam, sums=sums, dy=d1, dgamma=dg, dbeta=db),
+                          dict(y=y2, coef=coef, saved=saved, gamma=gam, sums=sums2, dy=d2, dgamma=dg, dbeta=db), "relu", dout=dy, row_lens=lens))
+    t = timeit(lambda: lib.lasr_bn_act_fwd(tail, out.data_ptr(), st()))
+    print("bn_act_fwd          : %6.1f us  (%.2f TB/s)" % (t, mb(3 * N * C * 2, t)))
+    nb = lib.lasr_bn_bwd_workspace_bytes(B, T, C); ws2 = torch.empty(nb, dtype=torch.uint8, device=dev)
+    t = timeit(lambda: lib.lasr_bn_act_bwd_stats(tail, ws2.data_ptr(), nb, st()))
+    print("bn_bwd_stats(+reduce): %6.1f us  (%.2f TB/s)" % (t, mb(3 * N * C * 2, t)))
+    t = timeit(lambda: lib.lasr_bn_act_bwd_apply(tail, ws2.data_ptr(), nb, st()))
     print("bn_bwd_apply        : %6.1f us  (%.2f TB/s)" % (t, mb(5 * N * C * 2, t)))
     z = torch.empty_like(x)
     t = timeit(lambda: z.copy_(x))
