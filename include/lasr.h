@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 115   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 116   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
@@ -39,7 +39,8 @@ extern "C" {
                               112: lasr_hotword_* (phrase bank), lasr_ctc_beam_decode_bias / _lm_bias (hotword biasing)
                               113: lasr_ctc_kws_workspace_bytes / lasr_ctc_kws (CTC keyword search: phrases with time spans)
                               114: lasr_grad_accumulate / lasr_grad_accumulate_ranges (gradient accumulation over micro-batches)
-                              115: lasr_bn_tail / lasr_bn_side / lasr_se_side: the BN entry points take one record; the _drop twins are gone */
+                              115: lasr_bn_tail / lasr_bn_side / lasr_se_side: the BN entry points take one record; the _drop twins are gone
+                              116: lasr_ema_state_bytes / lasr_ema_state_init / lasr_novograd_step_ema / lasr_ema_update (weight EMA) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -661,6 +662,30 @@ int lasr_novograd_step_keep(float* params, const float* grads, float* exp_avg, f
                             const int64_t* offsets, int64_t n_tensors, int64_t n_elems, const float* lr, float beta1, float beta2,
                             float eps, float weight_decay, float grad_scale, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* Weight EMA ("Weight EMA"): an exponential moving average of the PARAMETERS, kept in a flat f32 buffer `ema` of n_elems
+ * and updated by the last kernel of the optimiser step, which holds the new parameters in registers: no launch is added.
+ * Per element, three f32 operations of one rounding each (no FMA): diff = p_new - e; prod = w * diff; e = e + prod - bit-equal
+ * to torch's `e + (p - e) * w`.  The weight comes from a device record (lasr_ema_state_bytes() bytes: int64 num_updates; float
+ * decay; int warmup; float w): with t = num_updates, d = warmup ? min(decay, float(1 + t) / float(10 + t)) : decay (one correctly
+ * rounded f32 division), w = 1.0f - d, then num_updates = t + 1 - computed by the step's moment kernel, so a captured graph
+ * replays the warm-up and no host scalar enters the step.
+ * lasr_ema_state_init: HOST only - fills a host image of the record for the caller to upload (like lasr_lr_schedule_init).
+ *   LASR_E_ARG: a null or short buffer, decay outside [0, 1) or not finite, num_updates < 0.
+ * lasr_novograd_step_ema: lasr_novograd_step (keep_workspace == 0) or lasr_novograd_step_keep (!= 0) with the average folded in.
+ *   ema == NULL and ema_state == NULL: exactly the entry it mirrors, launch for launch and bit for bit.  LASR_E_ARG: one of
+ *   the two without the other; ema overlapping params, grads or exp_avg.
+ * lasr_ema_update: e[i] = e[i] + (p[i] - e[i]) * w over n elements with w from the host - the same expression outside a step
+ *   (folding a parameter buffer into an average; the tests' yardstick).  A 4-byte head up to the first 16-byte boundary, 16-byte
+ *   groups and a 4-byte tail (bases not congruent mod 16 bytes: 4-byte accesses throughout); one grid-strided launch of at most
+ *   2048 workgroups, no workspace.  n == 0: returns 0, nothing launched.  LASR_E_ARG: a null pointer, n < 0, overlapping buffers. */
+size_t lasr_ema_state_bytes(void);
+int lasr_ema_state_init(void* host_buf, size_t bytes, float decay, int warmup, int64_t num_updates);
+int lasr_novograd_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                           const int64_t* offsets, int64_t n_tensors, int64_t n_elems, const float* lr, float beta1, float beta2,
+                           float eps, float weight_decay, float grad_scale, void* workspace,
+                           size_t workspace_bytes, void* stream, float* ema, void* ema_state, int keep_workspace);
+int lasr_ema_update(float* ema, const float* params, int64_t n, float w, void* stream);
 
 /* Gradient accumulation (accumulate_grad_batches > 1; DESIGN 4, "Gradient accumulation"): acc[i] = acc[i] + g[i], a plain f32 add with one rounding
  * per element - bit-equal to `acc + g` in torch, whatever the alignment.  Every backward of the plan overwrites its whole

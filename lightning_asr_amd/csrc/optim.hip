@@ -56,10 +56,46 @@ __global__ __launch_bounds__(256) void novograd_norm_kernel(const float* __restr
   }
 }
 
+// Weight EMA ("Weight EMA"): the record lives on the device, so a captured graph replays the decay warm-up like the LR
+// schedule.  num_updates = EMA updates done so far; w = 1 - d is what the update kernel of the SAME step reads.
+struct EmaState {
+  int64_t num_updates;
+  float decay;
+  int warmup;
+  float w;
+};
+
+// the weight of update number t (0-based) - one correctly rounded f32 division, one f32 subtraction; ops.ema_weight is its host twin
+__device__ __forceinline__ float ema_weight(float decay, int warmup, int64_t t) {
+  float d = decay;
+  if (warmup) d = fminf(decay, __fdiv_rn((float)(1 + t), (float)(10 + t)));
+  return __fsub_rn(1.0f, d);
+}
+
+// e <- e + (p - e) w in three f32 operations of one rounding each (no FMA contraction): bit-equal to torch's `e + (p - e) * w`
+// (contraction is switched off for the block: the compiler's default would fuse the product and the sum into one FMA, and the
+// __f*_rn intrinsics are plain operators to it)
+__device__ __forceinline__ float ema_lerp(float e, float p, float w) {
+#pragma clang fp contract(off)
+  const float diff = p - e;
+  const float prod = w * diff;
+  return e + prod;
+}
+
 // Stage 2: v_i <- first ? ||g||^2 : b2 v + (1-b2)||g||^2 ; denom_i = sqrt(v_i)+eps ; norm2 re-zeroed
+// kEma: thread 0 also advances the EMA record - it runs between the norm and the update, so the update kernel reads this step's w
+template <bool kEma>
 __global__ __launch_bounds__(256) void novograd_moment_kernel(double* __restrict__ norm2, float* __restrict__ exp_avg_sq,
-                                                              float* __restrict__ denom, int n_tensors, float beta2, float eps) {
+                                                              float* __restrict__ denom, int n_tensors, float beta2, float eps,
+                                                              EmaState* __restrict__ ema_st) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (kEma) {
+    if (i == 0) {
+      const int64_t t = ema_st->num_updates;
+      ema_st->w = ema_weight(ema_st->decay, ema_st->warmup, t);
+      ema_st->num_updates = t + 1;
+    }
+  }
   if (i >= n_tensors) return;
   const float norm = (float)norm2[i];
   norm2[i] = 0.0;
@@ -69,11 +105,15 @@ __global__ __launch_bounds__(256) void novograd_moment_kernel(double* __restrict
   denom[i] = sqrtf(v) + eps;
 }
 
+// kEma: the new parameters are also folded into the average `ema` while they are still in registers (one more 16-byte load and
+// store per group, no launch); the kEma = false instantiation is the kernel as it always was
+template <bool kEma>
 __global__ __launch_bounds__(256) void novograd_update_kernel(float* __restrict__ params, const float* __restrict__ grads,
                                                               float* __restrict__ exp_avg, const int64_t* __restrict__ offsets,
                                                               int n_tensors, const float* __restrict__ denom,
                                                               const float* __restrict__ lr_ptr, float beta1, float wd,
-                                                              float grad_scale, int64_t n) {
+                                                              float grad_scale, int64_t n, float* __restrict__ ema,
+                                                              const EmaState* __restrict__ ema_st) {
   // The tensor of an element is found by bisection over the offset table: the table lives in LDS (a search from
   // global memory is seven dependent loads per element) and one search serves four consecutive elements, which
   // move as 16-byte vectors whenever the group lies inside one tensor (always, for this model's shapes).
@@ -81,6 +121,8 @@ __global__ __launch_bounds__(256) void novograd_update_kernel(float* __restrict_
   for (int i = threadIdx.x; i <= n_tensors; i += 256) s_off[i] = offsets[i];
   __syncthreads();
   const float lr = *lr_ptr;
+  float w = 0.f;
+  if constexpr (kEma) w = ema_st->w;
   const int64_t ngrp = (n + 3) >> 2;
   for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < ngrp; q += (int64_t)gridDim.x * blockDim.x) {
     const int64_t e = 4 * q;
@@ -94,6 +136,8 @@ __global__ __launch_bounds__(256) void novograd_update_kernel(float* __restrict_
       const float4 p = *reinterpret_cast<const float4*>(params + e);
       const float4 g = *reinterpret_cast<const float4*>(grads + e);
       const float4 m0 = *reinterpret_cast<const float4*>(exp_avg + e);
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (kEma) a = *reinterpret_cast<const float4*>(ema + e);
       float pv[4] = {p.x, p.y, p.z, p.w}, gv[4] = {g.x, g.y, g.z, g.w}, mv[4] = {m0.x, m0.y, m0.z, m0.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -104,6 +148,9 @@ __global__ __launch_bounds__(256) void novograd_update_kernel(float* __restrict_
       }
       *reinterpret_cast<float4*>(exp_avg + e) = make_float4(mv[0], mv[1], mv[2], mv[3]);
       *reinterpret_cast<float4*>(params + e) = make_float4(pv[0], pv[1], pv[2], pv[3]);
+      if constexpr (kEma)
+        *reinterpret_cast<float4*>(ema + e) =
+            make_float4(ema_lerp(a.x, pv[0], w), ema_lerp(a.y, pv[1], w), ema_lerp(a.z, pv[2], w), ema_lerp(a.w, pv[3], w));
     } else {
       for (int64_t ee = e; ee < e + 4 && ee < n; ++ee) {
         while (lo + 1 < n_tensors && s_off[lo + 1] <= ee) ++lo;
@@ -112,7 +159,9 @@ __global__ __launch_bounds__(256) void novograd_update_kernel(float* __restrict_
         if (wd != 0.f) gi = gi + wd * pe;
         const float m = exp_avg[ee] * beta1 + gi;
         exp_avg[ee] = m;
-        params[ee] = pe - lr * m;
+        const float pn = pe - lr * m;
+        params[ee] = pn;
+        if constexpr (kEma) ema[ee] = ema_lerp(ema[ee], pn, w);
       }
     }
   }
@@ -156,6 +205,30 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict_
   }
 }
 
+// Weight EMA outside a step: e[i] = e[i] + (p[i] - e[i]) w with w from the host, the expression of the fused update.  Like the
+// accumulate kernel: a 4-byte head up to the first 16-byte boundary, 16-byte groups, a 4-byte tail; two bases that are not
+// congruent mod 16 bytes move by single elements (nvec = 0, head = n).  Units: the groups first, then the head's and the tail's.
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, int64_t n, int64_t head,
+                                                         int64_t nvec, float w) {
+  const int64_t total = nvec + (n - 4 * nvec);
+  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < total; u += (int64_t)gridDim.x * blockDim.x) {
+    if (u < nvec) {
+      const int64_t e = head + 4 * u;
+      float4 a = *reinterpret_cast<const float4*>(ema + e);
+      const float4 b = *reinterpret_cast<const float4*>(p + e);
+      a.x = ema_lerp(a.x, b.x, w);
+      a.y = ema_lerp(a.y, b.y, w);
+      a.z = ema_lerp(a.z, b.z, w);
+      a.w = ema_lerp(a.w, b.w, w);
+      *reinterpret_cast<float4*>(ema + e) = a;
+    } else {
+      const int64_t s = u - nvec;
+      const int64_t e = s < head ? s : head + 4 * nvec + (s - head);
+      if (e < n) ema[e] = ema_lerp(ema[e], p[e], w);
+    }
+  }
+}
+
 // f32 -> bf16 copy of a flat buffer (weights for the bf16 MFMA kernels)
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ in, bf16_t* __restrict__ out, int64_t n) {
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
@@ -185,7 +258,8 @@ extern "C" size_t lasr_novograd_workspace_bytes(int64_t n_tensors, int64_t n_ele
 
 static int novograd_step_impl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* offsets,
                               int64_t n_tensors, int64_t n_elems, const float* lr, float beta1, float beta2, float eps,
-                              float weight_decay, float grad_scale, void* workspace, size_t workspace_bytes, void* stream, bool zeroed);
+                              float weight_decay, float grad_scale, void* workspace, size_t workspace_bytes, void* stream, bool zeroed,
+                              float* ema = nullptr, void* ema_state = nullptr);
 
 extern "C" int lasr_novograd_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* offsets,
                                   int64_t n_tensors, int64_t n_elems, const float* lr, float beta1, float beta2, float eps,
@@ -202,11 +276,29 @@ extern "C" int lasr_novograd_step_keep(float* params, const float* grads, float*
                             workspace, workspace_bytes, stream, true);
 }
 
+// the step with the weight EMA folded into its last kernel.  ema == NULL (and no state): lasr_novograd_step (keep_workspace == 0) or
+// lasr_novograd_step_keep (!= 0), launch for launch
+extern "C" int lasr_novograd_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* offsets,
+                                      int64_t n_tensors, int64_t n_elems, const float* lr, float beta1, float beta2, float eps,
+                                      float weight_decay, float grad_scale, void* workspace, size_t workspace_bytes, void* stream,
+                                      float* ema, void* ema_state, int keep_workspace) {
+  LASR_CHECK_ARG((ema != nullptr) == (ema_state != nullptr), "lasr_novograd_step_ema: ema and ema_state come together (ema %s, state %s)",
+                 ema ? "given" : "null", ema_state ? "given" : "null");
+  return novograd_step_impl(params, grads, exp_avg, exp_avg_sq, offsets, n_tensors, n_elems, lr, beta1, beta2, eps, weight_decay, grad_scale,
+                            workspace, workspace_bytes, stream, keep_workspace != 0, ema, ema_state);
+}
+
 static int novograd_step_impl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* offsets,
                               int64_t n_tensors, int64_t n_elems, const float* lr, float beta1, float beta2, float eps,
-                              float weight_decay, float grad_scale, void* workspace, size_t workspace_bytes, void* stream, bool zeroed) {
+                              float weight_decay, float grad_scale, void* workspace, size_t workspace_bytes, void* stream, bool zeroed,
+                              float* ema, void* ema_state) {
   LASR_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && offsets && lr && workspace, "lasr_novograd_step: null pointer");
   LASR_CHECK_SHAPE(n_tensors > 0 && n_tensors < (1 << 20) && n_elems > 0, "lasr_novograd_step: n_tensors=%lld", (long long)n_tensors);
+  if (ema) {   // the average may overlap none of the buffers the update kernel reads and writes in the same pass
+    const float* others[3] = {params, grads, exp_avg};
+    for (const float* o : others)
+      LASR_CHECK_ARG(ema + n_elems <= o || o + n_elems <= ema, "lasr_novograd_step_ema: ema aliases params, grads or exp_avg");
+  }
   if (workspace_bytes < lasr_novograd_workspace_bytes(n_tensors, n_elems)) return fail(LASR_E_WORKSPACE, "lasr_novograd_step: workspace");
   float* denom = reinterpret_cast<float*>(workspace);
   double* norm2 = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + align_up((size_t)n_tensors * sizeof(float), 256));
@@ -221,16 +313,61 @@ static int novograd_step_impl(float* params, const float* grads, float* exp_avg,
   hipLaunchKernelGGL(novograd_norm_kernel, dim3((unsigned)cdiv(n_elems, kNormChunk)), dim3(256), 0, st, grads, offsets, (int)n_tensors,
                      n_elems, norm2, grad_scale);
   LASR_LAUNCH_CHECK("novograd_norm_kernel");
-  hipLaunchKernelGGL(novograd_moment_kernel, dim3((unsigned)cdiv(n_tensors, 256)), dim3(256), 0, st, norm2, exp_avg_sq, denom,
-                     (int)n_tensors, beta2, eps);
+  EmaState* est = reinterpret_cast<EmaState*>(ema_state);
+  if (ema)
+    hipLaunchKernelGGL(novograd_moment_kernel<true>, dim3((unsigned)cdiv(n_tensors, 256)), dim3(256), 0, st, norm2, exp_avg_sq, denom,
+                       (int)n_tensors, beta2, eps, est);
+  else
+    hipLaunchKernelGGL(novograd_moment_kernel<false>, dim3((unsigned)cdiv(n_tensors, 256)), dim3(256), 0, st, norm2, exp_avg_sq, denom,
+                       (int)n_tensors, beta2, eps, est);
   LASR_LAUNCH_CHECK("novograd_moment_kernel");
   int64_t blocks = cdiv(cdiv(n_elems, 4), 256);
   if (blocks > 256 * 8) blocks = 256 * 8;
   const size_t off_bytes = (size_t)(n_tensors + 1) * sizeof(int64_t);
   LASR_CHECK_SHAPE(off_bytes <= 48 * 1024, "lasr_novograd_step: offset table too large for LDS (%lld tensors)", (long long)n_tensors);
-  hipLaunchKernelGGL(novograd_update_kernel, dim3((unsigned)blocks), dim3(256), off_bytes, st, params, grads, exp_avg, offsets,
-                     (int)n_tensors, denom, lr, beta1, weight_decay, grad_scale, n_elems);
+  if (ema)
+    hipLaunchKernelGGL(novograd_update_kernel<true>, dim3((unsigned)blocks), dim3(256), off_bytes, st, params, grads, exp_avg, offsets,
+                       (int)n_tensors, denom, lr, beta1, weight_decay, grad_scale, n_elems, ema, est);
+  else
+    hipLaunchKernelGGL(novograd_update_kernel<false>, dim3((unsigned)blocks), dim3(256), off_bytes, st, params, grads, exp_avg, offsets,
+                       (int)n_tensors, denom, lr, beta1, weight_decay, grad_scale, n_elems, ema, est);
   LASR_LAUNCH_CHECK("novograd_update_kernel");
+  return 0;
+}
+
+extern "C" size_t lasr_ema_state_bytes(void) { return sizeof(EmaState); }
+
+// host only: fills a HOST image of the record (the caller uploads it), like lasr_lr_schedule_init
+extern "C" int lasr_ema_state_init(void* host_buf, size_t bytes, float decay, int warmup, int64_t num_updates) {
+  LASR_CHECK_ARG(host_buf && bytes >= sizeof(EmaState), "lasr_ema_state_init: buffer of %zu bytes needed", sizeof(EmaState));
+  LASR_CHECK_ARG(decay >= 0.f && decay < 1.f, "lasr_ema_state_init: decay has to be in [0, 1), got %g", (double)decay);   // (NaN fails both)
+  LASR_CHECK_ARG(num_updates >= 0, "lasr_ema_state_init: num_updates=%lld", (long long)num_updates);
+  EmaState s;
+  memset(&s, 0, sizeof(s));
+  s.num_updates = num_updates;
+  s.decay = decay;
+  s.warmup = warmup != 0;
+  s.w = 0.f;                   // written by every step before it is read
+  memcpy(host_buf, &s, sizeof(s));
+  return 0;
+}
+
+extern "C" int lasr_ema_update(float* ema, const float* params, int64_t n, float w, void* stream) {
+  LASR_CHECK_ARG(ema && params, "lasr_ema_update: null pointer");
+  LASR_CHECK_ARG(n >= 0, "lasr_ema_update: n=%lld", (long long)n);
+  LASR_CHECK_ARG(ema + n <= params || params + n <= ema || n == 0, "lasr_ema_update: ema aliases params");
+  if (n == 0) return 0;
+  const uintptr_t pe = reinterpret_cast<uintptr_t>(ema), pp = reinterpret_cast<uintptr_t>(params);
+  int64_t head = n, nvec = 0;                           // bases not congruent mod 16 bytes: single elements throughout
+  if ((pe & 15) == (pp & 15) && (pe & 3) == 0) {
+    head = (int64_t)(((16 - (pe & 15)) & 15) >> 2);
+    if (head > n) head = n;
+    nvec = (n - head) >> 2;
+  }
+  int64_t blocks = cdiv(nvec + (n - 4 * nvec), 256);
+  if (blocks > 256 * 8) blocks = 256 * 8;
+  hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), ema, params, n, head, nvec, w);
+  LASR_LAUNCH_CHECK("ema_update_kernel");
   return 0;
 }
 

@@ -2,6 +2,7 @@
 buffer / gradient storage on the GPU plus per-tensor views named like the reference state_dict."""
 from __future__ import annotations
 
+import contextlib
 import os
 
 import ctypes as C
@@ -94,6 +95,22 @@ class NativeModel:
         if grads.dtype != torch.float32 or grads.dim() != 1 or grads.numel() != self.n_param or grads.device != self.device:
             raise ValueError("grads must be a flat float32 buffer of %d elements on %s" % (self.n_param, self.device))
         return grads
+
+    @contextlib.contextmanager
+    def using_params(self, flat: torch.Tensor):
+        """Inside the block every call that reads the parameters (``forward`` first of all) reads ``flat`` instead - another flat
+        f32 buffer of the same size on this device, e.g. the optimiser's weight EMA for validation.  The attribute is swapped,
+        nothing is copied: ``self.params`` is the same tensor at the same address afterwards (also after an exception), so
+        captured training graphs stay valid.  The buffers (BatchNorm running statistics) stay the live model's."""
+        if not torch.is_tensor(flat) or flat.dtype != torch.float32 or flat.dim() != 1 or flat.numel() != self.n_param \
+                or flat.device != self.device or not flat.is_contiguous():
+            raise ValueError("using_params needs a flat contiguous float32 buffer of %d elements on %s" % (self.n_param, self.device))
+        live = self.params
+        self.params = flat
+        try:
+            yield self
+        finally:
+            self.params = live
 
     def param_infos(self) -> List[TensorInfo]:
         return [t for t in self.tensors if t.kind == 0]

@@ -28,6 +28,20 @@ except Exception:  # noqa: BLE001
 logger = logging.getLogger(__name__)
 
 
+def select_state_dict(ckpt: Dict[str, Any], use_ema: Optional[bool] = None) -> Dict[str, Any]:
+    """Which weights of a checkpoint to load.  ``Trainer`` writes ``ema_state_dict`` next to ``state_dict`` when the run kept a
+    weight EMA ("Weight EMA"): the same keys, averaged parameters, the live buffers.  use_ema None: the averaged weights
+    when the checkpoint has them, the live ones otherwise (every EMA-less checkpoint loads as it always did); True: the averaged
+    ones, ValueError when there are none; False: the live ones."""
+    if use_ema not in (None, True, False):
+        raise ValueError("use_ema has to be None, True or False, got %r" % (use_ema,))
+    has = ckpt.get("ema_state_dict") is not None
+    if use_ema and not has:
+        raise ValueError("use_ema=True, but the checkpoint holds no averaged weights (no 'ema_state_dict': it was trained with "
+                         "train.ema_decay = 0)")
+    return ckpt["ema_state_dict"] if has and use_ema is not False else ckpt["state_dict"]
+
+
 def seed_everything(seed: int) -> int:
     random.seed(seed)
     np.random.seed(seed)
@@ -77,12 +91,14 @@ class _ModuleBase(nn.Module):
         pass
 
     @classmethod
-    def load_from_checkpoint(cls, checkpoint_path: str, map_location=None, **kwargs):
+    def load_from_checkpoint(cls, checkpoint_path: str, map_location=None, use_ema: Optional[bool] = None, **kwargs):
+        """use_ema: ``select_state_dict`` - None takes the averaged weights when the checkpoint has them"""
         ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
         hp = dict(ckpt.get("hyper_parameters", {}))
         hp.update(kwargs)
+        state = select_state_dict(ckpt, use_ema)
         model = cls(**hp)
-        model.load_state_dict(ckpt["state_dict"])
+        model.load_state_dict(state)
         return model
 
 
@@ -147,8 +163,14 @@ class Trainer:
                  check_val_every_n_epoch: int = 1, limit_train_batches=1.0, limit_val_batches=1.0,
                  accelerator: Optional[str] = None, num_nodes: int = 1, default_root_dir: str = ".",
                  callbacks=None, logger=None, save_top_k: int = 3, monitor: str = "val_wer", max_steps: Optional[int] = None,
-                 device: Optional[str] = None, log_every_n_steps: int = 50, accumulate_grad_batches: int = 1, **ignored):
+                 device: Optional[str] = None, log_every_n_steps: int = 50, accumulate_grad_batches: int = 1,
+                 ema_decay: float = 0.0, ema_warmup: bool = True, ema_eval: bool = True, **ignored):
+        from .scheduler.novograd import check_ema_decay
         from .step import check_accumulate
+        # weight EMA ("Weight EMA"): the module's configure_optimizers hands ema_decay / ema_warmup to Novograd, which then
+        # owns the average; ema_eval: validate / test (and so the monitored metric and the best-k checkpoints) run on the average
+        self.ema_decay, self.ema_warmup, self.ema_eval = check_ema_decay(ema_decay), bool(ema_warmup), bool(ema_eval)
+        self._opt = None                                # the optimiser of the last fit: where validate / test find the average
         self.max_epochs, self.max_steps = max_epochs, max_steps
         # train.py:244: K micro-batches per optimiser step, the gradient averaged over K; global_step, max_steps, the LR schedule and
         # log_every_n_steps count optimiser steps (fused_fit.window_roles).  An int >= 1; Lightning's epoch -> K dict is not implemented
@@ -245,6 +267,18 @@ class Trainer:
         ckpt = {"epoch": self.current_epoch, "global_step": self.global_step, "state_dict": model.state_dict(),
                 "optimizer_states": [opt.state_dict()], "lr_schedulers": [sched.state_dict()] if sched else [],
                 "hyper_parameters": dict(getattr(model, "hparams", {})), "pytorch-lightning_version": "lasr-native"}
+        if getattr(opt, "ema", None) is not None:
+            # state_dict stays the LIVE weights (reference compatibility, resume); the averaged model travels beside it as a
+            # complete state dict anything that loads state_dict can load: averaged parameters, the live buffers
+            native = model.encoder.native
+            ema_sd = type(ckpt["state_dict"])((k, v.detach().clone()) for k, v in ckpt["state_dict"].items())
+            for t in native.param_infos():
+                key = "encoder." + t.name
+                if key not in ema_sd:
+                    raise KeyError("ema_state_dict: the module's state_dict has no %r" % key)
+                ema_sd[key] = native.view(t, opt.ema).detach().clone()
+            ckpt["ema_state_dict"] = ema_sd
+            ckpt["ema"] = {"decay": opt.ema_decay, "warmup": opt.ema_warmup, "num_updates": opt.ema_num_updates}
         model.on_save_checkpoint(ckpt)
         path = os.path.join(d, name)
         torch.save(ckpt, path)
@@ -266,6 +300,7 @@ class Trainer:
         optimizers, schedulers = model.configure_optimizers()
         opt = optimizers[0]
         sched = schedulers[0]["scheduler"] if schedulers else None
+        self._opt = opt
         start_epoch = 0
         if self.resume_from_checkpoint:
             ckpt = torch.load(self.resume_from_checkpoint, map_location="cpu", weights_only=False)
@@ -362,8 +397,22 @@ class Trainer:
                 break
         return self.history
 
+    def _eval_params(self, model):
+        """the parameters validate / test read: the optimiser's weight EMA when there is one for this model and ema_eval is on
+        (``NativeModel.using_params``: an attribute swap for the block, no copy), else the live ones"""
+        import contextlib
+        ema = getattr(self._opt, "ema", None)
+        native = getattr(getattr(model, "encoder", None), "native", None)
+        if not self.ema_eval or ema is None or native is None or getattr(self._opt, "owner", None) is not model.encoder:
+            return contextlib.nullcontext()
+        return native.using_params(ema)
+
     @torch.no_grad()
     def validate(self, model, datamodule) -> Dict[str, float]:
+        with self._eval_params(model):
+            return self._validate(model, datamodule)
+
+    def _validate(self, model, datamodule) -> Dict[str, float]:
         model.eval()
         self._epoch_metrics = {}
         wer = getattr(model, "wer", None)
@@ -435,7 +484,8 @@ class Trainer:
             dm.trainer = self
             dm.setup("test")                       # PL calls setup('test') on a datamodule handed to .test()
         loader = test_dataloaders if test_dataloaders is not None else dm.test_dataloader()
-        outs = [model.test_step(batch, i) for i, batch in enumerate(self._eval_batches(loader, dm, len(loader)))]
+        with self._eval_params(model):
+            outs = [model.test_step(batch, i) for i, batch in enumerate(self._eval_batches(loader, dm, len(loader)))]
         model.test_epoch_end(outs)
         return outs
 

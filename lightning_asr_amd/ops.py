@@ -875,11 +875,26 @@ def novograd_workspace(n_tensors: int, n_elems: int, device) -> torch.Tensor:
 
 
 def novograd_step(params, grads, exp_avg, exp_avg_sq, offsets, lr_dev, beta1=0.8, beta2=0.5, eps=1e-8, weight_decay=0.0,
-                  grad_scale=1.0, ws: Optional[torch.Tensor] = None):
-    """ws: a workspace from novograd_workspace() kept by the caller - the step then issues no memset of its own"""
+                  grad_scale=1.0, ws: Optional[torch.Tensor] = None, ema: Optional[torch.Tensor] = None,
+                  ema_state: Optional[torch.Tensor] = None):
+    """ws: a workspace from novograd_workspace() kept by the caller - the step then issues no memset of its own.
+    ema + ema_state (``ema_state()``): the weight EMA of the parameters, updated by the step's last kernel with the weight the
+    device record yields ("Weight EMA"); both or neither."""
     n_t = exp_avg_sq.numel()
     n = params.numel()
     nb = _lib.load().lasr_novograd_workspace_bytes(n_t, n)
+    if ema is not None or ema_state is not None:
+        if ema is None or ema_state is None:
+            raise ValueError("novograd_step: ema and ema_state come together")
+        _ema_check("novograd_step", ema, params)
+        if ema_state.dtype != torch.uint8 or ema_state.numel() < ema_state_bytes() or ema_state.device != params.device:
+            raise ValueError("novograd_step: ema_state has to come from ops.ema_state() on %s" % (params.device,))
+        keep = ws is not None
+        if ws is None:
+            ws = _ws(nb, params.device)
+        call("lasr_novograd_step_ema", _p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), _p(offsets), n_t, n, _p(lr_dev), beta1,
+             beta2, eps, weight_decay, grad_scale, _p(ws), ws.numel(), _stream(), _p(ema), _p(ema_state), int(keep))
+        return
     if ws is not None:
         call("lasr_novograd_step_keep", _p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), _p(offsets), n_t, n, _p(lr_dev), beta1,
              beta2, eps, weight_decay, grad_scale, _p(ws), ws.numel(), _stream())
@@ -887,6 +902,70 @@ def novograd_step(params, grads, exp_avg, exp_avg_sq, offsets, lr_dev, beta1=0.8
     ws = _ws(nb, params.device)
     call("lasr_novograd_step", _p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), _p(offsets), n_t, n, _p(lr_dev), beta1,
          beta2, eps, weight_decay, grad_scale, _p(ws), nb, _stream())
+
+
+# ---- weight EMA ("Weight EMA") ----
+_EMA_STATE_FMT = "<qfif"        # lasr_ema_state: int64 num_updates; float decay; int warmup; float w (padded to 24 bytes)
+
+
+def ema_state_bytes() -> int:
+    return int(_lib.load().lasr_ema_state_bytes())
+
+
+def ema_state_host(decay: float, warmup: bool = True, num_updates: int = 0) -> bytes:
+    """the host image of the device record (lasr_ema_state_init); ValueError for a decay outside [0, 1) or a negative count"""
+    decay = float(decay)
+    if not (math.isfinite(decay) and 0.0 <= decay < 1.0):
+        raise ValueError("ema decay has to be in [0, 1), got %r" % (decay,))
+    if int(num_updates) < 0:
+        raise ValueError("ema num_updates has to be >= 0, got %r" % (num_updates,))
+    nb = ema_state_bytes()
+    host = ctypes.create_string_buffer(nb)
+    call("lasr_ema_state_init", host, nb, decay, int(bool(warmup)), int(num_updates))
+    return host.raw
+
+
+def ema_state(decay: float, warmup: bool = True, num_updates: int = 0, device="cuda") -> torch.Tensor:
+    """The device record the optimiser step advances: uint8 (lasr_ema_state_bytes()).  ``ema_state_read`` reads it back."""
+    return torch.frombuffer(bytearray(ema_state_host(decay, warmup, num_updates)), dtype=torch.uint8).to(device)
+
+
+def ema_state_read(state) -> dict:
+    """{"num_updates", "decay", "warmup", "w"} of a record (a tensor from ``ema_state`` - one device read - or host bytes)"""
+    import struct
+    raw = bytes(state.cpu().numpy().tobytes()) if torch.is_tensor(state) else bytes(state)
+    n, decay, warmup, w = struct.unpack_from(_EMA_STATE_FMT, raw)
+    return {"num_updates": int(n), "decay": float(decay), "warmup": bool(warmup), "w": float(w)}
+
+
+def ema_weight(decay: float, warmup: bool, t: int) -> np.float32:
+    """Host twin of the device weight of EMA update number t (0-based), in numpy f32: d = min(decay, f32(1 + t) / f32(10 + t))
+    with warm-up, else decay; w = 1 - d."""
+    d = np.float32(decay)
+    if warmup:
+        d = min(d, np.float32(1 + int(t)) / np.float32(10 + int(t)))
+    return np.float32(1.0) - np.float32(d)
+
+
+def _ema_check(who: str, ema: torch.Tensor, params: torch.Tensor) -> None:
+    for t in (ema, params):
+        if t.dtype != torch.float32:
+            raise TypeError("%s averages float32 buffers, got %s" % (who, t.dtype))
+        if not t.is_cuda:
+            raise _lib.LasrError("liblasr ops need GPU tensors (got a %s tensor); there is no CPU fallback" % t.device)
+    if ema.dim() != 1 or params.dim() != 1 or ema.numel() != params.numel():
+        raise ValueError("%s needs two flat buffers of one size, got %s and %s" % (who, tuple(ema.shape), tuple(params.shape)))
+    if ema.device != params.device:
+        raise ValueError("%s: buffers on %s and %s" % (who, ema.device, params.device))
+
+
+def ema_update(ema: torch.Tensor, params: torch.Tensor, w) -> None:
+    """``ema = ema + (params - ema) * w`` over two flat f32 GPU buffers of one size, in one launch and in the three roundings
+    of the torch expression (bit-equal to it) - the update the fused optimiser step applies, with the weight from the host."""
+    _ema_check("ema_update", ema, params)
+    if ema.numel() == 0:
+        return
+    call("lasr_ema_update", _p(ema), _p(params), ema.numel(), float(w), _stream())
 
 
 ACC_MAX_RANGES = 8          # LASR_ACC_MAX_RANGES

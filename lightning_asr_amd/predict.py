@@ -41,7 +41,7 @@ class AsrTranslator:
     def __init__(self, model_path: str, map_location: str = "cuda", lang: str = "en", labels: Optional[List[str]] = None,
                  verbose: bool = False, decoder: str = "greedy", beam_width: int = 16, cutoff_top_n: int = 40,
                  cutoff_prob: float = 1.0, lm_path: Optional[str] = None, alpha: float = 1.0, beta: float = 1.0, resample: bool = False,
-                 hotwords=None, hotword_weight: float = 2.0):
+                 hotwords=None, hotword_weight: float = 2.0, use_ema: Optional[bool] = None):
         """model_path: a ``.ckpt`` written by the reference or by ``Trainer``; map_location must name a GPU
         ("cuda" / "cuda:0"): there is no CPU path.  ``labels`` overrides the language's vocabulary.
         decoder: "greedy" (argmax + CTC collapse, the default) or "beam" (CTC prefix beam search; with ``lm_path``, a text ARPA
@@ -53,6 +53,9 @@ class AsrTranslator:
         phrase given without one, in natural-log units per matched label; the default 2.0 is a starting value: nobody has tuned
         it on a trained model.  decoder="greedy" with hotwords raises ValueError, a word-level LM NotImplementedError;
         ``set_hotwords`` swaps the bank later.
+        use_ema: which weights of a checkpoint whose run kept a weight EMA (``train.ema_decay`` > 0): None (the default) - the
+        averaged ones when the checkpoint has them, the live ones otherwise, so every other checkpoint loads as it always did;
+        True - the averaged ones, ValueError when the checkpoint has none; False - the live ones.
         resample: False (the default, the reference's behaviour) feeds a file's samples to the 16 kHz front-end whatever its
         sample rate; True converts a file of another rate on the device first (``ops.resample``) - ``translate``,
         ``translate_nbest``, ``align`` and ``translate_timed`` then hear it at its true speed and report its true times (each
@@ -73,7 +76,7 @@ class AsrTranslator:
         self.model_path = model_path
         self.map_location = map_location
         self.verbose = verbose
-        self.model = LightingModule.load_from_checkpoint(model_path, map_location=map_location, device=str(map_location))
+        self.model = LightingModule.load_from_checkpoint(model_path, map_location=map_location, use_ema=use_ema, device=str(map_location))
         self.audio_parser = AudioParser(device=str(map_location))
         self.audio_parser.act_dtype = self.model.encoder.native.act_dtype
         self.device = torch.device(map_location)

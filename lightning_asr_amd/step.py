@@ -18,6 +18,7 @@ from . import _lib, ops
 from .comm import Communicator
 from .engine import NativeModel
 from .schedule import CosineAnnealingWarmupRestarts
+from .scheduler.novograd import check_ema_decay
 
 
 _ROCTX = None
@@ -42,7 +43,8 @@ def check_accumulate(k) -> int:
 class TrainStep:
     def __init__(self, model: NativeModel, learning_rate: float = 1e-2, weight_decay: float = 1e-3,
                  betas=(0.8, 0.5), eps: float = 1e-8, schedule: Optional[CosineAnnealingWarmupRestarts] = None,
-                 process_group=None, comm: Optional[Communicator] = None, accumulate: int = 1):
+                 process_group=None, comm: Optional[Communicator] = None, accumulate: int = 1, ema_decay: float = 0.0,
+                 ema_warmup: bool = True):
         """comm: the library-owned RCCL communicator (lasr_comm_*).  Default for world > 1 on the nccl backend: one is built
         from the torch.distributed group (which then only bootstraps the unique id); ``LASR_COMM=torch`` keeps the gradient
         exchange on torch.distributed (the only choice for gloo groups: CPU rehearsal, two ranks sharing a GPU in the tests).
@@ -50,8 +52,17 @@ class TrainStep:
         ``model.grads_micro``, one launch that adds it into ``model.grads``); the K-th of a window - or one called with
         ``last=True`` - is the boundary, which additionally all-reduces, steps the optimiser with grad_scale 1 / (K world),
         steps the schedule and zeroes ``model.grads``, which is therefore zero between windows.  K = 1 is the step as it
-        always was: no second buffer, no extra launch."""
+        always was: no second buffer, no extra launch.
+        ema_decay > 0: ``self.ema`` is an exponential moving average of the parameters ("Weight EMA"), a copy of them
+        now and updated by the last kernel of every OPTIMISER step (under accumulate > 1 only the boundary reaches it) with the
+        weight the device record ``self.ema_state`` yields - no launch, no host scalar, so a captured graph replays it.  0 = off:
+        no buffer, and the step as it always was."""
         self.model = model
+        self.ema_decay, self.ema_warmup = check_ema_decay(ema_decay), bool(ema_warmup)
+        self.ema = self.ema_state = None
+        if self.ema_decay > 0.0:
+            self.ema = model.params.clone()
+            self.ema_state = ops.ema_state(self.ema_decay, self.ema_warmup, 0, device=model.device)
         self.accumulate = check_accumulate(accumulate)
         self.micro = 0             # micro-batches already added into model.grads in the current window (K > 1)
         if self.accumulate > 1:
@@ -124,10 +135,18 @@ class TrainStep:
         ts = cls(model, learning_rate=float(g["lr"]), weight_decay=g["weight_decay"], betas=tuple(g["betas"]), eps=g["eps"],
                  schedule=schedule, process_group=process_group, comm=comm, accumulate=accumulate)
         ts.exp_avg, ts.exp_avg_sq, ts.lr_dev = optimizer.exp_avg, optimizer.exp_avg_sq, optimizer.lr_dev
+        # the weight EMA is the optimiser's too (None with ema_decay = 0): checkpoints and resume go through its state_dict
+        ts.ema, ts.ema_state = getattr(optimizer, "ema", None), getattr(optimizer, "ema_state", None)
+        ts.ema_decay, ts.ema_warmup = getattr(optimizer, "ema_decay", 0.0), getattr(optimizer, "ema_warmup", True)
         ts.lr = float(g["lr"])
         ts.lr_dev.fill_(ts.lr)
         ts._optimizer = optimizer
         return ts
+
+    @property
+    def ema_num_updates(self) -> int:
+        """EMA updates done so far (one read of the device record); 0 with EMA off"""
+        return ops.ema_state_read(self.ema_state)["num_updates"] if self.ema_state is not None else 0
 
     def sync_device_schedule(self) -> None:
         """Re-upload the schedule after its host state changed behind the device twin's back (``load_state_dict`` on resume,
@@ -169,7 +188,8 @@ class TrainStep:
         if getattr(self, "_opt_ws", None) is None:       # kept across steps: zeroed once, left zeroed by every step (no memset launch)
             self._opt_ws = ops.novograd_workspace(self.exp_avg_sq.numel(), m.params.numel(), m.device)
         ops.novograd_step(m.params, m.grads, self.exp_avg, self.exp_avg_sq, self.offsets, self.lr_dev, self.betas[0],
-                          self.betas[1], self.eps, self.wd, grad_scale=1.0 / (self.accumulate * self.world), ws=self._opt_ws)
+                          self.betas[1], self.eps, self.wd, grad_scale=1.0 / (self.accumulate * self.world), ws=self._opt_ws,
+                          ema=self.ema, ema_state=self.ema_state)
         if self.schedule is not None:
             if self._lr_state is not None and self.schedule.last_epoch != self._lr_epoch:
                 self.sync_device_schedule()                # the host schedule was loaded / reset since the last step
@@ -368,7 +388,8 @@ class GraphedTrainStep:
         with bound inputs + feats_in, or when ``prime()`` hands the features over).
         The eager warm-up passes and the capture pass leave the training state (parameters, BN buffers, optimiser moments,
         schedule, dither / dropout counters) exactly as it was - also when the capture fails: it is snapshotted before and
-        restored in a ``finally`` (accumulate > 1: the running gradient sum, the micro-batch buffer and the window counter too)."""
+        restored in a ``finally`` (accumulate > 1: the running gradient sum, the micro-batch buffer and the window counter too;
+        with a weight EMA: the average and its device record)."""
         ts, m = self.ts, self.ts.model
         if ts.world > 1 and not graph_dp_enabled():
             raise RuntimeError("graph capture of the data-parallel step (RCCL inside the graph) is switched off: LASR_GRAPH_DP=0")
@@ -376,6 +397,8 @@ class GraphedTrainStep:
         dev_state = [m.params, m.buffers, ts.exp_avg, ts.exp_avg_sq, ts.lr_dev] + ([ts._lr_state] if ts._lr_state is not None else [])
         if ts.accumulate > 1:
             dev_state += [m.grads, m.grads_micro]
+        if ts.ema is not None:
+            dev_state += [ts.ema, ts.ema_state]       # the average and its update count: the warm-up passes advance both
         micro = ts.micro
         if hasattr(self.dither, "step"):
             dev_state.append(self.dither.step)

@@ -80,7 +80,10 @@ class LightingModule(LightningModule):
 
     def configure_optimizers(self):
         self.print("设置学习率" + str(self.learning_rate))
-        novo_optim = Novograd(self.parameters(), lr=self.learning_rate, weight_decay=self.weight_decay, betas=(0.8, 0.5))
+        # weight EMA (train.ema_decay; DESIGN 4, "Weight EMA"): the optimiser owns the average, the Trainer carries the setting
+        novo_optim = Novograd(self.parameters(), lr=self.learning_rate, weight_decay=self.weight_decay, betas=(0.8, 0.5),
+                              ema_decay=float(getattr(self.trainer, "ema_decay", 0.0) or 0.0),
+                              ema_warmup=bool(getattr(self.trainer, "ema_warmup", True)))
         # the schedule counts OPTIMISER steps: ceil(batches / K) per epoch under accumulate_grad_batches = K (the last window of an
         # epoch may be incomplete and still steps)
         K = int(getattr(self.trainer, "accumulate_grad_batches", 1) or 1)
@@ -199,7 +202,9 @@ def main(argv=None):
                       max_epochs=tran_cfg.get("total_epoch"), check_val_every_n_epoch=tran_cfg.get("check_val_every_n_epoch", 1),
                       num_nodes=tran_cfg.get("num_nodes"), default_root_dir=cfg.get("output_dir", "."),
                       max_steps=tran_cfg.get("max_steps"), log_every_n_steps=tran_cfg.get("log_every_n_steps", 50),
-                      accumulate_grad_batches=tran_cfg.get("accumulate_grad_batches", 1))
+                      accumulate_grad_batches=tran_cfg.get("accumulate_grad_batches", 1),
+                      ema_decay=tran_cfg.get("ema_decay", 0) or 0.0, ema_warmup=tran_cfg.get("ema_warmup", True),
+                      ema_eval=tran_cfg.get("ema_eval", True))
     trainer.fit(model, datamodule=data_module)
     trainer.test(model, test_dataloaders=data_module.test_dataloader())
     return trainer
