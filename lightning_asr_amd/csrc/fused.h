@@ -4,13 +4,27 @@
 
 namespace lasr {
 
+// THE convention of every fused helper below (and of gemm_multi_split_partials_with_bilstm_bwd, gemm.h): it returns kFusedTaken
+// when it launched its kernel, kFusedNotTaken when the mode or shape has no fused kernel - nothing was launched, the caller runs the
+// separate launches - or a negative error.  LASR_FUSED(var, call): var = the call was taken; an error leaves the calling function.
+static constexpr int kFusedTaken = 0, kFusedNotTaken = 1;
+#define LASR_FUSED(var, ...)                                        \
+  do {                                                              \
+    const int rc__ = (__VA_ARGS__);                                 \
+    if (rc__ != ::lasr::kFusedTaken && rc__ != ::lasr::kFusedNotTaken) return rc__; \
+    var = rc__ == ::lasr::kFusedTaken;                              \
+  } while (0)
+
+// segments of one lasr_reduce_many launch: its kernel's argument struct (ReduceMany, norm.hip), its check, the stage's collector
+static constexpr int kMaxReduceSegments = 64;
+
 // Depthwise forward of unit i+1 (stride 1, bf16) whose input is made on the fly from unit i's GEMM outputs:
 //   out = act(y a + b [+ y2 a2 + b2])     (bn_act_fwd_kernel's arithmetic: SeprationConv's BatchNorm, the block's residual add and
 //                                          ReLU, models/QuartNet.py:33-37,74-77 - bit-identical to the separate launch)
 //   u   = depthwise_conv(out, w)          (models/QuartNet.py:15-19 of the next unit)
 // `t` is unit i's tail (lasr_bn_tail: y / coef of both sides, act and the shape are read; coef [2][C] (scale | shift) as
 // lasr_bn_finalize_partials leaves them; res.y null: no residual branch).
-// Returns 0 (launched), 1 (this shape takes no fused kernel: nothing was launched, run the two launches) or a negative error.
+// Fused convention (above); not taken: run lasr_bn_act_fwd[_partials] and lasr_dwconv_fwd.
 // partials_of (null: the coefficients are final): the unit's lasr_bn_branch descriptions (one, or two with res.y) when its finalize
 // was left to its consumer - every workgroup folds the coefficients of its 64 channels from the GEMM's partial sums in its prologue
 // (bn_slice.h) and one workgroup per 64 channels leaves coef / saved / stats / the running statistics in memory.
@@ -47,17 +61,17 @@ const uint32_t* dw_taps_for(const float* w, int flip, int64_t C);
 bool dw_taps_enabled();
 
 // norm.hip: lasr_mask_lengths_step + lasr_cast_f32_to_bf16 (+ the depthwise tap tables, jobs != null) in one launch - the start of
-// every bf16 training forward; 1 = not taken
+// every bf16 training forward.  Fused convention (above).
 int mask_lengths_step_cast(const float* pct, int64_t B, int64_t T_, int32_t* lens, uint64_t* step_counter, const float* in, void* out,
                            int64_t n, const DwTapJobs* jobs, void* stream);
 // norm.hip: lasr_cast_pad_f32_to_bf16 + lasr_colsum_f32's first stage + lasr_scale_sum_f32 in one launch, then the column sums' second
-// stage (the tail of the dense small-vocabulary loss head); 1 = not taken
+// stage (the tail of the dense small-vocabulary loss head).  Fused convention (above).
 int head_tail(const float* gl, int64_t rows, int64_t C, void* gl_bf16, int64_t ld_out, float* bias_grad, void* workspace,
               size_t workspace_bytes, const float* nll, int64_t n_nll, float scale, float* loss, void* stream);
 
 // se.hip (round 5): the excite MLP (lasr_se_fwd's two launches) inside the BN + SE + residual add + activation pass, dealt over
 // (64-channel slab x utterance) workgroups that each recompute their utterance's hidden vector; bit-identical to the three launches.
-// 0 = launched, 1 = not taken (f32, dropout, odd shapes: the caller runs lasr_se_fwd + lasr_bn_act_fwd), negative = error
+// Fused convention (above); not taken (f32, dropout, odd shapes): the caller runs lasr_se_fwd + lasr_bn_act_fwd.
 // Of the tail: y / coef of both sides, dtype, act and the shape (its se_scale is what `scale` receives).
 int bn_se_act_fwd(const lasr_bn_tail& t, const float* sums, const float* W1, const float* W2, void* out, float* pooled, float* hidden,
                   float* scale, void* stream);

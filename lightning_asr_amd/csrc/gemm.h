@@ -23,9 +23,12 @@ int launch_gemm_bf16(const GemmArgs& g, int gz, int dtype_c, int transA, int tra
 int launch_gemm_bf16_batch(const GemmArgs* g, const int* gz, int n, int dtype_c, int transA, int transB, hipStream_t st,
                            int* stat_tiles);
 
-// up to 32 split-K weight-gradient problems (transA = transB = 1, f32 slabs in g[i].split_ws), one launch
 int launch_gemm_bf16_dual(const GemmArgs& g, const void* A2, int64_t lda2, int64_t K1, const float* bias, int act, hipStream_t st);
 namespace lstm { struct BwdArgs; }
+// The multi-problem split-K weight-gradient launch (transA = transB = 1, f32 slabs in g[i].split_ws): what its kernels' argument
+// struct holds (Bf16Multi, gemm_bf16.hip), checked by its launchers and relied on by the stage's collector (stage_grads.h).
+static constexpr int kMaxMultiProblems = 32;
+static constexpr int kMaxMultiRiders = 24;
 // lstm_job (optional): the BiLSTM backward recurrences run in the same grid as lstm_wgs workgroups, ahead of the tiles (lstm_body.h)
 // riders (optional): reductions that are already complete when this launch is issued; the first *riders_taken of them are done by
 // extra workgroups of this launch on the CUs its one round of tiles leaves idle (reduce_body.h) - the caller reduces the rest
@@ -38,8 +41,8 @@ int gemm_multi_split_partials_riders(const lasr_gemm_problem* probs, int n_probs
 int gemm_split_partials_one(const void* A, const void* B, int dtype_ab, int64_t M, int64_t N, int64_t K, int transA, int transB, int split_k,
                             void* workspace, size_t workspace_bytes, int* splits, void* stream);
 // lasr_gemm_multi_split_partials with the context branch's BiLSTM backward recurrences (lstm_body.h) in its grid, and the dW_hh /
-// bias-gradient partial sums (rec.pwhh [2][B * kDwZ][G*H], rec.pbias [2][B * kDwZ][G]: the caller reduces them) behind it; returns 1
-// without launching anything when the shapes do not take the combined grid (the caller then makes the separate calls).
+// bias-gradient partial sums (rec.pwhh [2][B * kDwZ][G*H], rec.pbias [2][B * kDwZ][G]: the caller reduces them) behind it.  Fused
+// convention (fused.h); not taken (shapes without the combined grid): the caller makes the separate calls.
 // Only the first *n_taken problems are launched (as many tiles as finish, in one round of workgroups, about when the recurrences do):
 // the caller keeps the rest for its next batched launch.
 int gemm_multi_split_partials_with_bilstm_bwd(const lasr_gemm_problem* probs, int n_probs, int* n_taken, int split_k, float* const* slabs, int* splits,

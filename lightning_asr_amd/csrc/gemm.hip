@@ -555,10 +555,10 @@ int lasr::gemm_multi_split_partials_with_bilstm_bwd(const lasr_gemm_problem* pro
 static int multi_split_impl(const lasr_gemm_problem* probs, int n_probs, int split_k, float* const* slabs, int* splits, void* stream,
                             const lstm::BwdArgs* lstm_job, int lstm_wgs, const lasr_reduce_desc* riders, int n_riders, int* riders_taken) {
   if (riders_taken) *riders_taken = 0;
-  LASR_CHECK_ARG(probs && slabs && splits && n_probs >= 1 && n_probs <= 32 && split_k >= 1 && split_k <= 1024,
+  LASR_CHECK_ARG(probs && slabs && splits && n_probs >= 1 && n_probs <= kMaxMultiProblems && split_k >= 1 && split_k <= 1024,
                  "lasr_gemm_multi_split_partials: bad argument");
-  GemmArgs g[32];
-  int gz[32];
+  GemmArgs g[kMaxMultiProblems];
+  int gz[kMaxMultiProblems];
   // Tile form and slice count for the whole launch (split_k is the cap the slabs were sized for).
   //  * 256 x 256 tiles, one workgroup per CU: as many slices as keep the launch to one round of workgroups;
   //  * 128 x 128 tiles, two workgroups per CU: ~3 rounds of resident workgroups (1536 tile-slices).

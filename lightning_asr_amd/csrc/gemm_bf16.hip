@@ -476,15 +476,13 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(Bf16Batch gb) {
   gemm_bf16_tile<TC, TRANS_A, TRANS_B, VEC>(g, second ? lid_all - gb.tiles0 : lid_all);
 }
 
-// Up to 32 problems in one launch: the 1x1 weight gradients of a whole backward stage.  Per unit their split-K
+// Up to kMaxMultiProblems (gemm.h) problems in one launch: the 1x1 weight gradients of a whole backward stage.  Per unit their split-K
 // launch is 16 K steps per workgroup between a prologue and a 32 MB partial-slab epilogue; batched, a stage needs
 // a third of the slices for the same number of workgroups, so slices are 3x longer and the slabs 3x smaller.
-static constexpr int kMaxMulti = 32;
 // riders (round 5): reductions of the stage that are already COMPLETE when the weight-gradient launch is issued (the depthwise
 // weight gradients' per-utterance partials, 64 MB of lasr_reduce_many's 123 MB at cfg2) run as n_rwg extra workgroups behind the tiles -
 // on the CUs the one round of tiles leaves idle (71 tiles x 3 slices = 213 of 256)
-static constexpr int kMaxRiders = 24;
-struct Bf16Multi { Bf16Args p[kMaxMulti]; int start[kMaxMulti + 1]; int n, total; lasr_reduce_desc rd[kMaxRiders]; int n_rd, n_rwg; };
+struct Bf16Multi { Bf16Args p[kMaxMultiProblems]; int start[kMaxMultiProblems + 1]; int n, total; lasr_reduce_desc rd[kMaxMultiRiders]; int n_rd, n_rwg; };
 template <bool VEC>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_multi_kernel(Bf16Multi gm) {
   const int lid_all = xcd_remap(blockIdx.x, gm.total);
@@ -1086,7 +1084,7 @@ int launch_gemm_bf16_rowstat(const GemmArgs& g, float* row_stat, int32_t* row_ar
 // n <= 32 split-K problems with f32 slab output, both operands row-contiguous ([K][M], [K][N]: weight gradients)
 int launch_gemm_bf16_multi(const GemmArgs* g, const int* gz, int n, bool big_tile, hipStream_t st, const lstm::BwdArgs* lstm_job, int lstm_wgs,
                            const lasr_reduce_desc* riders, int n_riders, int* riders_taken) {
-  if (n < 1 || n > kMaxMulti) return fail(LASR_E_ARG, "lasr_gemm_multi_split_partials: 1..%d problems", kMaxMulti);
+  if (n < 1 || n > kMaxMultiProblems) return fail(LASR_E_ARG, "lasr_gemm_multi_split_partials: 1..%d problems", kMaxMultiProblems);
   if (riders_taken) *riders_taken = 0;
   Bf16Multi m;
   m.n_rd = 0; m.n_rwg = 0;
@@ -1099,8 +1097,8 @@ int launch_gemm_bf16_multi(const GemmArgs* g, const int* gz, int n, bool big_til
     m.start[i] = total;
     total += m.p[i].gn * m.p[i].gm * m.p[i].gz;
   }
-  for (int i = n; i < kMaxMulti; ++i) m.p[i] = m.p[0];
-  for (int i = n; i <= kMaxMulti; ++i) m.start[i] = total;
+  for (int i = n; i < kMaxMultiProblems; ++i) m.p[i] = m.p[0];
+  for (int i = n; i <= kMaxMultiProblems; ++i) m.start[i] = total;
   m.n = n; m.total = total;
   if (big_tile) {
     if (!vec) return fail(LASR_E_ARG, "lasr_gemm_multi_split_partials: the 256-row tile needs 16-byte aligned operand rows");
@@ -1126,7 +1124,7 @@ int launch_gemm_bf16_multi(const GemmArgs* g, const int* gz, int n, bool big_til
       int ksteps = 0;
       for (int i = 0; i < n; ++i) ksteps = std::max(ksteps, (int)cdiv(m.p[i].k_per_split, 64));
       double budget = (double)idle * 20e9 * ((double)ksteps * 1.7e-6 + 20e-6) * 0.8;
-      while (m.n_rd < n_riders && m.n_rd < kMaxRiders) {
+      while (m.n_rd < n_riders && m.n_rd < kMaxMultiRiders) {
         const lasr_reduce_desc& q = riders[m.n_rd];
         const double bytes = (double)q.n * (q.n_partials + 1) * sizeof(float);
         if (bytes > budget) break;
@@ -1135,7 +1133,7 @@ int launch_gemm_bf16_multi(const GemmArgs* g, const int* gz, int n, bool big_til
       }
       if (m.n_rd > 0) { m.n_rwg = idle; *riders_taken = m.n_rd; }
     }
-    for (int i = m.n_rd; i < kMaxRiders; ++i) m.rd[i] = lasr_reduce_desc{nullptr, nullptr, 0, 0};
+    for (int i = m.n_rd; i < kMaxMultiRiders; ++i) m.rd[i] = lasr_reduce_desc{nullptr, nullptr, 0, 0};
     if (nt_loads_mask() & 8) hipLaunchKernelGGL(gemm_bf16_big_multi_kernel<true>, dim3((unsigned)(total + m.n_rwg)), dim3(big::NT), 0, st, m);
     else hipLaunchKernelGGL(gemm_bf16_big_multi_kernel<false>, dim3((unsigned)(total + m.n_rwg)), dim3(big::NT), 0, st, m);
     LASR_LAUNCH_CHECK("gemm_bf16_big_multi_kernel");

@@ -8,6 +8,7 @@
 #include "gemm.h"
 #include "lstm_body.h"
 #include "se_seqsum.h"
+#include "stage_grads.h"
 #include <string>
 #include <vector>
 #include <math.h>
@@ -453,6 +454,23 @@ static lasr_bn_tail unit_tail(const lasr_model* m, const Unit& u, const float* p
   return t;
 }
 
+// The BatchNorm side(s) of unit u for what MAKES the coefficients (main, then residual; returns how many).  partials / n_partials are
+// the caller's to fill from its GEMM; the eval coefficients and LASR_NO_FUSE's separate finalize read the same records.
+static int unit_bn_branches(const Unit& u, const float* params, float* buffers, void* ws, lasr_bn_branch br[2]) {
+  auto side = [&](const BnRef& bn, size_t o_coef, size_t o_saved, size_t o_stats) {
+    return lasr_bn_branch{nullptr, 0, params + bn.gamma, params + bn.beta, buffers + bn.rmean, buffers + bn.rvar,
+                          atf(ws, o_coef), atf(ws, o_saved), atf(ws, o_stats)};
+  };
+  br[0] = side(u.bn, u.o_coef, u.o_saved, u.o_stats);
+  if (u.has_res) br[1] = side(u.bn_res, u.o_coef2, u.o_saved2, u.o_stats2);
+  return u.has_res ? 2 : 1;
+}
+
+// What a model call was given, for the phases of the step below (plain values: nothing here computes)
+struct StepArgs {
+  lasr_model* m; const float* params; float* buffers; float* grads; void* ws; void* stream;
+  bool training, dropping;
+};
 // The step's depthwise tap tables (fused.h): made by the training forward's first launch, looked up by the depthwise host
 // functions while a model call is in progress on this thread.
 struct DwTapScope {
@@ -480,15 +498,101 @@ static bool eval_fold(int dtype) {
 }
 static bool fold_unit(const Unit& u) { return u.has_res && u.has_dw && !u.has_se && !u.ctx_before && u.ci % 64 == 0 && u.co % 8 == 0; }
 
-static int forward_impl(lasr_model_t* m, const float* params, float* buffers, const void* feats, const float* pct,
-                        int64_t B, int64_t T_in, int training, float* logp_out, int32_t* argmax_out, void* ws,
-                        size_t ws_bytes, void* stream, bool lean);
+// The start of a forward: the lengths (and the dropout masks' step counter), the weights' bf16 shadow, the tap tables (m->taps_valid)
+static int forward_prologue(const StepArgs& a, const float* pct) {
+  lasr_model* m = a.m;
+  const Plan& p = m->plan;
+  const int dt = m->cfg.dtype;
+  int32_t* lens = reinterpret_cast<int32_t*>(at(a.ws, p.o_lens));
+  uint64_t* drop_step = a.dropping ? m->drop_step : nullptr;
+  ProfScope ps(LASR_PROF_OTHER, a.stream, dt == LASR_BF16 ? 6.0 * m->n_param : 0.0);
+  bool merged = false;   // bf16: the lengths and the weights' bf16 shadow in one launch (two independent launch-floor kernels)
+  m->taps_valid = false;
+  if (dt == LASR_BF16) {
+    DwTapJobs jobs;                                       // the depthwise tap tables ride in the same launch (training and eval forwards)
+    jobs.n = 0; jobs.blk0[0] = 0;
+    for (const Unit& u : m->units)
+      if (u.o_taps && jobs.n < 16) {
+        jobs.w[jobs.n] = a.params + u.w_dw; jobs.out[jobs.n] = reinterpret_cast<uint32_t*>(at(a.ws, u.o_taps)); jobs.C[jobs.n] = u.ci; jobs.k[jobs.n] = u.k;
+        jobs.blk0[jobs.n + 1] = jobs.blk0[jobs.n] + (int)cdiv((int64_t)2 * u.ci * kDwTapRow, 256);
+        ++jobs.n;
+      }
+    LASR_FUSED(merged, mask_lengths_step_cast(pct, p.B, p.T, lens, drop_step, a.params, at(a.ws, p.o_wbf16), m->n_param, jobs.n ? &jobs : nullptr,
+                                              a.stream));
+    m->taps_valid = merged && jobs.n > 0;
+  }
+  if (!merged) {
+    LASR_TRY(lasr_mask_lengths_step(pct, p.B, p.T, lens, drop_step, a.stream));   // (bumps the masks' step counter)
+    if (dt == LASR_BF16) LASR_TRY(lasr_cast_f32_to_bf16(a.params, at(a.ws, p.o_wbf16), m->n_param, a.stream));
+  }
+  return 0;
+}
 
-extern "C" int lasr_model_forward(lasr_model_t* m, const float* params, float* buffers, const void* feats, const float* pct,
-                                  int64_t B, int64_t T_in, int training, float* logp_out, int32_t* argmax_out, void* ws,
-                                  size_t ws_bytes, void* stream) {
-  LASR_CHECK_ARG(logp_out, "lasr_model_forward: null pointer");
-  return forward_impl(m, params, buffers, feats, pct, B, T_in, training, logp_out, argmax_out, ws, ws_bytes, stream, false);
+// eval: BN coefficients of all layers from the running statistics, one launch; then BN folded into the residual units' 1x1 convs
+static int eval_coefficients(const StepArgs& a) {
+  const lasr_model* m = a.m;
+  std::vector<lasr_bn_eval_desc> descs;
+  for (const Unit& u : m->units) {
+    lasr_bn_branch br[2];
+    const int np = unit_bn_branches(u, a.params, a.buffers, a.ws, br);
+    for (int s = 0; s < np; ++s) descs.push_back({br[s].gamma, br[s].beta, br[s].running_mean, br[s].running_var, br[s].coef, u.co});
+  }
+  for (size_t i = 0; i < descs.size(); i += 64)
+    LASR_TRY(lasr_bn_eval_coef_many(descs.data() + i, (int)std::min<size_t>(64, descs.size() - i), kBnEps, a.stream));
+  if (eval_fold(m->cfg.dtype)) {   // one launch for all of them
+    std::vector<lasr_fold_desc> fd;
+    for (const Unit& u : m->units)
+      if (fold_unit(u))
+        fd.push_back({a.params + u.w_pw, a.params + u.w_res, atf(a.ws, u.o_coef), atf(a.ws, u.o_coef2), at(a.ws, u.o_wfold), atf(a.ws, u.o_bfold), u.co, u.ci});
+    for (size_t i = 0; i < fd.size(); i += 32)
+      LASR_TRY(lasr_fold_bn_weights_many(fd.data() + i, (int)std::min<size_t>(32, fd.size() - i), a.stream));
+  }
+  return 0;
+}
+
+// context branch: gates' input projection as two GEMMs (f32 out), the recurrence, then cat(x, lstm) -> [N][336] at o_cat
+static int context_fwd(const StepArgs& a, const void* x) {
+  const lasr_model* m = a.m;
+  const Plan& p = m->plan;
+  const int dt = m->cfg.dtype;
+  const int64_t N = p.B * p.T;
+  const float* params = a.params; void* ws = a.ws; void* stream = a.stream;
+  lasr_gemm_problem pr[2];
+  for (int d = 0; d < 2; ++d) pr[d] = {x, wptr(m, params, ws, m->lstm.w_ih[d]), atf(ws, p.o_gx[d]), N, 160, 256, nullptr, nullptr, 0, nullptr};
+  LASR_TRY(lasr_gemm_batch(pr, 2, dt, LASR_F32, 0, 0, 1, at(ws, p.o_scratch), p.scratch_bytes, stream));   // (one launch)
+  LASR_TRY(lasr_copy_cols(x, dt, 256, 0, at(ws, p.o_cat), dt, 336, 0, N, 256, 0, stream));
+  return lasr_bilstm_fwd(atf(ws, p.o_gx[0]), atf(ws, p.o_gx[1]), params + m->lstm.w_hh[0], params + m->lstm.w_hh[1],
+                         params + m->lstm.b_ih[0], params + m->lstm.b_hh[0], params + m->lstm.b_ih[1], params + m->lstm.b_hh[1],
+                         reinterpret_cast<const int32_t*>(at(ws, p.o_lens)), p.B, p.T, at(ws, p.o_cat), dt, 336, 256, atf(ws, p.o_lstm_saved), stream);
+}
+
+// decoder 1x1 1024 -> C with bias (models/QuartNet.py:275), f32 logits, then log_softmax (+argmax)
+static int decoder_fwd(const StepArgs& a, const void* x, float* logp_out, int32_t* argmax_out, bool lean) {
+  lasr_model* m = a.m;
+  const Plan& p = m->plan;
+  const int dt = m->cfg.dtype;
+  const int64_t N = p.B * p.T, C = m->cfg.n_class;
+  const float* params = a.params; void* ws = a.ws; void* stream = a.stream;
+  void* scratch = at(ws, p.o_scratch);
+  if (lean) {   // bf16 logits + per-tile softmax statistics; lse / emissions / gradient follow in lasr_ctc_loss_lean
+    float* rs = atf(ws, p.o_rowstat);
+    int32_t* ra = reinterpret_cast<int32_t*>(rs + (size_t)N * cdiv(C, 256) * 2);
+    return lasr_gemm_rowstat(x, wptr(m, params, ws, m->w_dec), params + m->b_dec, at(ws, p.o_logits), lean_ldc(m), N, C, 1024, rs, ra,
+                             &m->lean_tiles, stream);
+  }
+  // a narrow vocabulary leaves N/128 = 1 tile column: split K so that the 32 MB of activations are streamed by
+  // 4 x 126 workgroups instead of 126 (the split partials are C/1024 of the input: negligible)
+  const int dec_split = (dt == LASR_BF16 && C <= 128) ? dec_split_k() : 1;
+  if (dec_split > 1 && log_softmax_split_on(C)) {      // narrow head: the split-K slabs are summed by the log_softmax launch itself (fused.h)
+    int splits = 0;
+    LASR_TRY(gemm_split_partials_one(x, wptr(m, params, ws, m->w_dec), dt, N, C, 1024, 0, 0, dec_split, scratch, p.scratch_bytes, &splits, stream));
+    ProfScope ps(LASR_PROF_HEAD, stream, (2.0 + splits) * N * C * sizeof(float));
+    return log_softmax_split(reinterpret_cast<const float*>(scratch), splits, params + m->b_dec, atf(ws, p.o_logits), logp_out, argmax_out, N, C, stream);
+  }
+  LASR_TRY(lasr_gemm(x, wptr(m, params, ws, m->w_dec), atf(ws, p.o_logits), dt, LASR_F32, N, C, 1024, 0, 0, params + m->b_dec,
+                     nullptr, nullptr, 0, nullptr, dec_split, scratch, p.scratch_bytes, stream));
+  ProfScope ps(LASR_PROF_HEAD, stream, 2.0 * N * C * sizeof(float));
+  return lasr_log_softmax(atf(ws, p.o_logits), logp_out, argmax_out, N, C, stream);
 }
 
 static int forward_impl(lasr_model_t* m, const float* params, float* buffers, const void* feats, const float* pct,
@@ -503,52 +607,11 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
   const int64_t T = p.T, N = B * T;
   int32_t* lens = reinterpret_cast<int32_t*>(at(ws, p.o_lens));
   const bool dropping = training && m->drop_p > 0.f;
-  {
-    ProfScope ps(LASR_PROF_OTHER, stream, dt == LASR_BF16 ? 6.0 * m->n_param : 0.0);
-    int merged = 1;      // bf16: the lengths and the weights' bf16 shadow in one launch (two independent launch-floor kernels)
-    m->taps_valid = false;
-    if (dt == LASR_BF16) {
-      DwTapJobs jobs;                                       // the depthwise tap tables ride in the same launch (training and eval forwards)
-      jobs.n = 0; jobs.blk0[0] = 0;
-      {
-        for (const Unit& u : m->units)
-          if (u.o_taps && jobs.n < 16) {
-            jobs.w[jobs.n] = params + u.w_dw; jobs.out[jobs.n] = reinterpret_cast<uint32_t*>(at(ws, u.o_taps)); jobs.C[jobs.n] = u.ci; jobs.k[jobs.n] = u.k;
-            jobs.blk0[jobs.n + 1] = jobs.blk0[jobs.n] + (int)cdiv((int64_t)2 * u.ci * kDwTapRow, 256);
-            ++jobs.n;
-          }
-      }
-      merged = mask_lengths_step_cast(pct, B, T, lens, dropping ? m->drop_step : nullptr, params, at(ws, p.o_wbf16), m->n_param,
-                                      jobs.n ? &jobs : nullptr, stream);
-      if (merged < 0 || merged > 1) return merged;
-      m->taps_valid = merged == 0 && jobs.n > 0;
-    }
-    if (merged == 1) {
-      LASR_TRY(lasr_mask_lengths_step(pct, B, T, lens, dropping ? m->drop_step : nullptr, stream));   // (bumps the masks' step counter)
-      if (dt == LASR_BF16) LASR_TRY(lasr_cast_f32_to_bf16(params, at(ws, p.o_wbf16), m->n_param, stream));
-    }
-  }
+  const StepArgs sa = {m, params, buffers, nullptr, ws, stream, training != 0, dropping};
+  LASR_TRY(forward_prologue(sa, pct));
   DwTapScope tap_scope(m, params, ws, m->taps_valid);
   void* scratch = at(ws, p.o_scratch);
-  if (!training) {   // eval: BN coefficients of all layers from the running statistics, one launch
-    std::vector<lasr_bn_eval_desc> descs;
-    for (const Unit& u : m->units) {
-      descs.push_back({params + u.bn.gamma, params + u.bn.beta, buffers + u.bn.rmean, buffers + u.bn.rvar, atf(ws, u.o_coef), u.co});
-      if (u.has_res)
-        descs.push_back({params + u.bn_res.gamma, params + u.bn_res.beta, buffers + u.bn_res.rmean, buffers + u.bn_res.rvar,
-                         atf(ws, u.o_coef2), u.co});
-    }
-    for (size_t i = 0; i < descs.size(); i += 64)
-      LASR_TRY(lasr_bn_eval_coef_many(descs.data() + i, (int)std::min<size_t>(64, descs.size() - i), kBnEps, stream));
-    if (eval_fold(m->cfg.dtype)) {   // BN folded into the residual units' 1x1 convs: one launch for all of them
-      std::vector<lasr_fold_desc> fd;
-      for (const Unit& u : m->units)
-        if (fold_unit(u))
-          fd.push_back({params + u.w_pw, params + u.w_res, atf(ws, u.o_coef), atf(ws, u.o_coef2), at(ws, u.o_wfold), atf(ws, u.o_bfold), u.co, u.ci});
-      for (size_t i = 0; i < fd.size(); i += 32)
-        LASR_TRY(lasr_fold_bn_weights_many(fd.data() + i, (int)std::min<size_t>(32, fd.size() - i), stream));
-    }
-  }
+  if (!training) LASR_TRY(eval_coefficients(sa));
   const void* x = feats;
   int64_t Tx = T_in;
   // The BatchNorm + add + activation pass of a plain / residual unit is made by the depthwise launch of the unit above it (fused.h):
@@ -581,30 +644,20 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
       pend = nullptr;
     }
     if (u.ctx_before) {
-      // context branch: gates' input projection as two GEMMs (f32 out), the recurrence, then cat(x, lstm) -> [N][336]
-      {
-        lasr_gemm_problem pr[2];
-        for (int d = 0; d < 2; ++d) pr[d] = {x, wptr(m, params, ws, m->lstm.w_ih[d]), atf(ws, p.o_gx[d]), N, 160, 256, nullptr, nullptr, 0, nullptr};
-        LASR_TRY(lasr_gemm_batch(pr, 2, dt, LASR_F32, 0, 0, 1, scratch, p.scratch_bytes, stream));   // (one launch)
-      }
-      LASR_TRY(lasr_copy_cols(x, dt, 256, 0, at(ws, p.o_cat), dt, 336, 0, N, 256, 0, stream));
-      LASR_TRY(lasr_bilstm_fwd(atf(ws, p.o_gx[0]), atf(ws, p.o_gx[1]), params + m->lstm.w_hh[0], params + m->lstm.w_hh[1],
-                               params + m->lstm.b_ih[0], params + m->lstm.b_hh[0], params + m->lstm.b_ih[1], params + m->lstm.b_hh[1],
-                               lens, B, T, at(ws, p.o_cat), dt, 336, 256, atf(ws, p.o_lstm_saved), stream));
+      LASR_TRY(context_fwd(sa, x));
       x = at(ws, p.o_cat);
     }
     const void* gin = x;
     if (u.has_dw) {
-      int fused = 1;
+      bool fused = false;
       if (pend) {
-        fused = dwconv_fwd_bn(unit_tail(m, *pend, params, nullptr, ws, dropping), params + u.w_dw, at(ws, pend->o_out), at(ws, u.o_u), u.k,
-                              stream, owed == pend ? owed_br : nullptr, kBnEps, kBnMom);
-        if (fused < 0) return fused;
-        if (fused == 0) owed = nullptr;
-        if (fused == 1) LASR_TRY(bn_act_of(*pend));     // a shape without the fused kernel: the two launches
+        LASR_FUSED(fused, dwconv_fwd_bn(unit_tail(m, *pend, params, nullptr, ws, dropping), params + u.w_dw, at(ws, pend->o_out), at(ws, u.o_u),
+                                        u.k, stream, owed == pend ? owed_br : nullptr, kBnEps, kBnMom));
+        if (fused) owed = nullptr;
+        else LASR_TRY(bn_act_of(*pend));     // a shape without the fused kernel: the two launches
         pend = nullptr;
       }
-      if (fused == 1) LASR_TRY(lasr_dwconv_fwd(x, params + u.w_dw, nullptr, at(ws, u.o_u), dt, B, Tx, u.ci, u.k, u.stride, 0, stream));
+      if (!fused) LASR_TRY(lasr_dwconv_fwd(x, params + u.w_dw, nullptr, at(ws, u.o_u), dt, B, Tx, u.ci, u.k, u.stride, 0, stream));
       gin = at(ws, u.o_u);
     }
     if (!training && eval_fold(dt) && fold_unit(u)) {
@@ -616,25 +669,19 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
       Tx = T;
       continue;
     }
-    float* stats = training ? atf(ws, u.o_stats) : nullptr;
-    float* stats2 = (training && u.has_res) ? atf(ws, u.o_stats2) : nullptr;
     bool se_sums_done = false;
     {  // main 1x1 (masked, BN sums) and, for residual blocks, the residual 1x1 (never masked) in one launch
+      lasr_bn_branch br[2];
+      const int np = unit_bn_branches(u, params, buffers, ws, br);
       lasr_gemm_problem pr[2];
-      pr[0] = {gin, wptr(m, params, ws, u.w_pw), at(ws, u.o_y), N, u.co, u.ci, nullptr, u.masked ? lens : nullptr, T, stats};
-      if (u.has_res) pr[1] = {x, wptr(m, params, ws, u.w_res), at(ws, u.o_y2), N, u.co, u.ci, nullptr, nullptr, 0, stats2};
-      const int np = u.has_res ? 2 : 1;
+      pr[0] = {gin, wptr(m, params, ws, u.w_pw), at(ws, u.o_y), N, u.co, u.ci, nullptr, u.masked ? lens : nullptr, T, training ? br[0].stats : nullptr};
+      if (u.has_res) pr[1] = {x, wptr(m, params, ws, u.w_res), at(ws, u.o_y2), N, u.co, u.ci, nullptr, nullptr, 0, training ? br[1].stats : nullptr};
       if (training && !no_fuse()) {
         // the epilogue's per-tile BN sums go straight to ONE reduce+finalize launch for both branches
         const float* parts[2] = {nullptr, nullptr};
         int tiles[2] = {0, 0};
         LASR_TRY(lasr_gemm_batch_partials(pr, np, dt, dt, 0, 0, scratch, p.scratch_bytes, parts, tiles, stream));
-        lasr_bn_branch br[2];
-        br[0] = {parts[0], tiles[0], params + u.bn.gamma, params + u.bn.beta, buffers + u.bn.rmean, buffers + u.bn.rvar,
-                 atf(ws, u.o_coef), atf(ws, u.o_saved), stats};
-        if (u.has_res)
-          br[1] = {parts[1], tiles[1], params + u.bn_res.gamma, params + u.bn_res.beta, buffers + u.bn_res.rmean,
-                   buffers + u.bn_res.rvar, atf(ws, u.o_coef2), atf(ws, u.o_saved2), stats2};
+        for (int s = 0; s < np; ++s) { br[s].partials = parts[s]; br[s].n_partials = tiles[s]; }
         if (bn_fwd_finalize && dt == LASR_BF16 && !u.has_se && !dropping && u.co % 64 == 0) {
           owed = &u;                                      // the consumer pays (no launch, no bracket)
           owed_br[0] = br[0];
@@ -642,36 +689,25 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
         } else {
           ProfScope ps(LASR_PROF_BN, stream, 0.0);
           // SE units: the squeeze's per-utterance sums of y do not depend on the finalize - one launch for both (se_seqsum.h)
-          int merged = 1;
-          if (u.has_se) {
-            merged = bn_finalize_partials_seqsum(br, np, u.co, N, kBnEps, kBnMom, at(ws, u.o_y), dt, B, T, atf(ws, u.o_se_sum), stream);
-            if (merged < 0 || merged > 1) return merged;
-            se_sums_done = merged == 0;
-          }
-          if (merged == 1) LASR_TRY(lasr_bn_finalize_partials(br, np, u.co, N, kBnEps, kBnMom, stream));
+          if (u.has_se)
+            LASR_FUSED(se_sums_done, bn_finalize_partials_seqsum(br, np, u.co, N, kBnEps, kBnMom, at(ws, u.o_y), dt, B, T, atf(ws, u.o_se_sum), stream));
+          if (!se_sums_done) LASR_TRY(lasr_bn_finalize_partials(br, np, u.co, N, kBnEps, kBnMom, stream));
         }
       } else {
         LASR_TRY(lasr_gemm_batch(pr, np, dt, dt, 0, 0, 1, scratch, p.scratch_bytes, stream));
-        if (training) {   // (eval: every layer's coefficients were computed by one launch before the loop)
-          LASR_TRY(lasr_bn_finalize(stats, params + u.bn.gamma, params + u.bn.beta, buffers + u.bn.rmean, buffers + u.bn.rvar,
-                                    atf(ws, u.o_coef), atf(ws, u.o_saved), u.co, N, kBnEps, kBnMom, training, stream));
-          if (u.has_res)
-            LASR_TRY(lasr_bn_finalize(stats2, params + u.bn_res.gamma, params + u.bn_res.beta, buffers + u.bn_res.rmean,
-                                      buffers + u.bn_res.rvar, atf(ws, u.o_coef2), atf(ws, u.o_saved2), u.co, N, kBnEps, kBnMom,
-                                      training, stream));
-        }
+        // (eval: every layer's coefficients were computed by one launch before the loop)
+        for (int s = 0; training && s < np; ++s)
+          LASR_TRY(lasr_bn_finalize(br[s].stats, br[s].gamma, br[s].beta, br[s].running_mean, br[s].running_var, br[s].coef, br[s].saved, u.co, N,
+                                    kBnEps, kBnMom, training, stream));
       }
     }
     bool se_applied = false;
     if (u.has_se) {  // squeeze over all T' frames of BN(y) (affine in the per-utterance sums of y), excite MLP
       ProfScope ps_se(LASR_PROF_BN, stream, (double)N * u.co * dtype_size(dt));
       if (!se_sums_done) LASR_TRY(lasr_seqsum(at(ws, u.o_y), dt, B, T, u.co, atf(ws, u.o_se_sum), stream));
-      int folded = 1;
       if (training && !dropping && !no_fuse())   // round 5: the excite MLP inside the apply pass (one launch instead of three)
-        folded = bn_se_act_fwd(unit_tail(m, u, params, nullptr, ws, dropping), atf(ws, u.o_se_sum), params + u.w_se1, params + u.w_se2,
-                               at(ws, u.o_out), atf(ws, u.o_se_pool), atf(ws, u.o_se_hid), atf(ws, u.o_se_scale), stream);
-      if (folded < 0 || folded > 1) return folded;
-      se_applied = folded == 0;
+        LASR_FUSED(se_applied, bn_se_act_fwd(unit_tail(m, u, params, nullptr, ws, dropping), atf(ws, u.o_se_sum), params + u.w_se1, params + u.w_se2,
+                                             at(ws, u.o_out), atf(ws, u.o_se_pool), atf(ws, u.o_se_hid), atf(ws, u.o_se_scale), stream));
       if (!se_applied)
         LASR_TRY(lasr_se_fwd(atf(ws, u.o_se_sum), atf(ws, u.o_coef), params + u.w_se1, params + u.w_se2, B, T, u.co, atf(ws, u.o_se_pool),
                              atf(ws, u.o_se_hid), atf(ws, u.o_se_scale), stream));
@@ -688,52 +724,36 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
     Tx = T;
   }
   if (pend) LASR_TRY(bn_act_of(*pend));   // (not reached: the last unit has no unit above it)
-  // decoder 1x1 1024 -> C with bias (models/QuartNet.py:275), f32 logits, then log_softmax (+argmax)
-  const int64_t C = m->cfg.n_class;
-  // a narrow vocabulary leaves N/128 = 1 tile column: split K so that the 32 MB of activations are streamed by
-  // 4 x 126 workgroups instead of 126 (the split partials are C/1024 of the input: negligible)
-  if (lean) {   // bf16 logits + per-tile softmax statistics; lse / emissions / gradient follow in lasr_ctc_loss_lean
-    float* rs = atf(ws, p.o_rowstat);
-    int32_t* ra = reinterpret_cast<int32_t*>(rs + (size_t)N * cdiv(C, 256) * 2);
-    return lasr_gemm_rowstat(x, wptr(m, params, ws, m->w_dec), params + m->b_dec, at(ws, p.o_logits), lean_ldc(m), N, C, 1024, rs, ra,
-                             &m->lean_tiles, stream);
-  }
-  const int dec_split = (dt == LASR_BF16 && C <= 128) ? dec_split_k() : 1;
-  if (dec_split > 1 && log_softmax_split_on(C)) {      // narrow head: the split-K slabs are summed by the log_softmax launch itself (fused.h)
-    int splits = 0;
-    LASR_TRY(gemm_split_partials_one(x, wptr(m, params, ws, m->w_dec), dt, N, C, 1024, 0, 0, dec_split, scratch, p.scratch_bytes, &splits, stream));
-    ProfScope ps(LASR_PROF_HEAD, stream, (2.0 + splits) * N * C * sizeof(float));
-    const int rc = log_softmax_split(reinterpret_cast<const float*>(scratch), splits, params + m->b_dec, atf(ws, p.o_logits), logp_out, argmax_out,
-                                     N, C, stream);
-    return rc;
-  }
-  LASR_TRY(lasr_gemm(x, wptr(m, params, ws, m->w_dec), atf(ws, p.o_logits), dt, LASR_F32, N, C, 1024, 0, 0, params + m->b_dec,
-                     nullptr, nullptr, 0, nullptr, dec_split, scratch, p.scratch_bytes, stream));
-  ProfScope ps(LASR_PROF_HEAD, stream, 2.0 * N * C * sizeof(float));
-  LASR_TRY(lasr_log_softmax(atf(ws, p.o_logits), logp_out, argmax_out, N, C, stream));
-  return 0;
+  return decoder_fwd(sa, x, logp_out, argmax_out, lean);
 }
 
-// The 1x1 weight gradients collected over a backward stage, as ONE split-K launch.  The slice count is chosen for
-// ~3 rounds of resident workgroups (512 at two per CU): a single unit needs 16 slices for that, a stage of 6-13 units
-// needs 2-6, so every workgroup runs 3-8x more K steps between its prologue and its slab write-out.
-static int flush_wgrads(std::vector<lasr_gemm_problem>& probs, std::vector<float*>& slabs, std::vector<lasr_reduce_desc>& pending,
-                        void* stream) {
-  const int split = wgrad_split();   // the cap the slabs were sized for; the library picks the slice count for its tile form
-  int splits[32];
-  // round 5: whatever `pending` holds at this point is complete (the depthwise weight gradients' per-utterance partials, the BiLSTM's) -
-  // the launch's one round of tiles leaves CUs idle (71 tiles x 3 slices = 213 of 256 at cfg2), and extra workgroups of the same launch
-  // do those reductions there; what they took leaves the list lasr_reduce_many gets (123 -> 59 MB at cfg2).  Same sums, same order.
-  int taken = 0;
-  LASR_TRY(gemm_multi_split_partials_riders(probs.data(), (int)probs.size(), split, slabs.data(), splits, pending.data(), (int)pending.size(),
-                                            &taken, stream));
-  if (taken > 0) pending.erase(pending.begin(), pending.begin() + taken);
-  for (size_t i = 0; i < probs.size(); ++i)
-    pending.push_back({slabs[i], reinterpret_cast<float*>(probs[i].C), probs[i].M * probs[i].N, splits[i]});
-  probs.clear();
-  slabs.clear();
-  return 0;
+extern "C" int lasr_model_forward(lasr_model_t* m, const float* params, float* buffers, const void* feats, const float* pct,
+                                  int64_t B, int64_t T_in, int training, float* logp_out, int32_t* argmax_out, void* ws,
+                                  size_t ws_bytes, void* stream) {
+  LASR_CHECK_ARG(logp_out, "lasr_model_forward: null pointer");
+  return forward_impl(m, params, buffers, feats, pct, B, T_in, training, logp_out, argmax_out, ws, ws_bytes, stream, false);
 }
+
+// The two launches of a backward stage's collector (stage_grads.h) and what their kernels hold.  wgrads: the 1x1 weight gradients
+// collected over the stage as ONE split-K launch - a single unit needs 16 slices for ~3 rounds of resident workgroups, a stage of 6-13
+// units 2-6, so every workgroup runs 3-8x more K steps between its prologue and its slab write-out.  Riders (round 5): the launch's one
+// round of tiles leaves CUs idle (71 tiles x 3 slices = 213 of 256 at cfg2); extra workgroups do the complete reductions there, and
+// what they took leaves the list lasr_reduce_many gets (123 -> 59 MB at cfg2).
+struct StageLaunch {
+  static constexpr int kMaxProblems = kMaxMultiProblems, kMaxSegments = kMaxReduceSegments;
+  void* stream;
+  int wgrads(const lasr_gemm_problem* probs, int n, float* const* slabs, int* splits, const lasr_reduce_desc* riders, int n_riders, int* taken) const {
+    // wgrad_split(): the cap the slabs were sized for; the library picks the slice count for its tile form
+    return gemm_multi_split_partials_riders(probs, n, wgrad_split(), slabs, splits, riders, n_riders, taken, stream);
+  }
+  int reduce(const lasr_reduce_desc* descs, int n, bool closing) const {
+    if (!closing) return lasr_reduce_many(descs, n, stream);
+    double rb = 0;   // the stage's gradients are final
+    for (int i = 0; i < n; ++i) rb += (double)descs[i].n * (descs[i].n_partials + 1) * sizeof(float);
+    ProfScope ps(LASR_PROF_OTHER, stream, rb);
+    return lasr_reduce_many(descs, n, stream);
+  }
+};
 
 // Split-K slices of the decoder's weight gradient dW = gl^T h ([C][1024], K = N rows) on the 128 x 128 tile (two workgroups
 // per CU): rounds of resident workgroups x K steps per slice, against the f32 slabs every slice writes and the reduction reads
@@ -753,29 +773,16 @@ static int dec_wgrad_split(int64_t C, int64_t N) {
   return best;
 }
 
-// backward from d(loss)/d(logits) already in the workspace (o_glogits)
-// unit_stop: the unit loop runs from the last unit down to `unit_stop` (0 = the whole model); a later
-// lasr_model_backward_continue call picks up at unit_stop-1.  with_head: run the decoder part first.
-static int backward_from_glogits(lasr_model* m, const float* params, const void* feats, int64_t B, int64_t T_in, float* grads,
-                                 void* ws, void* stream, bool with_head = true, int unit_hi = -1, int unit_stop = 0) {
+// decoder backward (models/QuartNet.py:275): dW = gl^T h, db = colsum(gl), dh = gl W -> g[0]; tail_*: the loss mean left to its first launch
+static int decoder_bwd(const StepArgs& a, const float* tail_nll, float* tail_loss) {
+  const lasr_model* m = a.m;
   const Plan& p = m->plan;
   const int dt = m->cfg.dtype;
-  const int64_t T = p.T, N = B * T, C = m->cfg.n_class;
-  DwTapScope tap_scope(m, params, ws, m->taps_valid);     // (the tables of this step's forward: the parameters have not moved since)
-  void* scratch = at(ws, p.o_scratch);
-  const size_t sb = p.scratch_bytes;
-  const int32_t* lens = reinterpret_cast<const int32_t*>(at(ws, p.o_lens));
+  const int64_t B = p.B, N = B * p.T, C = m->cfg.n_class;
+  const float* params = a.params; float* grads = a.grads; void* ws = a.ws; void* stream = a.stream;
+  void* scratch = at(ws, p.o_scratch); const size_t sb = p.scratch_bytes;
   float* gl = atf(ws, p.o_glogits);
   const Unit& last = m->units.back();
-  int cur = m->bwd_cur;
-  // the batch-mean loss forward_and_loss left to this call's first launch: taken over HERE and forgotten by the model, so that an
-  // error return below (or a later, separate lasr_model_backward) can never write through a stale caller pointer
-  const float* tail_nll = m->tail_nll;
-  float* tail_loss = m->tail_loss;
-  m->tail_nll = nullptr; m->tail_loss = nullptr;
-  if (with_head) {
-  cur = 0;
-  // decoder (models/QuartNet.py:275): dW = gl^T h, db = colsum(gl), dh = gl W
   const void* gl_ab = gl;
   int64_t ld_gl = C;
   bool bias_done = false;
@@ -785,15 +792,12 @@ static int backward_from_glogits(lasr_model* m, const float* params, const void*
   } else if (dt == LASR_BF16) {  // GEMM operands share a dtype: bf16 shadow of the logits gradient, rows padded to 16-byte multiples
     ld_gl = (C + 7) / 8 * 8;
     ProfScope ps(LASR_PROF_HEAD, stream, (double)N * C * 6);
-    int merged = 1;
     if (tail_loss) {         // padded copy + bias-gradient column sums + the loss mean forward_and_loss left to this launch
-      merged = head_tail(gl, N, C, at(ws, p.o_d1), ld_gl, grads + m->b_dec, scratch, sb, tail_nll, B, 1.0f / (float)B, tail_loss, stream);
-      if (merged < 0 || merged > 1) return merged;
-      if (merged == 1) LASR_TRY(lasr_scale_sum_f32(tail_nll, B, 1.0f / (float)B, tail_loss, stream));
+      LASR_FUSED(bias_done, head_tail(gl, N, C, at(ws, p.o_d1), ld_gl, grads + m->b_dec, scratch, sb, tail_nll, B, 1.0f / (float)B, tail_loss, stream));
+      if (!bias_done) LASR_TRY(lasr_scale_sum_f32(tail_nll, B, 1.0f / (float)B, tail_loss, stream));
       tail_loss = nullptr;
-      bias_done = merged == 0;
     }
-    if (merged == 1) LASR_TRY(lasr_cast_pad_f32_to_bf16(gl, at(ws, p.o_d1), N, C, ld_gl, stream));
+    if (!bias_done) LASR_TRY(lasr_cast_pad_f32_to_bf16(gl, at(ws, p.o_d1), N, C, ld_gl, stream));
     gl_ab = at(ws, p.o_d1);
   }
   if (tail_loss) {           // (not reached in bf16; keeps the loss defined whatever path the head takes)
@@ -806,17 +810,106 @@ static int backward_from_glogits(lasr_model* m, const float* params, const void*
     ProfScope ps(LASR_PROF_HEAD, stream, (double)N * C * 4);
     LASR_TRY(lasr_colsum_f32(gl, grads + m->b_dec, N, C, scratch, sb, stream));
   }
-  LASR_TRY(lasr_gemm_ld(gl_ab, ld_gl, wptr(m, params, ws, m->w_dec), 1024, at(ws, p.o_g[cur]), 1024, dt, dt, N, 1024, C, 0, 1, nullptr,
-                        1, scratch, sb, stream));
+  return lasr_gemm_ld(gl_ab, ld_gl, wptr(m, params, ws, m->w_dec), 1024, at(ws, p.o_g[0]), 1024, dt, dt, N, 1024, C, 0, 1, nullptr,
+                      1, scratch, sb, stream);
+}
+
+// Context branch backward.  g[cur] holds d(cat) [N][336]: back through the BiLSTM, then
+// d(block23 out) = d(cat)[:, :256] + dG_f W_ih_f + dG_r W_ih_r  -> g[cur^1].  x23: block23's output, the branch's input.
+static int context_bwd(const StepArgs& a, StageGrads<StageLaunch>& sg, const void* x23, int cur, bool defer) {
+  const lasr_model* m = a.m;
+  const Plan& p = m->plan;
+  const int dt = m->cfg.dtype;
+  const int64_t B = p.B, T = p.T, N = B * T;
+  const float* params = a.params; float* grads = a.grads; void* ws = a.ws; void* stream = a.stream;
+  void* scratch = at(ws, p.o_scratch); const size_t sb = p.scratch_bytes;
+  const int32_t* lens = reinterpret_cast<const int32_t*>(at(ws, p.o_lens));
+  // The recurrence (437 us of dependent steps on 2 B small workgroups) next to the 1x1 weight gradients collected so far in this
+  // stage - the units above block3 and block3's own: they do not depend on it - in ONE grid (gemm_bf16.hip,
+  // gemm_bf16_big_multi_lstm_kernel; LASR_LSTM_BESIDE_WGRAD=0: the two launches one after the other).  `scratch` holds the
+  // recurrence's dW_hh partials; the GEMM part writes only its slabs.
+  bool beside = false;
+  if (!sg.probs.empty() && dt == LASR_BF16 && defer) {
+    int splits[kMaxMultiProblems], taken = 0;
+    const lstm::BwdArgs rec = {at(ws, p.o_g[cur]), 336, 256, params + m->lstm.w_hh[0], params + m->lstm.w_hh[1], lens, T, atf(ws, p.o_lstm_saved),
+                               atf(ws, p.o_dg[0]), atf(ws, p.o_dg[1]), atf(ws, p.o_lstm_part),
+                               reinterpret_cast<bf16_t*>(at(ws, p.o_dgb[0])), reinterpret_cast<bf16_t*>(at(ws, p.o_dgb[1])), atf(ws, p.o_lstm_bpart)};
+    LASR_FUSED(beside, gemm_multi_split_partials_with_bilstm_bwd(sg.probs.data(), (int)sg.probs.size(), &taken, wgrad_split(), sg.slabs.data(), splits,
+                                                                 rec, dt, B, stream));
+    if (beside) sg.retire(taken, splits);   // the first `taken` problems rode along; the rest wait for the stage's closing launch
   }
+  if (beside) {
+    // The recurrences' launch left dg as f32 and bf16, and per-workgroup partial sums of dW_hh and of dg's columns.  Their sums
+    // (dW_hh, and the bias gradients - b_ih and b_hh enter the gates as a sum: one gradient, stored twice) join the stage's closing
+    // reduction; dW_ih = dG^T x23 joins the stage's closing weight-gradient launch; only the data gradient
+    // d(block23 out) = d(cat)[:, :256] + dG_f W_ih_f + dG_r W_ih_r is needed now.   (7 small launches fewer than the separate form)
+    const int np = (int)B * lstm::kDwZ;
+    const int64_t gh = (int64_t)lstm::G * lstm::H;
+    LASR_TRY(sg.relieve(6, 2));      // six segments + two problems are about to join
+    for (int d = 0; d < 2; ++d) {
+      LASR_TRY(sg.add_reduction({atf(ws, p.o_lstm_part) + (int64_t)d * np * gh, grads + m->lstm.w_hh[d], gh, np}));
+      LASR_TRY(sg.add_reduction({atf(ws, p.o_lstm_bpart) + (int64_t)d * np * lstm::G, grads + m->lstm.b_ih[d], lstm::G, np}));
+      LASR_TRY(sg.add_reduction({atf(ws, p.o_lstm_bpart) + (int64_t)d * np * lstm::G, grads + m->lstm.b_hh[d], lstm::G, np}));
+      const lasr_gemm_problem pr = {at(ws, p.o_dgb[d]), x23, grads + m->lstm.w_ih[d], 160, 256, N, nullptr, nullptr, 0, nullptr};
+      float* const slab = atf(ws, p.o_lstm_wgp) + (int64_t)d * (p.lstm_wgp_bytes / sizeof(float));
+      LASR_TRY(sg.add_wgrads(&pr, 1, &slab));
+    }
+    LASR_TRY(sg.relieve());
+    LASR_TRY(lasr_copy_cols(at(ws, p.o_g[cur]), dt, 336, 0, at(ws, p.o_g[cur ^ 1]), dt, 256, 0, N, 256, 0, stream));
+    for (int d = 0; d < 2; ++d)
+      LASR_TRY(lasr_gemm(at(ws, p.o_dgb[d]), wptr(m, params, ws, m->lstm.w_ih[d]), at(ws, p.o_g[cur ^ 1]), dt, dt, N, 256, 160, 0, 1, nullptr,
+                         at(ws, p.o_g[cur ^ 1]), nullptr, 0, nullptr, 1, scratch, sb, stream));
+    return 0;
+  }
+  LASR_TRY(lasr_bilstm_bwd(at(ws, p.o_g[cur]), dt, 336, 256, params + m->lstm.w_hh[0], params + m->lstm.w_hh[1], lens, B, T,
+                           atf(ws, p.o_lstm_saved), atf(ws, p.o_dg[0]), atf(ws, p.o_dg[1]), grads + m->lstm.w_hh[0],
+                           grads + m->lstm.w_hh[1], scratch, sb, stream));
+  LASR_TRY(lasr_copy_cols(at(ws, p.o_g[cur]), dt, 336, 0, at(ws, p.o_g[cur ^ 1]), dt, 256, 0, N, 256, 0, stream));
+  for (int d = 0; d < 2; ++d) {
+    const void* dg_ab = atf(ws, p.o_dg[d]);
+    if (dt == LASR_BF16) {
+      LASR_TRY(lasr_cast_f32_to_bf16(atf(ws, p.o_dg[d]), at(ws, p.o_d1), N * 160, stream));
+      dg_ab = at(ws, p.o_d1);
+    }
+    LASR_TRY(lasr_colsum_f32(atf(ws, p.o_dg[d]), grads + m->lstm.b_ih[d], N, 160, scratch, sb, stream));
+    // both biases enter the gates as b_ih + b_hh: one gradient, stored twice
+    LASR_TRY(lasr_copy_cols(grads + m->lstm.b_ih[d], LASR_F32, 160, 0, grads + m->lstm.b_hh[d], LASR_F32, 160, 0, 1, 160, 0, stream));
+    // (dW_ih = dG^T x23 stays its own split-K launch: as problems 86 and 87 of the stage's batched launch the two one-tile problems
+    //  push it from 3 slices x 85 tiles = 255 workgroups to 2 x 87 = 174, +47 us - exactly what the two small launches cost)
+    LASR_TRY(lasr_gemm(dg_ab, x23, grads + m->lstm.w_ih[d], dt, LASR_F32, 160, 256, N, 1, 1, nullptr, nullptr, nullptr, 0, nullptr, 16,
+                       scratch, sb, stream));
+    LASR_TRY(lasr_gemm(dg_ab, wptr(m, params, ws, m->lstm.w_ih[d]), at(ws, p.o_g[cur ^ 1]), dt, dt, N, 256, 160, 0, 1, nullptr,
+                       at(ws, p.o_g[cur ^ 1]), nullptr, 0, nullptr, 1, scratch, sb, stream));
+  }
+  return 0;
+}
+
+// backward from d(loss)/d(logits) already in the workspace (o_glogits)
+// unit_stop: the unit loop runs from the last unit down to `unit_stop` (0 = the whole model); a later
+// lasr_model_backward_continue call picks up at unit_stop-1.  with_head: run the decoder part first.
+static int backward_from_glogits(lasr_model* m, const float* params, const void* feats, int64_t B, int64_t T_in, float* grads,
+                                 void* ws, void* stream, bool with_head = true, int unit_hi = -1, int unit_stop = 0) {
+  const Plan& p = m->plan;
+  const int dt = m->cfg.dtype;
+  const int64_t T = p.T, N = B * T;
+  const StepArgs sa = {m, params, nullptr, grads, ws, stream, true, true};
+  DwTapScope tap_scope(m, params, ws, m->taps_valid);     // (the tables of this step's forward: the parameters have not moved since)
+  void* scratch = at(ws, p.o_scratch);
+  const size_t sb = p.scratch_bytes;
+  int cur = m->bwd_cur;
+  // the batch-mean loss forward_and_loss left to this call's first launch: taken over HERE and forgotten by the model, so that an
+  // error return below (or a later, separate lasr_model_backward) can never write through a stale caller pointer
+  const float* tail_nll = m->tail_nll;
+  float* tail_loss = m->tail_loss;
+  m->tail_nll = nullptr; m->tail_loss = nullptr;
+  if (with_head) LASR_TRY(decoder_bwd(sa, tail_nll, tail_loss));
+  if (with_head) cur = 0;
   if (unit_hi < 0) unit_hi = (int)m->units.size() - 1;
   // The "sum the partial slabs" tails of the weight-gradient kernels are collected and issued as ONE launch when
   // the stage ends (27 launches of ~5 us each off the step; LASR_NO_FUSE=1 keeps them inline for A/B runs).
   static const bool no_defer = getenv("LASR_NO_DEFER") != nullptr;
   const bool defer = !no_fuse() && !no_defer;
-  std::vector<lasr_reduce_desc> pending;
-  std::vector<lasr_gemm_problem> wprobs;
-  std::vector<float*> wslabs;
+  StageGrads<StageLaunch> sg(StageLaunch{stream});
   RoctxRange rr_bwd("lasr:backward");
   for (int ui = unit_hi; ui >= unit_stop; --ui) {
     RoctxRange rr_unit(m->units[ui].rx_bwd.c_str());
@@ -856,14 +949,9 @@ static int backward_from_glogits(lasr_model* m, const float* params, const void*
       lasr_gemm_problem pr[2];
       pr[0] = {dy, gin, grads + u.w_pw, u.co, u.ci, N, nullptr, nullptr, 0, nullptr};
       if (u.has_res) pr[1] = {dy2, x_in, grads + u.w_res, u.co, u.ci, N, nullptr, nullptr, 0, nullptr};
-      if (defer_w) {
-        float* slab = atf(ws, u.o_wgp);
-        if (wprobs.size() + (u.has_res ? 2 : 1) > 32) LASR_TRY(flush_wgrads(wprobs, wslabs, pending, stream));   // (the launch takes 32 problems)
-        wprobs.push_back(pr[0]); wslabs.push_back(slab);
-        if (u.has_res) { wprobs.push_back(pr[1]); wslabs.push_back(slab + u.wgp_bytes / (2 * sizeof(float))); }
-      } else {
-        LASR_TRY(lasr_gemm_batch(pr, u.has_res ? 2 : 1, dt, LASR_F32, 1, 1, wgrad_split(), scratch, sb, stream));
-      }
+      float* const slab[2] = {atf(ws, u.o_wgp), atf(ws, u.o_wgp) + u.wgp_bytes / (2 * sizeof(float))};
+      if (defer_w) LASR_TRY(sg.add_wgrads(pr, u.has_res ? 2 : 1, slab));
+      else LASR_TRY(lasr_gemm_batch(pr, u.has_res ? 2 : 1, dt, LASR_F32, 1, 1, wgrad_split(), scratch, sb, stream));
     }
     const bool need_dx = ui > 0;
     void* dx = at(ws, p.o_g[cur ^ 1]);
@@ -876,24 +964,16 @@ static int backward_from_glogits(lasr_model* m, const float* params, const void*
       LASR_TRY(lasr_gemm_batch(pr, with_res ? 2 : 1, dt, dt, 0, 1, 1, scratch, sb, stream));
       // depthwise dW from (x, du); dx = flipped depthwise conv of du (+ residual dx)
       const bool fused_dw = defer && need_dx && u.stride == 1;   // both in one launch (falls back inside for other dtypes / shapes)
-      if (fused_dw) {
-        int npart = 0;
+      int npart = 0;
+      if (fused_dw)
         LASR_TRY(lasr_dwconv_bwd_fused(x_in, at(ws, p.o_du), params + u.w_dw, u.has_res ? at(ws, p.o_dxr) : nullptr, dx, dt, B, T, u.ci, u.k,
                                        at(ws, u.o_dwp), u.dwp_bytes, &npart, stream));
-        pending.push_back({atf(ws, u.o_dwp), grads + u.w_dw, u.ci * (int64_t)u.k, npart});
-      } else if (defer) {
-        int npart = 0;
-        LASR_TRY(lasr_dwconv_wgrad_partials(x_in, at(ws, p.o_du), dt, B, Tx, u.ci, u.k, u.stride, at(ws, u.o_dwp), u.dwp_bytes, &npart,
-                                            stream));
-        pending.push_back({atf(ws, u.o_dwp), grads + u.w_dw, u.ci * (int64_t)u.k, npart});
-      } else {
+      else if (defer)
+        LASR_TRY(lasr_dwconv_wgrad_partials(x_in, at(ws, p.o_du), dt, B, Tx, u.ci, u.k, u.stride, at(ws, u.o_dwp), u.dwp_bytes, &npart, stream));
+      else
         LASR_TRY(lasr_dwconv_wgrad(x_in, at(ws, p.o_du), grads + u.w_dw, dt, B, Tx, u.ci, u.k, u.stride, scratch, sb, stream));
-      }
-      if (pending.size() + wprobs.size() > 60) {
-        if (!wprobs.empty()) LASR_TRY(flush_wgrads(wprobs, wslabs, pending, stream));
-        LASR_TRY(lasr_reduce_many(pending.data(), (int)pending.size(), stream));
-        pending.clear();
-      }
+      if (defer) LASR_TRY(sg.add_reduction({atf(ws, u.o_dwp), grads + u.w_dw, u.ci * (int64_t)u.k, npart}));
+      LASR_TRY(sg.relieve());
       if (need_dx && !fused_dw)
         LASR_TRY(lasr_dwconv_fwd(at(ws, p.o_du), params + u.w_dw, u.has_res ? at(ws, p.o_dxr) : nullptr, dx, dt, B, T, u.ci, u.k, 1,
                                  1, stream));
@@ -906,92 +986,12 @@ static int backward_from_glogits(lasr_model* m, const float* params, const void*
     }
     cur ^= 1;
     if (u.ctx_before) {
-      // g[cur] holds d(cat) [N][336].  Back through the BiLSTM, then
-      // d(block23 out) = d(cat)[:, :256] + dG_f W_ih_f + dG_r W_ih_r  -> g[cur^1]
-      const void* x23 = at(ws, m->units[ui - 1].o_out);
-      // The recurrence (437 us of dependent steps on 2 B small workgroups) next to the 1x1 weight gradients collected so far in this
-      // stage - the units above block3 and block3's own: they do not depend on it - in ONE grid (gemm_bf16.hip,
-      // gemm_bf16_big_multi_lstm_kernel; LASR_LSTM_BESIDE_WGRAD=0: the two launches one after the other).  `scratch` holds the
-      // recurrence's dW_hh partials; the GEMM part writes only its slabs.
-      int beside = 1;
-      if (!wprobs.empty() && wprobs.size() <= 32 && dt == LASR_BF16 && defer) {
-        int splits[32], taken = 0;
-        const lstm::BwdArgs rec = {at(ws, p.o_g[cur]), 336, 256, params + m->lstm.w_hh[0], params + m->lstm.w_hh[1], lens, T, atf(ws, p.o_lstm_saved),
-                                   atf(ws, p.o_dg[0]), atf(ws, p.o_dg[1]), atf(ws, p.o_lstm_part),
-                                   reinterpret_cast<bf16_t*>(at(ws, p.o_dgb[0])), reinterpret_cast<bf16_t*>(at(ws, p.o_dgb[1])), atf(ws, p.o_lstm_bpart)};
-        beside = gemm_multi_split_partials_with_bilstm_bwd(wprobs.data(), (int)wprobs.size(), &taken, wgrad_split(), wslabs.data(), splits, rec, dt, B,
-                                                           stream);
-        if (beside < 0 || beside > 1) return beside;
-        if (beside == 0) {                                  // the first `taken` problems rode along; the rest wait for the stage's closing launch
-          for (int i = 0; i < taken; ++i)
-            pending.push_back({wslabs[i], reinterpret_cast<float*>(wprobs[i].C), wprobs[i].M * wprobs[i].N, splits[i]});
-          wprobs.erase(wprobs.begin(), wprobs.begin() + taken);
-          wslabs.erase(wslabs.begin(), wslabs.begin() + taken);
-        }
-      }
-      if (beside == 0) {
-        // The recurrences' launch left dg as f32 and bf16, and per-workgroup partial sums of dW_hh and of dg's columns.  Their sums
-        // (dW_hh, and the bias gradients - b_ih and b_hh enter the gates as a sum: one gradient, stored twice) join the stage's closing
-        // reduction; dW_ih = dG^T x23 joins the stage's closing weight-gradient launch; only the data gradient
-        // d(block23 out) = d(cat)[:, :256] + dG_f W_ih_f + dG_r W_ih_r is needed now.   (7 small launches fewer than the separate form)
-        const int np = (int)B * lstm::kDwZ;
-        const int64_t gh = (int64_t)lstm::G * lstm::H;
-        if (pending.size() + wprobs.size() + 8 > 64) {      // six segments + two problems are about to join (lasr_reduce_many takes 64)
-          LASR_TRY(flush_wgrads(wprobs, wslabs, pending, stream));
-          LASR_TRY(lasr_reduce_many(pending.data(), (int)pending.size(), stream));
-          pending.clear();
-        }
-        for (int d = 0; d < 2; ++d) {
-          pending.push_back({atf(ws, p.o_lstm_part) + (int64_t)d * np * gh, grads + m->lstm.w_hh[d], gh, np});
-          pending.push_back({atf(ws, p.o_lstm_bpart) + (int64_t)d * np * lstm::G, grads + m->lstm.b_ih[d], lstm::G, np});
-          pending.push_back({atf(ws, p.o_lstm_bpart) + (int64_t)d * np * lstm::G, grads + m->lstm.b_hh[d], lstm::G, np});
-          if (wprobs.size() + 1 > 32) LASR_TRY(flush_wgrads(wprobs, wslabs, pending, stream));
-          wprobs.push_back({at(ws, p.o_dgb[d]), x23, grads + m->lstm.w_ih[d], 160, 256, N, nullptr, nullptr, 0, nullptr});
-          wslabs.push_back(atf(ws, p.o_lstm_wgp) + (int64_t)d * (p.lstm_wgp_bytes / sizeof(float)));
-        }
-        if (pending.size() + wprobs.size() > 60) {          // (lasr_reduce_many takes 64 segments)
-          LASR_TRY(flush_wgrads(wprobs, wslabs, pending, stream));
-          LASR_TRY(lasr_reduce_many(pending.data(), (int)pending.size(), stream));
-          pending.clear();
-        }
-        LASR_TRY(lasr_copy_cols(at(ws, p.o_g[cur]), dt, 336, 0, at(ws, p.o_g[cur ^ 1]), dt, 256, 0, N, 256, 0, stream));
-        for (int d = 0; d < 2; ++d)
-          LASR_TRY(lasr_gemm(at(ws, p.o_dgb[d]), wptr(m, params, ws, m->lstm.w_ih[d]), at(ws, p.o_g[cur ^ 1]), dt, dt, N, 256, 160, 0, 1, nullptr,
-                             at(ws, p.o_g[cur ^ 1]), nullptr, 0, nullptr, 1, scratch, sb, stream));
-        cur ^= 1;
-        continue;
-      }
-      LASR_TRY(lasr_bilstm_bwd(at(ws, p.o_g[cur]), dt, 336, 256, params + m->lstm.w_hh[0], params + m->lstm.w_hh[1], lens, B, T,
-                               atf(ws, p.o_lstm_saved), atf(ws, p.o_dg[0]), atf(ws, p.o_dg[1]), grads + m->lstm.w_hh[0],
-                               grads + m->lstm.w_hh[1], scratch, sb, stream));
-      LASR_TRY(lasr_copy_cols(at(ws, p.o_g[cur]), dt, 336, 0, at(ws, p.o_g[cur ^ 1]), dt, 256, 0, N, 256, 0, stream));
-      for (int d = 0; d < 2; ++d) {
-        const void* dg_ab = atf(ws, p.o_dg[d]);
-        if (dt == LASR_BF16) {
-          LASR_TRY(lasr_cast_f32_to_bf16(atf(ws, p.o_dg[d]), at(ws, p.o_d1), N * 160, stream));
-          dg_ab = at(ws, p.o_d1);
-        }
-        LASR_TRY(lasr_colsum_f32(atf(ws, p.o_dg[d]), grads + m->lstm.b_ih[d], N, 160, scratch, sb, stream));
-        // both biases enter the gates as b_ih + b_hh: one gradient, stored twice
-        LASR_TRY(lasr_copy_cols(grads + m->lstm.b_ih[d], LASR_F32, 160, 0, grads + m->lstm.b_hh[d], LASR_F32, 160, 0, 1, 160, 0, stream));
-        // (dW_ih = dG^T x23 stays its own split-K launch: as problems 86 and 87 of the stage's batched launch the two one-tile problems
-        //  push it from 3 slices x 85 tiles = 255 workgroups to 2 x 87 = 174, +47 us - exactly what the two small launches cost)
-        LASR_TRY(lasr_gemm(dg_ab, x23, grads + m->lstm.w_ih[d], dt, LASR_F32, 160, 256, N, 1, 1, nullptr, nullptr, nullptr, 0, nullptr, 16,
-                           scratch, sb, stream));
-        LASR_TRY(lasr_gemm(dg_ab, wptr(m, params, ws, m->lstm.w_ih[d]), at(ws, p.o_g[cur ^ 1]), dt, dt, N, 256, 160, 0, 1, nullptr,
-                           at(ws, p.o_g[cur ^ 1]), nullptr, 0, nullptr, 1, scratch, sb, stream));
-      }
+      LASR_TRY(context_bwd(sa, sg, at(ws, m->units[ui - 1].o_out), cur, defer));
       cur ^= 1;
     }
   }
   RoctxRange rr_tail("lasr:wgrad flush + reduce");
-  if (!wprobs.empty()) LASR_TRY(flush_wgrads(wprobs, wslabs, pending, stream));
-  if (!pending.empty()) {   // the stage's gradients are final
-    double rb = 0;
-    for (const lasr_reduce_desc& d : pending) rb += (double)d.n * (d.n_partials + 1) * sizeof(float);
-    ProfScope ps(LASR_PROF_OTHER, stream, rb);
-    LASR_TRY(lasr_reduce_many(pending.data(), (int)pending.size(), stream));
-  }
+  LASR_TRY(sg.close());
   m->bwd_cur = cur;
   m->bwd_next = unit_stop - 1;
   return 0;

@@ -1421,7 +1421,7 @@ int lasr::head_tail(const float* gl, int64_t rows, int64_t C, void* gl_bf16, int
 // the deferred reductions of a backward stage (split-K slabs of the 1x1 weight gradients, per-(utterance, chunk)
 // partials of the depthwise weight gradients).  f64 accumulation in a fixed order, 16 loads in flight.
 namespace lasr {
-struct ReduceMany { lasr_reduce_desc d[64]; };
+struct ReduceMany { lasr_reduce_desc d[kMaxReduceSegments]; };   // (fused.h)
 static constexpr int kReduceEl = 4;        // elements per thread (reduce_many_kernel)
 __global__ __launch_bounds__(256) void reduce_many_kernel(ReduceMany a) {
   const lasr_reduce_desc& q = a.d[blockIdx.y];
@@ -1460,7 +1460,7 @@ __global__ __launch_bounds__(256) void reduce_many_kernel(ReduceMany a) {
 }  // namespace lasr
 
 extern "C" int lasr_reduce_many(const lasr_reduce_desc* descs, int n_descs, void* stream) {
-  LASR_CHECK_ARG(descs && n_descs >= 1 && n_descs <= 64, "lasr_reduce_many: 1..64 segments");
+  LASR_CHECK_ARG(descs && n_descs >= 1 && n_descs <= lasr::kMaxReduceSegments, "lasr_reduce_many: 1..%d segments", lasr::kMaxReduceSegments);
   lasr::ReduceMany a;
   int64_t nmax = 0;
   static const bool dump = getenv("LASR_REDUCE_DUMP") != nullptr;      // dev aid: the segments of every launch on stderr

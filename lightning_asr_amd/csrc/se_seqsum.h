@@ -45,8 +45,8 @@ __device__ __forceinline__ void seqsum_vec_body(const T* __restrict__ x, int Tt,
   }
 }
 
-// norm.hip: lasr_bn_finalize_partials and lasr_seqsum(x) in ONE launch.  Returns 0 (launched), 1 (shape outside the vector form:
-// nothing launched, make the two calls) or an error.
+// norm.hip: lasr_bn_finalize_partials and lasr_seqsum(x) in ONE launch.  Fused convention (fused.h); not taken (shape outside the
+// vector form): make the two calls.
 int bn_finalize_partials_seqsum(const lasr_bn_branch* branches, int n_branches, int64_t C, int64_t n_rows, float eps, float momentum,
                                 const void* x, int dtype, int64_t B, int64_t T_, float* sums, void* stream);
 

@@ -674,6 +674,31 @@ def test_wgrad_multi_exact_integers(dev):
             assert torch.equal(o.cpu(), d.t() @ x)
 
 
+def test_stage_launch_limits(dev):
+    """The capacities the backward stage's collector relies on (kMaxMultiProblems, gemm.h; kMaxReduceSegments, fused.h): a full
+    launch is computed - 32 weight-gradient problems against the f64 product, bit for bit as in test_wgrad_multi_exact_integers
+    (small-integer operands); 64 segments of two partials against the f64 sum, bit for bit - and one more is the argument error."""
+    from lightning_asr_amd import _lib, ops
+    g = torch.Generator().manual_seed(11)
+    dys = [torch.randint(-2, 3, (64, 8), generator=g).float() for _ in range(33)]
+    xs = [torch.randint(-1, 2, (64, 8), generator=g).float() for _ in range(33)]
+    dys_d, xs_d = [d.bfloat16().to(dev) for d in dys], [x.bfloat16().to(dev) for x in xs]
+    outs = ops.wgrad_multi(dys_d[:32], xs_d[:32])
+    assert len(outs) == 32
+    for d, x, o in zip(dys, xs, outs):
+        assert torch.equal(o.cpu().double(), d.double().t() @ x.double())
+    with pytest.raises(_lib.LasrError, match=r"lasr_gemm_multi_split_partials failed \(-1\)"):
+        ops.wgrad_multi(dys_d, xs_d)
+    parts = [torch.randn(2, 5, generator=g) for _ in range(65)]
+    segs = [(pt.to(dev), torch.full((5,), float("nan"), device=dev)) for pt in parts]
+    ops.reduce_many(segs[:64])
+    for pt, (_, out) in zip(parts[:64], segs):
+        assert torch.equal(out.cpu(), (pt[0].double() + pt[1].double()).float())
+    with pytest.raises(_lib.LasrError, match=r"lasr_reduce_many failed \(-1\)"):
+        ops.reduce_many(segs)
+    assert torch.isnan(segs[64][1]).all()                  # (nothing was launched)
+
+
 def test_gemm_bf16_random_shapes_exact(dev):
     """Seeded sweep over ragged shapes and all four operand layouts: small tiles, 256x256 and 256x128 one-per-CU tiles,
     aligned (16-byte) and unaligned pitches, K tails that are not multiples of 8 or 64.  Small-integer operands make

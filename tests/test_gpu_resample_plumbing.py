@@ -167,7 +167,7 @@ def _run_native(dev, ds, seed, speed_perturb):
             torch.cuda.current_stream().wait_event(db.ready)
             got.append({"pcm": db.pcm.clone(), "lens": db.lens.clone(), "aug": db.aug.clone(), "targets": db.targets.clone(),
                         "sizes": db.sizes.clone(), "L": db.L, "pitch": db.pitch, "key": db.key, "seconds": db.seconds, "speed": db.speed,
-                        "B": db.B, "S": db.S})
+                        "B": db.B, "S": db.S, "ld": db.ld})
             src.release(db)
     finally:
         src.close()
@@ -227,8 +227,13 @@ def test_native_source_without_the_key_is_todays_batches(dev, tmp_path):
     twin = AudioParser.__new__(AudioParser)
     twin.rand = random.Random(5)
     for bi, (x, y) in enumerate(zip(a, b)):
+        # An unperturbed row is written up to the host reader's pitch `ld`: the file's samples, then zeros.  Past it the class-pitch
+        # row is never written nor read (DeviceFeeder.upload) and holds whatever the slot's block held before: not compared.
+        ld = x["ld"]
+        assert ld == y["ld"] and ld <= x["pitch"] == y["pitch"]
         for k in x:
-            same = torch.equal(x[k], y[k]) if isinstance(x[k], torch.Tensor) else x[k] == y[k]
+            u, v = (x[k][:, :ld], y[k][:, :ld]) if k == "pcm" else (x[k], y[k])
+            same = torch.equal(u, v) if isinstance(u, torch.Tensor) else u == v
             assert same, k
         ns = [pcms[3 * bi + i].size for i in range(3)]
         assert x["speed"] is None and x["lens"].cpu().tolist() == ns
@@ -237,7 +242,7 @@ def test_native_source_without_the_key_is_todays_batches(dev, tmp_path):
         assert x["L"] == 160 * (frames - 1) + 95 and x["pitch"] == x["L"] + 1 and x["key"] == (3, x["pitch"], x["L"], x["S"], True)
         rows = x["pcm"].cpu().numpy()
         for i in range(3):
-            assert np.array_equal(rows[i, :ns[i]], pcms[3 * bi + i])
+            assert np.array_equal(rows[i, :ns[i]], pcms[3 * bi + i]) and not rows[i, ns[i]:ld].any()
 
 
 def test_loader_routes_apply_speed_perturbation(dev, tmp_path):
