@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 116   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 117   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
@@ -40,7 +40,8 @@ extern "C" {
                               113: lasr_ctc_kws_workspace_bytes / lasr_ctc_kws (CTC keyword search: phrases with time spans)
                               114: lasr_grad_accumulate / lasr_grad_accumulate_ranges (gradient accumulation over micro-batches)
                               115: lasr_bn_tail / lasr_bn_side / lasr_se_side: the BN entry points take one record; the _drop twins are gone
-                              116: lasr_ema_state_bytes / lasr_ema_state_init / lasr_novograd_step_ema / lasr_ema_update (weight EMA) */
+                              116: lasr_ema_state_bytes / lasr_ema_state_init / lasr_novograd_step_ema / lasr_ema_update (weight EMA)
+                              117: lasr_clip_state_bytes / lasr_clip_state_init / lasr_novograd_step_clip (gradient clipping, non-finite guard) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -686,6 +687,29 @@ int lasr_novograd_step_ema(float* params, const float* grads, float* exp_avg, fl
                            float eps, float weight_decay, float grad_scale, void* workspace,
                            size_t workspace_bytes, void* stream, float* ema, void* ema_state, int keep_workspace);
 int lasr_ema_update(float* ema, const float* params, int64_t n, float w, void* stream);
+
+/* Gradient clipping and the non-finite-step guard ("Gradient clipping and the non-finite guard"), decided on the device inside
+ * the optimiser step's own three launches.  One device record (lasr_clip_state_bytes() bytes: int64 steps; int64 skipped; int mode;
+ * float clip_val; int skip_nonfinite; float total_norm; float coef; int last_skipped).  With s = grad_scale and g^ = s g (f32):
+ *   mode 2 (value): g^ <- clamp(g^, -c, c) with torch's semantics (+-Inf -> +-c, NaN stays); the per-tensor norms and the update use it.
+ *   mode 1 (norm):  N = (float)sqrt(sum_t norm2[t]) (f64, tensor index order), coef = min(1, c / (N + 1e-6f)) (one f32 add, one correctly
+ *                   rounded f32 division); the update uses g^ coef, the per-tensor norm is coef^2 norm2[t].  coef == 1: every bit of the
+ *                   step is the un-clipped step's.
+ *   mode 0 (off):   the step as it is; the record is still filled in (total_norm: the global gradient norm, for logging).
+ *   skip_nonfinite: when the sum of squares is not finite (any NaN or +-Inf; in value mode any NaN), the step writes nothing to params,
+ *                   exp_avg, exp_avg_sq or ema and does not advance the EMA record; norm2 is re-zeroed; steps and skipped count it.
+ *                   Off: a non-finite gradient behaves as without the record, and as torch (coef becomes NaN).
+ * total_norm is the norm of the values the norm kernel squared: before the clip in norm mode, after the clamp in value mode.
+ * lasr_clip_state_init: HOST only - fills a host image for the caller to upload.  LASR_E_ARG: a null or short buffer, a mode outside
+ *   0..2, clip_val negative or not finite, a mode other than 0 with clip_val == 0, a negative count.
+ * lasr_novograd_step_clip: lasr_novograd_step_ema with the record.  clip_state == NULL: that entry, launch for launch and bit for bit.
+ *   With a record the moment kernel runs as ONE workgroup (the global norm needs every tensor's sum before any is re-zeroed). */
+size_t lasr_clip_state_bytes(void);
+int lasr_clip_state_init(void* host_buf, size_t bytes, int mode, float clip_val, int skip_nonfinite, int64_t steps, int64_t skipped);
+int lasr_novograd_step_clip(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                            const int64_t* offsets, int64_t n_tensors, int64_t n_elems, const float* lr, float beta1, float beta2,
+                            float eps, float weight_decay, float grad_scale, void* workspace,
+                            size_t workspace_bytes, void* stream, float* ema, void* ema_state, int keep_workspace, void* clip_state);
 
 /* Gradient accumulation (accumulate_grad_batches > 1; DESIGN 4, "Gradient accumulation"): acc[i] = acc[i] + g[i], a plain f32 add with one rounding
  * per element - bit-equal to `acc + g` in torch, whatever the alignment.  Every backward of the plan overwrites its whole

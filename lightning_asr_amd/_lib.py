@@ -156,6 +156,9 @@ SIGNATURES = {
     "lasr_ema_state_init": (_i32, [_p, _sz, _f32, _i32, _i64]),
     "lasr_novograd_step_ema": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p, _f32, _f32, _f32, _f32, _f32, _p, _sz, _p, _p, _p, _i32]),
     "lasr_ema_update": (_i32, [_p, _p, _i64, _f32, _p]),
+    "lasr_clip_state_bytes": (_sz, []),
+    "lasr_clip_state_init": (_i32, [_p, _sz, _i32, _f32, _i32, _i64, _i64]),
+    "lasr_novograd_step_clip": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p, _f32, _f32, _f32, _f32, _f32, _p, _sz, _p, _p, _p, _i32, _p]),
     "lasr_grad_accumulate": (_i32, [_p, _p, _i64, _p]),
     "lasr_grad_accumulate_ranges": (_i32, [_p, _p, _p, _p, _i32, _p]),
     "lasr_cast_f32_to_bf16": (_i32, [_p, _p, _i64, _p]),

@@ -2,6 +2,7 @@
 // Replaces scheduler/novograd.py:75-145 (betas=(0.8,0.5), eps=1e-8, weight_decay; no amsgrad,
 // grad_averaging or luc: train.py:46), which issues ~10 tiny kernels per parameter tensor.
 #include "common.h"
+#include <cfloat>
 
 namespace lasr {
 
@@ -9,9 +10,36 @@ namespace lasr {
 // that intersect it and adds each segment's sum of squares to norm2[tensor] (f64 atomics: a handful
 // per workgroup; f64 keeps the result independent of arrival order to well below f32 resolution).
 static constexpr int kNormChunk = 16384;
-__global__ __launch_bounds__(256) void novograd_norm_kernel(const float* __restrict__ grads, const int64_t* __restrict__ offsets,
-                                                            int n_tensors, int64_t n, double* __restrict__ norm2, float grad_scale) {
+
+// Gradient clipping and the non-finite guard ("Gradient clipping and the non-finite guard"): one device record, like
+// EmaState.  The run's configuration (mode, clip_val, skip_nonfinite) is written once by the host; the rest is written by thread 0
+// of the moment kernel of every step, with ordinary stores, and read by the update kernel of the SAME step (coef, last_skipped).
+enum { kClipOff = 0, kClipNorm = 1, kClipValue = 2 };
+struct ClipState {
+  int64_t steps;        // optimiser steps that passed through the record (skipped ones included)
+  int64_t skipped;      // of them, skipped as non-finite
+  int mode;
+  float clip_val;
+  int skip_nonfinite;
+  float total_norm;     // last step: (float)sqrt(sum over all tensors of the squares the norm kernel took) - pre-clip by norm, post-clamp by value
+  float coef;           // last step: what the update multiplied the gradient by (1 outside norm mode)
+  int last_skipped;
+};
+
+// the bound of the value clamp: c in value mode, +Inf otherwise (clamp_keep_nan(v, Inf) == v for every v, bit for bit)
+__device__ __forceinline__ float clip_value_bound(const ClipState* st) { return st->mode == kClipValue ? st->clip_val : INFINITY; }
+
+// torch.clamp(v, -c, c): +-Inf becomes +-c and NaN stays NaN (both comparisons are false for it; fminf / fmaxf would return c)
+__device__ __forceinline__ float clamp_keep_nan(float v, float c) { return v < -c ? -c : (v > c ? c : v); }
+
+// kClip: every scaled gradient passes the value clamp before it is squared (the bound comes from the record)
+template <bool kClip>
+__device__ __forceinline__ void novograd_norm_body(const float* __restrict__ grads, const int64_t* __restrict__ offsets, int n_tensors,
+                                                   int64_t n, double* __restrict__ norm2, float grad_scale,
+                                                   const ClipState* __restrict__ clip_st) {
   __shared__ double s_red[4];
+  float cl = 0.f;
+  if constexpr (kClip) cl = clip_value_bound(clip_st);
   const int64_t beg = (int64_t)blockIdx.x * kNormChunk;
   const int64_t end = beg + kNormChunk < n ? beg + kNormChunk : n;
   int lo = 0, hi = n_tensors;  // offsets[lo] <= beg < offsets[hi]
@@ -37,14 +65,23 @@ __global__ __launch_bounds__(256) void novograd_norm_kernel(const float* __restr
 #pragma unroll
         for (int u = 0; u < kInFlight; ++u) {
           const float mk = q0 + 256 * u < nv ? grad_scale : 0.f;
-          const float a = g4[u].x * mk, b = g4[u].y * mk, c = g4[u].z * mk, d = g4[u].w * mk;
+          float a = g4[u].x * mk, b = g4[u].y * mk, c = g4[u].z * mk, d = g4[u].w * mk;
+          if constexpr (kClip) {
+            // a masked duplicate of an Inf is 0 * Inf = NaN: as ever where the live lane's Inf makes the sum non-finite anyway (off and
+            // norm mode: cl = Inf, nothing changes), but in value mode the live lane's Inf is clamped to a finite c - the masked lanes
+            // then have to add exactly nothing
+            const bool live = q0 + 256 * u < nv || cl == INFINITY;
+            a = live ? clamp_keep_nan(a, cl) : 0.f, b = live ? clamp_keep_nan(b, cl) : 0.f;
+            c = live ? clamp_keep_nan(c, cl) : 0.f, d = live ? clamp_keep_nan(d, cl) : 0.f;
+          }
           acc += ((double)a * (double)a + (double)b * (double)b) + ((double)c * (double)c + (double)d * (double)d);
         }
       }
       e0 = seg + 4 * nv;
     }
     for (int64_t e = e0 + threadIdx.x; e < tend; e += 256) {
-      const float g = grads[e] * grad_scale;
+      float g = grads[e] * grad_scale;
+      if constexpr (kClip) g = clamp_keep_nan(g, cl);
       acc += (double)g * (double)g;
     }
     acc = wave_sum_d(acc);
@@ -54,6 +91,17 @@ __global__ __launch_bounds__(256) void novograd_norm_kernel(const float* __restr
     if (threadIdx.x == 0 && tend > seg) atomicAdd(&norm2[t], (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
     seg = tend;
   }
+}
+
+// (the clip variants are kernels of their own names: a step without a clip record launches the kernels it always launched, by name)
+__global__ __launch_bounds__(256) void novograd_norm_kernel(const float* __restrict__ grads, const int64_t* __restrict__ offsets,
+                                                            int n_tensors, int64_t n, double* __restrict__ norm2, float grad_scale) {
+  novograd_norm_body<false>(grads, offsets, n_tensors, n, norm2, grad_scale, nullptr);
+}
+__global__ __launch_bounds__(256) void novograd_norm_kernel_clip(const float* __restrict__ grads, const int64_t* __restrict__ offsets,
+                                                                 int n_tensors, int64_t n, double* __restrict__ norm2, float grad_scale,
+                                                                 const ClipState* __restrict__ clip_st) {
+  novograd_norm_body<true>(grads, offsets, n_tensors, n, norm2, grad_scale, clip_st);
 }
 
 // Weight EMA ("Weight EMA"): the record lives on the device, so a captured graph replays the decay warm-up like the LR
@@ -105,15 +153,90 @@ __global__ __launch_bounds__(256) void novograd_moment_kernel(double* __restrict
   denom[i] = sqrtf(v) + eps;
 }
 
+// the clip coefficient of torch.nn.utils.clip_grad_norm_: min(1, c / (N + 1e-6)) in one correctly rounded f32 add and one division; a
+// NaN stays a NaN (`q > 1` is false for it).  ops.clip_coef is its host twin
+__device__ __forceinline__ float clip_coef(float total_norm, float c) {
+  const float q = __fdiv_rn(c, __fadd_rn(total_norm, 1e-6f));
+  return q > 1.0f ? 1.0f : q;
+}
+
+// Stage 2 with a clip record: the step's one decision is taken here, between the norm and the update.  The global norm needs every
+// norm2[t] before any of them is zeroed, so the kernel is ONE workgroup: it stages the sums of squares through LDS, thread 0 adds them
+// in f64 in tensor index order, decides (coef, skip), writes the record and - unless the step is skipped - advances the EMA record;
+// after the barrier every thread strides over the tensors: the moment update (unless skipped) and the re-zeroing (always).
+static constexpr int kMomentStage = 2048;
+template <bool kEma>
+__global__ __launch_bounds__(256) void novograd_moment_kernel_clip(double* __restrict__ norm2, float* __restrict__ exp_avg_sq,
+                                                                   float* __restrict__ denom, int n_tensors, float beta2, float eps,
+                                                                   EmaState* __restrict__ ema_st, ClipState* __restrict__ clip_st) {
+  __shared__ double s_n2[kMomentStage];
+  __shared__ float s_coef;
+  __shared__ int s_skip;
+  double total2 = 0.0;       // (thread 0's)
+  for (int base = 0; base < n_tensors; base += kMomentStage) {
+    const int cnt = n_tensors - base < kMomentStage ? n_tensors - base : kMomentStage;
+    for (int i = threadIdx.x; i < cnt; i += 256) s_n2[i] = norm2[base + i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int i = 0;
+      for (; i + 8 <= cnt; i += 8) {     // eight LDS reads in flight ahead of the eight dependent adds
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = s_n2[i + u];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) total2 += v[u];
+      }
+      for (; i < cnt; ++i) total2 += s_n2[i];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const int mode = clip_st->mode;
+    const float total_norm = (float)sqrt(total2);
+    const float coef = mode == kClipNorm ? clip_coef(total_norm, clip_st->clip_val) : 1.0f;
+    const int skip = clip_st->skip_nonfinite != 0 && !isfinite(total2);
+    clip_st->steps = clip_st->steps + 1;
+    clip_st->skipped = clip_st->skipped + skip;
+    clip_st->total_norm = total_norm;
+    clip_st->coef = coef;
+    clip_st->last_skipped = skip;
+    if constexpr (kEma) {
+      if (!skip) {
+        const int64_t t = ema_st->num_updates;
+        ema_st->w = ema_weight(ema_st->decay, ema_st->warmup, t);
+        ema_st->num_updates = t + 1;
+      }
+    }
+    s_coef = coef;
+    s_skip = skip;
+  }
+  __syncthreads();
+  const bool skip = s_skip != 0;
+  const double coef2 = (double)s_coef * (double)s_coef;     // (coef == 1: 1.0 * n2 is n2 - every bit of the step is the un-clipped step's)
+  for (int i = threadIdx.x; i < n_tensors; i += 256) {
+    const double n2 = norm2[i];
+    norm2[i] = 0.0;
+    if (skip) continue;
+    const float norm = (float)(coef2 * n2);
+    float v = exp_avg_sq[i];
+    v = (v == 0.f) ? norm : beta2 * v + (1.f - beta2) * norm;
+    exp_avg_sq[i] = v;
+    denom[i] = sqrtf(v) + eps;
+  }
+}
+
 // kEma: the new parameters are also folded into the average `ema` while they are still in registers (one more 16-byte load and
 // store per group, no launch); the kEma = false instantiation is the kernel as it always was
-template <bool kEma>
-__global__ __launch_bounds__(256) void novograd_update_kernel(float* __restrict__ params, const float* __restrict__ grads,
-                                                              float* __restrict__ exp_avg, const int64_t* __restrict__ offsets,
-                                                              int n_tensors, const float* __restrict__ denom,
-                                                              const float* __restrict__ lr_ptr, float beta1, float wd,
-                                                              float grad_scale, int64_t n, float* __restrict__ ema,
-                                                              const EmaState* __restrict__ ema_st) {
+// kClip: the skip flag, the coefficient and the clamp bound are read once per thread next to lr; a skipped step returns before any store,
+// otherwise the scaled gradient is clamped (value mode) and multiplied by coef (1 outside norm mode) in registers
+template <bool kEma, bool kClip>
+__device__ __forceinline__ void novograd_update_body(float* __restrict__ params, const float* __restrict__ grads,
+                                                     float* __restrict__ exp_avg, const int64_t* __restrict__ offsets,
+                                                     int n_tensors, const float* __restrict__ denom,
+                                                     const float* __restrict__ lr_ptr, float beta1, float wd,
+                                                     float grad_scale, int64_t n, float* __restrict__ ema,
+                                                     const EmaState* __restrict__ ema_st, const ClipState* __restrict__ clip_st,
+                                                     const int64_t first_grp, const int64_t grid_grps) {
   // The tensor of an element is found by bisection over the offset table: the table lives in LDS (a search from
   // global memory is seven dependent loads per element) and one search serves four consecutive elements, which
   // move as 16-byte vectors whenever the group lies inside one tensor (always, for this model's shapes).
@@ -123,8 +246,14 @@ __global__ __launch_bounds__(256) void novograd_update_kernel(float* __restrict_
   const float lr = *lr_ptr;
   float w = 0.f;
   if constexpr (kEma) w = ema_st->w;
+  float coef = 1.f, cl = 0.f;
+  if constexpr (kClip) {
+    if (clip_st->last_skipped) return;
+    coef = clip_st->coef;
+    cl = clip_value_bound(clip_st);
+  }
   const int64_t ngrp = (n + 3) >> 2;
-  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < ngrp; q += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t q = first_grp; q < ngrp; q += grid_grps) {
     const int64_t e = 4 * q;
     int lo = 0, hi = n_tensors;  // s_off[lo] <= e < s_off[hi]
     while (hi - lo > 1) {
@@ -141,7 +270,9 @@ __global__ __launch_bounds__(256) void novograd_update_kernel(float* __restrict_
       float pv[4] = {p.x, p.y, p.z, p.w}, gv[4] = {g.x, g.y, g.z, g.w}, mv[4] = {m0.x, m0.y, m0.z, m0.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        float gi = (gv[i] * grad_scale) / dn;
+        float gs = gv[i] * grad_scale;
+        if constexpr (kClip) gs = clamp_keep_nan(gs, cl) * coef;
+        float gi = gs / dn;
         if (wd != 0.f) gi = gi + wd * pv[i];
         mv[i] = mv[i] * beta1 + gi;
         pv[i] = pv[i] - lr * mv[i];
@@ -155,7 +286,9 @@ __global__ __launch_bounds__(256) void novograd_update_kernel(float* __restrict_
       for (int64_t ee = e; ee < e + 4 && ee < n; ++ee) {
         while (lo + 1 < n_tensors && s_off[lo + 1] <= ee) ++lo;
         const float pe = params[ee];
-        float gi = (grads[ee] * grad_scale) / denom[lo];
+        float gs = grads[ee] * grad_scale;
+        if constexpr (kClip) gs = clamp_keep_nan(gs, cl) * coef;
+        float gi = gs / denom[lo];
         if (wd != 0.f) gi = gi + wd * pe;
         const float m = exp_avg[ee] * beta1 + gi;
         exp_avg[ee] = m;
@@ -165,6 +298,28 @@ __global__ __launch_bounds__(256) void novograd_update_kernel(float* __restrict_
       }
     }
   }
+}
+
+template <bool kEma>
+__global__ __launch_bounds__(256) void novograd_update_kernel(float* __restrict__ params, const float* __restrict__ grads,
+                                                              float* __restrict__ exp_avg, const int64_t* __restrict__ offsets,
+                                                              int n_tensors, const float* __restrict__ denom,
+                                                              const float* __restrict__ lr_ptr, float beta1, float wd,
+                                                              float grad_scale, int64_t n, float* __restrict__ ema,
+                                                              const EmaState* __restrict__ ema_st) {
+  novograd_update_body<kEma, false>(params, grads, exp_avg, offsets, n_tensors, denom, lr_ptr, beta1, wd, grad_scale, n, ema, ema_st, nullptr,
+                                   blockIdx.x * (int64_t)blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+template <bool kEma>
+__global__ __launch_bounds__(256) void novograd_update_kernel_clip(float* __restrict__ params, const float* __restrict__ grads,
+                                                                   float* __restrict__ exp_avg, const int64_t* __restrict__ offsets,
+                                                                   int n_tensors, const float* __restrict__ denom,
+                                                                   const float* __restrict__ lr_ptr, float beta1, float wd,
+                                                                   float grad_scale, int64_t n, float* __restrict__ ema,
+                                                                   const EmaState* __restrict__ ema_st,
+                                                                   const ClipState* __restrict__ clip_st) {
+  novograd_update_body<kEma, true>(params, grads, exp_avg, offsets, n_tensors, denom, lr_ptr, beta1, wd, grad_scale, n, ema, ema_st, clip_st,
+                                  blockIdx.x * (int64_t)blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 // Gradient accumulation: acc[i] = acc[i] + g[i] over up to LASR_ACC_MAX_RANGES [lo, hi) pieces of two flat f32 buffers in ONE
@@ -259,7 +414,7 @@ extern "C" size_t lasr_novograd_workspace_bytes(int64_t n_tensors, int64_t n_ele
 static int novograd_step_impl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* offsets,
                               int64_t n_tensors, int64_t n_elems, const float* lr, float beta1, float beta2, float eps,
                               float weight_decay, float grad_scale, void* workspace, size_t workspace_bytes, void* stream, bool zeroed,
-                              float* ema = nullptr, void* ema_state = nullptr);
+                              float* ema = nullptr, void* ema_state = nullptr, void* clip_state = nullptr);
 
 extern "C" int lasr_novograd_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* offsets,
                                   int64_t n_tensors, int64_t n_elems, const float* lr, float beta1, float beta2, float eps,
@@ -288,10 +443,22 @@ extern "C" int lasr_novograd_step_ema(float* params, const float* grads, float* 
                             workspace, workspace_bytes, stream, keep_workspace != 0, ema, ema_state);
 }
 
+// the step with a clip record ("Gradient clipping and the non-finite guard").  clip_state == NULL: lasr_novograd_step_ema, launch
+// for launch
+extern "C" int lasr_novograd_step_clip(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* offsets,
+                                       int64_t n_tensors, int64_t n_elems, const float* lr, float beta1, float beta2, float eps,
+                                       float weight_decay, float grad_scale, void* workspace, size_t workspace_bytes, void* stream,
+                                       float* ema, void* ema_state, int keep_workspace, void* clip_state) {
+  LASR_CHECK_ARG((ema != nullptr) == (ema_state != nullptr), "lasr_novograd_step_clip: ema and ema_state come together (ema %s, state %s)",
+                 ema ? "given" : "null", ema_state ? "given" : "null");
+  return novograd_step_impl(params, grads, exp_avg, exp_avg_sq, offsets, n_tensors, n_elems, lr, beta1, beta2, eps, weight_decay, grad_scale,
+                            workspace, workspace_bytes, stream, keep_workspace != 0, ema, ema_state, clip_state);
+}
+
 static int novograd_step_impl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* offsets,
                               int64_t n_tensors, int64_t n_elems, const float* lr, float beta1, float beta2, float eps,
                               float weight_decay, float grad_scale, void* workspace, size_t workspace_bytes, void* stream, bool zeroed,
-                              float* ema, void* ema_state) {
+                              float* ema, void* ema_state, void* clip_state) {
   LASR_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && offsets && lr && workspace, "lasr_novograd_step: null pointer");
   LASR_CHECK_SHAPE(n_tensors > 0 && n_tensors < (1 << 20) && n_elems > 0, "lasr_novograd_step: n_tensors=%lld", (long long)n_tensors);
   if (ema) {   // the average may overlap none of the buffers the update kernel reads and writes in the same pass
@@ -310,11 +477,22 @@ static int novograd_step_impl(float* params, const float* grads, float* exp_avg,
     hipError_t me = hipMemsetAsync(norm2, 0, (size_t)n_tensors * sizeof(double), st);
     if (me != hipSuccess) return hip_fail(me, "lasr_novograd_step memset");
   }
-  hipLaunchKernelGGL(novograd_norm_kernel, dim3((unsigned)cdiv(n_elems, kNormChunk)), dim3(256), 0, st, grads, offsets, (int)n_tensors,
-                     n_elems, norm2, grad_scale);
+  ClipState* cst = reinterpret_cast<ClipState*>(clip_state);
+  if (cst)
+    hipLaunchKernelGGL(novograd_norm_kernel_clip, dim3((unsigned)cdiv(n_elems, kNormChunk)), dim3(256), 0, st, grads, offsets,
+                       (int)n_tensors, n_elems, norm2, grad_scale, cst);
+  else
+    hipLaunchKernelGGL(novograd_norm_kernel, dim3((unsigned)cdiv(n_elems, kNormChunk)), dim3(256), 0, st, grads, offsets, (int)n_tensors,
+                       n_elems, norm2, grad_scale);
   LASR_LAUNCH_CHECK("novograd_norm_kernel");
   EmaState* est = reinterpret_cast<EmaState*>(ema_state);
-  if (ema)
+  if (cst && ema)          // one workgroup: the global norm needs every tensor's sum before any is zeroed
+    hipLaunchKernelGGL(novograd_moment_kernel_clip<true>, dim3(1), dim3(256), 0, st, norm2, exp_avg_sq, denom, (int)n_tensors, beta2, eps,
+                       est, cst);
+  else if (cst)
+    hipLaunchKernelGGL(novograd_moment_kernel_clip<false>, dim3(1), dim3(256), 0, st, norm2, exp_avg_sq, denom, (int)n_tensors, beta2, eps,
+                       est, cst);
+  else if (ema)
     hipLaunchKernelGGL(novograd_moment_kernel<true>, dim3((unsigned)cdiv(n_tensors, 256)), dim3(256), 0, st, norm2, exp_avg_sq, denom,
                        (int)n_tensors, beta2, eps, est);
   else
@@ -325,13 +503,45 @@ static int novograd_step_impl(float* params, const float* grads, float* exp_avg,
   if (blocks > 256 * 8) blocks = 256 * 8;
   const size_t off_bytes = (size_t)(n_tensors + 1) * sizeof(int64_t);
   LASR_CHECK_SHAPE(off_bytes <= 48 * 1024, "lasr_novograd_step: offset table too large for LDS (%lld tensors)", (long long)n_tensors);
-  if (ema)
+  if (cst && ema)
+    hipLaunchKernelGGL(novograd_update_kernel_clip<true>, dim3((unsigned)blocks), dim3(256), off_bytes, st, params, grads, exp_avg, offsets,
+                       (int)n_tensors, denom, lr, beta1, weight_decay, grad_scale, n_elems, ema, est, cst);
+  else if (cst)
+    hipLaunchKernelGGL(novograd_update_kernel_clip<false>, dim3((unsigned)blocks), dim3(256), off_bytes, st, params, grads, exp_avg, offsets,
+                       (int)n_tensors, denom, lr, beta1, weight_decay, grad_scale, n_elems, ema, est, cst);
+  else if (ema)
     hipLaunchKernelGGL(novograd_update_kernel<true>, dim3((unsigned)blocks), dim3(256), off_bytes, st, params, grads, exp_avg, offsets,
                        (int)n_tensors, denom, lr, beta1, weight_decay, grad_scale, n_elems, ema, est);
   else
     hipLaunchKernelGGL(novograd_update_kernel<false>, dim3((unsigned)blocks), dim3(256), off_bytes, st, params, grads, exp_avg, offsets,
                        (int)n_tensors, denom, lr, beta1, weight_decay, grad_scale, n_elems, ema, est);
   LASR_LAUNCH_CHECK("novograd_update_kernel");
+  return 0;
+}
+
+extern "C" size_t lasr_clip_state_bytes(void) { return sizeof(ClipState); }
+
+// host only: fills a HOST image of the record (the caller uploads it), like lasr_ema_state_init
+extern "C" int lasr_clip_state_init(void* host_buf, size_t bytes, int mode, float clip_val, int skip_nonfinite, int64_t steps,
+                                    int64_t skipped) {
+  LASR_CHECK_ARG(host_buf && bytes >= sizeof(ClipState), "lasr_clip_state_init: buffer of %zu bytes needed", sizeof(ClipState));
+  LASR_CHECK_ARG(mode == kClipOff || mode == kClipNorm || mode == kClipValue, "lasr_clip_state_init: mode %d (0 off, 1 norm, 2 value)", mode);
+  LASR_CHECK_ARG(clip_val >= 0.f && clip_val <= FLT_MAX, "lasr_clip_state_init: clip_val has to be finite and >= 0, got %g",
+                 (double)clip_val);   // (NaN fails both)
+  LASR_CHECK_ARG(mode == kClipOff || clip_val > 0.f, "lasr_clip_state_init: mode %d needs clip_val > 0", mode);
+  LASR_CHECK_ARG(steps >= 0 && skipped >= 0, "lasr_clip_state_init: steps=%lld skipped=%lld", (long long)steps,
+                 (long long)skipped);
+  ClipState s;
+  memset(&s, 0, sizeof(s));
+  s.steps = steps;
+  s.skipped = skipped;
+  s.mode = mode;
+  s.clip_val = clip_val;
+  s.skip_nonfinite = skip_nonfinite != 0;
+  s.total_norm = 0.f;          // the last step's three: written by every step
+  s.coef = 1.f;
+  s.last_skipped = 0;
+  memcpy(host_buf, &s, sizeof(s));
   return 0;
 }
 

@@ -360,6 +360,8 @@ class FusedLoop:
                         for k in ("train_loss", "train_wer"):
                             if k + "_step" in m:
                                 tr.callback_metrics[k] = m[k + "_step"]
+                        if hasattr(tr, "publish_grad_clip"):     # the clip record rides on the same synchronisation
+                            tr.publish_grad_clip(getattr(self.ts, "_optimizer", None))
                 if on_step is not None:
                     on_step(tr)
         finally:

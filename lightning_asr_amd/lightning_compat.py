@@ -164,12 +164,18 @@ class Trainer:
                  accelerator: Optional[str] = None, num_nodes: int = 1, default_root_dir: str = ".",
                  callbacks=None, logger=None, save_top_k: int = 3, monitor: str = "val_wer", max_steps: Optional[int] = None,
                  device: Optional[str] = None, log_every_n_steps: int = 50, accumulate_grad_batches: int = 1,
-                 ema_decay: float = 0.0, ema_warmup: bool = True, ema_eval: bool = True, **ignored):
-        from .scheduler.novograd import check_ema_decay
+                 ema_decay: float = 0.0, ema_warmup: bool = True, ema_eval: bool = True, gradient_clip_val: float = 0,
+                 gradient_clip_algorithm: str = "norm", skip_nonfinite_steps: bool = False, track_grad_norm: bool = False, **ignored):
+        from .scheduler.novograd import check_ema_decay, check_grad_clip
         from .step import check_accumulate
         # weight EMA ("Weight EMA"): the module's configure_optimizers hands ema_decay / ema_warmup to Novograd, which then
         # owns the average; ema_eval: validate / test (and so the monitored metric and the best-k checkpoints) run on the average
         self.ema_decay, self.ema_warmup, self.ema_eval = check_ema_decay(ema_decay), bool(ema_warmup), bool(ema_eval)
+        # train.py:249-250 and the non-finite guard ("Gradient clipping and the non-finite guard"): handed to Novograd the same
+        # way, so both routes of fit get them; track_grad_norm publishes grad_norm / grad_clip_coef / skipped_steps in callback_metrics
+        self.gradient_clip_val, self.gradient_clip_algorithm = check_grad_clip(gradient_clip_val, gradient_clip_algorithm)
+        self.skip_nonfinite_steps, self.track_grad_norm = bool(skip_nonfinite_steps), bool(track_grad_norm)
+        self._skips_seen = 0                            # skipped_steps at the last read (the first growth is logged)
         self._opt = None                                # the optimiser of the last fit: where validate / test find the average
         self.max_epochs, self.max_steps = max_epochs, max_steps
         # train.py:244: K micro-batches per optimiser step, the gradient averaged over K; global_step, max_steps, the LR schedule and
@@ -209,6 +215,23 @@ class Trainer:
     def _record(self, name: str, v: float) -> None:
         self._epoch_metrics.setdefault(name, []).append(v)
         self.callback_metrics[name] = v
+
+    def publish_grad_clip(self, opt) -> None:
+        """grad_norm / grad_clip_coef (the last step's) and skipped_steps from the optimiser's clip record into callback_metrics: one
+        small device read, so only where the loop synchronises anyway (a metrics read, the end of an epoch)"""
+        state = getattr(opt, "clip_state", None)
+        if state is None:
+            return
+        from . import ops
+        st = ops.clip_state_read(state)
+        self.callback_metrics.update(grad_norm=st["total_norm"], grad_clip_coef=st["coef"], skipped_steps=st["skipped"])
+        if st["skipped"] > self._skips_seen:
+            if self._skips_seen == 0:
+                logger.warning(
+                    "%d of %d optimiser steps so far had a non-finite gradient (a NaN or an Inf, e.g. an utterance with fewer output "
+                    "frames than its transcript needs) and were skipped: parameters, moments and the weight average were left alone",
+                    st["skipped"], st["steps"])
+            self._skips_seen = st["skipped"]
 
     def _limit(self, n: int, lim) -> int:
         if isinstance(lim, float):
@@ -375,6 +398,7 @@ class Trainer:
                         self.global_step += 1
                         opened = False
                     on_step(self)
+            self.publish_grad_clip(opt)
             rec = {"epoch": epoch, "global_step": self.global_step, "train_time_s": time.time() - t0,
                    "lr": opt.param_groups[0]["lr"]}
             rec.update({k: float(np.mean(v)) for k, v in self._epoch_metrics.items()})

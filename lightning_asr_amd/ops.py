@@ -876,13 +876,30 @@ def novograd_workspace(n_tensors: int, n_elems: int, device) -> torch.Tensor:
 
 def novograd_step(params, grads, exp_avg, exp_avg_sq, offsets, lr_dev, beta1=0.8, beta2=0.5, eps=1e-8, weight_decay=0.0,
                   grad_scale=1.0, ws: Optional[torch.Tensor] = None, ema: Optional[torch.Tensor] = None,
-                  ema_state: Optional[torch.Tensor] = None):
+                  ema_state: Optional[torch.Tensor] = None, clip_state: Optional[torch.Tensor] = None):
     """ws: a workspace from novograd_workspace() kept by the caller - the step then issues no memset of its own.
     ema + ema_state (``ema_state()``): the weight EMA of the parameters, updated by the step's last kernel with the weight the
-    device record yields ("Weight EMA"); both or neither."""
+    device record yields ("Weight EMA"); both or neither.
+    clip_state (``clip_state()``): gradient clipping and the non-finite guard, decided on the device inside the step's three launches
+    ("Gradient clipping and the non-finite guard"); None: the step as it always was, kernel for kernel."""
     n_t = exp_avg_sq.numel()
     n = params.numel()
     nb = _lib.load().lasr_novograd_workspace_bytes(n_t, n)
+    if clip_state is not None:
+        if (ema is None) != (ema_state is None):
+            raise ValueError("novograd_step: ema and ema_state come together")
+        if ema is not None:
+            _ema_check("novograd_step", ema, params)
+        for who, st, need in (("ema_state", ema_state, ema_state_bytes), ("clip_state", clip_state, clip_state_bytes)):
+            if st is not None and (st.dtype != torch.uint8 or st.numel() < need() or st.device != params.device):
+                raise ValueError("novograd_step: %s has to come from ops.%s() on %s" % (who, who, params.device))
+        keep = ws is not None
+        if ws is None:
+            ws = _ws(nb, params.device)
+        call("lasr_novograd_step_clip", _p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), _p(offsets), n_t, n, _p(lr_dev), beta1,
+             beta2, eps, weight_decay, grad_scale, _p(ws), ws.numel(), _stream(), _p(ema) if ema is not None else None,
+             _p(ema_state) if ema_state is not None else None, int(keep), _p(clip_state))
+        return
     if ema is not None or ema_state is not None:
         if ema is None or ema_state is None:
             raise ValueError("novograd_step: ema and ema_state come together")
@@ -902,6 +919,65 @@ def novograd_step(params, grads, exp_avg, exp_avg_sq, offsets, lr_dev, beta1=0.8
     ws = _ws(nb, params.device)
     call("lasr_novograd_step", _p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), _p(offsets), n_t, n, _p(lr_dev), beta1,
          beta2, eps, weight_decay, grad_scale, _p(ws), nb, _stream())
+
+
+# ---- gradient clipping and the non-finite guard ("Gradient clipping and the non-finite guard") ----
+# lasr_clip_state: int64 steps; int64 skipped; int mode; float clip_val; int skip_nonfinite; float total_norm; float coef;
+# int last_skipped (40 bytes)
+_CLIP_STATE_FMT = "<qqififfi"
+CLIP_MODES = {"off": 0, "norm": 1, "value": 2}
+
+
+def clip_state_bytes() -> int:
+    return int(_lib.load().lasr_clip_state_bytes())
+
+
+def clip_state_host(algorithm: str = "off", clip_val: float = 0.0, skip_nonfinite: bool = False, steps: int = 0,
+                    skipped: int = 0) -> bytes:
+    """the host image of the device record (lasr_clip_state_init).  ValueError: an algorithm outside off / norm / value, a value
+    that is negative or not finite, norm / value without a value > 0, a negative count"""
+    if algorithm not in CLIP_MODES:
+        raise ValueError("clip algorithm has to be one of %s, got %r" % (sorted(CLIP_MODES), algorithm))
+    clip_val = float(clip_val)
+    if not (math.isfinite(clip_val) and clip_val >= 0.0):
+        raise ValueError("clip value has to be a finite number >= 0, got %r" % (clip_val,))
+    if algorithm != "off" and not float(np.float32(clip_val)) > 0.0:
+        raise ValueError("clip algorithm %r needs a value > 0, got %r" % (algorithm, clip_val))
+    if int(steps) < 0 or int(skipped) < 0:
+        raise ValueError("clip steps / skipped have to be >= 0, got %r / %r" % (steps, skipped))
+    nb = clip_state_bytes()
+    host = ctypes.create_string_buffer(nb)
+    call("lasr_clip_state_init", host, nb, CLIP_MODES[algorithm], clip_val, int(bool(skip_nonfinite)), int(steps), int(skipped))
+    return host.raw
+
+
+def clip_state(algorithm: str = "off", clip_val: float = 0.0, skip_nonfinite: bool = False, steps: int = 0, skipped: int = 0,
+               device="cuda") -> torch.Tensor:
+    """The device record ``novograd_step(clip_state=...)`` reads and fills in: uint8 (lasr_clip_state_bytes()).  algorithm "off" with
+    the guard off changes nothing in the step's arithmetic and still records the gradient norm.  ``clip_state_read`` reads it back."""
+    return torch.frombuffer(bytearray(clip_state_host(algorithm, clip_val, skip_nonfinite, steps, skipped)), dtype=torch.uint8).to(device)
+
+
+def clip_state_read(state) -> dict:
+    """{"algorithm", "clip_val", "skip_nonfinite", "steps", "skipped", "total_norm", "coef", "last_skipped"} of a record (a tensor
+    from ``clip_state`` - one device read - or host bytes).  steps counts the optimiser steps that went through the record, skipped
+    those of them that were dropped as non-finite; the last three describe the LAST step.  total_norm is the global norm of the
+    scaled gradient g^ = grad_scale * g as the norm kernel squared it: BEFORE the clip in norm mode, AFTER the clamp in value mode (the
+    one quantity the kernels already hold); coef is what the update multiplied g^ by (1 outside norm mode)."""
+    import struct
+    raw = bytes(state.cpu().numpy().tobytes()) if torch.is_tensor(state) else bytes(state)
+    steps, skipped, mode, c, guard, total_norm, coef, last = struct.unpack_from(_CLIP_STATE_FMT, raw)
+    names = {v: k for k, v in CLIP_MODES.items()}
+    return {"algorithm": names[mode], "clip_val": float(c), "skip_nonfinite": bool(guard), "steps": int(steps), "skipped": int(skipped),
+            "total_norm": float(total_norm), "coef": float(coef), "last_skipped": bool(last)}
+
+
+def clip_coef(total_norm, c) -> np.float32:
+    """Host twin of the device coefficient of norm clipping, in numpy f32: min(1, f32(c) / (f32(total_norm) + f32(1e-6))) - one add,
+    one division, the constants of ``torch.nn.utils.clip_grad_norm_``; a NaN stays a NaN."""
+    with np.errstate(all="ignore"):
+        q = np.float32(c) / (np.float32(total_norm) + np.float32(1e-6))
+    return np.float32(1.0) if q > np.float32(1.0) else np.float32(q)
 
 
 # ---- weight EMA (DESIGN 4, "Weight EMA") ----

@@ -18,7 +18,7 @@ from . import _lib, ops
 from .comm import Communicator
 from .engine import NativeModel
 from .schedule import CosineAnnealingWarmupRestarts
-from .scheduler.novograd import check_ema_decay
+from .scheduler.novograd import check_ema_decay, check_grad_clip, make_clip_state
 
 
 _ROCTX = None
@@ -44,7 +44,8 @@ class TrainStep:
     def __init__(self, model: NativeModel, learning_rate: float = 1e-2, weight_decay: float = 1e-3,
                  betas=(0.8, 0.5), eps: float = 1e-8, schedule: Optional[CosineAnnealingWarmupRestarts] = None,
                  process_group=None, comm: Optional[Communicator] = None, accumulate: int = 1, ema_decay: float = 0.0,
-                 ema_warmup: bool = True):
+                 ema_warmup: bool = True, gradient_clip_val: float = 0.0, gradient_clip_algorithm: str = "norm",
+                 skip_nonfinite: bool = False, track_grad_norm: bool = False):
         """comm: the library-owned RCCL communicator (lasr_comm_*).  Default for world > 1 on the nccl backend: one is built
         from the torch.distributed group (which then only bootstraps the unique id); ``LASR_COMM=torch`` keeps the gradient
         exchange on torch.distributed (the only choice for gloo groups: CPU rehearsal, two ranks sharing a GPU in the tests).
@@ -56,13 +57,22 @@ class TrainStep:
         ema_decay > 0: ``self.ema`` is an exponential moving average of the parameters ("Weight EMA"), a copy of them
         now and updated by the last kernel of every OPTIMISER step (under accumulate > 1 only the boundary reaches it) with the
         weight the device record ``self.ema_state`` yields - no launch, no host scalar, so a captured graph replays it.  0 = off:
-        no buffer, and the step as it always was."""
+        no buffer, and the step as it always was.
+        gradient_clip_val > 0 / gradient_clip_algorithm ("norm": by the global norm, "value": element-wise) / skip_nonfinite (a step
+        whose gradient holds a NaN or an Inf leaves parameters, moments and the average alone, and still counts as a step for the
+        schedule, ``global_step`` and the accumulation window) / track_grad_norm: decided on the device by the optimiser's own
+        kernels through the record ``self.clip_state`` ("Gradient clipping and the non-finite guard") - no launch, no host
+        decision, so a captured graph replays it; under accumulate > 1 once per window, on the window's sum.  All off: no record."""
         self.model = model
+        self.gradient_clip_val, self.gradient_clip_algorithm = check_grad_clip(gradient_clip_val, gradient_clip_algorithm)
+        self.skip_nonfinite, self.track_grad_norm = bool(skip_nonfinite), bool(track_grad_norm)
         self.ema_decay, self.ema_warmup = check_ema_decay(ema_decay), bool(ema_warmup)
         self.ema = self.ema_state = None
         if self.ema_decay > 0.0:
             self.ema = model.params.clone()
             self.ema_state = ops.ema_state(self.ema_decay, self.ema_warmup, 0, device=model.device)
+        self.clip_state = make_clip_state(self.gradient_clip_val, self.gradient_clip_algorithm, self.skip_nonfinite,
+                                          self.track_grad_norm, model.device)
         self.accumulate = check_accumulate(accumulate)
         self.micro = 0             # micro-batches already added into model.grads in the current window (K > 1)
         if self.accumulate > 1:
@@ -138,6 +148,11 @@ class TrainStep:
         # the weight EMA is the optimiser's too (None with ema_decay = 0): checkpoints and resume go through its state_dict
         ts.ema, ts.ema_state = getattr(optimizer, "ema", None), getattr(optimizer, "ema_state", None)
         ts.ema_decay, ts.ema_warmup = getattr(optimizer, "ema_decay", 0.0), getattr(optimizer, "ema_warmup", True)
+        # and so is the clip record (None with everything off): its counts travel in the optimiser's state_dict
+        ts.clip_state = getattr(optimizer, "clip_state", None)
+        ts.gradient_clip_val = getattr(optimizer, "gradient_clip_val", 0.0)
+        ts.gradient_clip_algorithm = getattr(optimizer, "gradient_clip_algorithm", "norm")
+        ts.skip_nonfinite, ts.track_grad_norm = getattr(optimizer, "skip_nonfinite", False), getattr(optimizer, "track_grad_norm", False)
         ts.lr = float(g["lr"])
         ts.lr_dev.fill_(ts.lr)
         ts._optimizer = optimizer
@@ -147,6 +162,11 @@ class TrainStep:
     def ema_num_updates(self) -> int:
         """EMA updates done so far (one read of the device record); 0 with EMA off"""
         return ops.ema_state_read(self.ema_state)["num_updates"] if self.ema_state is not None else 0
+
+    @property
+    def skipped_steps(self) -> int:
+        """optimiser steps dropped as non-finite so far (one read of the device record); 0 without a record"""
+        return ops.clip_state_read(self.clip_state)["skipped"] if self.clip_state is not None else 0
 
     def sync_device_schedule(self) -> None:
         """Re-upload the schedule after its host state changed behind the device twin's back (``load_state_dict`` on resume,
@@ -189,7 +209,7 @@ class TrainStep:
             self._opt_ws = ops.novograd_workspace(self.exp_avg_sq.numel(), m.params.numel(), m.device)
         ops.novograd_step(m.params, m.grads, self.exp_avg, self.exp_avg_sq, self.offsets, self.lr_dev, self.betas[0],
                           self.betas[1], self.eps, self.wd, grad_scale=1.0 / (self.accumulate * self.world), ws=self._opt_ws,
-                          ema=self.ema, ema_state=self.ema_state)
+                          ema=self.ema, ema_state=self.ema_state, clip_state=self.clip_state)
         if self.schedule is not None:
             if self._lr_state is not None and self.schedule.last_epoch != self._lr_epoch:
                 self.sync_device_schedule()                # the host schedule was loaded / reset since the last step
@@ -389,7 +409,7 @@ class GraphedTrainStep:
         The eager warm-up passes and the capture pass leave the training state (parameters, BN buffers, optimiser moments,
         schedule, dither / dropout counters) exactly as it was - also when the capture fails: it is snapshotted before and
         restored in a ``finally`` (accumulate > 1: the running gradient sum, the micro-batch buffer and the window counter too;
-        with a weight EMA: the average and its device record)."""
+        with a weight EMA: the average and its device record; with a clip record: that record)."""
         ts, m = self.ts, self.ts.model
         if ts.world > 1 and not graph_dp_enabled():
             raise RuntimeError("graph capture of the data-parallel step (RCCL inside the graph) is switched off: LASR_GRAPH_DP=0")
@@ -399,6 +419,8 @@ class GraphedTrainStep:
             dev_state += [m.grads, m.grads_micro]
         if ts.ema is not None:
             dev_state += [ts.ema, ts.ema_state]       # the average and its update count: the warm-up passes advance both
+        if ts.clip_state is not None:
+            dev_state.append(ts.clip_state)           # the warm-up passes advance its counts
         micro = ts.micro
         if hasattr(self.dither, "step"):
             dev_state.append(self.dither.step)

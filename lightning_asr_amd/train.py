@@ -83,7 +83,12 @@ class LightingModule(LightningModule):
         # weight EMA (train.ema_decay; DESIGN 4, "Weight EMA"): the optimiser owns the average, the Trainer carries the setting
         novo_optim = Novograd(self.parameters(), lr=self.learning_rate, weight_decay=self.weight_decay, betas=(0.8, 0.5),
                               ema_decay=float(getattr(self.trainer, "ema_decay", 0.0) or 0.0),
-                              ema_warmup=bool(getattr(self.trainer, "ema_warmup", True)))
+                              ema_warmup=bool(getattr(self.trainer, "ema_warmup", True)),
+                              # clipping and the non-finite guard (train.gradient_clip_val ...): likewise the optimiser's record
+                              gradient_clip_val=getattr(self.trainer, "gradient_clip_val", 0.0) or 0.0,
+                              gradient_clip_algorithm=getattr(self.trainer, "gradient_clip_algorithm", "norm"),
+                              skip_nonfinite=bool(getattr(self.trainer, "skip_nonfinite_steps", False)),
+                              track_grad_norm=bool(getattr(self.trainer, "track_grad_norm", False)))
         # the schedule counts OPTIMISER steps: ceil(batches / K) per epoch under accumulate_grad_batches = K (the last window of an
         # epoch may be incomplete and still steps)
         K = int(getattr(self.trainer, "accumulate_grad_batches", 1) or 1)
@@ -204,7 +209,11 @@ def main(argv=None):
                       max_steps=tran_cfg.get("max_steps"), log_every_n_steps=tran_cfg.get("log_every_n_steps", 50),
                       accumulate_grad_batches=tran_cfg.get("accumulate_grad_batches", 1),
                       ema_decay=tran_cfg.get("ema_decay", 0) or 0.0, ema_warmup=tran_cfg.get("ema_warmup", True),
-                      ema_eval=tran_cfg.get("ema_eval", True))
+                      ema_eval=tran_cfg.get("ema_eval", True),
+                      gradient_clip_val=tran_cfg.get("gradient_clip_val", 0) or 0.0,
+                      gradient_clip_algorithm=tran_cfg.get("gradient_clip_algorithm", "value"),
+                      skip_nonfinite_steps=tran_cfg.get("skip_nonfinite_steps", False),
+                      track_grad_norm=tran_cfg.get("track_grad_norm", False))
     trainer.fit(model, datamodule=data_module)
     trainer.test(model, test_dataloaders=data_module.test_dataloader())
     return trainer
