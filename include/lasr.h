@@ -45,7 +45,8 @@ extern "C" {
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
-enum { LASR_VARIANT_PLAIN = 0, LASR_VARIANT_CONTEXT = 1, LASR_VARIANT_CONTEXT_SE = 2 };
+enum { LASR_VARIANT_PLAIN = 0, LASR_VARIANT_CONTEXT = 1, LASR_VARIANT_CONTEXT_SE = 2,
+       LASR_VARIANT_Q105 = 3 /* QuartNet105: ten residual blocks of five separable convolutions (models/QuartNet.py:175-224) */ };
 enum {
   LASR_E_ARG = -1,      /* null pointer / negative size / unsupported enum */
   LASR_E_SHAPE = -2,    /* shape outside what the kernels are built for */
@@ -174,7 +175,8 @@ int lasr_gemm_ld(const void* A, int64_t lda, const void* B, int64_t ldb, void* C
  *   lasr_fold_bn_weights_many: w_out [co][ci (+ci)] bf16 and bias_out [co] f32 for up to 32 units in one launch
  *       (coef / coef2 = the [a | b] vectors of lasr_bn_eval_coef_many; w_res = coef2 = NULL without a residual branch);
  *   lasr_gemm_dual: C[M][N] bf16 = act([A1 (rows past row_lens zeroed) | A2] . W^T + bias), A1 [M][K1], A2 [M][K2] bf16,
- *       W [N][K1+K2] bf16; K1, K2 multiples of 64, everything 16-byte aligned.  One GEMM, no separate BN pass.   */
+ *       W [N][K1+K2] bf16; K1, K2 multiples of 64, everything 16-byte aligned.  One GEMM, no separate BN pass.
+ *       K2 = 0 with A2 = NULL: a unit without a residual branch, C = act(mask(A1) . W^T + bias).                  */
 typedef struct {
   const float* w; const float* w_res; const float* coef; const float* coef2; void* w_out; float* bias_out; int64_t co, ci;
 } lasr_fold_desc;
@@ -831,7 +833,9 @@ int lasr_model_loss_backward(lasr_model_t* m, const float* params, float* buffer
  * below it are still being differentiated (Lightning DDP's bucketed overlap, conf/conf.yaml:30).
  * Units are numbered in forward order (lasr_model_unit_info gives their names).  _partial runs forward,
  * loss, the decoder and units [unit_stop, n); each _continue call runs units [unit_stop, previous stop).
- * Gradients of a unit's parameters are final once the call that covers the unit has been enqueued.      */
+ * Gradients of a unit's parameters are final once the call that covers the unit has been enqueued.
+ * LASR_VARIANT_Q105: a residual block is five units, "<block>.seq.0" .. "<block>.seq.3" and the closing "<block>"; unit_stop may
+ * fall inside a block (the residual branch's data gradient waits in the workspace for the block's first unit).       */
 int64_t lasr_model_num_units(const lasr_model_t* m);
 int lasr_model_unit_info(const lasr_model_t* m, int64_t i, char* name, size_t name_cap);
 int lasr_model_loss_backward_partial(lasr_model_t* m, const float* params, float* buffers, const void* feats,

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("LASR_LIB_PATH", os.path.join(_HERE, "liblasr.so"))   
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_SWISH = 0, 1, 2
 LEN_LEAD = 1 << 30          # LASR_LEN_LEAD: a row of samples that starts with one lead-in sample (crop after pre-emphasis)
-VARIANT = {"plain": 0, "context": 1, "context_se": 2}
+VARIANT = {"plain": 0, "context": 1, "context_se": 2, "q105": 3}
 
 _p, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 

@@ -38,8 +38,9 @@ int bn_slice_in(const lasr_bn_branch* branches, int n_branches, int64_t n_rows, 
 // [2 (flip)][C][kDwTapRow] packed bf16 pairs - the layout dwconv_s1_mfma_body keeps in LDS: row = TE[0..79] | TO[0..79] of the
 // zero-padded tap row W[i] = w'[i - 24], TE[i] = (W[2i], W[2i+1]), TO[i] = (W[2i+1], W[2i+2]); flip = 1: taps reversed (data gradient).
 static constexpr int kDwTapRow = 160;
-struct DwTapJobs {                       // up to 16 layers; blk0: first 256-entry block of each layer's table in the builder's grid
-  int n; int blk0[17]; const float* w[16]; uint32_t* out[16]; int C[16]; int k[16];
+static constexpr int kDwTapLayers = 64;  // QuartNet105 has 50 stride-1 depthwise layers (the other variants 13 / 14); 1.8 KB of kernel arguments
+struct DwTapJobs {                       // up to kDwTapLayers layers; blk0: first 256-entry block of each layer's table in the builder's grid
+  int n; int blk0[kDwTapLayers + 1]; const float* w[kDwTapLayers]; uint32_t* out[kDwTapLayers]; int C[kDwTapLayers]; int k[kDwTapLayers];
 };
 __device__ __forceinline__ uint32_t dw_tap_entry(const float* __restrict__ w, int C, int k, int e) {   // e in [0, 2 * C * kDwTapRow)
   const int flip = e / (C * kDwTapRow), r = e - flip * (C * kDwTapRow);
@@ -55,7 +56,7 @@ __device__ __forceinline__ uint32_t dw_tap_entry(const float* __restrict__ w, in
 // The tables of the model call in progress on this thread (model.hip sets it around its forward / backward; null outside):
 // lasr_dwconv_fwd / dwconv_fwd_bn / lasr_dwconv_bwd_fused look their weight pointer up and hand the table to the kernel, which then
 // copies its 64 (32) rows instead of building them.  LASR_DW_TAPS=0 disables the whole path.
-struct DwTapCtx { int n; const float* w[16]; const uint32_t* t[16]; int C[16]; };
+struct DwTapCtx { int n; const float* w[kDwTapLayers]; const uint32_t* t[kDwTapLayers]; int C[kDwTapLayers]; };
 void dw_taps_set_ctx(const DwTapCtx* ctx);
 const uint32_t* dw_taps_for(const float* w, int flip, int64_t C);
 bool dw_taps_enabled();

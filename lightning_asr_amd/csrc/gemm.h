@@ -36,7 +36,8 @@ int launch_gemm_bf16_multi(const GemmArgs* g, const int* gz, int n, bool big_til
                            int lstm_wgs = 0, const lasr_reduce_desc* riders = nullptr, int n_riders = 0, int* riders_taken = nullptr);
 // gemm.hip: lasr_gemm_multi_split_partials with riders (above)
 int gemm_multi_split_partials_riders(const lasr_gemm_problem* probs, int n_probs, int split_k, float* const* slabs, int* splits,
-                                     const lasr_reduce_desc* riders, int n_riders, int* riders_taken, void* stream);
+                                     const lasr_reduce_desc* riders, int n_riders, int* riders_taken, void* stream, int fixed_split = 0);
+// (fixed_split > 0: that many slices whatever the launch holds - the caller wants the sums' order independent of how a stage is cut)
 // gemm.hip: lasr_gemm(split_k > 1, f32 result) without its final sum: the slabs stay at the head of `workspace`, [*splits][M*N] f32
 int gemm_split_partials_one(const void* A, const void* B, int dtype_ab, int64_t M, int64_t N, int64_t K, int transA, int transB, int split_k,
                             void* workspace, size_t workspace_bytes, int* splits, void* stream);

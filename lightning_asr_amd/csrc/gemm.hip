@@ -503,7 +503,7 @@ extern "C" int lasr_gemm_batch_split_partials(const lasr_gemm_problem* probs, in
 
 static int multi_split_impl(const lasr_gemm_problem* probs, int n_probs, int split_k, float* const* slabs, int* splits, void* stream,
                             const lstm::BwdArgs* lstm_job, int lstm_wgs, const lasr_reduce_desc* riders = nullptr, int n_riders = 0,
-                            int* riders_taken = nullptr);
+                            int* riders_taken = nullptr, int fixed_split = 0);
 
 extern "C" int lasr_gemm_multi_split_partials(const lasr_gemm_problem* probs, int n_probs, int split_k, float* const* slabs,
                                               int* splits, void* stream) {
@@ -511,8 +511,8 @@ extern "C" int lasr_gemm_multi_split_partials(const lasr_gemm_problem* probs, in
 }
 
 int lasr::gemm_multi_split_partials_riders(const lasr_gemm_problem* probs, int n_probs, int split_k, float* const* slabs, int* splits,
-                                           const lasr_reduce_desc* riders, int n_riders, int* riders_taken, void* stream) {
-  return multi_split_impl(probs, n_probs, split_k, slabs, splits, stream, nullptr, 0, riders, n_riders, riders_taken);
+                                           const lasr_reduce_desc* riders, int n_riders, int* riders_taken, void* stream, int fixed_split) {
+  return multi_split_impl(probs, n_probs, split_k, slabs, splits, stream, nullptr, 0, riders, n_riders, riders_taken, fixed_split);
 }
 
 int lasr::gemm_multi_split_partials_with_bilstm_bwd(const lasr_gemm_problem* probs, int n_probs, int* n_taken, int split_k, float* const* slabs, int* splits,
@@ -553,7 +553,8 @@ int lasr::gemm_multi_split_partials_with_bilstm_bwd(const lasr_gemm_problem* pro
 }
 
 static int multi_split_impl(const lasr_gemm_problem* probs, int n_probs, int split_k, float* const* slabs, int* splits, void* stream,
-                            const lstm::BwdArgs* lstm_job, int lstm_wgs, const lasr_reduce_desc* riders, int n_riders, int* riders_taken) {
+                            const lstm::BwdArgs* lstm_job, int lstm_wgs, const lasr_reduce_desc* riders, int n_riders, int* riders_taken,
+                            int fixed_split) {
   if (riders_taken) *riders_taken = 0;
   LASR_CHECK_ARG(probs && slabs && splits && n_probs >= 1 && n_probs <= kMaxMultiProblems && split_k >= 1 && split_k <= 1024,
                  "lasr_gemm_multi_split_partials: bad argument");
@@ -584,6 +585,7 @@ static int multi_split_impl(const lasr_gemm_problem* probs, int n_probs, int spl
   } else {
     split = (int)std::min<int64_t>(std::max<int64_t>(cdiv(1536, tiles_small), 1), split_k);
   }
+  if (fixed_split > 0) split = std::min(fixed_split, split_k);
   for (int i = 0; i < n_probs; ++i) {
     const lasr_gemm_problem& q = probs[i];
     GemmArgs& a = g[i];
@@ -646,17 +648,18 @@ extern "C" int lasr_fold_bn_weights_many(const lasr_fold_desc* descs, int n_desc
 
 extern "C" int lasr_gemm_dual(const void* A1, int64_t K1, const void* A2, int64_t K2, const void* W, const float* bias, void* C,
                               int64_t M, int64_t N, const int32_t* row_lens, int64_t rows_per_seq, int act, void* stream) {
-  LASR_CHECK_ARG(A1 && A2 && W && bias && C, "lasr_gemm_dual: null pointer");
+  LASR_CHECK_ARG(A1 && (A2 || K2 == 0) && W && bias && C, "lasr_gemm_dual: null pointer");
   LASR_CHECK_ARG(!(row_lens && rows_per_seq <= 0), "lasr_gemm_dual: rows_per_seq");
   LASR_CHECK_ARG(act == LASR_ACT_NONE || act == LASR_ACT_RELU || act == LASR_ACT_SWISH, "lasr_gemm_dual: act");
-  LASR_CHECK_SHAPE(M > 0 && N > 0 && K1 > 0 && K2 > 0, "lasr_gemm_dual: shape");
+  LASR_CHECK_SHAPE(M > 0 && N > 0 && K1 > 0 && K2 >= 0, "lasr_gemm_dual: shape");
+  if (K2 == 0) A2 = A1;   // no second operand: every K step lies in [0, K1), A2 is never read
   GemmArgs g;
   g.A = A1; g.B = W; g.C = C; g.M = M; g.N = N; g.K = K1 + K2; g.lda = K1; g.ldb = K1 + K2; g.ldc = N;
   g.bias = bias; g.addend = nullptr; g.row_lens = row_lens; g.rows_per_seq = rows_per_seq; g.stat_partials = nullptr; g.split_ws = nullptr;
   g.k_per_split = K1 + K2; g.vecA = 1; g.vecB = 1;
   hipStream_t st = as_stream(stream);
   const int tok = prof_begin(LASR_PROF_GEMM, st, 2.0 * (double)M * N * (K1 + K2), (double)(M * (K1 + K2) + N * (K1 + K2) + M * N) * 2);
-  const int rc = launch_gemm_bf16_dual(g, A2, K2, K1, bias, act, st);
+  const int rc = launch_gemm_bf16_dual(g, A2, K2 ? K2 : K1, K1, bias, act, st);
   prof_end(tok, st);
   return rc;
 }

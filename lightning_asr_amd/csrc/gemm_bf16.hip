@@ -1048,7 +1048,7 @@ int launch_gemm_bf16_batch(const GemmArgs* g, const int* gz, int n, int dtype_c,
 }
 
 int launch_gemm_bf16_dual(const GemmArgs& g, const void* A2, int64_t lda2, int64_t K1, const float* bias, int act, hipStream_t st) {
-  if (K1 <= 0 || K1 >= g.K || K1 % TK || (g.K - K1) % TK || lda2 % 8 || g.lda % 8 || g.ldb % 8 || g.ldc % 8 ||
+  if (K1 <= 0 || K1 > g.K || K1 % TK || (g.K - K1) % TK || lda2 % 8 || g.lda % 8 || g.ldb % 8 || g.ldc % 8 ||
       reinterpret_cast<uintptr_t>(g.A) % 16 || reinterpret_cast<uintptr_t>(A2) % 16 || reinterpret_cast<uintptr_t>(g.B) % 16 ||
       reinterpret_cast<uintptr_t>(g.C) % 16 || !bias)
     return fail(LASR_E_SHAPE, "lasr_gemm_dual: K parts must be multiples of %d, pitches of 8, pointers 16-byte aligned, bias given", TK);

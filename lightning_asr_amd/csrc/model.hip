@@ -40,6 +40,11 @@ struct Unit {
   std::string rx_fwd, rx_bwd;     // roctx range names "lasr:fwd <tap>" / "lasr:bwd <tap>" (made once, at model creation)
   int ci = 0, co = 0, k = 0, stride = 1;
   bool has_dw = false, has_res = false, masked = false, act = true, has_se = false, ctx_before = false;
+  // Blocks of several units (QuartNet105): `inner` = a sub-unit before the closing one (no residual branch of its own);
+  // res_src = the block's first sub-unit, whose INPUT the closing unit's residual branch reads (-1: the unit's own input);
+  // res_sink = that first sub-unit: its depthwise data gradient takes the closing unit's residual data gradient as addend
+  bool inner = false, res_sink = false;
+  int res_src = -1;
   int64_t w_dw = -1, w_pw = -1, w_res = -1, w_se1 = -1, w_se2 = -1;
   BnRef bn, bn_res;
   // workspace offsets (bytes) filled by plan()
@@ -88,6 +93,9 @@ struct lasr_model {
   int bwd_cur = 0;       // ping-pong index of the gradient buffers between partial backward calls
   bool taps_valid = false;   // the workspace holds this step's depthwise tap tables (made by the last training forward)
   int bwd_next = -1;     // next unit a lasr_model_backward_continue call would process (-1: nothing pending)
+  // a closing sub-unit's residual data gradient dxr = dy2 Wr waits at o_dxr for its block's first sub-unit (carried between partial
+  // backward calls like bwd_cur: only one block is in flight at a time, and nothing between the two units writes o_dxr)
+  bool bwd_res_pending = false;
   // one-shot feature prefetch consumed by the next loss_backward call (lasr_model_set_prefetch)
   struct Prefetch {
     bool armed = false;
@@ -128,9 +136,12 @@ struct lasr_model {
   }
 };
 
+// the BiLSTM context branch in front of block3 (Context / ContextSE)
+static bool has_context(const lasr_model_config& c) { return c.variant == LASR_VARIANT_CONTEXT || c.variant == LASR_VARIANT_CONTEXT_SE; }
+
 static int build_model(lasr_model* m) {
   const lasr_model_config& c = m->cfg;
-  const bool ctx = c.variant != LASR_VARIANT_PLAIN;
+  const bool ctx = has_context(c);
   {  // first_cnn: SeprationConv(in_c, 256, k=33, stride=2)            models/QuartNet.py:129
     Unit u;
     u.tap = "first_cnn"; u.ci = c.in_c; u.co = 256; u.k = 33; u.stride = 2; u.has_dw = true; u.masked = c.mask != 0;
@@ -144,6 +155,35 @@ static int build_model(lasr_model* m) {
                            {"block4", 512, 512, 63}, {"block42", 512, 512, 63}, {"block43", 512, 512, 63},
                            {"block5", 512, 512, 75}};
   if (ctx) blocks.push_back({"block6", 512, 512, 87});
+  if (c.variant == LASR_VARIANT_Q105) {  // QuartNet105: QuartNetBlock(repeat=5) x 10           models/QuartNet.py:175-224
+    blocks = {{"block1", 256, 256, 33}, {"block12", 256, 256, 33}, {"block2", 256, 256, 39}, {"block22", 256, 256, 39},
+              {"block3", 256, 512, 51}, {"block32", 512, 512, 51}, {"block4", 512, 512, 63}, {"block42", 512, 512, 63},
+              {"block5", 512, 512, 75}, {"block52", 512, 512, 75}};
+    for (const B& b : blocks) {
+      const std::string p = std::string("encoder.") + b.name;
+      // state-dict order: reside.0, reside.1.*, seq.0 .. seq.4 (QuartNetBlock.__init__ assigns `reside` before `seq`)
+      const int64_t w_res = m->add_tensor(p + ".reside.0.weight", {b.co, b.ci, 1}, 0);
+      const BnRef bn_res = m->add_bn(p + ".reside.1", b.co);
+      const int first = (int)m->units.size();
+      for (int s = 0; s < 5; ++s) {
+        Unit u;
+        const bool closing = s == 4;
+        u.ci = b.ci; u.co = closing ? b.co : b.ci; u.k = b.k; u.has_dw = true;
+        if (closing) {  // seq.4 = SeprationConv(in, out, k, last=True, mask=mask); out = relu(seq.4(..) + reside(start))
+          u.tap = b.name; u.has_res = true; u.masked = c.mask != 0; u.res_src = first;
+          u.w_res = w_res; u.bn_res = bn_res;
+        } else {
+          // seq.0..3 = SeprationConv(in, in, k, mask, drop_rate=..): the fourth positional argument is `last`, so last = cfg.mask and
+          // the sub-unit's own mask keeps its default True (models/QuartNet.py:60 against :9) - reproduced, not repaired
+          u.tap = std::string(b.name) + ".seq." + std::to_string(s); u.inner = true; u.masked = true; u.act = c.mask == 0;
+          u.res_sink = s == 0;
+        }
+        m->add_sep(u, p + ".seq." + std::to_string(s));
+        m->units.push_back(u);
+      }
+    }
+    blocks.clear();
+  }
   for (const B& b : blocks) {  // QuartNetBlock(repeat=1)                 models/QuartNet.py:55-78
     Unit u;
     u.tap = b.name; u.ci = b.ci; u.co = b.co; u.k = b.k; u.has_dw = true; u.has_res = true; u.masked = c.mask != 0;
@@ -236,7 +276,7 @@ static void make_plan(lasr_model* m, int64_t B, int64_t T_in, int64_t S_max) {
   scratch = std::max(scratch, lasr_gemm_workspace_bytes(C, 1024, 16, 0));
   scratch = std::max(scratch, lasr_gemm_workspace_bytes(N, C, 16, 0));   // decoder forward, split-K partials
   scratch = std::max(scratch, lasr_colsum_workspace_bytes(N, C));
-  if (m->cfg.variant != LASR_VARIANT_PLAIN) {
+  if (has_context(m->cfg)) {
     p.o_cat = take(cur, (size_t)N * 336 * es);
     for (int d = 0; d < 2; ++d) { p.o_gx[d] = take(cur, (size_t)N * 160 * sizeof(float)); p.o_dg[d] = take(cur, (size_t)N * 160 * sizeof(float)); }
     p.o_lstm_saved = take(cur, lasr_bilstm_saved_bytes(B, p.T));
@@ -258,8 +298,8 @@ static void make_plan(lasr_model* m, int64_t B, int64_t T_in, int64_t S_max) {
   p.o_glogits = p.o_logits;
   p.o_nll = take(cur, (size_t)(B + 1) * sizeof(float));
   for (Unit& u : m->units) {   // eval-mode folded weights
-    if (u.has_res) {
-      u.o_wfold = take(cur, (size_t)u.co * 2 * u.ci * sizeof(bf16_t));
+    if (u.has_res || u.inner) {
+      u.o_wfold = take(cur, (size_t)u.co * (u.has_res ? 2 : 1) * u.ci * sizeof(bf16_t));
       u.o_bfold = take(cur, (size_t)u.co * sizeof(float));
     }
   }
@@ -303,7 +343,7 @@ static void make_plan(lasr_model* m, int64_t B, int64_t T_in, int64_t S_max) {
 
 extern "C" int lasr_model_create(const lasr_model_config* cfg, lasr_model_t** out) {
   LASR_CHECK_ARG(cfg && out, "lasr_model_create: null pointer");
-  LASR_CHECK_ARG(cfg->variant >= 0 && cfg->variant <= 2 && cfg->n_class >= 2 && cfg->in_c > 0 && cfg->in_c % 4 == 0,
+  LASR_CHECK_ARG(cfg->variant >= 0 && cfg->variant <= LASR_VARIANT_Q105 && cfg->n_class >= 2 && cfg->in_c > 0 && cfg->in_c % 4 == 0,
                  "lasr_model_create: bad config (variant=%d n_class=%d in_c=%d)", cfg->variant, cfg->n_class, cfg->in_c);
   LASR_CHECK_ARG(cfg->dtype == LASR_F32 || cfg->dtype == LASR_BF16, "lasr_model_create: bad dtype");
   LASR_CHECK_ARG(cfg->act == LASR_ACT_RELU || cfg->act == LASR_ACT_SWISH, "lasr_model_create: bad activation");
@@ -401,7 +441,7 @@ extern "C" int64_t lasr_model_tap(lasr_model_t* m, const char* name, int64_t B, 
     shape[0] = B; shape[1] = p.T; shape[2] = cmax;
     return (int64_t)p.o_g[n == "bwd.g_cur" ? m->bwd_cur : (m->bwd_cur ^ 1)];
   }
-  if (n == "ctx_in" && m->cfg.variant != LASR_VARIANT_PLAIN) { shape[0] = B; shape[1] = p.T; shape[2] = 336; return (int64_t)p.o_cat; }
+  if (n == "ctx_in" && has_context(m->cfg)) { shape[0] = B; shape[1] = p.T; shape[2] = 336; return (int64_t)p.o_cat; }
   if (n == "logits") { shape[0] = B; shape[1] = p.T; shape[2] = m->cfg.n_class; return (int64_t)p.o_logits; }
   if (n == "grad_logits") { shape[0] = B; shape[1] = p.T; shape[2] = m->cfg.n_class; return (int64_t)p.o_glogits; }
   if (n == "lens") { shape[0] = B; shape[1] = 1; shape[2] = 1; return (int64_t)p.o_lens; }
@@ -480,7 +520,7 @@ struct DwTapScope {
     ctx.n = 0;
     if (!valid) return;
     for (const Unit& u : m->units)
-      if (u.o_taps && ctx.n < 16) {
+      if (u.o_taps && ctx.n < kDwTapLayers) {
         ctx.w[ctx.n] = params + u.w_dw; ctx.t[ctx.n] = reinterpret_cast<const uint32_t*>(at(ws, u.o_taps)); ctx.C[ctx.n] = u.ci;
         ++ctx.n;
       }
@@ -496,7 +536,7 @@ static bool eval_fold(int dtype) {
   static const bool off = getenv("LASR_NO_EVAL_FOLD") != nullptr;
   return !off && dtype == LASR_BF16;
 }
-static bool fold_unit(const Unit& u) { return u.has_res && u.has_dw && !u.has_se && !u.ctx_before && u.ci % 64 == 0 && u.co % 8 == 0; }
+static bool fold_unit(const Unit& u) { return (u.has_res || u.inner) && u.has_dw && !u.has_se && !u.ctx_before && u.ci % 64 == 0 && u.co % 8 == 0; }
 
 // The start of a forward: the lengths (and the dropout masks' step counter), the weights' bf16 shadow, the tap tables (m->taps_valid)
 static int forward_prologue(const StepArgs& a, const float* pct) {
@@ -512,7 +552,7 @@ static int forward_prologue(const StepArgs& a, const float* pct) {
     DwTapJobs jobs;                                       // the depthwise tap tables ride in the same launch (training and eval forwards)
     jobs.n = 0; jobs.blk0[0] = 0;
     for (const Unit& u : m->units)
-      if (u.o_taps && jobs.n < 16) {
+      if (u.o_taps && jobs.n < kDwTapLayers) {
         jobs.w[jobs.n] = a.params + u.w_dw; jobs.out[jobs.n] = reinterpret_cast<uint32_t*>(at(a.ws, u.o_taps)); jobs.C[jobs.n] = u.ci; jobs.k[jobs.n] = u.k;
         jobs.blk0[jobs.n + 1] = jobs.blk0[jobs.n] + (int)cdiv((int64_t)2 * u.ci * kDwTapRow, 256);
         ++jobs.n;
@@ -543,7 +583,8 @@ static int eval_coefficients(const StepArgs& a) {
     std::vector<lasr_fold_desc> fd;
     for (const Unit& u : m->units)
       if (fold_unit(u))
-        fd.push_back({a.params + u.w_pw, a.params + u.w_res, atf(a.ws, u.o_coef), atf(a.ws, u.o_coef2), at(a.ws, u.o_wfold), atf(a.ws, u.o_bfold), u.co, u.ci});
+        fd.push_back({a.params + u.w_pw, u.has_res ? a.params + u.w_res : nullptr, atf(a.ws, u.o_coef), u.has_res ? atf(a.ws, u.o_coef2) : nullptr,
+                      at(a.ws, u.o_wfold), atf(a.ws, u.o_bfold), u.co, u.ci});   // (a block's inner units: no residual side)
     for (size_t i = 0; i < fd.size(); i += 32)
       LASR_TRY(lasr_fold_bn_weights_many(fd.data() + i, (int)std::min<size_t>(32, fd.size() - i), a.stream));
   }
@@ -648,6 +689,8 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
       x = at(ws, p.o_cat);
     }
     const void* gin = x;
+    // what the residual branch reads: the unit's own input, or the input of its block's first sub-unit
+    const void* xr = u.res_src < 0 ? x : at(ws, m->units[u.res_src - 1].o_out);
     if (u.has_dw) {
       bool fused = false;
       if (pend) {
@@ -663,7 +706,8 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
     if (!training && eval_fold(dt) && fold_unit(u)) {
       // out = act([mask(u) | x] . [a W | a2 Wr]^T + (b + b2)): the unit's two 1x1 convs, both BatchNorms, the residual add and
       // the activation as ONE GEMM (no y / y2 round trip, no BN pass)
-      LASR_TRY(lasr_gemm_dual(gin, u.ci, x, u.ci, at(ws, u.o_wfold), atf(ws, u.o_bfold), at(ws, u.o_out), N, u.co, u.masked ? lens : nullptr,
+      // (a block's inner units have no residual side: out = act(mask(u) . (a W)^T + b))
+      LASR_TRY(lasr_gemm_dual(gin, u.ci, u.has_res ? xr : nullptr, u.has_res ? u.ci : 0, at(ws, u.o_wfold), atf(ws, u.o_bfold), at(ws, u.o_out), N, u.co, u.masked ? lens : nullptr,
                               T, u.act ? m->cfg.act : LASR_ACT_NONE, stream));
       x = at(ws, u.o_out);
       Tx = T;
@@ -675,7 +719,7 @@ static int forward_impl(lasr_model_t* m, const float* params, float* buffers, co
       const int np = unit_bn_branches(u, params, buffers, ws, br);
       lasr_gemm_problem pr[2];
       pr[0] = {gin, wptr(m, params, ws, u.w_pw), at(ws, u.o_y), N, u.co, u.ci, nullptr, u.masked ? lens : nullptr, T, training ? br[0].stats : nullptr};
-      if (u.has_res) pr[1] = {x, wptr(m, params, ws, u.w_res), at(ws, u.o_y2), N, u.co, u.ci, nullptr, nullptr, 0, training ? br[1].stats : nullptr};
+      if (u.has_res) pr[1] = {xr, wptr(m, params, ws, u.w_res), at(ws, u.o_y2), N, u.co, u.ci, nullptr, nullptr, 0, training ? br[1].stats : nullptr};
       if (training && !no_fuse()) {
         // the epilogue's per-tile BN sums go straight to ONE reduce+finalize launch for both branches
         const float* parts[2] = {nullptr, nullptr};
@@ -742,9 +786,10 @@ extern "C" int lasr_model_forward(lasr_model_t* m, const float* params, float* b
 struct StageLaunch {
   static constexpr int kMaxProblems = kMaxMultiProblems, kMaxSegments = kMaxReduceSegments;
   void* stream;
+  int fixed_split = 0;   // > 0: every launch cuts K into that many slices (wgrad_fixed_split below); 0: the library picks per launch
   int wgrads(const lasr_gemm_problem* probs, int n, float* const* slabs, int* splits, const lasr_reduce_desc* riders, int n_riders, int* taken) const {
     // wgrad_split(): the cap the slabs were sized for; the library picks the slice count for its tile form
-    return gemm_multi_split_partials_riders(probs, n, wgrad_split(), slabs, splits, riders, n_riders, taken, stream);
+    return gemm_multi_split_partials_riders(probs, n, wgrad_split(), slabs, splits, riders, n_riders, taken, stream, fixed_split);
   }
   int reduce(const lasr_reduce_desc* descs, int n, bool closing) const {
     if (!closing) return lasr_reduce_many(descs, n, stream);
@@ -754,6 +799,16 @@ struct StageLaunch {
     return lasr_reduce_many(descs, n, stream);
   }
 };
+
+// QuartNet105: a whole-model backward holds more 1x1 weight-gradient problems (62) than one launch takes (kMaxMultiProblems), so
+// where the launches are cut depends on where the stages are - and a slice count picked per launch would make the gradients' bits
+// depend on the staging (a data-parallel run's buckets against a single-GPU run).  There the slice count follows K = B T' alone:
+// one slice per 8192 rows (2 at the cfg2 shape, where a two-bucket stage's launches hold 100-130 tiles of 256 x 256: one round).
+// The other variants keep the per-launch choice (0), and with it their bits.
+static int wgrad_fixed_split(const lasr_model* m, int64_t N) {
+  if (m->cfg.variant != LASR_VARIANT_Q105) return 0;
+  return (int)std::min<int64_t>(std::max<int64_t>(cdiv(N, 8192), 1), wgrad_split());
+}
 
 // Split-K slices of the decoder's weight gradient dW = gl^T h ([C][1024], K = N rows) on the 128 x 128 tile (two workgroups
 // per CU): rounds of resident workgroups x K steps per slice, against the f32 slabs every slice writes and the reduction reads
@@ -903,19 +958,20 @@ static int backward_from_glogits(lasr_model* m, const float* params, const void*
   float* tail_loss = m->tail_loss;
   m->tail_nll = nullptr; m->tail_loss = nullptr;
   if (with_head) LASR_TRY(decoder_bwd(sa, tail_nll, tail_loss));
-  if (with_head) cur = 0;
+  if (with_head) { cur = 0; m->bwd_res_pending = false; }
   if (unit_hi < 0) unit_hi = (int)m->units.size() - 1;
   // The "sum the partial slabs" tails of the weight-gradient kernels are collected and issued as ONE launch when
   // the stage ends (27 launches of ~5 us each off the step; LASR_NO_FUSE=1 keeps them inline for A/B runs).
   static const bool no_defer = getenv("LASR_NO_DEFER") != nullptr;
   const bool defer = !no_fuse() && !no_defer;
-  StageGrads<StageLaunch> sg(StageLaunch{stream});
+  StageGrads<StageLaunch> sg(StageLaunch{stream, wgrad_fixed_split(m, N)});
   RoctxRange rr_bwd("lasr:backward");
   for (int ui = unit_hi; ui >= unit_stop; --ui) {
     RoctxRange rr_unit(m->units[ui].rx_bwd.c_str());
     const Unit& u = m->units[ui];
     const void* x_in = ui > 0 ? at(ws, m->units[ui - 1].o_out) : feats;
     if (u.ctx_before) x_in = at(ws, p.o_cat);
+    const void* x_res = u.res_src < 0 ? x_in : at(ws, m->units[u.res_src - 1].o_out);   // the residual branch's input (Unit::res_src)
     const int64_t Tx = ui > 0 ? T : T_in;
     void* dout = at(ws, p.o_g[cur]);
     // weight-gradient GEMMs batched per stage (the multi-problem kernel loads 16-byte operand rows)
@@ -948,7 +1004,7 @@ static int backward_from_glogits(lasr_model* m, const float* params, const void*
     {
       lasr_gemm_problem pr[2];
       pr[0] = {dy, gin, grads + u.w_pw, u.co, u.ci, N, nullptr, nullptr, 0, nullptr};
-      if (u.has_res) pr[1] = {dy2, x_in, grads + u.w_res, u.co, u.ci, N, nullptr, nullptr, 0, nullptr};
+      if (u.has_res) pr[1] = {dy2, x_res, grads + u.w_res, u.co, u.ci, N, nullptr, nullptr, 0, nullptr};
       float* const slab[2] = {atf(ws, u.o_wgp), atf(ws, u.o_wgp) + u.wgp_bytes / (2 * sizeof(float))};
       if (defer_w) LASR_TRY(sg.add_wgrads(pr, u.has_res ? 2 : 1, slab));
       else LASR_TRY(lasr_gemm_batch(pr, u.has_res ? 2 : 1, dt, LASR_F32, 1, 1, wgrad_split(), scratch, sb, stream));
@@ -962,11 +1018,21 @@ static int backward_from_glogits(lasr_model* m, const float* params, const void*
       const bool with_res = u.has_res && need_dx;
       if (with_res) pr[1] = {dy2, wptr(m, params, ws, u.w_res), at(ws, p.o_dxr), N, u.ci, u.co, nullptr, nullptr, 0, nullptr};
       LASR_TRY(lasr_gemm_batch(pr, with_res ? 2 : 1, dt, dt, 0, 1, 1, scratch, sb, stream));
+      // Where dxr joins the data gradient: in this unit's own depthwise data gradient when the residual branch read this unit's
+      // input; a closing sub-unit leaves it at o_dxr for its block's first sub-unit (res_sink), whatever call that unit runs in
+      const void* dxr = nullptr;
+      if (u.has_res && u.res_src < 0) dxr = at(ws, p.o_dxr);
+      if (u.has_res && u.res_src >= 0) m->bwd_res_pending = true;
+      if (u.res_sink) {
+        if (!m->bwd_res_pending) return fail(LASR_E_ARG, "lasr_model backward: %s has no residual gradient waiting", u.tap.c_str());
+        dxr = at(ws, p.o_dxr);
+        m->bwd_res_pending = false;
+      }
       // depthwise dW from (x, du); dx = flipped depthwise conv of du (+ residual dx)
       const bool fused_dw = defer && need_dx && u.stride == 1;   // both in one launch (falls back inside for other dtypes / shapes)
       int npart = 0;
       if (fused_dw)
-        LASR_TRY(lasr_dwconv_bwd_fused(x_in, at(ws, p.o_du), params + u.w_dw, u.has_res ? at(ws, p.o_dxr) : nullptr, dx, dt, B, T, u.ci, u.k,
+        LASR_TRY(lasr_dwconv_bwd_fused(x_in, at(ws, p.o_du), params + u.w_dw, dxr, dx, dt, B, T, u.ci, u.k,
                                        at(ws, u.o_dwp), u.dwp_bytes, &npart, stream));
       else if (defer)
         LASR_TRY(lasr_dwconv_wgrad_partials(x_in, at(ws, p.o_du), dt, B, Tx, u.ci, u.k, u.stride, at(ws, u.o_dwp), u.dwp_bytes, &npart, stream));
@@ -975,7 +1041,7 @@ static int backward_from_glogits(lasr_model* m, const float* params, const void*
       if (defer) LASR_TRY(sg.add_reduction({atf(ws, u.o_dwp), grads + u.w_dw, u.ci * (int64_t)u.k, npart}));
       LASR_TRY(sg.relieve());
       if (need_dx && !fused_dw)
-        LASR_TRY(lasr_dwconv_fwd(at(ws, p.o_du), params + u.w_dw, u.has_res ? at(ws, p.o_dxr) : nullptr, dx, dt, B, T, u.ci, u.k, 1,
+        LASR_TRY(lasr_dwconv_fwd(at(ws, p.o_du), params + u.w_dw, dxr, dx, dt, B, T, u.ci, u.k, 1,
                                  1, stream));
     } else if (need_dx) {
       if (u.has_res)

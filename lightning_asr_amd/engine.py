@@ -349,7 +349,8 @@ class NativeModel:
             n_buckets = int(os.environ.get("LASR_DP_BUCKETS", "2"))
         names = self.unit_names()
         bounds = self.bucket_bounds()                      # [0, |first_cnn|, |256 blocks|, |512 blocks|, n]
-        first512 = next(i for i, n in enumerate(names) if n == "block3")
+        # a stage ends at a block's FIRST unit (q105: "block3.seq.0"; "block3" itself is that block's closing unit there)
+        first512 = next(i for i, n in enumerate(names) if n == "block3" or n.startswith("block3."))
         last = len(names) - 1                              # last_cnn2 (+ decoder head)
         if n_buckets <= 1:
             return [(0, [(0, self.n_param)])]

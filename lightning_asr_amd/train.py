@@ -21,7 +21,7 @@ from .utils.asr_metrics import WER
 
 logger = logging.getLogger(__name__)
 
-MODEL_FILES = {"plain": "QuartNet", "context": "QuartNetContext", "context_se": "QuartNetContextSE"}
+MODEL_FILES = {"plain": "QuartNet", "context": "QuartNetContext", "context_se": "QuartNetContextSE", "q105": "QuartNet105"}
 
 
 def _model_class(variant: str):
