@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 117   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 118   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
@@ -41,7 +41,8 @@ extern "C" {
                               114: lasr_grad_accumulate / lasr_grad_accumulate_ranges (gradient accumulation over micro-batches)
                               115: lasr_bn_tail / lasr_bn_side / lasr_se_side: the BN entry points take one record; the _drop twins are gone
                               116: lasr_ema_state_bytes / lasr_ema_state_init / lasr_novograd_step_ema / lasr_ema_update (weight EMA)
-                              117: lasr_clip_state_bytes / lasr_clip_state_init / lasr_novograd_step_clip (gradient clipping, non-finite guard) */
+                              117: lasr_clip_state_bytes / lasr_clip_state_init / lasr_novograd_step_clip (gradient clipping, non-finite guard)
+                              118: lasr_ctc_beam_stream_* (resumable beam search: a sequence decoded chunk by chunk) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -647,6 +648,50 @@ int lasr_ctc_beam_decode_lm_bias(const float* logp, const int32_t* lens, int64_t
                                  float alpha, float beta, const void* bias_image, int32_t* tokens, int32_t* n_tokens,
                                  float* scores, float* am_scores, float* bias_scores, void* workspace, size_t workspace_bytes,
                                  void* stream);
+
+/* The resumable form of the five searches above: one sequence per stream, fed chunk by chunk.
+ * CONTRACT: decoding a sequence in chunks of any sizes gives, after the last feed, the same tokens, n_tokens and f32 scores
+ * (am_scores / bias_scores included) as the one-shot call of the same kind on the concatenated frames, bit for bit; and after
+ * every feed the outputs are those of the one-shot call on the frames fed so far, end-of-utterance terms included (</s>, the
+ * word LM's last word, the hotword give-back).  There is no finish call: the last feed's outputs are the result.
+ *
+ * The state lives in a caller-owned device buffer of lasr_ctc_beam_stream_state_bytes(B, T_cap, beam_width, kind): per stream
+ * a 64-byte header (frames searched, live entries, which half of the beam is current, frames dropped, a live flag), an image
+ * of the search kernel's LDS record for that kind (under 64 KB) and the prefix trie of 1 + T_cap * beam_width nodes.  The
+ * buffer must be 16-byte aligned.  lasr_ctc_beam_stream_reset makes the streams listed in rows (DEVICE int32, n_rows of them;
+ * NULL, 0: every stream; a row outside [0, B) is skipped) the empty prefix again: one launch, it reads no image, and it is also
+ * how a fresh buffer is initialised.  B, T_cap, beam_width and kind describe the buffer and must be those of every feed.
+ *
+ * lasr_ctc_beam_stream_feed: logp (B, T_chunk, C) holds the next frames of each stream, lens (B) how many of them (NULL =
+ * T_chunk, clamped to [0, T_chunk]; 0 = idle: the stream keeps its state and its outputs are rewritten).  scorer selects the
+ * search and carries what that search takes beside the common arguments (unused fields are ignored); the images, alpha and
+ * beta MUST NOT change between a reset and the last feed of a stream, nor may beam_width, cutoff_top_n, cutoff_prob, C or
+ * blank: the saved state refers to them.  tokens (B, n_best, T_cap), n_tokens / scores (and scorer->am_scores / bias_scores)
+ * (B, n_best) as in the one-shot calls; n_frames (B): frames searched so far; n_dropped (B): frames fed beyond T_cap, which are
+ * counted and not searched (the device clamps; this is no error).  The workspace, lasr_ctc_beam_stream_workspace_bytes, holds
+ * the kept lists of one chunk only.  A wrong LM or hotword image gives empty slots and leaves the state as it is.
+ * Checks before any launch, as the one-shot calls: LASR_E_ARG for a null pointer (scorer, state, outputs, n_frames, n_dropped,
+ * the images and score outputs the kind needs), an unknown kind, n_best outside [1, beam_width], cutoff_prob outside (0, 1],
+ * blank outside [0, C), alpha / beta not finite; LASR_E_SHAPE outside the one-shot ranges for (B, T_chunk, C) or (B, T_cap)
+ * (the size functions return 0 there); LASR_E_WORKSPACE for a state buffer or workspace too small.  A feed is two launches on
+ * `stream`, nothing allocated or synchronised; it can be captured into a graph, and every replay advances the state. */
+enum { LASR_BEAM_PLAIN = 0, LASR_BEAM_LM = 1, LASR_BEAM_WLM = 2, LASR_BEAM_BIAS = 3, LASR_BEAM_LM_BIAS = 4 };
+typedef struct {
+  int kind;                 /* LASR_BEAM_*: lasr_ctc_beam_decode, _lm, _wlm, _bias, _lm_bias */
+  const void* lm_image;     /* LM, WLM, LM_BIAS */
+  float alpha, beta;        /* LM, WLM, LM_BIAS */
+  const void* bias_image;   /* BIAS, LM_BIAS */
+  float* am_scores;         /* every kind but PLAIN */
+  float* bias_scores;       /* BIAS, LM_BIAS */
+} lasr_beam_scorer;
+size_t lasr_ctc_beam_stream_state_bytes(int64_t B, int64_t T_cap, int beam_width, int kind);
+size_t lasr_ctc_beam_stream_workspace_bytes(int64_t B, int64_t T_chunk, int64_t C, int beam_width, int cutoff_top_n);
+int lasr_ctc_beam_stream_reset(void* state, size_t state_bytes, int64_t B, int64_t T_cap, int beam_width, int kind,
+                               const int32_t* rows, int n_rows, void* stream);
+int lasr_ctc_beam_stream_feed(const float* logp, const int32_t* lens, int64_t B, int64_t T_chunk, int64_t C, int blank,
+                              int beam_width, int cutoff_top_n, float cutoff_prob, int n_best, const lasr_beam_scorer* scorer,
+                              void* state, size_t state_bytes, int64_t T_cap, int32_t* tokens, int32_t* n_tokens, float* scores,
+                              int32_t* n_frames, int32_t* n_dropped, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- optimiser ----------------
  * scheduler/novograd.py:75-145 with betas=(0.8,0.5), eps=1e-8, no amsgrad/grad_averaging/luc

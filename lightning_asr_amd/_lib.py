@@ -64,6 +64,15 @@ DW_WGRAD = ("strided", "valu", "mfma")
 DW_BWD = ("two_launches", "two_kind", "uni32", "uni64")
 
 
+BEAM_PLAIN, BEAM_LM, BEAM_WLM, BEAM_BIAS, BEAM_LM_BIAS = range(5)      # LASR_BEAM_*: the search a stream runs
+
+
+class BeamScorer(C.Structure):
+    """lasr_beam_scorer: the kind of search of lasr_ctc_beam_stream_feed and what that kind takes beside the common arguments"""
+    _fields_ = [("kind", C.c_int), ("lm_image", C.c_void_p), ("alpha", C.c_float), ("beta", C.c_float), ("bias_image", C.c_void_p),
+                ("am_scores", C.c_void_p), ("bias_scores", C.c_void_p)]
+
+
 class ModelConfig(C.Structure):
     _fields_ = [("variant", C.c_int32), ("n_class", C.c_int32), ("in_c", C.c_int32),
                 ("mask", C.c_int32), ("act", C.c_int32), ("dtype", C.c_int32)]
@@ -149,6 +158,11 @@ SIGNATURES = {
     "lasr_ctc_beam_decode_bias": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "lasr_ctc_beam_decode_lm_bias": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _p, _f32, _f32, _p, _p, _p, _p, _p,
                                             _p, _p, _sz, _p]),
+    "lasr_ctc_beam_stream_state_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "lasr_ctc_beam_stream_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32]),
+    "lasr_ctc_beam_stream_reset": (_i32, [_p, _sz, _i64, _i64, _i32, _i32, _p, _i32, _p]),
+    "lasr_ctc_beam_stream_feed": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, C.POINTER(BeamScorer), _p, _sz, _i64,
+                                         _p, _p, _p, _p, _p, _p, _sz, _p]),
     "lasr_novograd_workspace_bytes": (_sz, [_i64, _i64]),
     "lasr_novograd_step": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p, _f32, _f32, _f32, _f32, _f32, _p, _sz, _p]),
     "lasr_novograd_step_keep": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p, _f32, _f32, _f32, _f32, _f32, _p, _sz, _p]),

@@ -113,6 +113,16 @@ class BeamSearchDecoderWithLM(torch.nn.Module):
         return ops.ctc_beam_decode(lp, lens, len(self.vocab), self.beam_width, self.cutoff_top_n, self.cutoff_prob,
                                    n_best) + (None,)
 
+    def open_stream(self, n_streams: int = 1, t_cap: int = 3000, n_best: int = 1) -> ops.CtcBeamStream:
+        """A resumable search configured like this decoder (LM kind, alpha / beta, hotwords as they are now, widths and cutoffs):
+        ops.CtcBeamStream, whose feed() takes the log-probs chunk by chunk and returns, after every chunk, what search_full
+        returns for the frames so far.  t_cap: the most frames a stream takes between two resets.  A later set_hotwords does
+        not reach a stream that is already open."""
+        return ops.CtcBeamStream(n_streams, len(self.vocab) + 1, len(self.vocab), self.beam_width, self.cutoff_top_n, self.cutoff_prob,
+                                 n_best, t_cap, lm=self.scorer, bank=self.hotwords,
+                                 alpha=None if self.scorer is None else self.alpha,
+                                 beta=None if self.scorer is None else self.beta, device=self.device)
+
     def _text(self, toks) -> str:
         return "".join(self.vocab[int(c)] for c in toks)
 

@@ -1064,15 +1064,66 @@ struct WlmScorer {
 
 static_assert(sizeof(BeamLmBiasLds) < 64 * 1024 && sizeof(WlmScorer::Lds) < 64 * 1024, "static LDS of the widest searches");
 
+// ------------------------------------------------------------------ the search: one-shot or resumable ------------------
+// What a search does with its state between two launches is a Mode policy beside the Scorer.  OneShot: nothing, the beam lives
+// and dies in LDS.  Streamed (lasr_ctc_beam_stream_feed): between two frames the whole state of a search is the scorer's LDS
+// record (values and indices, no pointers), the trie and the registers nbeam and cur; a launch searches the frames of one chunk,
+// and the workgroup loads that state when it starts and stores it when the chunk's last frame is done.  Per stream the
+// caller's buffer holds a StreamHeader, the LDS image and the trie of T_cap frames (stream_layout).
+struct StreamHeader {
+  int32_t t0;         // frames searched so far: the next frame's trie nodes are 1 + t0 * W ..
+  int32_t nbeam, cur;
+  int32_t dropped;    // frames fed beyond T_cap: counted, never searched
+  int32_t live;       // 0: the empty prefix (after a reset); the image and nbeam / cur mean nothing
+  int32_t pad[11];
+};
+static_assert(sizeof(StreamHeader) == 64, "the LDS image behind the header stays 16-byte aligned");
+
+struct OneShot {
+  static constexpr bool kStream = false;
+  struct Args {};
+};
+
+struct Streamed {
+  static constexpr bool kStream = true;
+  struct Args {
+    char* state;                  // stream b: state + b * stride
+    size_t stride, trie_off;      // the image is at sizeof(StreamHeader), the trie at trie_off
+    int64_t T_cap;
+    int32_t* n_frames;
+    int32_t* n_dropped;
+  };
+};
+
+// the LDS record to or from its image, 16 bytes per thread and round (every Lds is a multiple of 8 bytes; the image's size is
+// rounded up to 16, and so is the static LDS allocation's granule)
+template <class Lds, bool kStore>
+__device__ __forceinline__ void stream_copy_lds(Lds& s, char* image, int tid) {
+  constexpr int kWords = (int)(sizeof(Lds) / sizeof(uint32_t));
+  static_assert(sizeof(Lds) % sizeof(uint32_t) == 0, "the LDS record is copied word by word");
+  uint32_t* lds = reinterpret_cast<uint32_t*>(&s);
+  uint32_t* img = reinterpret_cast<uint32_t*>(image);
+  for (int i = tid; i < kWords; i += kSearchThreads) {
+    if constexpr (kStore) img[i] = lds[i];
+    else lds[i] = img[i];
+  }
+}
+
 // ------------------------------------------------------------------ the search: one frame loop -------------------------
 // The kept lists come as kernel parameters of their own, const and __restrict__, not inside BeamIo: only so does the compiler
 // know that a frame's trie stores leave them alone, and the next frame's count, which every thread reads, is prefetched by a
 // scalar load.  As a vector load it is waited for on the spot, and the kept list's prefetch with it.
-template <int J, class Scorer>
+//
+// Mode = Streamed: io.T, io.lens, the kept lists and the scorer's logp are the CHUNK's, frames are indexed locally into them;
+// the trie, the tokens' pitch and the node numbers go by T_cap and the stream's frame count.  Everything a frame computes reads
+// the LDS record, nbeam, cur and that frame's kept list alone, so a sequence cut into chunks anywhere gives the frames the same
+// inputs in the same order as one launch over the whole of it: the same tokens and the same f32 scores, bit for bit.
+template <int J, class Scorer, class Mode = OneShot>
 __global__ __launch_bounds__(kSearchThreads) void beam_search_kernel(const int32_t* __restrict__ kcls_g,
                                                                      const float* __restrict__ klp_g,
                                                                      const int32_t* __restrict__ kn_g, const BeamIo io,
-                                                                     const typename Scorer::Args sargs) {
+                                                                     const typename Scorer::Args sargs,
+                                                                     const typename Mode::Args margs) {
   __shared__ typename Scorer::Lds s;
   BeamCore& core = s.core;
   float* const asc = Scorer::ascore(s);     // acoustic logaddexp(b, nb) of the current beam: core.score itself without a scorer
@@ -1082,12 +1133,42 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_kernel(const int32
   const int blank = io.blank, W = io.W, n_best = io.n_best;
   Scorer sc;
   const bool ok = sc.open(io, sargs);       // a wrong image: no frames, empty slots
-  const int64_t L = !ok ? 0 : io.lens ? min((int64_t)max(io.lens[ub], 0), T) : T;
-  int2* trie = io.trie + ub * (1 + T * (int64_t)W);
+  int64_t L = !ok ? 0 : io.lens ? min((int64_t)max(io.lens[ub], 0), T) : T;
+  int64_t Tout = T;                         // the tokens' pitch and the trie's frames
+  int2* trie;
+  [[maybe_unused]] StreamHeader* hdr = nullptr;
+  [[maybe_unused]] int t0 = 0, dropped = 0;
+  [[maybe_unused]] bool live = false;
+  if constexpr (Mode::kStream) {
+    char* mine = margs.state + (size_t)ub * margs.stride;
+    hdr = reinterpret_cast<StreamHeader*>(mine);
+    trie = reinterpret_cast<int2*>(mine + margs.trie_off);
+    Tout = margs.T_cap;
+    live = hdr->live != 0;
+    if (live) { t0 = min(max(hdr->t0, 0), (int)Tout); dropped = hdr->dropped; }
+    const int64_t room = Tout - t0;         // the device's clamp: frames past T_cap are counted, not searched
+    if (ok && L > room) { dropped += (int)(L - room); L = room; }
+  } else {
+    trie = io.trie + ub * (1 + T * (int64_t)W);
+  }
   BeamFetch pf{kcls_g + ub * T * kBeamMaxTopN, klp_g + ub * T * kBeamMaxTopN, kn_g + ub * T};
-  beam_init_root(core, tid);
-  if (tid == 0) sc.init_root(s);
   int nbeam = 1, cur = 0;
+  bool resumed = false;
+  if constexpr (Mode::kStream) {
+    if (ok && live) {
+      // the record as the last chunk's last frame left it (its histogram zeroed, as beam_init_root leaves it); the barrier
+      // keeps begin_frame's and beam_fetch_frame's stores of this chunk's first frame behind the load
+      stream_copy_lds<typename Scorer::Lds, false>(s, reinterpret_cast<char*>(hdr) + sizeof(StreamHeader), tid);
+      nbeam = min(max(hdr->nbeam, 0), W);
+      cur = hdr->cur & 1;
+      resumed = true;
+      __syncthreads();
+    }
+  }
+  if (!resumed) {
+    beam_init_root(core, tid);
+    if (tid == 0) sc.init_root(s);
+  }
   // the early cutoff's reference, the frame's unpruned blank log-prob, is fetched a frame ahead like the kept list
   [[maybe_unused]] const float* lrow = nullptr;
   [[maybe_unused]] float pblank = 0.f, cut_slack = 0.f;
@@ -1207,7 +1288,9 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_kernel(const int32
       } else {
         const int q = i - nbeam, p = q / nk, k = q - p * nk;
         const int c = core.kcls[k];
-        beam_new_entry(core, cur, nxt, rank, p, c, t, W, trie);
+        int64_t frame = t;                  // the trie numbers its nodes by the utterance's frame, not the chunk's
+        if constexpr (Mode::kStream) frame += t0;
+        beam_new_entry(core, cur, nxt, rank, p, c, frame, W, trie);
         core.nb[nxt][rank] = core.klp[k] + (c == core.last[cur][p] ? core.b[cur][p] : asc[p]);
         sc.new_entry(s, cur, nxt, rank, p, k, c, tid);
       }
@@ -1215,6 +1298,21 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_kernel(const int32
     nbeam = nsel;
     cur = nxt;
     __syncthreads();
+  }
+  if constexpr (Mode::kStream) {
+    // the state after this chunk, before the end phase below touches the record: the re-rank writes core.score, fin and the
+    // cur ^ 1 halves of node / len, none of which a frame reads before writing it, but the image is taken first all the same.
+    // A chunk of no frames leaves the image as it is (a stream that was never fed stays the empty prefix).
+    if (ok && L > 0) stream_copy_lds<typename Scorer::Lds, true>(s, reinterpret_cast<char*>(hdr) + sizeof(StreamHeader), tid);
+    __syncthreads();                        // every thread's header reads and image loads are behind it
+    if (tid == 0) {
+      if (ok) {
+        hdr->t0 = t0 + (int)L; hdr->nbeam = nbeam; hdr->cur = cur; hdr->dropped = dropped;
+        hdr->live = (live || L > 0) ? 1 : 0;
+      }
+      margs.n_frames[ub] = t0 + (int)L;
+      margs.n_dropped[ub] = dropped;
+    }
   }
   // end of utterance: the scorer's final values of each entry, re-ranked where its end term can change the order
   const bool have = ok && tid < nbeam;
@@ -1226,7 +1324,7 @@ __global__ __launch_bounds__(kSearchThreads) void beam_search_kernel(const int32
     if (have) sc.final_scores(s, cur, tid, out);
     src = beam_final_rerank(core, Scorer::fin(s), cur, ok ? nbeam : 0, tid, out);
   }
-  beam_write_back(core, src, nbeam, n_best, T, trie, io.tokens + ub * (int64_t)n_best * T, io.n_tokens + ub * n_best, ok, tid);
+  beam_write_back(core, src, nbeam, n_best, Tout, trie, io.tokens + ub * (int64_t)n_best * Tout, io.n_tokens + ub * n_best, ok, tid);
   if (tid < n_best) {
     const int64_t o = ub * n_best + tid;
     if constexpr (Scorer::kRerank) {
@@ -1289,20 +1387,22 @@ int beam_check_args(const BeamArgs& a, bool ptrs_ok) {
 
 // Checks the shape and the workspace, carves it, launches the prune kernel and then search(J, grid, stream, kc, kl, kn, trie)
 // with J, the candidates per thread, as a std::integral_constant: the caller launches its kernel's instantiation.
+// own_trie: the trie is the caller's (a stream's state holds it); the workspace is then the kept lists alone and `trie` null.
 template <class Search>
-int beam_launch(const BeamArgs& a, const char* search_name, Search search) {
+int beam_launch(const BeamArgs& a, const char* search_name, Search search, bool own_trie = false) {
   LASR_CHECK_SHAPE(beam_shape_ok(a.B, a.T, a.C, a.beam_width, a.cutoff_top_n),
                    "%s: B %lld T %lld C %lld beam_width %d cutoff_top_n %d outside the supported range "
                    "(C <= %d, beam_width 1..%d, cutoff_top_n 1..%d)", a.who, (long long)a.B, (long long)a.T, (long long)a.C,
                    a.beam_width, a.cutoff_top_n, kBeamMaxClasses, kBeamMaxWidth, kBeamMaxTopN);
   const BeamWs w = beam_ws(a.B, a.T, a.beam_width);
-  if (a.workspace_bytes < w.total)
-    return fail(LASR_E_WORKSPACE, "%s: workspace %zu < %zu bytes", a.who, a.workspace_bytes, w.total);
+  const size_t need = own_trie ? w.trie : w.total;
+  if (a.workspace_bytes < need)
+    return fail(LASR_E_WORKSPACE, "%s: workspace %zu < %zu bytes", a.who, a.workspace_bytes, need);
   char* ws = static_cast<char*>(a.workspace);
   int32_t* kc = reinterpret_cast<int32_t*>(ws + w.kcls);
   float* kl = reinterpret_cast<float*>(ws + w.klp);
   int32_t* kn = reinterpret_cast<int32_t*>(ws + w.kn);
-  int2* trie = reinterpret_cast<int2*>(ws + w.trie);
+  int2* trie = own_trie ? nullptr : reinterpret_cast<int2*>(ws + w.trie);
   hipStream_t st = as_stream(a.stream);
   hipLaunchKernelGGL(beam_prune_kernel, dim3((unsigned)(a.B * a.T)), dim3(64), 0, st, a.logp, a.lens, a.T, (int)a.C,
                      a.cutoff_top_n, a.cutoff_prob, kc, kl, kn);
@@ -1330,8 +1430,70 @@ int beam_decode(const BeamArgs& a, const typename Scorer::Args& sargs, int32_t* 
                    (double)sargs.alpha, (double)sargs.beta);
   return beam_launch(a, Scorer::kName, [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2* trie) {
     const BeamIo io{a.lens, a.T, (int)a.C, a.blank, a.beam_width, a.n_best, trie, tokens, n_tokens, scores};
-    hipLaunchKernelGGL((beam_search_kernel<decltype(j)::value, Scorer>), grid, dim3(kSearchThreads), 0, st, kc, kl, kn, io, sargs);
+    hipLaunchKernelGGL((beam_search_kernel<decltype(j)::value, Scorer>), grid, dim3(kSearchThreads), 0, st, kc, kl, kn, io, sargs,
+                       OneShot::Args{});
   });
+}
+
+// ------------------------------------------------------------------ host side: streams ---------------------------------
+// A stream's share of the caller's state buffer: header, LDS image of the kind's scorer, trie of T_cap frames.
+struct StreamLayout {
+  size_t trie, stride;
+};
+
+size_t stream_lds_bytes(int kind) {
+  switch (kind) {
+    case LASR_BEAM_PLAIN: return sizeof(NullScorer::Lds);
+    case LASR_BEAM_LM: return sizeof(LmScorer<false>::Lds);
+    case LASR_BEAM_WLM: return sizeof(WlmScorer::Lds);
+    case LASR_BEAM_BIAS: return sizeof(BiasScorer::Lds);
+    case LASR_BEAM_LM_BIAS: return sizeof(LmScorer<true>::Lds);
+    default: return 0;
+  }
+}
+
+bool stream_shape_ok(int64_t B, int64_t T_cap, int W, int kind) {
+  return stream_lds_bytes(kind) != 0 && beam_shape_ok(B, T_cap, 1, W, 1);
+}
+
+StreamLayout stream_layout(int64_t T_cap, int W, int kind) {
+  StreamLayout l;
+  l.trie = align_up(sizeof(StreamHeader) + stream_lds_bytes(kind), 256);
+  l.stride = align_up(l.trie + (size_t)(1 + T_cap * (int64_t)W) * sizeof(int2), 256);
+  return l;
+}
+
+__global__ void beam_stream_reset_kernel(char* state, size_t stride, int64_t B, const int32_t* __restrict__ rows, int n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t b = rows ? (int64_t)rows[i] : i;
+  if (b < 0 || b >= B) return;              // a row outside the buffer resets nothing
+  StreamHeader* h = reinterpret_cast<StreamHeader*>(state + (size_t)b * stride);
+  h->t0 = 0; h->nbeam = 1; h->cur = 0; h->dropped = 0; h->live = 0;
+}
+
+// what lasr_ctc_beam_stream_feed does once the kind has chosen Scorer: beam_decode's checks with the stream's own, then the
+// prune launch over the chunk and the Streamed search
+template <class Scorer>
+int beam_stream_feed(const BeamArgs& a, const typename Scorer::Args& sargs, void* state, size_t state_bytes, int64_t T_cap, int kind,
+                     int32_t* tokens, int32_t* n_tokens, float* scores, int32_t* n_frames, int32_t* n_dropped) {
+  LASR_TRY(beam_check_args(a, a.logp && tokens && n_tokens && scores && n_frames && n_dropped && state && a.workspace &&
+                                  Scorer::args_set(sargs)));
+  if constexpr (std::is_same_v<typename Scorer::Args, LmArgs>)
+    LASR_CHECK_ARG(std::isfinite(sargs.alpha) && std::isfinite(sargs.beta), "%s: alpha %g / beta %g not finite", a.who,
+                   (double)sargs.alpha, (double)sargs.beta);
+  LASR_CHECK_SHAPE(stream_shape_ok(a.B, T_cap, a.beam_width, kind),
+                   "%s: B %lld T_cap %lld beam_width %d outside the supported range (beam_width 1..%d, 1 + T_cap * beam_width < 2^31)",
+                   a.who, (long long)a.B, (long long)T_cap, a.beam_width, kBeamMaxWidth);
+  const StreamLayout l = stream_layout(T_cap, a.beam_width, kind);
+  if (state_bytes < (size_t)a.B * l.stride)
+    return fail(LASR_E_WORKSPACE, "%s: state %zu < %zu bytes", a.who, state_bytes, (size_t)a.B * l.stride);
+  return beam_launch(a, Scorer::kName, [&](auto j, dim3 grid, hipStream_t st, int32_t* kc, float* kl, int32_t* kn, int2*) {
+    const BeamIo io{a.lens, a.T, (int)a.C, a.blank, a.beam_width, a.n_best, nullptr, tokens, n_tokens, scores};
+    const Streamed::Args m{static_cast<char*>(state), l.stride, l.trie, T_cap, n_frames, n_dropped};
+    hipLaunchKernelGGL((beam_search_kernel<decltype(j)::value, Scorer, Streamed>), grid, dim3(kSearchThreads), 0, st, kc, kl, kn, io,
+                       sargs, m);
+  }, true);
 }
 
 struct ArpaHandle {
@@ -1409,6 +1571,63 @@ extern "C" int lasr_ctc_beam_decode_lm_bias(const float* logp, const int32_t* le
   const BeamArgs a{"lasr_ctc_beam_decode_lm_bias", logp, lens, B, T, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best, workspace,
                    workspace_bytes, stream};
   return beam_decode<LmScorer<true>>(a, {logp, lm_image, alpha, beta, am_scores, bias_image, bias_scores}, tokens, n_tokens, scores);
+}
+
+// ------------------------------------------------------------------ the C ABI: resumable search ------------------------
+extern "C" size_t lasr_ctc_beam_stream_state_bytes(int64_t B, int64_t T_cap, int beam_width, int kind) {
+  if (!stream_shape_ok(B, T_cap, beam_width, kind)) return 0;
+  return (size_t)B * stream_layout(T_cap, beam_width, kind).stride;
+}
+
+extern "C" size_t lasr_ctc_beam_stream_workspace_bytes(int64_t B, int64_t T_chunk, int64_t C, int beam_width, int cutoff_top_n) {
+  if (!beam_shape_ok(B, T_chunk, C, beam_width, cutoff_top_n)) return 0;
+  return beam_ws(B, T_chunk, beam_width).trie;      // the kept lists of one chunk; the trie is part of the state
+}
+
+extern "C" int lasr_ctc_beam_stream_reset(void* state, size_t state_bytes, int64_t B, int64_t T_cap, int beam_width, int kind,
+                                          const int32_t* rows, int n_rows, void* stream) {
+  const char* who = "lasr_ctc_beam_stream_reset";
+  LASR_CHECK_ARG(state, "%s: null pointer", who);
+  LASR_CHECK_ARG(n_rows >= 0 && (rows || n_rows == 0), "%s: n_rows %d without rows, or negative", who, n_rows);
+  LASR_CHECK_SHAPE(stream_shape_ok(B, T_cap, beam_width, kind),
+                   "%s: B %lld T_cap %lld beam_width %d kind %d outside the supported range (beam_width 1..%d, 1 + T_cap * "
+                   "beam_width < 2^31, kind 0..4)", who, (long long)B, (long long)T_cap, beam_width, kind, kBeamMaxWidth);
+  const StreamLayout l = stream_layout(T_cap, beam_width, kind);
+  if (state_bytes < (size_t)B * l.stride)
+    return fail(LASR_E_WORKSPACE, "%s: state %zu < %zu bytes", who, state_bytes, (size_t)B * l.stride);
+  const int n = rows ? n_rows : (int)B;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(beam_stream_reset_kernel, dim3((unsigned)cdiv((int64_t)n, 256)), dim3(256), 0, as_stream(stream),
+                     static_cast<char*>(state), l.stride, B, rows, n);
+  LASR_LAUNCH_CHECK("beam_stream_reset_kernel");
+  return 0;
+}
+
+extern "C" int lasr_ctc_beam_stream_feed(const float* logp, const int32_t* lens, int64_t B, int64_t T_chunk, int64_t C, int blank,
+                                         int beam_width, int cutoff_top_n, float cutoff_prob, int n_best,
+                                         const lasr_beam_scorer* scorer, void* state, size_t state_bytes, int64_t T_cap,
+                                         int32_t* tokens, int32_t* n_tokens, float* scores, int32_t* n_frames, int32_t* n_dropped,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  const BeamArgs a{"lasr_ctc_beam_stream_feed", logp, lens, B, T_chunk, C, blank, beam_width, cutoff_top_n, cutoff_prob, n_best,
+                   workspace, workspace_bytes, stream};
+  LASR_CHECK_ARG(scorer, "%s: null pointer", a.who);
+  const lasr_beam_scorer& s = *scorer;
+  const LmArgs lm{logp, s.lm_image, s.alpha, s.beta, s.am_scores, s.bias_image, s.bias_scores};
+  switch (s.kind) {
+    case LASR_BEAM_PLAIN:
+      return beam_stream_feed<NullScorer>(a, {}, state, state_bytes, T_cap, s.kind, tokens, n_tokens, scores, n_frames, n_dropped);
+    case LASR_BEAM_LM:
+      return beam_stream_feed<LmScorer<false>>(a, lm, state, state_bytes, T_cap, s.kind, tokens, n_tokens, scores, n_frames, n_dropped);
+    case LASR_BEAM_WLM:
+      return beam_stream_feed<WlmScorer>(a, lm, state, state_bytes, T_cap, s.kind, tokens, n_tokens, scores, n_frames, n_dropped);
+    case LASR_BEAM_BIAS:
+      return beam_stream_feed<BiasScorer>(a, {s.bias_image, s.am_scores, s.bias_scores}, state, state_bytes, T_cap, s.kind, tokens,
+                                          n_tokens, scores, n_frames, n_dropped);
+    case LASR_BEAM_LM_BIAS:
+      return beam_stream_feed<LmScorer<true>>(a, lm, state, state_bytes, T_cap, s.kind, tokens, n_tokens, scores, n_frames, n_dropped);
+    default:
+      return fail(LASR_E_ARG, "%s: scorer kind %d outside 0..4", a.who, s.kind);
+  }
 }
 
 // ------------------------------------------------------------------ the C ABI: ARPA models ------------------------------

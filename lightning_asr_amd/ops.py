@@ -868,6 +868,232 @@ def ctc_beam_decode_biased(logp: torch.Tensor, lens: Optional[torch.Tensor], bla
     return tokens, n, scores, am, bias
 
 
+def _chunk_lens(lens, n_streams: int, t_chunk: int, device):
+    """lens of one feed -> (device int32 tensor or None, per-stream upper bounds of the frames it adds).  A list or a host
+    tensor is exact; a device tensor is not read back, so each stream is bounded by the chunk's length."""
+    if lens is None:
+        return None, [t_chunk] * n_streams
+    if torch.is_tensor(lens) and lens.is_cuda:
+        if lens.dtype != torch.int32 or lens.shape != (n_streams,):
+            raise TypeError("lens must be (%d,) int32" % n_streams)
+        return lens.contiguous(), [t_chunk] * n_streams
+    host = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+    if len(host) != n_streams:
+        raise ValueError("%d lens for %d streams" % (len(host), n_streams))
+    return torch.tensor(host, dtype=torch.int32).to(device), [min(max(v, 0), t_chunk) for v in host]
+
+
+class CtcBeamStream:
+    """The resumable CTC prefix beam search (lasr_ctc_beam_stream_*): `n_streams` sequences decoded chunk by chunk.  After every
+    feed() the outputs are those of the one-shot decode (ctc_beam_decode / _lm / _biased) of the frames fed so far, bit for bit,
+    however the frames were cut into chunks; the last feed's outputs are the final result.  lm: an ArpaLm (character or word),
+    bank: a HotwordBank (not with a word LM); both, alpha and beta are fixed for the life of the object.  The object owns the
+    state, the workspace and the output tensors; feed() returns views of the outputs, which the next feed overwrites.
+
+    t_cap: the most frames a stream can take between two resets.  The host keeps an upper bound of the frames fed to each stream
+    (exact when lens is None, a list or a host tensor; the chunk's length when lens is a device tensor) and feed() raises
+    ValueError before launching when that bound would pass t_cap.  A feed replayed from a captured graph bypasses this
+    bookkeeping: there the device's own clamp holds (frames past t_cap are counted in `dropped`, not searched)."""
+
+    def __init__(self, n_streams: int, n_classes: int, blank: int, beam_width: int = 16, cutoff_top_n: int = 40,
+                 cutoff_prob: float = 1.0, n_best: int = 1, t_cap: int = 3000, lm: Optional[ArpaLm] = None,
+                 bank: Optional[HotwordBank] = None, alpha: Optional[float] = None, beta: Optional[float] = None, device="cuda"):
+        if lm is not None and not isinstance(lm, ArpaLm):
+            raise TypeError("lm must be an ArpaLm (ops.load_arpa) or None")
+        if bank is not None and not isinstance(bank, HotwordBank):
+            raise TypeError("bank must be a HotwordBank (ops.build_hotwords) or None")
+        B, Cc, W = int(n_streams), int(n_classes), int(beam_width)
+        topn = min(int(cutoff_top_n), Cc) if Cc >= 1 else int(cutoff_top_n)
+        if B < 1 or int(t_cap) < 1:
+            raise ValueError("n_streams %d / t_cap %d must be >= 1" % (B, int(t_cap)))
+        if not 1 <= W <= CTC_BEAM_MAX_WIDTH:
+            raise ValueError("beam_width %d outside 1..%d" % (W, CTC_BEAM_MAX_WIDTH))
+        if not 1 <= topn <= CTC_BEAM_MAX_TOP_N:
+            raise ValueError("cutoff_top_n %d outside 1..%d" % (topn, CTC_BEAM_MAX_TOP_N))
+        if not 1 <= Cc <= CTC_BEAM_MAX_CLASSES:
+            raise ValueError("%d classes: the beam decoder takes at most %d" % (Cc, CTC_BEAM_MAX_CLASSES))
+        if not 1 <= n_best <= W:
+            raise ValueError("n_best %d outside 1..beam_width (%d)" % (n_best, W))
+        if not 0.0 < cutoff_prob <= 1.0:
+            raise ValueError("cutoff_prob %r outside (0, 1]" % (cutoff_prob,))
+        if not 0 <= blank < Cc:
+            raise ValueError("blank %d outside [0, %d)" % (blank, Cc))
+        if lm is not None and bank is not None and not lm.is_character_based():
+            raise NotImplementedError("hotword biasing of the word-level LM search is not implemented: its lexicon confines the "
+                                      "search to the LM's words")
+        self.device = torch.device(device)
+        if lm is not None:
+            alpha = lm.alpha if alpha is None else float(alpha)
+            beta = lm.beta if beta is None else float(beta)
+            if not (math.isfinite(alpha) and math.isfinite(beta)):
+                raise ValueError("alpha %r / beta %r must be finite" % (alpha, beta))
+            if len(lm.vocab) != Cc - 1:
+                raise ValueError("the LM was loaded for %d labels; the stream has %d classes" % (len(lm.vocab), Cc))
+        if bank is not None and (bank.n_classes != Cc or bank.blank != blank):
+            raise ValueError("the hotword bank was built for %d classes with blank %d; the stream has %d classes, blank %d"
+                             % (bank.n_classes, bank.blank, Cc, blank))
+        if lm is None:
+            self.kind = _lib.BEAM_PLAIN if bank is None else _lib.BEAM_BIAS
+        elif not lm.is_character_based():
+            self.kind = _lib.BEAM_WLM
+        else:
+            self.kind = _lib.BEAM_LM if bank is None else _lib.BEAM_LM_BIAS
+        self.n_streams, self.n_classes, self.blank, self.beam_width = B, Cc, int(blank), W
+        self.cutoff_top_n, self.cutoff_prob, self.n_best, self.t_cap = topn, float(cutoff_prob), int(n_best), int(t_cap)
+        self.lm, self.bank = lm, bank
+        lib = _lib.load()
+        self._state_bytes = int(lib.lasr_ctc_beam_stream_state_bytes(B, self.t_cap, W, self.kind))
+        if self._state_bytes == 0:
+            raise ValueError("CtcBeamStream: %d streams of t_cap %d at beam_width %d are outside the kernel's range" % (B, self.t_cap, W))
+        dev = self.device
+        self._state = torch.empty(self._state_bytes, dtype=torch.uint8, device=dev)
+        self._ws, self._ws_bytes = None, 0
+        self.tokens = torch.full((B, self.n_best, self.t_cap), -1, dtype=torch.int32, device=dev)
+        self.n_tokens = torch.zeros(B, self.n_best, dtype=torch.int32, device=dev)
+        self.scores = torch.zeros(B, self.n_best, dtype=torch.float32, device=dev)
+        self.am_scores = torch.zeros_like(self.scores) if self.kind != _lib.BEAM_PLAIN else None
+        self.bias_scores = torch.zeros_like(self.scores) if bank is not None else None
+        self._n_frames = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._n_dropped = torch.zeros(B, dtype=torch.int32, device=dev)
+        lm_image = None if lm is None else lm.image.to(dev)
+        bias_image = None if bank is None else bank.image.to(dev)
+        self._images = (lm_image, bias_image)          # kept alive: the scorer record holds their addresses
+        self._scorer = _lib.BeamScorer(self.kind, _p(lm_image), float(alpha or 0.0), float(beta or 0.0), _p(bias_image),
+                                       _p(self.am_scores), _p(self.bias_scores))
+        self._fed = [0] * B
+        self.reset()
+
+    @property
+    def frames(self) -> torch.Tensor:
+        """(n_streams,) int32 on the device: the frames each stream has searched since its last reset"""
+        return self._n_frames
+
+    @property
+    def dropped(self) -> torch.Tensor:
+        """(n_streams,) int32 on the device: the frames fed beyond t_cap, counted and not searched"""
+        return self._n_dropped
+
+    def reset(self, rows=None) -> None:
+        """Make the streams `rows` (a list of indices; None: all of them) the empty prefix again."""
+        if rows is None:
+            rows_t, n = None, 0
+            self._fed = [0] * self.n_streams
+        else:
+            rows = [int(r) for r in rows]
+            if any(not 0 <= r < self.n_streams for r in rows):
+                raise ValueError("rows %r outside [0, %d)" % (rows, self.n_streams))
+            if not rows:
+                return
+            rows_t, n = torch.tensor(rows, dtype=torch.int32).to(self.device), len(rows)
+            for r in rows:
+                self._fed[r] = 0
+        call("lasr_ctc_beam_stream_reset", _p(self._state), self._state_bytes, self.n_streams, self.t_cap, self.beam_width, self.kind,
+             _p(rows_t), n, _stream())
+        if rows is None:
+            self._n_frames.zero_()
+            self._n_dropped.zero_()
+        else:
+            self._n_frames[rows_t.long()] = 0
+            self._n_dropped[rows_t.long()] = 0
+
+    def feed(self, logp: torch.Tensor, lens=None):
+        """logp (n_streams, T_chunk, C) f32: the next frames of every stream; lens: how many of them per stream (None: all; 0:
+        the stream idles).  Returns (tokens (B, n_best, t_cap), n_tokens, scores[, am_scores[, bias_scores]]) as the one-shot
+        decode of this stream's kind returns them, for the frames fed so far."""
+        if logp.dtype != torch.float32 or logp.dim() != 3:
+            raise TypeError("CtcBeamStream.feed takes (B, T, C) float32 log-probs")
+        B, T, Cc = logp.shape
+        if B != self.n_streams or Cc != self.n_classes:
+            raise ValueError("feed of shape %s to %d streams of %d classes" % (tuple(logp.shape), self.n_streams, self.n_classes))
+        if logp.device != self._state.device:
+            raise ValueError("the log-probs are on %s, the stream on %s" % (logp.device, self._state.device))
+        lens_t, add = _chunk_lens(lens, B, T, self.device)
+        for b in range(B):
+            if self._fed[b] + add[b] > self.t_cap:
+                raise ValueError("stream %d: %d frames fed + %d would pass t_cap %d; reset() it or build a larger stream"
+                                 % (b, self._fed[b], add[b], self.t_cap))
+        nb = int(_lib.load().lasr_ctc_beam_stream_workspace_bytes(B, T, Cc, self.beam_width, self.cutoff_top_n))
+        if nb == 0:
+            raise ValueError("CtcBeamStream.feed: chunk (%d, %d, %d) outside the kernel's range" % (B, T, Cc))
+        if nb > self._ws_bytes:
+            self._ws, self._ws_bytes = _ws(nb, self.device), nb
+        call("lasr_ctc_beam_stream_feed", _p(logp), _p(lens_t), B, T, Cc, self.blank, self.beam_width, self.cutoff_top_n,
+             self.cutoff_prob, self.n_best, ctypes.byref(self._scorer), _p(self._state), self._state_bytes, self.t_cap,
+             _p(self.tokens), _p(self.n_tokens), _p(self.scores), _p(self._n_frames), _p(self._n_dropped), _p(self._ws),
+             self._ws_bytes, _stream())
+        for b in range(B):
+            self._fed[b] += add[b]
+        out = (self.tokens, self.n_tokens, self.scores)
+        if self.am_scores is not None:
+            out += (self.am_scores,)
+        if self.bias_scores is not None:
+            out += (self.bias_scores,)
+        return out
+
+
+class GreedyStream:
+    """Greedy CTC decoding chunk by chunk, with CtcBeamStream's feed / reset: the last raw argmax id of each stream is carried
+    over the chunk border, prepended to the next chunk's ids, and the token it yields again is dropped, so the tokens equal
+    greedy_decode of the whole row however it was cut.  feed() takes the argmax ids, not log-probs."""
+
+    def __init__(self, n_streams: int, blank: int, t_cap: int = 3000, device="cuda"):
+        self.n_streams, self.blank, self.t_cap = int(n_streams), int(blank), int(t_cap)
+        self.device = torch.device(device)
+        B = self.n_streams
+        self._tokens = torch.full((B, self.t_cap + 1), -1, dtype=torch.int32, device=self.device)   # last column: discarded writes
+        self.n_tokens = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self._carry = torch.full((B,), self.blank, dtype=torch.int32, device=self.device)
+        self._n_frames = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self._fed = [0] * B
+
+    @property
+    def tokens(self) -> torch.Tensor:
+        return self._tokens[:, :self.t_cap]
+
+    @property
+    def frames(self) -> torch.Tensor:
+        return self._n_frames
+
+    def reset(self, rows=None) -> None:
+        idx = slice(None) if rows is None else torch.tensor([int(r) for r in rows], dtype=torch.long).to(self.device)
+        self._tokens[idx] = -1
+        self.n_tokens[idx] = 0
+        self._carry[idx] = self.blank
+        self._n_frames[idx] = 0
+        for b in (range(self.n_streams) if rows is None else rows):
+            self._fed[int(b)] = 0
+
+    def feed(self, ids: torch.Tensor, lens=None):
+        """ids (n_streams, T_chunk) int32 argmax ids, lens as CtcBeamStream.feed.  Returns (tokens (B, t_cap), -1 past each
+        hypothesis; n_tokens (B)) for the frames fed so far."""
+        if ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[0] != self.n_streams:
+            raise TypeError("GreedyStream.feed takes (%d, T) int32 ids" % self.n_streams)
+        B, T = ids.shape
+        lens_t, add = _chunk_lens(lens, B, T, self.device)
+        for b in range(B):
+            if self._fed[b] + add[b] > self.t_cap:
+                raise ValueError("stream %d: %d frames fed + %d would pass t_cap %d" % (b, self._fed[b], add[b], self.t_cap))
+        if lens_t is None:
+            lens_t = torch.full((B,), T, dtype=torch.int32, device=self.device)
+        lens_t = lens_t.clamp(0, T)
+        ext = torch.cat([self._carry[:, None], ids], dim=1).contiguous()
+        tok, n = greedy_decode(ext, (lens_t + 1).contiguous(), self.blank)
+        drop = (self._carry != self.blank).to(torch.int64)                 # the carried label's token came out last feed
+        col = torch.arange(T, device=self.device)[None, :]
+        new = tok.gather(1, (col + drop[:, None]).clamp(max=T))
+        n_new = n.to(torch.int64) - drop
+        dst = self.n_tokens.to(torch.int64)[:, None] + col
+        dst = torch.where((col < n_new[:, None]) & (dst < self.t_cap), dst, torch.full_like(dst, self.t_cap))
+        self._tokens.scatter_(1, dst, new)
+        self.n_tokens += n_new.to(torch.int32)
+        last = ids.gather(1, (lens_t.to(torch.int64) - 1).clamp(min=0)[:, None])[:, 0]
+        self._carry = torch.where(lens_t > 0, last, self._carry)
+        self._n_frames += lens_t
+        for b in range(B):
+            self._fed[b] += add[b]
+        return self.tokens, self.n_tokens
+
+
 # ---------------------------------------------------------------------------------- optimiser
 def novograd_workspace(n_tensors: int, n_elems: int, device) -> torch.Tensor:
     """a ZEROED workspace a caller keeps across novograd_step(ws=...) calls (every call leaves it zeroed)"""

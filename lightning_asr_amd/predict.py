@@ -449,6 +449,18 @@ class AsrTranslator:
         result["text"] = (" " if " " in self.labels else "").join(r["text"] for r in records)
         return result
 
+    # ------------------------------------------------------------------------------------------ streaming
+    def stream(self, chunk_s: float = 1.0, left_s: float = 4.0, right_s: float = 1.0, max_segment_s: float = 30.0,
+               endpoint_silence_s: Optional[float] = 0.8, dither: bool = True, keep_logp: bool = False):
+        """A recogniser for live audio (streaming.StreamingRecognizer): ``feed(samples)`` takes 16 kHz packets of any size and
+        returns {"text", "committed", "partial", "frames", "final"} after each, ``finish()`` the final record.  The audio goes
+        through overlapping windows of left_s + chunk_s + right_s, each through translate()'s feature chain and forward, and
+        the frames of its middle chunk_s through this translator's own decoder (greedy, or the beam search with its LM and
+        hotwords as they are now) in its resumable form.  The three context defaults are starting values: nobody has measured
+        accuracy against context on a trained model."""
+        from .streaming import StreamingRecognizer
+        return StreamingRecognizer(self, chunk_s, left_s, right_s, max_segment_s, endpoint_silence_s, dither, keep_logp)
+
     # ------------------------------------------------------------------------------------------ keyword search
     def _keyword_bank(self, keywords, who: str):
         """keywords (list of str) -> (names, ops.KeywordBank for the model's classes on the translator's device)"""
