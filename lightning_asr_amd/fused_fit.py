@@ -162,7 +162,7 @@ def make_source(datamodule, loader, device, mask: bool, limit: int, max_seconds:
 
 class FusedLoop:
     def __init__(self, trainer, model, datamodule, optimizer, scheduler):
-        self.trainer, self.model, self.dm = trainer, model, datamodule
+        self.trainer, self.model, self.dm, self.optimizer = trainer, model, datamodule, optimizer
         self.native = model.encoder.native
         dev = self.native.device
         self.K = check_accumulate(getattr(trainer, "accumulate_grad_batches", 1))
@@ -361,7 +361,7 @@ class FusedLoop:
                             if k + "_step" in m:
                                 tr.callback_metrics[k] = m[k + "_step"]
                         if hasattr(tr, "publish_grad_clip"):     # the clip record rides on the same synchronisation
-                            tr.publish_grad_clip(getattr(self.ts, "_optimizer", None))
+                            tr.publish_grad_clip(self.optimizer)
                 if on_step is not None:
                     on_step(tr)
         finally:

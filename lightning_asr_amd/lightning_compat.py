@@ -216,14 +216,19 @@ class Trainer:
         self._epoch_metrics.setdefault(name, []).append(v)
         self.callback_metrics[name] = v
 
+    @staticmethod
+    def _opt_state(opt):
+        """the optimiser's ``OptimState`` - moments, weight EMA, clip record; None for an optimiser that is not the HIP NovoGrad"""
+        return getattr(opt, "opt_state", None)
+
     def publish_grad_clip(self, opt) -> None:
         """grad_norm / grad_clip_coef (the last step's) and skipped_steps from the optimiser's clip record into callback_metrics: one
         small device read, so only where the loop synchronises anyway (a metrics read, the end of an epoch)"""
-        state = getattr(opt, "clip_state", None)
-        if state is None:
+        rec = self._opt_state(opt)
+        if rec is None or rec.clip_state is None:
             return
         from . import ops
-        st = ops.clip_state_read(state)
+        st = ops.clip_state_read(rec.clip_state)
         self.callback_metrics.update(grad_norm=st["total_norm"], grad_clip_coef=st["coef"], skipped_steps=st["skipped"])
         if st["skipped"] > self._skips_seen:
             if self._skips_seen == 0:
@@ -290,7 +295,8 @@ class Trainer:
         ckpt = {"epoch": self.current_epoch, "global_step": self.global_step, "state_dict": model.state_dict(),
                 "optimizer_states": [opt.state_dict()], "lr_schedulers": [sched.state_dict()] if sched else [],
                 "hyper_parameters": dict(getattr(model, "hparams", {})), "pytorch-lightning_version": "lasr-native"}
-        if getattr(opt, "ema", None) is not None:
+        rec = self._opt_state(opt)
+        if rec is not None and rec.ema is not None:
             # state_dict stays the LIVE weights (reference compatibility, resume); the averaged model travels beside it as a
             # complete state dict anything that loads state_dict can load: averaged parameters, the live buffers
             native = model.encoder.native
@@ -299,9 +305,9 @@ class Trainer:
                 key = "encoder." + t.name
                 if key not in ema_sd:
                     raise KeyError("ema_state_dict: the module's state_dict has no %r" % key)
-                ema_sd[key] = native.view(t, opt.ema).detach().clone()
+                ema_sd[key] = native.view(t, rec.ema).detach().clone()
             ckpt["ema_state_dict"] = ema_sd
-            ckpt["ema"] = {"decay": opt.ema_decay, "warmup": opt.ema_warmup, "num_updates": opt.ema_num_updates}
+            ckpt["ema"] = {"decay": rec.ema_decay, "warmup": rec.ema_warmup, "num_updates": rec.ema_num_updates}
         model.on_save_checkpoint(ckpt)
         path = os.path.join(d, name)
         torch.save(ckpt, path)
@@ -425,11 +431,11 @@ class Trainer:
         """the parameters validate / test read: the optimiser's weight EMA when there is one for this model and ema_eval is on
         (``NativeModel.using_params``: an attribute swap for the block, no copy), else the live ones"""
         import contextlib
-        ema = getattr(self._opt, "ema", None)
+        rec = self._opt_state(self._opt)
         native = getattr(getattr(model, "encoder", None), "native", None)
-        if not self.ema_eval or ema is None or native is None or getattr(self._opt, "owner", None) is not model.encoder:
+        if not self.ema_eval or rec is None or rec.ema is None or native is None or self._opt.owner is not model.encoder:
             return contextlib.nullcontext()
-        return native.using_params(ema)
+        return native.using_params(rec.ema)
 
     @torch.no_grad()
     def validate(self, model, datamodule) -> Dict[str, float]:

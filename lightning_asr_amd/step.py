@@ -11,6 +11,7 @@ from typing import Optional
 
 import torch
 
+import contextlib
 import ctypes as C
 import os
 
@@ -18,7 +19,7 @@ from . import _lib, ops
 from .comm import Communicator
 from .engine import NativeModel
 from .schedule import CosineAnnealingWarmupRestarts
-from .scheduler.novograd import check_ema_decay, check_grad_clip, make_clip_state
+from .scheduler.novograd import OptimState, forwards_opt_state
 
 
 _ROCTX = None
@@ -40,12 +41,35 @@ def check_accumulate(k) -> int:
     return k
 
 
+class _TorchDistExchange:
+    """``Communicator``'s collectives over torch.distributed (gloo groups, ``LASR_COMM=torch``, the fall-back of the communicator's
+    self-check): the bucket all-reduces are asynchronous and ``wait`` joins them; the flat all-reduce and the broadcast block"""
+
+    def __init__(self, process_group):
+        self.pg, self.works = process_group, []
+
+    def all_reduce_ranges(self, flat, ranges) -> None:
+        self.works.extend(torch.distributed.all_reduce(flat[lo:hi], group=self.pg, async_op=True) for lo, hi in ranges)
+
+    def all_reduce(self, flat) -> None:
+        torch.distributed.all_reduce(flat, group=self.pg)
+
+    def broadcast(self, flat, root: int = 0) -> None:
+        torch.distributed.broadcast(flat, root, group=self.pg)
+
+    def wait(self) -> None:
+        works, self.works = self.works, []
+        for w in works:
+            w.wait()
+
+
+@forwards_opt_state
 class TrainStep:
     def __init__(self, model: NativeModel, learning_rate: float = 1e-2, weight_decay: float = 1e-3,
                  betas=(0.8, 0.5), eps: float = 1e-8, schedule: Optional[CosineAnnealingWarmupRestarts] = None,
                  process_group=None, comm: Optional[Communicator] = None, accumulate: int = 1, ema_decay: float = 0.0,
                  ema_warmup: bool = True, gradient_clip_val: float = 0.0, gradient_clip_algorithm: str = "norm",
-                 skip_nonfinite: bool = False, track_grad_norm: bool = False):
+                 skip_nonfinite: bool = False, track_grad_norm: bool = False, opt_state: Optional[OptimState] = None):
         """comm: the library-owned RCCL communicator (lasr_comm_*).  Default for world > 1 on the nccl backend: one is built
         from the torch.distributed group (which then only bootstraps the unique id); ``LASR_COMM=torch`` keeps the gradient
         exchange on torch.distributed (the only choice for gloo groups: CPU rehearsal, two ranks sharing a GPU in the tests).
@@ -54,50 +78,36 @@ class TrainStep:
         ``last=True`` - is the boundary, which additionally all-reduces, steps the optimiser with grad_scale 1 / (K world),
         steps the schedule and zeroes ``model.grads``, which is therefore zero between windows.  K = 1 is the step as it
         always was: no second buffer, no extra launch.
-        ema_decay > 0: ``self.ema`` is an exponential moving average of the parameters ("Weight EMA"), a copy of them
-        now and updated by the last kernel of every OPTIMISER step (under accumulate > 1 only the boundary reaches it) with the
-        weight the device record ``self.ema_state`` yields - no launch, no host scalar, so a captured graph replays it.  0 = off:
-        no buffer, and the step as it always was.
-        gradient_clip_val > 0 / gradient_clip_algorithm ("norm": by the global norm, "value": element-wise) / skip_nonfinite (a step
-        whose gradient holds a NaN or an Inf leaves parameters, moments and the average alone, and still counts as a step for the
-        schedule, ``global_step`` and the accumulation window) / track_grad_norm: decided on the device by the optimiser's own
-        kernels through the record ``self.clip_state`` ("Gradient clipping and the non-finite guard") - no launch, no host
-        decision, so a captured graph replays it; under accumulate > 1 once per window, on the window's sum.  All off: no record."""
+        opt_state: the optimiser's device state (moments, learning rate, weight EMA, clip record) as ONE ``OptimState``, whose names
+        read through on the step (``self.ema``, ``self.clip_state``, ``self.skipped_steps`` ...): the one handed in (``from_optimizer``)
+        or, by default, its own, made from the six settings before it (``OptimState.__init__``).  Under accumulate > 1 only the
+        boundary reaches the EMA update, and clipping and the non-finite guard act once per window, on the window's sum."""
         self.model = model
-        self.gradient_clip_val, self.gradient_clip_algorithm = check_grad_clip(gradient_clip_val, gradient_clip_algorithm)
-        self.skip_nonfinite, self.track_grad_norm = bool(skip_nonfinite), bool(track_grad_norm)
-        self.ema_decay, self.ema_warmup = check_ema_decay(ema_decay), bool(ema_warmup)
-        self.ema = self.ema_state = None
-        if self.ema_decay > 0.0:
-            self.ema = model.params.clone()
-            self.ema_state = ops.ema_state(self.ema_decay, self.ema_warmup, 0, device=model.device)
-        self.clip_state = make_clip_state(self.gradient_clip_val, self.gradient_clip_algorithm, self.skip_nonfinite,
-                                          self.track_grad_norm, model.device)
+        self.schedule = schedule
+        self.lr = schedule.lr if schedule is not None else learning_rate
+        settings = (ema_decay, ema_warmup, gradient_clip_val, gradient_clip_algorithm, skip_nonfinite, track_grad_norm)
+        if opt_state is not None and settings != (0.0, True, 0.0, "norm", False, False):
+            raise ValueError("opt_state carries its own settings: ema_decay ... track_grad_norm cannot be passed beside it")
+        self.opt_state = opt_state if opt_state is not None else OptimState(*settings).allocate(model, self.lr)
         self.accumulate = check_accumulate(accumulate)
         self.micro = 0             # micro-batches already added into model.grads in the current window (K > 1)
         if self.accumulate > 1:
             model.grads.zero_()
         self.wd, self.betas, self.eps = weight_decay, betas, eps
-        dev = model.device
-        self.exp_avg = torch.zeros_like(model.params)
-        self.exp_avg_sq = torch.zeros(len(model.param_infos()), dtype=torch.float32, device=dev)
-        self.offsets = model.param_offsets()
-        self.schedule = schedule
-        self.lr = schedule.lr if schedule is not None else learning_rate
-        self.lr_dev = torch.tensor([self.lr], dtype=torch.float32, device=dev)
         self.pg = process_group
         self.world = 1
         if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
             self.world = torch.distributed.get_world_size(process_group)
         self.global_step = 0
         self.overlap = True        # overlap the gradient all-reduce with backward (world > 1)
-        self._reduced = False
         self.comm = comm
         if comm is not None:
             self.world = comm.world
         elif self.world > 1 and os.environ.get("LASR_COMM", "rccl") == "rccl" and \
                 (torch.distributed.get_backend(process_group) == "nccl" or os.environ.get("LASR_RCCL_PATH")):   # (gloo + LASR_RCCL_PATH: rehearsal over the test stub)
-            self.comm = self._checked_communicator(dev, process_group)
+            self.comm = self._checked_communicator(model.device, process_group)
+        # how gradients and parameters travel between the ranks, chosen once (at world 1 without a communicator: nothing calls it)
+        self._exchange = self.comm if self.comm is not None else _TorchDistExchange(process_group)
         # exercise the staged + async all-reduce path on a 1-rank group too (validation on one GPU)
         self.force_staged = bool(int(os.environ.get("LASR_FORCE_OVERLAP", "0"))) and \
             (self.comm is not None or torch.distributed.is_initialized())
@@ -138,35 +148,15 @@ class TrainStep:
     @classmethod
     def from_optimizer(cls, model: NativeModel, optimizer, schedule=None, process_group=None, comm: Optional[Communicator] = None,
                        accumulate: int = 1):
-        """The fused step over the state of a ``scheduler.novograd.Novograd`` (+ its ``CosineAnnealingWarmupRestarts``): the
-        moments and the device learning rate ARE the optimizer's tensors, so ``optimizer.state_dict()`` / checkpoints / resume
-        keep working while ``Trainer.fit`` drives this step instead of ``loss.backward(); optimizer.step()``."""
+        """The fused step over the state of a ``scheduler.novograd.Novograd`` (+ its ``CosineAnnealingWarmupRestarts``): the step's
+        ``opt_state`` IS the optimizer's - moments, device learning rate, weight EMA, clip record - so ``optimizer.state_dict()`` /
+        checkpoints / resume keep working while ``Trainer.fit`` drives this step instead of ``loss.backward(); optimizer.step()``."""
         g = optimizer.param_groups[0]
         ts = cls(model, learning_rate=float(g["lr"]), weight_decay=g["weight_decay"], betas=tuple(g["betas"]), eps=g["eps"],
-                 schedule=schedule, process_group=process_group, comm=comm, accumulate=accumulate)
-        ts.exp_avg, ts.exp_avg_sq, ts.lr_dev = optimizer.exp_avg, optimizer.exp_avg_sq, optimizer.lr_dev
-        # the weight EMA is the optimiser's too (None with ema_decay = 0): checkpoints and resume go through its state_dict
-        ts.ema, ts.ema_state = getattr(optimizer, "ema", None), getattr(optimizer, "ema_state", None)
-        ts.ema_decay, ts.ema_warmup = getattr(optimizer, "ema_decay", 0.0), getattr(optimizer, "ema_warmup", True)
-        # and so is the clip record (None with everything off): its counts travel in the optimiser's state_dict
-        ts.clip_state = getattr(optimizer, "clip_state", None)
-        ts.gradient_clip_val = getattr(optimizer, "gradient_clip_val", 0.0)
-        ts.gradient_clip_algorithm = getattr(optimizer, "gradient_clip_algorithm", "norm")
-        ts.skip_nonfinite, ts.track_grad_norm = getattr(optimizer, "skip_nonfinite", False), getattr(optimizer, "track_grad_norm", False)
+                 schedule=schedule, process_group=process_group, comm=comm, accumulate=accumulate, opt_state=optimizer.opt_state)
         ts.lr = float(g["lr"])
         ts.lr_dev.fill_(ts.lr)
-        ts._optimizer = optimizer
         return ts
-
-    @property
-    def ema_num_updates(self) -> int:
-        """EMA updates done so far (one read of the device record); 0 with EMA off"""
-        return ops.ema_state_read(self.ema_state)["num_updates"] if self.ema_state is not None else 0
-
-    @property
-    def skipped_steps(self) -> int:
-        """optimiser steps dropped as non-finite so far (one read of the device record); 0 without a record"""
-        return ops.clip_state_read(self.clip_state)["skipped"] if self.clip_state is not None else 0
 
     def sync_device_schedule(self) -> None:
         """Re-upload the schedule after its host state changed behind the device twin's back (``load_state_dict`` on resume,
@@ -174,19 +164,16 @@ class TrainStep:
         if self.schedule is not None:
             self.lr = self.schedule.lr
         self.lr_dev.fill_(float(self.lr))
-        if self._lr_state is not None:
-            self._lr_state = None
-            self.use_device_schedule()
+        if self._lr_state is not None:         # in place: a captured graph holds the address of the device state
+            self._lr_state.copy_(self._schedule_image())
+            self._lr_epoch = int(self.schedule.last_epoch)
 
     def broadcast_parameters(self, src: int = 0) -> None:
-        """DDP wrap-time broadcast of parameters and buffers from rank 0."""
-        if self.comm is not None:
-            self.comm.broadcast(self.model.params, src)
-            self.comm.broadcast(self.model.buffers, src)
-            self.comm.wait()
-        elif self.world > 1:
-            torch.distributed.broadcast(self.model.params, src, group=self.pg)
-            torch.distributed.broadcast(self.model.buffers, src, group=self.pg)
+        """DDP wrap-time broadcast of parameters and buffers from rank 0 (a one-rank communicator still runs its own)."""
+        if self.comm is not None or self.world > 1:
+            self._exchange.broadcast(self.model.params, src)
+            self._exchange.broadcast(self.model.buffers, src)
+            self._exchange.wait()
 
     def features(self, wave, sample_lens=None, dither=None, aug=None, logical_len=None):
         """wave (B, L) f32 on the GPU -> ([B][T][64] features in the activation dtype, pct (B)).  logical_len: the longest utterance
@@ -195,32 +182,61 @@ class TrainStep:
                                  logical_len=logical_len)
         return btf, pct
 
-    def optimizer_step(self) -> None:
+    def optimizer_step(self, reduced: bool = False) -> None:
+        """reduced: the step body has already exchanged the gradient bucket by bucket; otherwise, at world > 1, one flat 20 MB SUM
+        all-reduce here.  The 1/world average is folded into the optimiser's grad scale.  An optimiser step closes the accumulation
+        window: called on its own in the middle of one (accumulate > 1), it resets ``self.micro`` too."""
         m = self.model
-        if self.world > 1 and not getattr(self, "_reduced", False):
-            # one flat 20 MB SUM all-reduce; the 1/world average is folded into the optimiser's grad scale
-            if self.comm is not None:
-                self.comm.all_reduce(m.grads)
-                self.comm.wait()
-            else:
-                torch.distributed.all_reduce(m.grads, group=self.pg)
-        self._reduced = False
-        if getattr(self, "_opt_ws", None) is None:       # kept across steps: zeroed once, left zeroed by every step (no memset launch)
-            self._opt_ws = ops.novograd_workspace(self.exp_avg_sq.numel(), m.params.numel(), m.device)
-        ops.novograd_step(m.params, m.grads, self.exp_avg, self.exp_avg_sq, self.offsets, self.lr_dev, self.betas[0],
-                          self.betas[1], self.eps, self.wd, grad_scale=1.0 / (self.accumulate * self.world), ws=self._opt_ws,
-                          ema=self.ema, ema_state=self.ema_state, clip_state=self.clip_state)
+        if self.world > 1 and not reduced:
+            self._exchange.all_reduce(m.grads)
+            self._exchange.wait()
+        self.opt_state.step(m.params, m.grads, self.betas, self.eps, self.wd, 1.0 / (self.accumulate * self.world))
+        self.count_optimizer_step(advance_device=True)
+
+    def count_optimizer_step(self, advance_device: bool) -> None:
+        """Host bookkeeping after an optimiser step, eager or replayed: the host copy of the schedule (logging / checkpoints),
+        ``global_step``, the window counter.  advance_device: the rate the next step reads is still to be advanced (not after a replay)."""
         if self.schedule is not None:
             if self._lr_state is not None and self.schedule.last_epoch != self._lr_epoch:
-                self.sync_device_schedule()                # the host schedule was loaded / reset since the last step
-            self.lr = self.schedule.step()                 # host copy of the schedule: bookkeeping / logging / checkpoints
+                self.sync_device_schedule()                # the host schedule was loaded / reset since the last step: the device
+                advance_device = True                      # twin restarts (in place) at the host's position and advances with it
+            self.lr = self.schedule.step()
             self._lr_epoch = self.schedule.last_epoch
-            if self._lr_state is not None:                 # the rate the next step uses is computed on the device
+            if advance_device and self._lr_state is not None:      # the rate the next step uses is computed on the device
                 _lib.call("lasr_lr_schedule_step", self._lr_state.data_ptr(), self.lr_dev.data_ptr(),
                           torch.cuda.current_stream().cuda_stream)
-            else:
+            elif advance_device:
                 self.lr_dev.fill_(self.lr)
         self.global_step += 1
+        self.micro = 0
+
+    @contextlib.contextmanager
+    def preserved(self, extra=()):
+        """Everything a training step changes - parameters, BN buffers and counters, the optimiser's state, the gradient sum and the
+        micro-batch buffer (accumulate > 1), the schedule on both sides, the dropout counter, the step / window counters - plus the
+        tensors in ``extra``: snapshotted on entry, put back on exit, also when the block raises.  No prefetch stays armed."""
+        m = self.model
+        tensors = [m.params, m.buffers] + self.opt_state.tensors() + ([m.grads, m.grads_micro] if self.accumulate > 1 else []) + \
+            [t for t in (self._lr_state, getattr(m, "drop_step", None)) if t is not None] + list(extra)
+        snap = [t.clone() for t in tensors]
+        sched_sd = dict(self.schedule.state_dict()) if self.schedule is not None else None
+        host = (self.global_step, self.micro, self._lr_epoch, m._bump)
+        counters = {k: v.clone() for k, v in m.counters.items()}
+        try:
+            yield
+        finally:
+            torch.cuda.synchronize()
+            for t, s_ in zip(tensors, snap):
+                t.copy_(s_)
+            if sched_sd is not None:
+                self.schedule.load_state_dict(sched_sd)
+                self.lr = self.schedule.lr
+                self.schedule._publish()
+            self.global_step, self.micro, self._lr_epoch, m._bump = host
+            m.counters.update(counters)
+            self._prefetched = None
+            m.disarm_prefetch()
+            torch.cuda.synchronize()
 
     def use_device_schedule(self) -> None:
         """Move the LR schedule's state onto the GPU (csrc/sched.hip): from now on every optimizer_step advances it with a
@@ -228,99 +244,71 @@ class TrainStep:
         alongside (same values to f32 rounding) for logging and checkpoints."""
         if self.schedule is None or self._lr_state is not None:
             return
+        self._lr_state = self._schedule_image().to(self.model.device)
+        self._lr_epoch = int(self.schedule.last_epoch)
+
+    def _schedule_image(self) -> torch.Tensor:
+        """the host schedule as it stands, as the bytes of the device state"""
         sc = self.schedule
         nb = int(_lib.load().lasr_lr_schedule_state_bytes())
         host = C.create_string_buffer(nb)
         _lib.call("lasr_lr_schedule_init", host, nb, int(sc.first_cycle_steps), float(sc.cycle_mult), float(sc.base_max_lr),
                   float(sc.min_lr), int(sc.warmup_steps), float(sc.gamma), int(sc.cycle), int(sc.step_in_cycle),
                   int(sc.cur_cycle_steps), int(sc.last_epoch))
-        self._lr_state = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(self.model.device)
-        self._lr_epoch = int(sc.last_epoch)
+        return torch.frombuffer(bytearray(host.raw), dtype=torch.uint8)
 
     def step_features(self, feats, pct, targets, tgt_lens, want_logp: bool = True, last: Optional[bool] = None,
                       role: Optional[str] = None):
         """last (accumulate > 1): None - the boundary follows the window counter ``self.micro``; True - this micro-batch closes
         the window whatever it holds (the flush at the end of an epoch).  role: "accumulate" / "boundary" fixes the role
         outright (a captured graph holds one role).  Both are ignored at accumulate = 1."""
+        boundary = True
         if self.accumulate > 1:
             if role not in (None, "accumulate", "boundary"):
                 raise ValueError("role has to be 'accumulate' or 'boundary', got %r" % (role,))
             boundary = (role == "boundary") if role is not None else (bool(last) or self.micro + 1 >= self.accumulate)
-            body, args = self._micro_step, (feats, pct, targets, tgt_lens, want_logp, boundary)
-        else:
-            body, args = self._step_features, (feats, pct, targets, tgt_lens, want_logp)
+        args = (feats, pct, targets, tgt_lens, want_logp, boundary)
         if _roctx_on():                      # LASR_ROCTX=1: "lasr:step" around the whole step (rocprofv3 --marker-trace)
             _lib.load().lasr_roctx_range_push(b"lasr:step")
             try:
-                return body(*args)
+                return self._step_body(*args)
             finally:
                 _lib.load().lasr_roctx_range_pop()
-        return body(*args)
+        return self._step_body(*args)
 
-    def _micro_step(self, feats, pct, targets, tgt_lens, want_logp: bool, boundary: bool):
-        """One micro-step of an accumulation window (accumulate > 1).  Two uniform roles: every micro-step ADDS its gradient to
-        ``model.grads`` (zero at the start of a window), the boundary also exchanges, steps and zeroes - so a batch shape
-        needs two captured graphs, not the three of "the first micro-batch overwrites"."""
+    def _step_body(self, feats, pct, targets, tgt_lens, want_logp: bool, boundary: bool):
+        """Backward, gradient exchange, optimiser step.  accumulate > 1 - one micro-step of a window, in two uniform roles: every
+        micro-step ADDS its gradient to ``model.grads`` (zero at the start of a window), the boundary also exchanges, steps and
+        zeroes - so a batch shape needs two captured graphs, not the three of "the first micro-batch overwrites".  accumulate = 1:
+        always the boundary, straight into ``model.grads`` - no second buffer, no add, no zeroing."""
         m = self.model
-        gm = m.grads_micro
-        if self.overlap and (self.world > 1 or self.force_staged):
-            # data parallel: EVERY micro-step of a window takes the staged backward (the same kernels in the same split-K order
-            # throughout); each bucket is added into the running sum as soon as its stage is enqueued, and only the boundary
-            # hands it to the all-reduce right behind that add - the other micro-steps issue no collective (Lightning's no_sync)
-            works = []
-            if self.comm is not None:
-                def on_bucket(ranges):
+        gm = m.grads_micro if self.accumulate > 1 else None
+        staged = self.overlap and (self.world > 1 or self.force_staged)
+        if staged:
+            # data parallel: bucketed SUM all-reduce, launched bucket by bucket in reverse layer order while the units below are
+            # still being differentiated (it waits only for the kernels enqueued so far; the optimiser waits for all buckets).
+            # EVERY micro-step of a window takes this staged backward (the same kernels in the same split-K order throughout) and
+            # adds each bucket into the running sum as soon as its stage is enqueued; only the boundary hands it to the all-reduce
+            # right behind that add - the other micro-steps issue no collective (Lightning's no_sync)
+            def on_bucket(ranges):
+                if gm is not None:
                     ops.grad_accumulate(m.grads, gm, ranges)
-                    if boundary:
-                        self.comm.all_reduce_ranges(m.grads, ranges)
-            else:
-                def on_bucket(ranges):
-                    ops.grad_accumulate(m.grads, gm, ranges)
-                    if boundary:
-                        works.extend(torch.distributed.all_reduce(m.grads[lo:hi], group=self.pg, async_op=True) for lo, hi in ranges)
-            loss, nll, logp, am = m.loss_backward_staged(feats, pct, targets, tgt_lens, on_bucket, want_logp=want_logp, grads=gm)
+                if boundary:
+                    self._exchange.all_reduce_ranges(m.grads, ranges)
+            out = m.loss_backward_staged(feats, pct, targets, tgt_lens, on_bucket, want_logp=want_logp, grads=gm)
             if boundary:
-                if self.comm is not None:
-                    self.comm.wait()
-                for w in works:
-                    w.wait()
-                self._reduced = True
+                self._exchange.wait()
         else:
-            loss, nll, logp, am = m.loss_backward(feats, pct, targets, tgt_lens, want_logp=want_logp, grads=gm)
-            ops.grad_accumulate(m.grads, gm)
-            self._reduced = False
+            out = m.loss_backward(feats, pct, targets, tgt_lens, want_logp=want_logp, grads=gm)
+            if gm is not None:
+                ops.grad_accumulate(m.grads, gm)
         if boundary:
-            self.optimizer_step()          # (world > 1 and not staged: its one flat all-reduce, on the boundary only)
-            m.grads.zero_()
-            self.micro = 0
+            self.optimizer_step(reduced=staged)    # (world > 1 and not staged: its one flat all-reduce, on the boundary only)
+            if gm is not None:
+                m.grads.zero_()
         else:
             self.micro += 1
-        return loss, nll, logp, am
-
-    def _step_features(self, feats, pct, targets, tgt_lens, want_logp: bool = True):
-        m = self.model
-        if self.overlap and (self.world > 1 or self.force_staged):
-            # bucketed SUM all-reduce, launched bucket by bucket in reverse layer order while the units below
-            # are still being differentiated: RCCL runs on its own stream and waits (event) only for the
-            # kernels enqueued so far; the optimiser waits for all buckets.
-            if self.comm is not None:       # library-owned communicator and side stream (lasr_comm_*)
-                loss, nll, logp, am = m.loss_backward_staged(feats, pct, targets, tgt_lens,
-                                                             lambda ranges: self.comm.all_reduce_ranges(m.grads, ranges), want_logp=want_logp)
-                self.comm.wait()
-            else:
-                works = []
-                loss, nll, logp, am = m.loss_backward_staged(
-                    feats, pct, targets, tgt_lens,
-                    lambda ranges: works.extend(torch.distributed.all_reduce(m.grads[lo:hi], group=self.pg, async_op=True)
-                                                for lo, hi in ranges), want_logp=want_logp)
-                for w in works:
-                    w.wait()
-            self._reduced = True
-        else:
-            loss, nll, logp, am = m.loss_backward(feats, pct, targets, tgt_lens, want_logp=want_logp)
-            self._reduced = False
-        self.optimizer_step()
-        return loss, nll, logp, am
+        return out
 
     @staticmethod
     def _prefetch_key(wave, sample_lens, dither, aug):
@@ -406,43 +394,27 @@ class GraphedTrainStep:
                 first_aug: Optional[torch.Tensor] = None) -> None:
         """first_wave: the batch the first replay trains on (prefetch mode: its features are computed eagerly here; not needed
         with bound inputs + feats_in, or when ``prime()`` hands the features over).
-        The eager warm-up passes and the capture pass leave the training state (parameters, BN buffers, optimiser moments,
-        schedule, dither / dropout counters) exactly as it was - also when the capture fails: it is snapshotted before and
-        restored in a ``finally`` (accumulate > 1: the running gradient sum, the micro-batch buffer and the window counter too;
-        with a weight EMA: the average and its device record; with a clip record: that record)."""
+        The eager warm-up passes and the capture pass leave the training state exactly as it was - also when the capture fails:
+        they run inside ``TrainStep.preserved``, which knows what that state is."""
         ts, m = self.ts, self.ts.model
         if ts.world > 1 and not graph_dp_enabled():
             raise RuntimeError("graph capture of the data-parallel step (RCCL inside the graph) is switched off: LASR_GRAPH_DP=0")
         ts.use_device_schedule()
-        dev_state = [m.params, m.buffers, ts.exp_avg, ts.exp_avg_sq, ts.lr_dev] + ([ts._lr_state] if ts._lr_state is not None else [])
-        if ts.accumulate > 1:
-            dev_state += [m.grads, m.grads_micro]
-        if ts.ema is not None:
-            dev_state += [ts.ema, ts.ema_state]       # the average and its update count: the warm-up passes advance both
-        if ts.clip_state is not None:
-            dev_state.append(ts.clip_state)           # the warm-up passes advance its counts
-        micro = ts.micro
-        if hasattr(self.dither, "step"):
-            dev_state.append(self.dither.step)
-        if getattr(m, "drop_step", None) is not None:
-            dev_state.append(m.drop_step)
-        snap = [t.clone() for t in dev_state]
-        sched_sd = dict(ts.schedule.state_dict()) if ts.schedule is not None else None
-        gstep, bump, lr_epoch = ts.global_step, m._bump, ts._lr_epoch
-        counters = {k: v.clone() for k, v in m.counters.items()}
-        f = p_ = None
-        try:
-            if not self.bound and first_wave is not None:
-                self.wave.copy_(first_wave)              # warm-up needs real audio (an all-zero wave has zero variance)
-                if self.lens is not None and first_lens is not None:
-                    self.lens.copy_(first_lens)
-                if self.aug is not None and first_aug is not None:
-                    self.aug.copy_(first_aug)
-            if self.prefetch and self.F_cur is None:
-                f, p_ = ts.features(first_wave, first_lens, None, first_aug, logical_len=self.logical_len)
-                self.F_cur, self.pct_cur = f.clone(), p_.clone()
-            elif self.prefetch and not self.bound and self.feats_out is None:
-                f, p_ = self.F_cur.clone(), self.pct_cur.clone()     # (the warm-up passes overwrite the primed features)
+        if not self.bound and first_wave is not None:
+            self.wave.copy_(first_wave)              # warm-up needs real audio (an all-zero wave has zero variance)
+            if self.lens is not None and first_lens is not None:
+                self.lens.copy_(first_lens)
+            if self.aug is not None and first_aug is not None:
+                self.aug.copy_(first_aug)
+        # the graph's own state: the dither counter, and the first replay's features where the warm-up passes overwrite them
+        own = [self.dither.step] if hasattr(self.dither, "step") else []
+        if self.prefetch and self.F_cur is None:
+            f, p_ = ts.features(first_wave, first_lens, None, first_aug, logical_len=self.logical_len)
+            self.F_cur, self.pct_cur = f.clone(), p_.clone()
+            own += [self.F_cur, self.pct_cur]
+        elif self.prefetch and not self.bound and self.feats_out is None:
+            own += [self.F_cur, self.pct_cur]
+        with ts.preserved(own):
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream(device=m.device)
             side.wait_stream(cur)
@@ -457,22 +429,6 @@ class GraphedTrainStep:
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):            # records the launches; nothing executes
                 self.out = self._body()
             self.graph = graph
-        finally:
-            torch.cuda.synchronize()
-            for t, s_ in zip(dev_state, snap):
-                t.copy_(s_)
-            if f is not None:
-                self.F_cur.copy_(f)
-                self.pct_cur.copy_(p_)
-            if sched_sd is not None:
-                ts.schedule.load_state_dict(sched_sd)
-                ts.lr = ts.schedule.lr
-                ts.schedule._publish()
-            ts.global_step, m._bump, ts._lr_epoch, ts.micro = gstep, bump, lr_epoch, micro
-            m.counters.update(counters)
-            ts._prefetched = None
-            m.disarm_prefetch()
-            torch.cuda.synchronize()
 
     def prime(self, feats: torch.Tensor, pct: torch.Tensor) -> None:
         """the features of the batch the next replay trains on (prefetch mode with the graph's own feature buffers)"""
@@ -507,12 +463,8 @@ class GraphedTrainStep:
         ts.model.bump_counters(1)
         if self.role == "accumulate":
             ts.micro += 1
-            return self.out
-        ts.micro = 0
-        if ts.schedule is not None:
-            ts.lr = ts.schedule.step()
-            ts._lr_epoch = ts.schedule.last_epoch
-        ts.global_step += 1
+        else:
+            ts.count_optimizer_step(advance_device=False)      # (the graph has advanced the device schedule itself)
         return self.out
 
 

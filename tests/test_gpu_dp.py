@@ -204,6 +204,50 @@ def test_device_lr_schedule_matches_host(dev):
     assert sc.cycle >= 2                                   # the range covered at least two restarts
 
 
+def test_schedule_reloaded_between_replays_restarts_the_device_twin_in_place(dev):
+    """``schedule.load_state_dict`` behind the device twin's back, between two steps: the step after it notices, re-uploads the
+    schedule INTO the device state a captured graph holds the address of, and advances it - replayed steps then read, step for step,
+    the rate, the device state and the host position the eager steps read, and land on the same parameters."""
+    from lightning_asr_amd.engine import NativeModel
+    from lightning_asr_amd.schedule import CosineAnnealingWarmupRestarts
+    from lightning_asr_amd.step import GraphedTrainStep, TrainStep
+    batches = [tuple(t.to(dev) for t in _batch(0, s)) for s in range(5)]
+
+    def schedule(steps=0):
+        sc = CosineAnnealingWarmupRestarts(None, first_cycle_steps=50, cycle_mult=2, max_lr=1e-2, min_lr=1e-4, warmup_steps=10, gamma=0.5)
+        for _ in range(steps):
+            sc.step()
+        return sc
+    resumed = dict(schedule(17).state_dict())
+
+    def run(graph):
+        m = NativeModel("plain", 28, mask=True, act="relu", dtype=torch.bfloat16, device=dev)
+        m.init_parameters(seed=9)
+        ts = TrainStep(m, 1e-2, 1e-3, schedule=schedule())
+        ts.use_device_schedule()
+        step = ts.step
+        if graph:
+            g = GraphedTrainStep(ts, B, L, S, prefetch=False, want_logp=True)
+            g.capture(batches[0][0])
+            step = g.step
+        address, seen = ts._lr_state.data_ptr(), []
+        for i, (wave, tg, tl) in enumerate(batches):
+            if i == 2:
+                ts.schedule.load_state_dict(dict(resumed))
+            step(wave, tg, tl)
+            seen.append((ts.lr_dev.clone(), ts._lr_state.clone(), ts.lr, ts.schedule.last_epoch))
+        torch.cuda.synchronize()
+        assert ts._lr_state.data_ptr() == address             # the re-upload wrote in place
+        return seen, m.params.clone()
+    eager, p0 = run(False)
+    replayed, p1 = run(True)
+    assert [s[3] for s in eager] == [1, 2, 18, 19, 20]
+    for (lr0, st0, host0, ep0), (lr1, st1, host1, ep1) in zip(eager, replayed):
+        assert torch.equal(lr0.view(torch.int32), lr1.view(torch.int32)) and torch.equal(st0, st1) and host0 == host1 and ep0 == ep1
+        assert abs(float(lr1) - host1) <= 2e-7 * host1        # the device's rate is the host's, to f32 rounding
+    assert torch.equal(p0, p1)
+
+
 @pytest.mark.parametrize("variant,prefetch", [("plain", True), ("plain", False), ("context_se", True)])
 def test_graphed_step_equals_eager(dev, variant, prefetch):
     """GraphedTrainStep (the step captured into a hipGraph and replayed) against the eager TrainStep on the same batches:
@@ -507,7 +551,7 @@ def _stub_graph_worker(rank, world, port, q):
                 for wave, tg, tl in batches:
                     ts.step(wave, tg, tl)
             else:
-                g = GraphedTrainStep(ts, B, L, S, prefetch=False)
+                g = GraphedTrainStep(ts, B, L, S, prefetch=False, want_logp=True)
                 g.capture(first_wave=batches[0][0])
                 for wave, tg, tl in batches:
                     g.step(wave, tg, tl)
@@ -570,7 +614,7 @@ def test_staged_step_with_real_rccl_replays_from_a_graph_one_rank(dev, monkeypat
             for wave, tg, tl in batches:
                 ts.step(wave, tg, tl)
         else:
-            g = GraphedTrainStep(ts, B, L, S, prefetch=False)
+            g = GraphedTrainStep(ts, B, L, S, prefetch=False, want_logp=True)
             g.capture(first_wave=batches[0][0])
             for wave, tg, tl in batches:
                 g.step(wave, tg, tl)
