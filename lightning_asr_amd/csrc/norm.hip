@@ -587,17 +587,34 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
 // statistics -> apply, nothing in between.  block = 8 column threads (16 bytes each) x 64 row lanes.
 static constexpr int kSlCh = 64, kSlThreads = 512, kSlLanes = 64;
 
+// An empty volatile statement that reads and writes the values in place: the compiler can move no use of them across it, and keeps
+// such statements in program order.
+__device__ __forceinline__ void pin_regs(float (&a)[8]) {
+  asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]));
+}
+__device__ __forceinline__ void pin_regs(uint4& v) {
+  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+  u32x4_t t = {v.x, v.y, v.z, v.w};
+  asm volatile("" : "+v"(t));
+  v = make_uint4(t.x, t.y, t.z, t.w);
+}
+
 // SE (ContextSE units): a chunk is one utterance (rpc = T'), so the excite scale of the thread's 8 channels is a register constant
 // and the partial rows ARE the per-utterance sums P[b][4][C] the excite backward starts from (sums of the gradient at the BN
 // output without the SE factors, as bn_bwd_stats_kernel(per_utt)).
-template <bool HAS2, bool SE, bool NTL = false>
+// RB: rows in flight per thread.  ONE: the chunk holds at most RB rows per row lane (the launcher checks), so there is no row loop:
+// every lane asks for the coefficient vectors and all of its RB rows at entry - clamped addresses, no branch around a load - and
+// no later request waits for an earlier answer (the waits behind the last load count the rows down in the order they were asked
+// for).  The rows are added in the same ascending order as the loop adds them (rb + i * 64), and a row past the
+// chunk adds d * 0, so the partial rows are the same bits (LASR_BN_STATS_BATCH, profiles/bn_stats_batch_ab.txt).
+template <bool HAS2, bool SE, bool NTL = false, int RB = 4, bool ONE = false>
 __global__ __launch_bounds__(512) void bn_bwd_stats_sliced_kernel(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ y,
                                                                   const float* __restrict__ coef, const float* __restrict__ saved,
                                                                   const bf16_t* __restrict__ y2, const float* __restrict__ coef2,
                                                                   const float* __restrict__ saved2, const float* __restrict__ se,
                                                                   float* __restrict__ partials, int rows, int C, int act_rt, int rpc) {
   __shared__ float s_red[8][4][kSlCh];
-  constexpr int V = 8, RB = 4;
+  constexpr int V = 8;
   const int tid = threadIdx.x, cl = tid & 7, rl = tid >> 3, lane = tid & 63, wid = tid >> 6;
   const int c = blockIdx.x * kSlCh + cl * V;
   const int r0 = blockIdx.y * rpc, r1 = min(r0 + rpc, rows);
@@ -616,20 +633,28 @@ __global__ __launch_bounds__(512) void bn_bwd_stats_sliced_kernel(const bf16_t* 
   for (int k = 0; k < 4; ++k)
 #pragma unroll
     for (int j = 0; j < V; ++j) acc[k][j] = 0.f;
-  // (act stays a runtime value here: as a constant the loop body is one basic block, the scheduler overlaps the four rows further and
-  //  the 256-register budget spills - measured equal, 12.0 us either way: the pass waits on memory)
-  const int act = act_rt;
-  for (int rb = r0 + rl; rb < r1; rb += RB * kSlLanes) {
-    uint4 rd[RB], ry[RB], rr[RB];
+  uint4 rd[RB], ry[RB], rr[RB];
+  auto load_rows = [&](int rb) {
 #pragma unroll
     for (int i = 0; i < RB; ++i) {
-      const uint32_t off = (uint32_t)min(rb + i * kSlLanes, rows - 1) * (uint32_t)C + (uint32_t)c;
+      // ONE: a row past the chunk re-reads the chunk's last row, a line the workgroup fetches anyway, not the next chunk's rows
+      const uint32_t off = (uint32_t)min(rb + i * kSlLanes, (ONE ? r1 : rows) - 1) * (uint32_t)C + (uint32_t)c;
       rd[i] = Vec<bf16_t>::raw(dout + off);                     // (written a moment ago by the unit above: default policy)
       ry[i] = Vec<bf16_t>::raw_if_nt<NTL>(y + off);
       if (HAS2) rr[i] = Vec<bf16_t>::raw_if_nt<NTL>(y2 + off);
     }
+  };
+  auto add_rows = [&](int rb, int act) {
 #pragma unroll
     for (int i = 0; i < RB; ++i) {
+      // ONE: one row at a time, the raw vectors of the later rows stay packed (unpacked ahead, the 24 rows do not fit 256 registers).
+      // The empty statements keep their order: the sums of the rows before, then this row's vectors, which nothing unpacks earlier.
+      if (ONE) {
+#pragma unroll
+        for (int k = 0; k < (HAS2 ? 4 : 2); ++k) pin_regs(acc[k]);
+        pin_regs(rd[i]); pin_regs(ry[i]);
+        if (HAS2) pin_regs(rr[i]);
+      }
       float dvi[V], yvi[V], rvi[V];
       Vec<bf16_t>::unpack(rd[i], dvi);
       Vec<bf16_t>::unpack(ry[i], yvi);
@@ -647,6 +672,20 @@ __global__ __launch_bounds__(512) void bn_bwd_stats_sliced_kernel(const bf16_t* 
         }
       }
     }
+  };
+  if constexpr (ONE) {
+    // the activation is chosen once, behind the loads: a runtime `act` inside the rows puts a branch around every element, and
+    // the values that live across those blocks spill
+    const int rb = r0 + rl;
+    load_rows(rb);
+    if (act_rt == LASR_ACT_RELU) add_rows(rb, LASR_ACT_RELU);
+    else if (act_rt == LASR_ACT_SWISH) add_rows(rb, LASR_ACT_SWISH);
+    else add_rows(rb, LASR_ACT_NONE);
+  } else {
+    // (act stays a runtime value here: as a constant the loop body is one basic block, the scheduler overlaps the four rows further and
+    //  the 256-register budget spills - measured equal, 12.0 us either way: the pass waits on memory)
+    const int act = act_rt;
+    for (int rb = r0 + rl; rb < r1; rb += RB * kSlLanes) { load_rows(rb); add_rows(rb, act); }
   }
   // the wave's 8 row lanes (lane bits 3-5), then the 8 waves through LDS in a fixed order
 #pragma unroll
@@ -862,6 +901,7 @@ struct BnSwitches {
   const int sliced = env_int("LASR_BN_SLICED", 256);          // backward pair: workgroups per pass, 0 = the row-major kernels
   const int apply_split = env_int("LASR_BN_APPLY_SPLIT", 2);  // backward apply: its chunks per chunk of the statistics pass
   const int fwd_sliced = env_int("LASR_BN_FWD_SLICED", 0);    // forward apply: workgroups, 0 = the default of 256
+  const int stats_batch = env_int("LASR_BN_STATS_BATCH", 1);  // backward statistics: chunks of <= 8 rows per lane in one load batch, 0 = the row loop
 };
 static const BnSwitches& bn_switches() {
   static const BnSwitches s;
@@ -1092,12 +1132,20 @@ static int bn_bwd_stats_impl(const lasr_bn_tail& t, float* partials, void* strea
   const int nblk = per_utt ? (int)(t.B * cdiv(t.T, kRowsPerBlock)) : (int)cdiv(rows, kRowsPerBlock);
   if (const int rpc = bn_sliced_rpc(t.dtype, rows, C, t.se_scale != nullptr, da.step != nullptr, per_utt, m.sums != nullptr)) {
     const dim3 grid((unsigned)(C / kSlCh), (unsigned)cdiv(rows, rpc));
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(kSlThreads), 0, as_stream(stream), (const bf16_t*)t.dout, (const bf16_t*)m.y, m.coef, m.saved,
+                         (const bf16_t*)r.y, r.coef, r.saved, nullptr, partials, (int)rows, (int)C, t.act, rpc);
+    };
+    // at most 8 rows per row lane (every cfg2 shape but the 1024-channel unit, the 256- and 512-channel shapes of cfg5): one load
+    // batch, no row loop.  Up to 4 rows per lane take a batch of 4: in a batch of 8 the four dead rows cost the 256-channel
+    // launches 2 us each (profiles/bn_stats_batch_ab.txt)
+    const int64_t rpl = cdiv(rpc, kSlLanes);
+    const bool one_batch = bn_switches().stats_batch != 0 && (nt_loads_mask() & 1) == 0 && rpl <= 8;
     with_bool(r.y != nullptr, [&](auto h2) {
-      with_bool((nt_loads_mask() & 1) != 0, [&](auto nt) {
-        hipLaunchKernelGGL((bn_bwd_stats_sliced_kernel<decltype(h2)::value, false, decltype(nt)::value>), grid, dim3(kSlThreads), 0,
-                           as_stream(stream), (const bf16_t*)t.dout, (const bf16_t*)m.y, m.coef, m.saved, (const bf16_t*)r.y, r.coef, r.saved,
-                           nullptr, partials, (int)rows, (int)C, t.act, rpc);
-      });
+      constexpr bool H2 = decltype(h2)::value;
+      if (one_batch && rpl <= 4) launch(bn_bwd_stats_sliced_kernel<H2, false, false, 4, true>);
+      else if (one_batch) launch(bn_bwd_stats_sliced_kernel<H2, false, false, 8, true>);
+      else with_bool((nt_loads_mask() & 1) != 0, [&](auto nt) { launch(bn_bwd_stats_sliced_kernel<H2, false, decltype(nt)::value>); });
     });
     LASR_LAUNCH_CHECK("bn_bwd_stats_sliced_kernel");
     return 0;
