@@ -480,6 +480,42 @@ int lasr_ctc_kws(const float* logp, const int32_t* in_lens, int64_t B, int64_t T
 int lasr_greedy_decode(const int32_t* ids, const int32_t* lens, int64_t B, int64_t T, int blank,
                        int32_t* tokens, int32_t* n_tokens, void* stream);
 
+/* Greedy CTC decode WITH confidences, straight from the log-probs: the collapsed tokens, their frame spans, per-token and
+ * per-utterance confidences.  It replaces the host loop of the reference's pseudo-labelling (ssl_codec/utils.py:8-66, called
+ * from train_ssl.py:223-260 on a (T', C) host copy per utterance): logp is read once, nothing larger than (B, T) is written.
+ *
+ * logp (B, T, C) f32 contiguous, entries finite or -inf (NaN is not supported); lens (B) int32, clamped to [0, T], NULL = T;
+ * blank in [0, C).  For utterance b with Tb frames:
+ *  - frame statistics: m_t = max_c logp[b][t][c] (exact), a_t = the lowest class attaining it - lasr_log_softmax's tie rule, so
+ *    a tie between a label and the blank goes to the smaller id.  A row of -inf only has m_t = -inf, a_t = 0.  Frames t >= Tb
+ *    are never read.
+ *  - collapse (utils/asr_metrics.py:159-166; lasr_greedy_decode on a): frame t emits iff a_t != blank and (t == 0 or
+ *    a_t != a_{t-1}).  Token i is the i-th emitting frame's class; its run is the maximal stretch of consecutive frames with
+ *    that argmax, from the emitting frame on, cut at Tb.
+ *  - per token, each (B, T): tokens = the class, -1 in slots i >= n_tokens[b]; tok_start / tok_end = the run's first frame and
+ *    one past its last, -1 beyond n_tokens; tok_min = min of m_t over the run (exact), 0 beyond n_tokens; tok_mean = the f64
+ *    sum of m_t over the run divided by the run length, rounded once to f32, 0 beyond n_tokens.
+ *  - per utterance: n_tokens (B) int32; utt_sum (B, 2) f64: [0] = sum of m_t over t < Tb, [1] = the same over the frames with
+ *    a_t != blank; n_nonblank (B) int32 = the number of those frames; conf (B, 2) f32:
+ *        conf[k] = f32( -( -1e-5 + utt_sum[k] ) / ( n_k + 1e-6 ) ) evaluated in f64, n_0 = Tb, n_1 = n_nonblank.
+ *    conf[0] is the reference's value: in sum_logprob / seq_sum_logprob_np the test `index == vocab_size` never fires (an
+ *    argmax over C classes is at most C - 1), so blank frames are counted.  conf[1] is what that code evidently meant.
+ *    Smaller is more confident (the reference's sign).  Tb == 0 gives 10.0; -inf propagates by IEEE rules.  The f64 sums are
+ *    taken in an order of the kernel's choosing.
+ * Two launches on `stream` (row statistics over the whole chip into the workspace, 8 * B * T bytes; then one workgroup per
+ * utterance), nothing allocated or synchronised: the call can be captured in a hipGraph.  Refused before any launch: a null
+ * pointer (lens excepted) LASR_E_ARG; blank outside [0, C), B * T >= 2^31, B < 1, T < 1 or C < 1 LASR_E_SHAPE (the workspace
+ * function returns 0); a short workspace LASR_E_WORKSPACE.
+ * lasr_greedy_confidence_frame_tile: the frames the collapse takes per step; lasr_greedy_confidence_narrow_classes: the
+ * largest C whose rows share a wave in the row pass (wider rows take a wave each) - the sizes the tests put their cases at. */
+int64_t lasr_greedy_confidence_frame_tile(void);
+int64_t lasr_greedy_confidence_narrow_classes(void);
+size_t lasr_greedy_confidence_workspace_bytes(int64_t B, int64_t T, int64_t C);
+int lasr_greedy_confidence(const float* logp, const int32_t* lens, int64_t B, int64_t T, int64_t C, int blank,
+                           int32_t* tokens, int32_t* n_tokens, int32_t* tok_start, int32_t* tok_end,
+                           float* tok_mean, float* tok_min, double* utt_sum, int32_t* n_nonblank, float* conf,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* CTC prefix beam search without an external scorer: beam_search.py:17-57 (ctc_decoders' ctc_beam_search_decoder_batch with
  * ext_scoring_func=None).  Per frame the classes ranked by (log-prob desc, id asc) are cut to the shortest leading run whose
  * cumulative probability reaches cutoff_prob (when < 1), then to cutoff_top_n; blank is pruned like any class.  Each prefix

@@ -137,6 +137,10 @@ SIGNATURES = {
     "lasr_ctc_kws_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "lasr_ctc_kws": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _p, _p, _i64, _i64, _f32, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "lasr_greedy_decode": (_i32, [_p, _p, _i64, _i64, _i32, _p, _p, _p]),
+    "lasr_greedy_confidence_frame_tile": (_i64, []),
+    "lasr_greedy_confidence_narrow_classes": (_i64, []),
+    "lasr_greedy_confidence_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "lasr_greedy_confidence": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "lasr_ctc_beam_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32]),
     "lasr_ctc_beam_decode": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _p, _p, _p, _p, _sz, _p]),
     "lasr_arpa_load": (_i32, [C.c_char_p, _p, _i32, C.POINTER(_p)]),

@@ -388,7 +388,9 @@ class AudioParser:
 
 
 class MyAudioDataset(Dataset):
-    def __init__(self, manifest_path: list, labels, max_duration=16.7, mask=False, win_len=0.02, sr=16000):
+    def __init__(self, manifest_path: list, labels, max_duration=16.7, mask=False, win_len=0.02, sr=16000, text_optional=False):
+        """text_optional: a manifest line without "text" is an utterance with the empty transcript (the unlabelled manifest of
+        pseudo-labelling, ``LibriDataModule(pesudo_manifest=...)``); everywhere else such a line fails where its text is read"""
         self.datasets = []
         self.labels = labels
         self.mask = mask
@@ -403,6 +405,8 @@ class MyAudioDataset(Dataset):
                         total_count += 1
                         total_duration += data["duration"]
                         continue
+                    if text_optional:
+                        data.setdefault("text", "")
                     self.datasets.append(data)
             logging.info("过滤音频条数:{:d}条".format(total_count))
             logging.info("过滤音频时长:{:.2f}分钟".format(total_duration / 60))
@@ -486,10 +490,16 @@ class LibriDataModule(LightningDataModule):
     def __init__(self, train_manifest, dev_manifest, test_manifest, labels: list, train_bs=16, dev_bs=16, num_worker=0,
                  train_max_duration=16.7, dev_max_duration=40, device="cuda", act_dtype=torch.float32,
                  bucket_by_length: bool = False, bucket_batches: int = 50, train_crop: bool = True, speed_perturb=None,
-                 noise_manifest=None, noise_prob=0.5, noise_snr_db=(5, 20), noise_max_seconds=600, rir_manifest=None, rir_prob=0.3):
+                 noise_manifest=None, noise_prob=0.5, noise_snr_db=(5, 20), noise_max_seconds=600, rir_manifest=None, rir_prob=0.3,
+                 pesudo_manifest=None):
         super().__init__()
         as_list = lambda m: list(m) if isinstance(m, (list, tuple)) else [m]  # noqa: E731
         self.train_manifest, self.dev_manifest, self.test_manifest = as_list(train_manifest), as_list(dev_manifest), as_list(test_manifest)
+        # the unlabelled manifest of pseudo-label self-training (the reference's spelling, conf/ssl-conf.yaml / train_ssl.py:357;
+        # conf key data.pesudo_manifest, null = off): lines need "audio_filepath" and "duration" only
+        self.pesudo_manifest = as_list(pesudo_manifest) if pesudo_manifest else None
+        self.pesudo_train_datasets = None
+        self._train_base, self._pesudo_injected = None, []
         self.train_bs, self.dev_bs = train_bs, dev_bs
         self.labels = labels
         self.num_worker = num_worker
@@ -524,6 +534,64 @@ class LibriDataModule(LightningDataModule):
         self.train_datasets = MyAudioDataset(self.train_manifest, self.labels, mask=True, max_duration=self.train_max_duration)
         self.dev_datasets = MyAudioDataset(self.dev_manifest, self.labels, max_duration=self.dev_max_duration)
         self.test_datasets = MyAudioDataset(self.test_manifest, self.labels, max_duration=self.dev_max_duration)
+        self._train_base, self._pesudo_injected = list(self.train_datasets.datasets), []
+        if self.pesudo_manifest:           # ssl_data_module.py:240: the unlabelled clips are cut at the DEV duration
+            self.pesudo_train_datasets = MyAudioDataset(self.pesudo_manifest, self.labels, max_duration=self.dev_max_duration,
+                                                        text_optional=True)
+
+    # ---- pseudo-label self-training (ssl_data_module.py:232-281) ------------------------------------------------------------------
+    def pseudo_train_dataloader(self):
+        """the unlabelled clips in manifest order with the eval collate (the reference shuffles them: only the order differs)"""
+        if self.pesudo_train_datasets is None:
+            raise RuntimeError("pseudo_train_dataloader: the data module was built without pesudo_manifest (or setup() has not run)")
+        return self._loader(self.pesudo_train_datasets, self.dev_bs, False)
+
+    def inject_pesudo_datasets(self, datas) -> int:
+        """The pseudo-labelled clips of one round join the training set: `datas` is the reference's [(audio_path, text), ...] or a
+        list of {"audio_filepath", "text", "duration"?, ...} (pseudo_label.label_loader).  They REPLACE the previous round's and
+        stay until the next call; train_dataloader() then serves original + injected.  Dropped with a warning: an entry whose file
+        is missing (as the reference does), and - unlike the reference, which injects them and lets the batch grow - one longer
+        than train_max_duration or with a character outside the labels.  Returns the number injected."""
+        if self._train_base is None:
+            raise RuntimeError("inject_pesudo_datasets: setup() has not run")
+        known = dict((d["audio_filepath"], d.get("duration")) for d in self.pesudo_train_datasets.datasets) \
+            if self.pesudo_train_datasets is not None else {}
+        c2i = self.train_datasets.char2index
+        kept, missing, too_long, bad_text = [], 0, 0, 0
+        for item in datas:
+            if isinstance(item, dict):
+                rec = dict(item)
+            else:
+                path, text = item
+                rec = {"audio_filepath": path, "text": text}
+            path = rec["audio_filepath"]
+            if not os.path.exists(path):
+                logging.warning("伪标签音频路径不存在 " + str(path))
+                missing += 1
+                continue
+            if rec.get("duration") is None:
+                dur = known.get(path)
+                if dur is None:
+                    from .ingest import wav_info
+                    frames, _ch, rate, _bits = wav_info(path)
+                    dur = frames / float(rate)
+                rec["duration"] = float(dur)
+            if self.train_max_duration and rec["duration"] > self.train_max_duration:
+                too_long += 1
+                continue
+            if any(ch not in c2i for ch in rec["text"]):
+                bad_text += 1
+                continue
+            kept.append(rec)
+        if missing or too_long or bad_text:
+            logging.warning("pseudo labels dropped: %d missing files, %d longer than train_max_duration, %d with unknown characters",
+                            missing, too_long, bad_text)
+        self._pesudo_injected = kept
+        ds = self.train_datasets
+        ds.datasets = self._train_base + kept
+        for cached in ("_lasr_ids_cache", "_lasr_fast_ingest_ok"):      # per-entry caches of the native ingest: the entries changed
+            ds.__dict__.pop(cached, None)
+        return len(kept)
 
     def _loader(self, ds, bs, train, distributed=None):
         if train and getattr(self, "bucket_by_length", False):

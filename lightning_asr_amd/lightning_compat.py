@@ -165,7 +165,8 @@ class Trainer:
                  callbacks=None, logger=None, save_top_k: int = 3, monitor: str = "val_wer", max_steps: Optional[int] = None,
                  device: Optional[str] = None, log_every_n_steps: int = 50, accumulate_grad_batches: int = 1,
                  ema_decay: float = 0.0, ema_warmup: bool = True, ema_eval: bool = True, gradient_clip_val: float = 0,
-                 gradient_clip_algorithm: str = "norm", skip_nonfinite_steps: bool = False, track_grad_norm: bool = False, **ignored):
+                 gradient_clip_algorithm: str = "norm", skip_nonfinite_steps: bool = False, track_grad_norm: bool = False, pseudo_label=None,
+                 **ignored):
         from .scheduler.novograd import check_ema_decay, check_grad_clip
         from .step import check_accumulate
         # weight EMA ("Weight EMA"): the module's configure_optimizers hands ema_decay / ema_warmup to Novograd, which then
@@ -175,6 +176,9 @@ class Trainer:
         # way, so both routes of fit get them; track_grad_norm publishes grad_norm / grad_clip_coef / skipped_steps in callback_metrics
         self.gradient_clip_val, self.gradient_clip_algorithm = check_grad_clip(gradient_clip_val, gradient_clip_algorithm)
         self.skip_nonfinite_steps, self.track_grad_norm = bool(skip_nonfinite_steps), bool(track_grad_norm)
+        # pseudo-label self-training ("Self-training"): a pseudo_label.PseudoLabelConfig, or None = off - fit then does
+        # exactly what it does without the keyword
+        self.pseudo_label = pseudo_label
         self._skips_seen = 0                            # skipped_steps at the last read (the first growth is logged)
         self._opt = None                                # the optimiser of the last fit: where validate / test find the average
         self.max_epochs, self.max_steps = max_epochs, max_steps
@@ -408,6 +412,18 @@ class Trainer:
             rec = {"epoch": epoch, "global_step": self.global_step, "train_time_s": time.time() - t0,
                    "lr": opt.param_groups[0]["lr"]}
             rec.update({k: float(np.mean(v)) for k, v in self._epoch_metrics.items()})
+            if self.pseudo_label is not None:
+                from .pseudo_label import round_due, run_round
+                if round_due(epoch, self.pseudo_label):
+                    # train_ssl.py:223-260: after the epoch's training, before its validation.  The loader is rebuilt, so the next
+                    # epoch's len(loader), the fused loop's source and the bucket sampler see the new set; the LR schedule keeps
+                    # the first_cycle_steps configure_optimizers computed, as in the reference
+                    rec.update(run_round(model, self, datamodule, self.pseudo_label))
+                    loader = datamodule.train_dataloader()
+                    if self.world > 1:
+                        loader = datamodule.train_dataloader(distributed=(self.world, self.rank))
+                    if fused is not None:
+                        fused._ws_reserved = False          # (the injected transcripts may be longer than any original)
             if (epoch + 1) % self.check_val_every_n_epoch == 0:
                 rec.update(self.validate(model, datamodule))
             self.history.append(rec)

@@ -567,7 +567,69 @@ def greedy_decode(ids: torch.Tensor, lens: Optional[torch.Tensor], blank: int):
     return tokens, n
 
 
-CTC_BEAM_MAX_WIDTH = 128      # lasr_ctc_beam_decode's supported range (include/lasr.h)
+class GreedyConfidence(NamedTuple):
+    tokens: torch.Tensor         # (B, T) i32 collapsed classes, -1 from n_tokens on
+    n_tokens: torch.Tensor       # (B,) i32
+    tok_start: torch.Tensor      # (B, T) i32 first frame of token i's run, -1 from n_tokens on
+    tok_end: torch.Tensor        # (B, T) i32 one past its last frame
+    tok_mean: torch.Tensor       # (B, T) f32 mean of the frame maxima over the run, 0 from n_tokens on
+    tok_min: torch.Tensor        # (B, T) f32 their minimum
+    utt_sum: torch.Tensor        # (B, 2) f64 sum of the frame maxima over [all frames, frames whose argmax is a label]
+    n_nonblank: torch.Tensor     # (B,) i32 frames whose argmax is a label
+    conf: torch.Tensor           # (B, 2) f32 [reference confidence, the same over label frames only]; smaller = more confident
+
+
+def greedy_confidence_frame_tile() -> int:
+    """frames the collapse of greedy_confidence takes per step (the sizes its tests sit at)"""
+    return int(_lib.load().lasr_greedy_confidence_frame_tile())
+
+
+def greedy_confidence_narrow_classes() -> int:
+    """the largest class count whose rows share a wave in greedy_confidence's row pass"""
+    return int(_lib.load().lasr_greedy_confidence_narrow_classes())
+
+
+def greedy_confidence(logp: torch.Tensor, lens: Optional[torch.Tensor], blank: int) -> GreedyConfidence:
+    """Greedy CTC decode of logp (B, T, C) f32 with token spans and confidences (include/lasr.h lasr_greedy_confidence), lens
+    (B) i32 or None (= T).  Two launches, nothing synchronised; outputs as in GreedyConfidence."""
+    if logp.dim() != 3 or logp.dtype != torch.float32:
+        raise ValueError("greedy_confidence takes (B, T, C) float32 log-probs")
+    B, T, Cc = logp.shape
+    if lens is not None and (lens.shape != (B,) or lens.dtype != torch.int32):
+        raise ValueError("greedy_confidence: lens must be (B,) int32")
+    dev = logp.device
+    ptrs = [_p(logp), _p(lens)]                                         # CPU tensors are refused here, before anything is allocated
+    i32 = dict(dtype=torch.int32, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = GreedyConfidence(torch.empty(B, T, **i32), torch.empty(B, **i32), torch.empty(B, T, **i32), torch.empty(B, T, **i32),
+                           torch.empty(B, T, **f32), torch.empty(B, T, **f32), torch.empty(B, 2, dtype=torch.float64, device=dev),
+                           torch.empty(B, **i32), torch.empty(B, 2, **f32))
+    nb = int(_lib.load().lasr_greedy_confidence_workspace_bytes(B, T, Cc))
+    ws = _ws(nb, dev)
+    call("lasr_greedy_confidence", ptrs[0], ptrs[1], B, T, Cc, int(blank), _p(out.tokens), _p(out.n_tokens), _p(out.tok_start),
+         _p(out.tok_end), _p(out.tok_mean), _p(out.tok_min), _p(out.utt_sum), _p(out.n_nonblank), _p(out.conf), _p(ws), nb, _stream())
+    return out
+
+
+def hyp_neg_logprob(logp: torch.Tensor, lens: Optional[torch.Tensor], tokens: torch.Tensor, n_tokens: torch.Tensor,
+                    blank: int, max_tokens: Optional[int] = None) -> torch.Tensor:
+    """The "posterior" confidence of a hypothesis: ctc_loss of logp (B, T, C) against each utterance's own tokens (B, T) i32 /
+    n_tokens (B) i32 (as greedy_confidence writes them), i.e. minus the log of the total probability of ALL its alignments,
+    divided by (Tb + 1e-6): per frame, comparable with GreedyConfidence.conf[:, 0] under one threshold.  An empty hypothesis
+    scores -sum_t logp[t][blank] / (Tb + 1e-6).  max_tokens: the largest n_tokens when the caller knows it (a narrower label
+    matrix; the result is the same); hypotheses of more than CTC_MAX_LABELS tokens are not supported.  Returns (B,) f32;
+    nothing synchronised."""
+    B, T, _ = logp.shape
+    if lens is None:
+        lens = torch.full((B,), T, dtype=torch.int32, device=logp.device)
+    S = min(T if max_tokens is None else int(max_tokens), T, CTC_MAX_LABELS)
+    # slots past n_tokens hold -1: the loss reads only the first n_tokens labels of a row, so any valid label does there
+    tg = tokens[:, :max(S, 1)].clamp(min=0).to(torch.int64).contiguous()
+    nll, _ = ctc_loss(logp, tg, lens, n_tokens.contiguous(), int(blank), want_grad=False)
+    return nll / (lens.clamp(0, T).to(torch.float32) + 1e-6)
+
+
+CTC_BEAM_MAX_WIDTH = 128     # lasr_ctc_beam_decode's supported range (include/lasr.h)
 CTC_BEAM_MAX_TOP_N = 64
 CTC_BEAM_MAX_CLASSES = 8192
 

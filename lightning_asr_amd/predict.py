@@ -349,6 +349,53 @@ class AsrTranslator:
             return "", []
         return text, self._align_ids(out, self.text_to_ids(text), duration)
 
+    # ------------------------------------------------------------------------------------------ pseudo labels, confidences
+    @torch.no_grad()
+    def pseudo_label_manifest(self, manifest: str, out_path: str, threshold: float = 0.01, measure: str = "ref", batch_size: int = 32,
+                              min_tokens: int = 1) -> dict:
+        """Label an unlabelled manifest (JSON lines with audio_filepath and duration; a "text" is ignored) with the greedy
+        hypotheses that are confident enough (``pseudo_label.label_loader``: measure <= threshold, at least min_tokens tokens) and
+        write them to out_path as a training-format manifest with an extra "confidence" key.  Returns {"pseudo_seen",
+        "pseudo_count", "pseudo_fraction"}.  The default threshold is the reference's constant; nobody has tuned it here."""
+        from .pseudo_label import PseudoLabelConfig, label_loader
+        if self.resample:
+            self._require_16k(manifest, "pseudo_label_manifest")
+        cfg = PseudoLabelConfig(manifest=manifest, start_epoch=0, every_n_epochs=1, threshold=threshold, measure=measure,
+                                min_tokens=min_tokens, batch_size=batch_size)
+        model = self.model
+        dev = model.encoder.native.device
+        dm = LibriDataModule(train_manifest=manifest, dev_manifest=manifest, test_manifest=manifest, dev_bs=batch_size, num_worker=0,
+                             labels=self.labels, device=str(dev), act_dtype=model.encoder.native.act_dtype, pesudo_manifest=manifest)
+        trainer = Trainer(gpus=1, device=str(dev))
+        model.trainer = trainer
+        dm.trainer = trainer
+        dm.setup("test")
+        selected, stats = label_loader(model, trainer, dm, dm.pseudo_train_dataloader(), cfg)
+        with open(out_path, "w", encoding="utf-8") as f:
+            for rec in selected:
+                f.write(json.dumps(rec, ensure_ascii=False) + "\n")
+        return stats
+
+    @torch.no_grad()
+    def utterance_confidence(self, audio_path, resample: Optional[bool] = None) -> dict:
+        """The greedy hypothesis of one audio file with its confidences (``ops.greedy_confidence``): {"text", "ref", "nonblank",
+        "posterior" (the three utterance measures of pseudo_label.PseudoLabelConfig; smaller = more confident), "tokens":
+        [{"label", "start", "end" (seconds), "mean", "min" (of the frame maxima over the token's run, log-probs)}, ...]}."""
+        out, duration = self._encode_file(audio_path, resample)
+        logp = out.float().contiguous()
+        blank = len(self.labels)
+        gc = ops.greedy_confidence(logp, None, blank)
+        post = ops.hyp_neg_logprob(logp, None, gc.tokens, gc.n_tokens, blank)
+        n = int(gc.n_tokens[0])
+        secs = self.frame_seconds()
+        ids, st, en = gc.tokens[0, :n].tolist(), gc.tok_start[0, :n].tolist(), gc.tok_end[0, :n].tolist()
+        mean, mn = gc.tok_mean[0, :n].tolist(), gc.tok_min[0, :n].tolist()
+        conf = gc.conf[0].tolist()
+        return {"text": "".join(self.labels[int(c)] for c in ids), "ref": float(conf[0]), "nonblank": float(conf[1]),
+                "posterior": float(post[0]),
+                "tokens": [{"label": self.labels[int(c)], "start": min(s * secs, duration), "end": min(e * secs, duration),
+                            "mean": float(a), "min": float(b)} for c, s, e, a, b in zip(ids, st, en, mean, mn)]}
+
     # ------------------------------------------------------------------------------------------ long recordings
     def _segment_batch(self, wave: torch.Tensor, segs):
         """segments [(start, end), ...] in samples of the (L,) device wave -> (log-probs (n, T', C), frames (n,) int32): one gather

@@ -198,11 +198,20 @@ def main(argv=None):
                                   speed_perturb=data_cfg.get("speed_perturb", None),
                                   noise_manifest=data_cfg.get("noise_manifest", None), noise_prob=data_cfg.get("noise_prob", 0.5),
                                   noise_snr_db=data_cfg.get("noise_snr_db", (5, 20)), noise_max_seconds=data_cfg.get("noise_max_seconds", 600),
-                                  rir_manifest=data_cfg.get("rir_manifest", None), rir_prob=data_cfg.get("rir_prob", 0.3))
+                                  rir_manifest=data_cfg.get("rir_manifest", None), rir_prob=data_cfg.get("rir_prob", 0.3),
+                                  pesudo_manifest=data_cfg.get("pesudo_manifest", None))
     model = LightingModule(learning_rate=tran_cfg.get("learning_rate"), weight_decay=tran_cfg.get("weight_decay"), labels=labels,
                            total_epoch=tran_cfg.get("total_epoch"), drop_rate=model_cfg.get("drop_rate"), mask=model_cfg.get("mask"),
                            use_cer=use_cer, variant=model_cfg.get("variant", "plain"), act=model_cfg.get("act", "relu"), dtype=dtype,
                            warmup_steps=tran_cfg.get("warmup_steps", 1000), device=device)
+    pseudo = None
+    if data_cfg.get("pesudo_manifest", None):           # train_ssl.py:223-260 on the mel path ("Self-training")
+        from .pseudo_label import PseudoLabelConfig
+        pseudo = PseudoLabelConfig(manifest=data_cfg.get("pesudo_manifest"), start_epoch=int(tran_cfg.get("pseudo_start_epoch", 300)),
+                                   every_n_epochs=int(tran_cfg.get("pseudo_every_n_epochs", 7)),
+                                   threshold=float(tran_cfg.get("pseudo_threshold", 0.01)),
+                                   measure=str(tran_cfg.get("pseudo_measure", "ref")),
+                                   min_tokens=int(tran_cfg.get("pseudo_min_tokens", 1)))
     trainer = Trainer(gpus=tran_cfg.get("gpus"), resume_from_checkpoint=tran_cfg.get("checkpoint"), accelerator=tran_cfg.get("accelerator"),
                       max_epochs=tran_cfg.get("total_epoch"), check_val_every_n_epoch=tran_cfg.get("check_val_every_n_epoch", 1),
                       num_nodes=tran_cfg.get("num_nodes"), default_root_dir=cfg.get("output_dir", "."),
@@ -213,7 +222,7 @@ def main(argv=None):
                       gradient_clip_val=tran_cfg.get("gradient_clip_val", 0) or 0.0,
                       gradient_clip_algorithm=tran_cfg.get("gradient_clip_algorithm", "value"),
                       skip_nonfinite_steps=tran_cfg.get("skip_nonfinite_steps", False),
-                      track_grad_norm=tran_cfg.get("track_grad_norm", False))
+                      track_grad_norm=tran_cfg.get("track_grad_norm", False), pseudo_label=pseudo)
     trainer.fit(model, datamodule=data_module)
     trainer.test(model, test_dataloaders=data_module.test_dataloader())
     return trainer
