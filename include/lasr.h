@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LASR_VERSION 118   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
+#define LASR_VERSION 119   /* 101: lasr_mel_fwd_src / lasr_wav_read_batch / lasr_step_metrics / lasr_model_set_prefetch_src
                               102: LASR_LEN_LEAD (crop after pre-emphasis), lasr_wav_read_batch(lead_in), lasr_comm_timing*
                               103: lasr_ctc_beam_workspace_bytes / lasr_ctc_beam_decode (CTC prefix beam search)
                               104: lasr_arpa_* (ARPA n-gram LM), lasr_ctc_beam_decode_lm (beam search fused with it)
@@ -42,7 +42,8 @@ extern "C" {
                               115: lasr_bn_tail / lasr_bn_side / lasr_se_side: the BN entry points take one record; the _drop twins are gone
                               116: lasr_ema_state_bytes / lasr_ema_state_init / lasr_novograd_step_ema / lasr_ema_update (weight EMA)
                               117: lasr_clip_state_bytes / lasr_clip_state_init / lasr_novograd_step_clip (gradient clipping, non-finite guard)
-                              118: lasr_ctc_beam_stream_* (resumable beam search: a sequence decoded chunk by chunk) */
+                              118: lasr_ctc_beam_stream_* (resumable beam search: a sequence decoded chunk by chunk)
+                              119: lasr_ctc_align_long* (banded forced alignment of long recordings) */
 
 enum { LASR_F32 = 0, LASR_BF16 = 1 };
 enum { LASR_ACT_NONE = 0, LASR_ACT_RELU = 1, LASR_ACT_SWISH = 2 };
@@ -434,6 +435,42 @@ int lasr_ctc_align(const float* logp, const int64_t* targets, const int32_t* in_
                    int64_t B, int64_t T, int64_t C, int64_t S_max, int blank, float* score, int32_t* frame_state,
                    float* frame_logp, int32_t* label_start, int32_t* label_end, void* workspace, size_t workspace_bytes,
                    void* stream);
+
+/* Forced alignment of LONG recordings: lasr_ctc_align on a band of `band` = W states that follows the path, for transcripts far
+ * above LASR_CTC_MAX_LABELS (an hour of speech is T ~ 180 000 frames and ~50 000 labels; its full lattice is 1.8e10 cells).  One
+ * launch of one workgroup per recording on `stream`; nothing is allocated or synchronised, so the call can be captured.
+ * The lattice, the emission rule, the max, the tie rule (stay, then step, then skip), the end rule, the dead-state convention and
+ * the outputs score / frame_state / frame_logp / label_start / label_end are those of lasr_ctc_align, word for word.  The band:
+ *   W is a multiple of 256 in [256, 4096] or a multiple of 1024 up to LASR_CTC_ALIGN_LONG_MAX_BAND.  G = 64 states
+ *   (lasr_ctc_align_long_granule), R = 32 frames (lasr_ctc_align_long_period).
+ *   Frame t keeps states [lo_t, lo_t + W).  lo_0 = 0; lo changes only at frames t0 that are positive multiples of R.  There
+ *     a      = the live state (value above -5e29, state below 2S+1) of row t0-1 with the largest value, the lowest state on ties;
+ *              lo_prev when no state is live
+ *     centre = floor((a - W/2) / G) * G
+ *     reach  = ceil((s_min(te) - (W-1)) / G) * G with te = min(t0 + R - 1, Tb - 1) and s_min(t) = 2S-1 - 2 (Tb-1-t), the lowest
+ *              state from which the end can still be reached
+ *     lo     = min(max(lo_prev, centre, reach), ceil(max(0, 2S+1 - W) / G) * G)
+ *   A candidate read from a state outside the previous frame's band is dead; states >= 2S+1 are dead.  W/2 - G >= 2R: a path that
+ *   advances two states per frame for a whole period stays inside the band above the argmax.
+ *   A band of at least 2S+1 states never moves and the result is lasr_ctc_align's, bit for bit.  A narrower band prunes: it can
+ *   return a feasible path that is not the best one, without any flag, or lose every path (status 2).
+ * status (B) int32: 0 aligned; 1 infeasible by count (Tb < S + adjacent equal labels, or Tb == 0 < S); 2 lost (feasible by count,
+ * but neither end state is live in the last frame's band).  On 1 and 2 the other outputs are the infeasible ones of
+ * lasr_ctc_align.  band_lo (B, T) int32: lo_t for t < Tb (by the rule above whatever the status), -1 from Tb on.
+ * S_max <= LASR_CTC_ALIGN_LONG_MAX_LABELS; every offset into logp, the outputs and the workspace is 64-bit (no T * C < 2^31 bound).
+ * The workspace holds the backpointers, 2 bits per banded state: W / 4 bytes per frame (an hour at W = 4096: about 180 MB).
+ * Before any launch: a null pointer (or a workspace that is not 4-byte aligned) LASR_E_ARG; a band, blank, S_max or shape outside
+ * the above LASR_E_SHAPE; a workspace below lasr_ctc_align_long_workspace_bytes (0 for arguments the call refuses)
+ * LASR_E_WORKSPACE. */
+#define LASR_CTC_ALIGN_LONG_MAX_LABELS (1 << 24)
+#define LASR_CTC_ALIGN_LONG_MAX_BAND 8192
+int64_t lasr_ctc_align_long_period(void);
+int64_t lasr_ctc_align_long_granule(void);
+size_t lasr_ctc_align_long_workspace_bytes(int64_t B, int64_t T, int64_t S_max, int64_t band);
+int lasr_ctc_align_long(const float* logp, const int64_t* targets, const int32_t* in_lens, const int32_t* tgt_lens,
+                        int64_t B, int64_t T, int64_t C, int64_t S_max, int blank, int64_t band, float* score,
+                        int32_t* frame_state, float* frame_logp, int32_t* label_start, int32_t* label_end, int32_t* status,
+                        int32_t* band_lo, void* workspace, size_t workspace_bytes, void* stream);
 
 /* CTC keyword search: where in each utterance is each of K phrases said, and how well?  The third member of the lattice family:
  * a max-product walk like lasr_ctc_align's, with a free start and a free end.  One wave per (utterance, keyword) pair, the

@@ -134,6 +134,10 @@ SIGNATURES = {
                                  _p, _p, _p, _p, _i64, _i64, _i32, _p, _p, _i32, _p, _p, _p, _sz, _p]),
     "lasr_ctc_align_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "lasr_ctc_align": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "lasr_ctc_align_long_period": (_i64, []),
+    "lasr_ctc_align_long_granule": (_i64, []),
+    "lasr_ctc_align_long_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "lasr_ctc_align_long": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "lasr_ctc_kws_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "lasr_ctc_kws": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _p, _p, _i64, _i64, _f32, _i32, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "lasr_greedy_decode": (_i32, [_p, _p, _i64, _i64, _i32, _p, _p, _p]),

@@ -166,7 +166,7 @@ __device__ __forceinline__ void ctc_label_chain(const int32_t* s_tg, int S, int 
 // ---- the emission stream: advance(em) once per step 1 .. Tb-1 (alpha: t = step, beta: t = Tb - 1 - step) with em[] the
 // emissions of the lane's states at t.  lp: the utterance's emission matrix; s_rows (EM_LDS): the same in LDS, row t at
 // s_rows + t * C with a pad row on either side (ctc_fill_emissions).  Every wave of a workgroup passes the same Tb.
-template <int NS, bool EM_LDS, bool BETA, class Step>
+template <int NS, bool EM_LDS, bool BETA, int kPre = 8, class Step>
 __device__ __forceinline__ void ctc_for_each_step(const float* __restrict__ lp, const float* s_rows, const int (&cls4)[NS], int Tb, int C,
                                                   Step&& advance) {
   const int t_first = BETA ? Tb - 1 : 0;
@@ -189,8 +189,8 @@ __device__ __forceinline__ void ctc_for_each_step(const float* __restrict__ lp, 
   } else {
     // Emissions are fetched kPre steps ahead into a register ring.  On CDNA4 s_waitcnt vmcnt counts
     // stores as well as loads, in issue order: with a one-step prefetch every step would also wait for
-    // the previous step's stores (lattice rows, backpointer dwords) to retire (~0.7 us).  Eight steps of slack hide both.
-    constexpr int kPre = 8;
+    // the previous step's stores (lattice rows, backpointer dwords) to retire (~0.7 us).  Eight steps of slack hide both (kPre:
+    // the ring is kPre * NS registers; ctc_align_long.hip's eight-wave form has room for four steps).
     float ring[kPre][NS];
 #pragma unroll
     for (int u = 0; u < kPre; ++u)

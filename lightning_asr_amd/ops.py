@@ -474,6 +474,82 @@ def ctc_align(logp: torch.Tensor, targets: torch.Tensor, in_lens: Optional[torch
     return out
 
 
+CTC_ALIGN_LONG_MAX_LABELS = 1 << 24   # LASR_CTC_ALIGN_LONG_MAX_LABELS (include/lasr.h)
+CTC_ALIGN_LONG_MAX_BAND = 8192        # LASR_CTC_ALIGN_LONG_MAX_BAND: the widest band of ctc_align_long
+
+
+class CtcAlignmentLong(NamedTuple):
+    score: torch.Tensor          # the fields of CtcAlignment ...
+    frame_state: torch.Tensor
+    frame_logp: torch.Tensor
+    label_start: torch.Tensor
+    label_end: torch.Tensor
+    status: torch.Tensor         # (B,) i32: 0 aligned, 1 infeasible by count, 2 lost by the band
+    band_lo: torch.Tensor        # (B, T) i32: the band's first state in every frame, -1 past in_lens
+
+
+def ctc_align_long_period() -> int:
+    """R: the band of ctc_align_long can move only at frames that are multiples of it"""
+    return int(_lib.load().lasr_ctc_align_long_period())
+
+
+def ctc_align_long_granule() -> int:
+    """G: the band origin of ctc_align_long is a multiple of it"""
+    return int(_lib.load().lasr_ctc_align_long_granule())
+
+
+def ctc_align_long_band_at_least(n: int) -> Optional[int]:
+    """the narrowest band ctc_align_long takes that holds at least n states (a multiple of 256 up to 4096, of 1024 up to
+    CTC_ALIGN_LONG_MAX_BAND), or None when n is above the widest"""
+    n = max(int(n), 256)
+    band = -(-n // 256) * 256 if n <= 4096 else -(-n // 1024) * 1024
+    return band if band <= CTC_ALIGN_LONG_MAX_BAND else None
+
+
+def ctc_align_long(logp: torch.Tensor, targets: torch.Tensor, in_lens: Optional[torch.Tensor], tgt_lens: torch.Tensor,
+                   blank: int, band: int = 4096) -> CtcAlignmentLong:
+    """ctc_align for long recordings (include/lasr.h lasr_ctc_align_long): the Viterbi path inside a band of `band` states that
+    follows it, so targets (B,S) may be far wider than CTC_MAX_LABELS and T * C is not bounded by 2^31.  band: a multiple of 256 up
+    to 4096 or a multiple of 1024 up to CTC_ALIGN_LONG_MAX_BAND.  With band >= 2 S + 1 the result is ctc_align's bit for bit; a
+    narrower band prunes - it may return a feasible path that is not the best one without any flag, or none (status 2).  One
+    launch, nothing synchronised, except for the host-side label check of ctc_align (skipped during graph capture)."""
+    if logp.dim() != 3 or logp.dtype != torch.float32:
+        raise ValueError("ctc_align_long takes (B, T, C) float32 log-probs")
+    B, T, Cc = logp.shape
+    if targets.dim() != 2 or targets.shape[0] != B or targets.dtype != torch.int64:
+        raise ValueError("ctc_align_long: targets must be (B, S) int64")
+    S = targets.shape[1]
+    if S > CTC_ALIGN_LONG_MAX_LABELS:
+        raise ValueError("ctc_align_long: targets are %d labels wide; the kernel takes at most %d" % (S, CTC_ALIGN_LONG_MAX_LABELS))
+    for name, t in (("in_lens", in_lens), ("tgt_lens", tgt_lens)):
+        if t is None and name == "in_lens":
+            continue
+        if t is None or t.shape != (B,) or t.dtype != torch.int32:
+            raise ValueError("ctc_align_long: %s must be (B,) int32" % name)
+    if B < 1 or T < 1 or not 0 <= blank < Cc or Cc < 2:
+        raise ValueError("ctc_align_long: shape (%d, %d, %d) with blank %d" % (B, T, Cc, blank))
+    band = int(band)
+    nb = int(_lib.load().lasr_ctc_align_long_workspace_bytes(B, T, S, band))
+    if nb == 0:
+        raise ValueError("ctc_align_long: band %d is not a multiple of 256 up to 4096 or of 1024 up to %d" % (band, CTC_ALIGN_LONG_MAX_BAND))
+    if S > 0 and not (logp.is_cuda and torch.cuda.is_current_stream_capturing()):
+        live = torch.arange(S, device=targets.device).unsqueeze(0) < tgt_lens.unsqueeze(1)
+        bad = live & ((targets == blank) | (targets < 0) | (targets >= Cc))
+        if bool(bad.any()):
+            b, i = [int(v) for v in bad.nonzero()[0]]
+            raise ValueError("ctc_align_long: targets[%d][%d] = %d is the blank or outside [0, %d)" % (b, i, int(targets[b, i]), Cc))
+    dev = logp.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = CtcAlignmentLong(torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, T, **i32),
+                           torch.empty(B, T, dtype=torch.float32, device=dev), torch.empty(B, S, **i32), torch.empty(B, S, **i32),
+                           torch.empty(B, **i32), torch.empty(B, T, **i32))
+    ws = _ws(nb, dev)
+    call("lasr_ctc_align_long", _p(logp), _p(targets) if S else None, _p(in_lens), _p(tgt_lens), B, T, Cc, S, int(blank), band,
+         _p(out.score), _p(out.frame_state), _p(out.frame_logp), _p(out.label_start) if S else None, _p(out.label_end) if S else None,
+         _p(out.status), _p(out.band_lo), _p(ws), nb, _stream())
+    return out
+
+
 KWS_MAX_LABELS = 64     # LASR_KWS_MAX_LABELS (include/lasr.h): the longest phrase of a keyword bank
 
 

@@ -5,6 +5,7 @@ file: a character LM, or - the labels having exactly one " ", as EN_LABELS has -
 ``error_report`` splits a manifest's WER / CER into substitutions, deletions and insertions (``ops.edit_ops_batch``: the aligned reference and hypothesis of every utterance, the most confused pairs).
 ``translate_long`` takes a recording of any length: cut into utterances on the device (``ops.vad_segments``), decoded in batches, times relative to the recording.
 ``align`` / ``translate_timed`` / ``align_manifest`` add word timings: the CTC forced alignment of a known transcript (or of the decoder's own hypothesis) to the audio, ``ops.ctc_align`` + the record functions of align.py.
+``encode_long`` / ``align_long`` / ``cut_corpus`` go the other way at scale: the log-probs of a whole recording (overlapping windows, batched), the banded forced alignment of its transcript (``ops.ctc_align_long``), and utterance wavs + a training manifest cut from it.
 ``find_keywords`` / ``find_keywords_long`` / ``keyword_scores`` spot phrases in the frame posteriors with time spans and scores, without decoding: ``ops.ctc_keyword_search`` + the record functions of kws.py.
 
 The checkpoint is the PL-style dict the reference's ``ModelCheckpoint`` writes and ``Trainer`` here
@@ -495,6 +496,178 @@ class AsrTranslator:
         result["segments"] = records
         result["text"] = (" " if " " in self.labels else "").join(r["text"] for r in records)
         return result
+
+    # ------------------------------------------------------------------------------------------ long recordings with a transcript
+    def _load_wave(self, audio_path, resample: Optional[bool] = None):
+        """one audio file -> (wave (L,) f32 on the device at the parser's rate, duration in seconds), as translate_long loads it"""
+        if isinstance(audio_path, str) and not os.path.exists(audio_path):
+            raise Exception("音频路径不存在 " + audio_path)
+        if self._resample(resample):
+            y, rate = load_wav_rate(audio_path)
+            duration = y.shape[1] / float(rate)
+            y = self.audio_parser.resample_to_sr(y, rate)
+        else:
+            y = load_wav(audio_path)
+            duration = y.shape[1] / float(self.audio_parser.sr)
+        return y[0].to(self.device).contiguous(), duration
+
+    def _encode_wave_long(self, wave: torch.Tensor, window_s: float = 20.0, context_s: float = 4.0, batch_size: int = 8,
+                          dither: bool = False) -> torch.Tensor:
+        """encode_long on the (L,) device wave"""
+        from . import streaming
+        from .align import window_batches, window_frame_offsets
+        sr = int(self.audio_parser.sr)
+        if sr != 16000 or self.audio_parser.hop_length != streaming.HOP:
+            raise ValueError("encode_long takes 16 kHz audio at hop %d" % streaming.HOP)
+        native = self.model.encoder.native
+        out_frames = lambda n_mel: int(native.out_frames(int(n_mel)))
+        if out_frames(2 * 4096 + 1) - out_frames(4096 + 1) != 4096 // streaming.STRIDE:
+            raise ValueError("encode_long is written for a model of time stride %d" % streaming.STRIDE)
+        to_samples = lambda s: int(round(float(s) * sr / streaming.FRAME)) * streaming.FRAME
+        chunk, ctx = to_samples(window_s), to_samples(context_s)
+        if chunk <= 0 or ctx < 0:
+            raise ValueError("encode_long: window_s must be at least one frame, context_s not negative")
+        if int(batch_size) < 1:
+            raise ValueError("encode_long: batch_size must be at least 1")
+        total = int(wave.numel())
+        n_classes = len(self.labels) + 1
+        windows = streaming.plan_windows(total, True, chunk, ctx, ctx, 0, out_frames)
+        T = streaming.total_frames(total, out_frames)
+        offs = window_frame_offsets(windows, T, streaming.FRAME)
+        logp = torch.empty(T, n_classes, dtype=torch.float32, device=self.device)
+        for batch in window_batches(windows, batch_size):
+            length = windows[batch[0]][1] - windows[batch[0]][0]
+            rows = torch.zeros(len(batch), max(length, MIN_ROW_SAMPLES), dtype=torch.float32, device=self.device)
+            for r, i in enumerate(batch):
+                rows[r, :length] = wave[windows[i][0]:windows[i][1]]
+            lens = torch.full((len(batch),), length, dtype=torch.int32, device=self.device)
+            inputs, pct = self.audio_parser.features_device(rows, lens, None, dither, logical_len=rows.shape[1])
+            out = self.model._encode(inputs, pct)
+            for r, i in enumerate(batch):
+                first, n = windows[i][2], windows[i][3]
+                logp[offs[i]:offs[i] + n] = out[r, first:first + n].float()
+        return logp
+
+    @torch.no_grad()
+    def encode_long(self, audio_path, window_s: float = 20.0, context_s: float = 4.0, batch_size: int = 8,
+                    resample: Optional[bool] = None, dither: bool = False):
+        """The log-probs of a WHOLE recording: (logp (T', C) f32 on the device, duration in seconds).  The recording is cut into the
+        overlapping windows of ``streaming.plan_windows(total, True, window, context, context, 0)`` - ``window_s`` of new audio
+        with ``context_s`` before and after it - each window goes through the feature chain and the eval forward exactly as a
+        window of the streaming recogniser does (normalised over its own frames), and only the rows of its middle are kept: the
+        kept rows tile the recording's ``streaming.total_frames`` exactly once.  Windows of equal sample length run together,
+        ``batch_size`` per forward; the first and the last window have lengths of their own and a forward each.  With
+        batch_size=1 the rows are bit for bit those ``stream(window_s, context_s, context_s, dither=False, keep_logp=True)``
+        emits; a larger batch may select other kernels by shape and reorder sums (DESIGN.md has the measured difference).
+        dither: off by default, so that an alignment is reproducible.
+        window_s and context_s ARE STARTING VALUES: nobody has measured accuracy against them on a trained model.
+        Memory: T' x C f32 stays on the device - C = 29: 21 MB per hour of audio; C = 4334 (AISHELL): 3.1 GB per hour."""
+        wave, duration = self._load_wave(audio_path, resample)
+        return self._encode_wave_long(wave, window_s, context_s, int(batch_size), bool(dither)), duration
+
+    def _align_long(self, logp: torch.Tensor, sentences: List[str], duration: float, band: int, max_band: int) -> dict:
+        from .align import sentence_records
+        sents = [s for s in sentences if s]
+        joiner = " " if " " in self.labels else ""
+        sentence_ids = [self.text_to_ids(s) for s in sents]
+        sep = self.text_to_ids(joiner)
+        ids: List[int] = []
+        for k, i in enumerate(sentence_ids):
+            ids.extend((sep if k else []) + i)
+        result = {"duration": duration, "score": 0.0, "band": int(band), "words": [], "sentences": []}
+        if not ids:
+            return result
+        T, S = int(logp.shape[0]), len(ids)
+        tg = torch.tensor([ids], dtype=torch.int64, device=logp.device)
+        tl = torch.tensor([S], dtype=torch.int32, device=logp.device)
+        band, most = int(band), min(int(max_band), ops.CTC_ALIGN_LONG_MAX_BAND)
+        while True:
+            al = ops.ctc_align_long(logp.unsqueeze(0), tg, None, tl, logp.shape[-1] - 1, band=band) if T else None
+            status = int(al.status[0]) if T else 1
+            if status == 0:
+                break
+            if status == 1:
+                raise ValueError("align_long: no alignment exists: the transcript (%d labels) is too long for the recording (%d frames)"
+                                 % (S, T))
+            wider = ops.ctc_align_long_band_at_least(2 * band)     # twice the band, or the next band above that the kernel takes
+            if band >= 2 * S + 1 or wider is None or wider > most:
+                raise ValueError("align_long: the band of %d states lost every path (max_band %d): the transcript does not follow the "
+                                 "recording closely enough, or cannot be spoken on these log-probs at all" % (band, most))
+            band = wider
+        result["score"], result["band"] = float(al.score[0]), band
+        result["words"], result["sentences"] = sentence_records(sentence_ids, al.label_start[0].tolist(), al.label_end[0].tolist(),
+                                                                al.frame_logp[0].tolist(), self.labels, self.frame_seconds(), duration,
+                                                                sep=len(sep))
+        return result
+
+    @torch.no_grad()
+    def align_long(self, audio_path, text, band: int = 4096, max_band: int = ops.CTC_ALIGN_LONG_MAX_BAND, **encode) -> dict:
+        """Forced alignment of a whole recording (minutes to hours) to its transcript: ``encode_long`` (``**encode`` are its
+        keywords), ``text_to_ids``, ``ops.ctc_align_long`` - the Viterbi path inside a band of ``band`` lattice states that
+        follows it.  text: a string, or a list of sentences (joined by the space label where the vocabulary has one; empty
+        sentences are left out; nothing is normalised, so a sentence should neither start nor end with a space).  Returns {"duration", "score" (the path's log-probability), "band" (the band that aligned),
+        "words": the records of ``align``, "sentences": [{"text", "start", "end", "score", "min_word_score", "first_word",
+        "n_words"}, ...]} (align.sentence_records), times in seconds of the recording.
+        When the band loses every path (status 2 of the kernel) it is doubled (rounded up to the next band the kernel takes), up
+        to ``max_band``, whose default is the kernel's widest band, ops.CTC_ALIGN_LONG_MAX_BAND = 8192; above that there is no
+        escalation left (a band of 2 S + 1 states or more cannot lose a path: that holds for S <= 4095 only), then ValueError.  ValueError
+        also for a transcript with more labels than the recording has frames.  A band narrower than the lattice prunes: it can
+        return a feasible path that is not the best one, WITHOUT ANY FLAG - inherent to pruning; low sentence scores are the
+        only sign.  The transcript has to cover the whole recording: there is no free start or end."""
+        sentences = [text] if isinstance(text, str) else list(text)
+        logp, duration = self.encode_long(audio_path, **encode)
+        return self._align_long(logp, sentences, duration, band, max_band)
+
+    @torch.no_grad()
+    def cut_corpus(self, audio_path, sentences, out_dir: str, manifest_path: str, max_duration: float = 16.7,
+                   min_score: Optional[float] = None, band: int = 4096, max_band: int = ops.CTC_ALIGN_LONG_MAX_BAND, prefix: Optional[str] = None,
+                   pad_s: float = 0.5, **encode) -> dict:
+        """A long recording and its transcript, sentence by sentence -> training utterances: ``align_long``, then consecutive
+        sentences are grouped greedily into utterances of at most ``max_duration`` seconds, cut in the middle of the gap between
+        neighbouring sentences (``pad_s`` before the first and after the last; align.group_sentences), cut out on the device
+        (``ops.gather_segments``) and written to ``out_dir`` as 16-bit PCM wavs ``<prefix>_<index>.wav`` at the parser's sample
+        rate (prefix: the audio file's stem).  One line {"audio_filepath", "duration", "text", "score"} per utterance is APPENDED
+        to ``manifest_path``, the format ``LibriDataModule`` trains on; score is the lowest word score of the utterance.
+        min_score: utterances whose lowest word score is under it are dropped; None (the default) drops nothing - the threshold
+        is untuned: nobody has measured it on a trained model.  A sentence longer than max_duration on its own is dropped.
+        Returns {"duration", "score", "band", "utterances": the manifest records, "spans": their (start, end) in samples of the
+        recording, "dropped": [{"text", "reason"}, ...]}."""
+        import wave as wavmod
+        from .align import cut_samples, group_sentences
+        wave, duration = self._load_wave(audio_path, encode.pop("resample", None))
+        logp = self._encode_wave_long(wave, **encode)
+        res = self._align_long(logp, [sentences] if isinstance(sentences, str) else list(sentences), duration, band, max_band)
+        sents = res["sentences"]
+        sr = int(self.audio_parser.sr)
+        joiner = " " if " " in self.labels else ""
+        groups, too_long = group_sentences(sents, max_duration, min(duration, wave.numel() / float(sr)), joiner, pad_s)
+        dropped = [{"text": sents[i]["text"], "reason": "longer than max_duration"} for i in too_long]
+        if min_score is not None:
+            dropped += [{"text": g["text"], "reason": "min_word_score %.4f under min_score" % g["min_word_score"]}
+                        for g in groups if g["min_word_score"] < min_score]
+            groups = [g for g in groups if g["min_word_score"] >= min_score]
+        spans = cut_samples(groups, sr, int(wave.numel()), max_duration)
+        os.makedirs(out_dir, exist_ok=True)
+        if prefix is None:
+            prefix = os.path.splitext(os.path.basename(audio_path))[0] if isinstance(audio_path, str) else "utt"
+        records = []
+        for k in range(0, len(groups), 64):                       # 64 utterances per gather: rows as wide as the longest of them
+            part = spans[k:k + 64]
+            rows, _ = ops.gather_segments(wave, [(0, s, e) for s, e in part])
+            pcm = (rows * 32768.0).round().clamp(-32768, 32767).to(torch.int16).cpu().numpy()
+            for r, (s, e) in enumerate(part):
+                g = groups[k + r]
+                path = os.path.join(out_dir, "%s_%05d.wav" % (prefix, g["first"]))
+                with wavmod.open(path, "wb") as f:
+                    f.setnchannels(1)
+                    f.setsampwidth(2)
+                    f.setframerate(sr)
+                    f.writeframes(pcm[r, :e - s].tobytes())
+                records.append({"audio_filepath": path, "duration": (e - s) / float(sr), "text": g["text"], "score": g["min_word_score"]})
+        with open(manifest_path, "a", encoding="utf-8") as f:
+            for rec in records:
+                f.write(json.dumps(rec, ensure_ascii=False) + "\n")
+        return {"duration": duration, "score": res["score"], "band": res["band"], "utterances": records, "spans": spans, "dropped": dropped}
 
     # ------------------------------------------------------------------------------------------ streaming
     def stream(self, chunk_s: float = 1.0, left_s: float = 4.0, right_s: float = 1.0, max_segment_s: float = 30.0,
